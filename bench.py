@@ -17,6 +17,14 @@ population -- and the all-gathered fitness vector (`fitness_checksum`) -- is the
 
     python bench.py --gpus N --steps K --warmup W [--config auto|config2|config3|...] [--scaling strong|weak]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the result line (the metric,
+`ms_per_step`, the workload, `fitness_checksum`).  `--dump-outputs DIR` also writes the fitness
+vector of the last timed step as DIR/fitness.npy (float64; the inputs depend only on the
+arguments, so two builds can be compared output for output).  `--full` adds everything else the
+line can carry, each in a run of its own beside the timed steps: the CPU baseline and the parity
+check of every timed fitness against it, the second timed pass with per-kernel HIP events and the
+roofline from it, the GPU decode / DE step timings and their host reference.
 """
 import argparse
 import json
@@ -75,7 +83,12 @@ def parse():
                     help="population (whole job under --scaling strong, per rank under weak; default: the config's)")
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--h2", type=float, default=0.4)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the CPU baseline and the parity check, the per-kernel event pass and the "
+                         "roofline, the decode / DE step timings (off: only the timed steps and the result line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's fitness vector to DIR/fitness.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and parity")
     ap.add_argument("--cpu-seconds", type=float, default=15.0, help="target wall time of the CPU baseline sample")
     ap.add_argument("--profile-json", default=None, help="write the per-kernel-class event timing here")
     ap.add_argument("--no-events", action="store_true", help="time without per-kernel HIP events (no roofline)")
@@ -197,7 +210,7 @@ def main():
     if k > 8192:
         keys = None
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(geno, pheno, T, V, genomes, args.h2, args.cpu_seconds)
 
     import torch
@@ -246,17 +259,92 @@ def main():
     torch.cuda.synchronize()
     # pass 1: the metric, uninstrumented (per-launch HIP events add ~5% of launch gaps)
     elapsed = timed_steps()
-    # pass 2: the same K steps with a HIP event pair around every launch, on the stream each
-    # kernel runs on: per-kernel-class time, the roofline's average launch duration
-    eng.reset_profile()
-    eng.set_profiling(not args.no_events)
-    elapsed_events = timed_steps()
-    eng.set_profiling(False)
-    prof = eng.profile()
+    # what the last timed step computed: the fitness vector a caller of the timed path receives
+    if world > 1:
+        fit_all = full.cpu().numpy().reshape(world, shard_max)
+        spans = [shard_range(total, r, world) if args.scaling == "strong" else (pop * r, pop * (r + 1))
+                 for r in range(world)]
+        fit = np.concatenate([fit_all[r, :b - a] for r, (a, b) in enumerate(spans)])
+    else:
+        fit = d_fit.cpu().numpy()[:pop]
+    elapsed_events = prof = None
+    if args.full:
+        # pass 2: the same K steps with a HIP event pair around every launch, on the stream each
+        # kernel runs on: per-kernel-class time, the roofline's average launch duration
+        eng.reset_profile()
+        eng.set_profiling(not args.no_events)
+        elapsed_events = timed_steps()
+        eng.set_profiling(False)
+        prof = eng.profile()
     # every timed evaluation must have succeeded: raises for an index error or an expired
     # chained-solve wait (tblup_solve_error), never reports a rate over invalid fitnesses
     eng.check_device_status(stream.cuda_stream)
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "fitness.npy"), np.ascontiguousarray(fit, dtype=np.float64))
 
+    decode_ms = de_ms = host_ref = None
+    if args.full:
+        decode_ms, de_ms, host_ref = generation_step_timings(args, eng, keys, idx, off, d_off, pop, P, k, device,
+                                                             stream, cpu is not None)
+    # the timed fitnesses against the oracle's for every individual the CPU baseline evaluated
+    # (evaluator.py:298-314 restated in oracle/blup_oracle.py): the line proves its own results
+    parity = None
+    if cpu is not None:
+        parity = fitness_parity(fit, cpu.pop("_oracle_fit"), pop)
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    total_evals = total * args.steps
+    value = total_evals / elapsed
+
+    roofline = step_ms = None
+    if args.full:
+        roofline, step_ms = roofline_report(args, prof, config, cfg, rank, world, pop, shard_max, elapsed, value)
+    if rank == 0:
+        line = {
+            "metric": METRIC,
+            "value": round(value, 2), "unit": "evals/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": ("fp4 e2m1 system tiles (exact integer genotype products, fp32 accumulate)" if k < nT else
+                      "int8 GRM (exact int32 accumulate)") + " + f64 Cholesky/solve",
+            "data": "synthetic (Binomial(2, U(0.05,0.5)) genotypes, N(0,1) phenotype, RandomKey individuals)",
+            "config": {"workload": f"{config}: {n} animals x {P} SNPs, panel k={k}, DE pop {total} "
+                                   f"({shard_max} per GPU), n_train={nT}, n_valid={nV}, h2={args.h2}"
+                                   + (f", {traits} traits (one Cholesky, {traits} RHS)" if traits > 1 else ""),
+                       "pop_total": total, "pop_per_gpu": shard_max,
+                       "parallelism": f"population sharded over {world} GPU(s) ({args.scaling} scaling)"
+                                      + (f", {tdist.backend_name()} fitness all-gather" if world > 1 else "")},
+            "fitness_checksum": float(np.nansum(fit)),
+        }
+        if args.full:
+            line.update({
+                "roofline": roofline,
+                "cpu_baseline": cpu,
+                "kernel_ms_per_step": step_ms,
+                "ms_per_step_with_events": round(elapsed_events / args.steps * 1e3, 4),
+                "gpu_decode_ms": None if decode_ms is None else round(decode_ms, 4),
+                "gpu_de_step_ms": None if de_ms is None else round(de_ms, 4),
+                "host_reference_ms": host_ref,
+                "parity_max_abs_fit": None if parity is None else parity["max_abs_fit"],
+                "parity": parity,
+            })
+        print(json.dumps(line), flush=True)
+        if parity is not None and not (parity["max_abs_fit"] is not None and parity["max_abs_fit"] <= PARITY_ATOL):
+            print(f"bench: GPU fitness differs from the oracle by {parity['max_abs_fit']} > {PARITY_ATOL}",
+                  file=sys.stderr)
+            sys.exit(3)
+    eng.close()
+    if owns_group:
+        tdist.destroy()
+
+
+def generation_step_timings(args, eng, keys, idx, off, d_off, pop, P, k, device, stream, with_host):
+    """--full: the GPU genome decode and DE generation step of the same population, and (with the
+    CPU baseline) the reference's two host steps; reported beside the metric, not part of it."""
+    import torch
     # GPU genome decode of the same population (RandomKeyIndividual.genome, individual.py:154-156)
     # from device-resident keys: reported beside the metric, not part of it
     decode_ms = de_ms = None
@@ -295,7 +383,7 @@ def main():
     # the same two host steps the reference runs per generation (numpy evolve loop, argsort
     # decode), timed beside them on rank 0 (oracle restatement; reported, not the metric)
     host_ref = None
-    if cpu is not None and keys is not None:
+    if with_host and keys is not None:
         import random as _random
         from oracle import de_oracle
         rows = [keys[i] for i in range(pop)]
@@ -308,25 +396,13 @@ def main():
         host_ref = {"de_step_ms": round((t2 - t1) * 1e3, 2), "decode_ms": round((t3 - t2) * 1e3, 2), "cores": 1,
                     "kind": "port", "sample": f"one generation of {pop} x {P} keys (evolver.py:140-157, "
                                               "individual.py:154-156), numpy on one host core"}
-    if world > 1:
-        fit_all = full.cpu().numpy().reshape(world, shard_max)
-        spans = [shard_range(total, r, world) if args.scaling == "strong" else (pop * r, pop * (r + 1))
-                 for r in range(world)]
-        fit = np.concatenate([fit_all[r, :b - a] for r, (a, b) in enumerate(spans)])
-    else:
-        fit = d_fit.cpu().numpy()[:pop]
-    # the timed fitnesses against the oracle's for every individual the CPU baseline evaluated
-    # (evaluator.py:298-314 restated in oracle/blup_oracle.py): the line proves its own results
-    parity = None
-    if cpu is not None:
-        parity = fitness_parity(fit, cpu.pop("_oracle_fit"), pop)
-    if world > 1:
-        t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
-    total_evals = total * args.steps
-    value = total_evals / elapsed
+    return decode_ms, de_ms, host_ref
 
+
+def roofline_report(args, prof, config, cfg, rank, world, pop, shard_max, elapsed, value):
+    """--full: the roofline of the dominant kernel class from the event-timed pass (with the committed
+    rocprof / PMC summaries where they were taken on this workload) and the per-class ms per step."""
+    n, P, k, _, nT, nV = cfg
     # roofline of the dominant kernel class, from live HIP-event timing over the timed region.
     # The library counts the flops of the padded 128-row tiles (ns = 1024 at k = 1000); the
     # algorithmic work of the Cholesky classes scales as ns^3, so frac uses (k / ns)^3 of it.
@@ -433,40 +509,7 @@ def main():
     # build does not run) times the eval rate, over the fp32 MFMA peak -- above 1 because the
     # build's exact SNP-space form needs ~3.4x fewer flops than the canonical count
     roofline["canonical_flop_rate_over_fp32_peak"] = round(f_canon * value / world / (PEAKS["fp32_mfma_tflops"] * 1e12), 4)
-    if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": round(value, 2), "unit": "evals/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": ("fp4 e2m1 system tiles (exact integer genotype products, fp32 accumulate)" if k < nT else
-                      "int8 GRM (exact int32 accumulate)") + " + f64 Cholesky/solve",
-            "data": "synthetic (Binomial(2, U(0.05,0.5)) genotypes, N(0,1) phenotype, RandomKey individuals)",
-            "config": {"workload": f"{config}: {n} animals x {P} SNPs, panel k={k}, DE pop {total} "
-                                   f"({shard_max} per GPU), n_train={nT}, n_valid={nV}, h2={args.h2}"
-                                   + (f", {traits} traits (one Cholesky, {traits} RHS)" if traits > 1 else ""),
-                       "pop_total": total, "pop_per_gpu": shard_max,
-                       "parallelism": f"population sharded over {world} GPU(s) ({args.scaling} scaling)"
-                                      + (f", {tdist.backend_name()} fitness all-gather" if world > 1 else "")},
-            "roofline": roofline,
-            "cpu_baseline": cpu,
-            "kernel_ms_per_step": step_ms,
-            "ms_per_step_with_events": round(elapsed_events / args.steps * 1e3, 4),
-            "gpu_decode_ms": None if decode_ms is None else round(decode_ms, 4),
-            "gpu_de_step_ms": None if de_ms is None else round(de_ms, 4),
-            "host_reference_ms": host_ref,
-            "fitness_checksum": float(np.nansum(fit)),
-            "parity_max_abs_fit": None if parity is None else parity["max_abs_fit"],
-            "parity": parity,
-        }
-        print(json.dumps(line), flush=True)
-        if parity is not None and not (parity["max_abs_fit"] is not None and parity["max_abs_fit"] <= PARITY_ATOL):
-            print(f"bench: GPU fitness differs from the oracle by {parity['max_abs_fit']} > {PARITY_ATOL}",
-                  file=sys.stderr)
-            sys.exit(3)
-    eng.close()
-    if owns_group:
-        tdist.destroy()
+    return roofline, step_ms
 
 
 if __name__ == "__main__":

@@ -17,6 +17,16 @@ def test_fitness_parity_covers_and_flags():
     assert bench.fitness_parity(fit, {}, 4)["max_abs_fit"] is None
 
 
+def test_plain_run_is_the_default(monkeypatch):
+    """--full and --dump-outputs are off unless asked for; the flags --full governs still parse."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "d", "--no-cpu-baseline", "--no-events"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.no_cpu_baseline and a.no_events
+
+
 def test_cpu_baseline_keeps_its_oracle_fitnesses(monkeypatch):
     """cpu_baseline's sample covers individual i % pop at evaluation i and returns their fitnesses."""
     rng = np.random.default_rng(0)

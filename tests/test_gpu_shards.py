@@ -110,7 +110,8 @@ def test_bench_multi_rank_rehearsal(gpu, tmp_path):
     env = dict(os.environ, TBLUP_DIST_BACKEND="gloo", PYTHONUNBUFFERED="1")
     base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
             "--no-events"]
-    one = subprocess.run(base + ["--config", "config3"], env=env, capture_output=True, text=True, timeout=600)
+    one = subprocess.run(base + ["--config", "config3", "--dump-outputs", str(tmp_path / "one")], env=env,
+                         capture_output=True, text=True, timeout=600)
     assert one.returncode == 0, one.stderr[-3000:]
     port = _free_port()
     two = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
@@ -123,6 +124,12 @@ def test_bench_multi_rank_rehearsal(gpu, tmp_path):
     assert l2["n_gpus"] == 2 and l2["config"]["pop_total"] == 1024 and l2["config"]["pop_per_gpu"] == 512
     assert l2["scaling"] == "strong"
     assert l1["fitness_checksum"] == l2["fitness_checksum"]
+    # --dump-outputs: the last timed step's fitness vector, the one the line's checksum sums
+    dumped = np.load(tmp_path / "one" / "fitness.npy")
+    assert dumped.dtype == np.float64 and dumped.shape == (1024,)
+    assert float(np.nansum(dumped)) == l1["fitness_checksum"]
+    # a plain run carries the headline figures only; the rest needs --full
+    assert l1["steps"] == 2 and l1["ms_per_step"] > 0 and "roofline" not in l1 and "cpu_baseline" not in l1
 
 
 @pytest.mark.parametrize("case", ["rk_rand1", "intercv"])

@@ -10,8 +10,9 @@ for r in $(seq 1 $R); do
   for spec in "$@"; do
     v=${spec%%=*}; ev=${spec#*=}
     lib=ab/var.so; [ -f ab/$v.so ] && lib=ab/$v.so
-    env ${ev//,/ } X=0 TBLUP_GPU_LIB=$lib timeout -k 10 200 python bench.py --pop $P --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/ab_$v.log 2> gpurun_out/ab_$v.err || { tail -5 gpurun_out/ab_$v.err; exit 1; }
-    python3 -c "import json;d=json.loads(open('gpurun_out/ab_$v.log').read().strip().splitlines()[-1]);print($P, '$v', d['value'], d['kernel_ms_per_step'])"
+    O=${BENCH_OUT:-bench_out}; mkdir -p $O   # the bench lines' directory
+    env ${ev//,/ } X=0 TBLUP_GPU_LIB=$lib timeout -k 10 200 python bench.py --full --pop $P --steps 20 --warmup 5 --no-cpu-baseline > $O/ab_$v.log 2> $O/ab_$v.err || { tail -5 $O/ab_$v.err; exit 1; }
+    python3 -c "import json;d=json.loads(open('$O/ab_$v.log').read().strip().splitlines()[-1]);print($P, '$v', d['value'], d['kernel_ms_per_step'])"
   done
 done
 done

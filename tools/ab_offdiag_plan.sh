@@ -7,8 +7,9 @@ tail -1 gpurun_out/nds_test.log
 for rep in 1 2; do
 for P in 32 64 128 192 256; do
   for v in base var; do
-  TBLUP_GPU_LIB=ab/$v.so timeout -k 10 120 python bench.py --pop $P --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/nds.log 2> gpurun_out/nds.err || { tail -5 gpurun_out/nds.err; exit 1; }
-  python -c "import json; d=json.loads(open('gpurun_out/nds.log').read().strip().splitlines()[-1]); print($P, '$v', d['value'], d['kernel_ms_per_step']['chol_offdiag'])"
+  O=${BENCH_OUT:-bench_out}; mkdir -p $O   # the bench lines' directory
+  TBLUP_GPU_LIB=ab/$v.so timeout -k 10 120 python bench.py --full --pop $P --steps 10 --warmup 3 --no-cpu-baseline > $O/nds.log 2> $O/nds.err || { tail -5 $O/nds.err; exit 1; }
+  python -c "import json; d=json.loads(open('$O/nds.log').read().strip().splitlines()[-1]); print($P, '$v', d['value'], d['kernel_ms_per_step']['chol_offdiag'])"
   done
 done
 done

@@ -5,6 +5,7 @@
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 for v in $1; do
-  TBLUP_GPU_LIB=ab/diag.so TBLUP_DBG_SKIP=$v timeout -k 10 200 python bench.py --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/abl_$v.log 2>&1 || { tail -5 gpurun_out/abl_$v.log; exit 1; }
-  python -c "import json,sys; d=json.loads(open('gpurun_out/abl_$v.log').read().strip().splitlines()[-1]); print('skip', $v, d['value'], d['kernel_ms_per_step'])"
+  O=${BENCH_OUT:-bench_out}; mkdir -p $O   # the bench lines' directory
+  TBLUP_GPU_LIB=ab/diag.so TBLUP_DBG_SKIP=$v timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline > $O/abl_$v.log 2>&1 || { tail -5 $O/abl_$v.log; exit 1; }
+  python -c "import json,sys; d=json.loads(open('$O/abl_$v.log').read().strip().splitlines()[-1]); print('skip', $v, d['value'], d['kernel_ms_per_step'])"
 done

@@ -14,7 +14,7 @@ fi
 # PART=a: everything but the generation / IntraGCV / knockout / timeline runs; PART=b (with
 # SKIP_TESTS=1): only those -- two GPU calls under one tag when one would run too long
 if [ "$PART" != "b" ]; then
-B="python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline"
+B="python3 bench.py --full --steps 2 --warmup 1 --no-cpu-baseline"
 timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE -d $O/pmcf_$TAG -o pmc --output-format csv -- $B > $O/pmcf_$TAG.log 2>&1 || { echo "pmc fetch failed"; tail -5 $O/pmcf_$TAG.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE -d $O/pmcw_$TAG -o pmc --output-format csv -- $B > $O/pmcw_$TAG.log 2>&1 || { echo "pmc write failed"; tail -5 $O/pmcw_$TAG.log; exit 1; }
 timeout -s KILL 120 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d $O/pmcm_$TAG -o pmc --output-format csv -- $B > $O/pmcm_$TAG.log 2>&1 || { echo "pmc mfma failed"; tail -5 $O/pmcm_$TAG.log; exit 1; }
@@ -24,8 +24,8 @@ W=$(find $O/pmcw_$TAG -name "*counter_collection.csv" | head -1)
 M=$(find $O/pmcm_$TAG -name "*counter_collection.csv" | head -1)
 python3 tools/pmc_traffic.py $F $W --out $O/pmc_traffic_$TAG.json || exit 1
 python3 tools/pmc_mfma.py $M --out $O/pmc_mfma_$TAG.json || exit 1
-timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o trace --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --pmc-json $O/pmc_traffic_$TAG.json --pmc-mfma-json $O/pmc_mfma_$TAG.json > $O/prof_bench_$TAG.log 2>&1 || { echo "kernel-trace failed"; tail -20 $O/prof_bench_$TAG.log; exit 1; }
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 --pmc-json $O/pmc_traffic_$TAG.json --pmc-mfma-json $O/pmc_mfma_$TAG.json > $O/bench_$TAG.log 2> $O/bench_$TAG.err || { tail -20 $O/bench_$TAG.err; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$TAG -o trace --output-format csv -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --pmc-json $O/pmc_traffic_$TAG.json --pmc-mfma-json $O/pmc_mfma_$TAG.json > $O/prof_bench_$TAG.log 2>&1 || { echo "kernel-trace failed"; tail -20 $O/prof_bench_$TAG.log; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 --pmc-json $O/pmc_traffic_$TAG.json --pmc-mfma-json $O/pmc_mfma_$TAG.json > $O/bench_$TAG.log 2> $O/bench_$TAG.err || { tail -20 $O/bench_$TAG.err; exit 1; }
 tail -1 $O/bench_$TAG.log | cut -c1-300
 fi
 if [ "$PART" != "a" ]; then
@@ -45,12 +45,12 @@ timeout -k 10 200 python tools/wg_trace.py $O/wg_trace_$TAG.npy > $O/wg_trace_$T
 timeout -k 10 200 python tools/wg_trace.py $O/wg_trace128_$TAG.npy --pop 128 > $O/wg_trace128_$TAG.txt 2>&1 || { tail -20 $O/wg_trace128_$TAG.txt; exit 1; }
 fi
 [ "$PART" = "b" ] && { echo "evidence part b done"; exit 0; }
-timeout -k 10 400 python bench.py --config config4 --steps 5 --warmup 2 > $O/bench_config4_$TAG.log 2> $O/bench_config4_$TAG.err || { tail -20 $O/bench_config4_$TAG.err; exit 1; }
-timeout -k 10 300 python bench.py --config config5 --steps 20 --warmup 5 > $O/bench_config5_$TAG.log 2> $O/bench_config5_$TAG.err || { tail -20 $O/bench_config5_$TAG.err; exit 1; }
+timeout -k 10 400 python bench.py --full --config config4 --steps 5 --warmup 2 > $O/bench_config4_$TAG.log 2> $O/bench_config4_$TAG.err || { tail -20 $O/bench_config4_$TAG.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config config5 --steps 20 --warmup 5 > $O/bench_config5_$TAG.log 2> $O/bench_config5_$TAG.err || { tail -20 $O/bench_config5_$TAG.err; exit 1; }
 for P in 32 64 128; do
-timeout -k 10 300 python bench.py --pop $P --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_pop${P}_$TAG.log 2> $O/bench_pop${P}_$TAG.err || { tail -20 $O/bench_pop${P}_$TAG.err; exit 1; }
+timeout -k 10 300 python bench.py --full --pop $P --steps 20 --warmup 5 --no-cpu-baseline > $O/bench_pop${P}_$TAG.log 2> $O/bench_pop${P}_$TAG.err || { tail -20 $O/bench_pop${P}_$TAG.err; exit 1; }
 done
-timeout -k 10 300 python bench.py --config config3 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config3_$TAG.log 2> $O/bench_config3_$TAG.err || { tail -20 $O/bench_config3_$TAG.err; exit 1; }
+timeout -k 10 300 python bench.py --full --config config3 --steps 5 --warmup 2 --no-cpu-baseline > $O/bench_config3_$TAG.log 2> $O/bench_config3_$TAG.err || { tail -20 $O/bench_config3_$TAG.err; exit 1; }
 for c in config3 config4 config5 pop32 pop64 pop128; do tail -1 $O/bench_${c}_$TAG.log | cut -c1-200; done
 timeout -k 10 100 ./tools/mfma_peak > $O/mfma_peak_$TAG.json 2>&1 || exit 1
 timeout -k 10 100 ./tools/fp4_probe > $O/fp4_probe_$TAG.json 2>&1 || exit 1

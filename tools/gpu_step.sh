@@ -44,7 +44,8 @@ POPS="${POPS:-256 128}" bash tools/ab_env.sh ${ROUNDS:-3} "$@" 2>&1 | tee gpurun
 for c in ${CONFIG5:+config5} ${CONFIG4:+config4}; do
   for r in 1 2; do for spec in "$@"; do
     v=${spec%%=*}; ev=${spec#*=}
-    env ${ev//,/ } X=0 TBLUP_GPU_LIB=$(lib_of $spec) timeout -k 10 300 python bench.py --config $c --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/ab_${c}_$v.log 2> gpurun_out/ab_${c}_$v.err || { tail -5 gpurun_out/ab_${c}_$v.err; exit 1; }
-    python3 -c "import json;d=json.loads(open('gpurun_out/ab_${c}_$v.log').read().strip().splitlines()[-1]);print('$c', '$v', d['value'], d['kernel_ms_per_step'])" | tee -a gpurun_out/${OUT}.txt
+    O=${BENCH_OUT:-bench_out}; mkdir -p $O   # the config bench lines' directory
+    env ${ev//,/ } X=0 TBLUP_GPU_LIB=$(lib_of $spec) timeout -k 10 300 python bench.py --full --config $c --steps 10 --warmup 3 --no-cpu-baseline > $O/ab_${c}_$v.log 2> $O/ab_${c}_$v.err || { tail -5 $O/ab_${c}_$v.err; exit 1; }
+    python3 -c "import json;d=json.loads(open('$O/ab_${c}_$v.log').read().strip().splitlines()[-1]);print('$c', '$v', d['value'], d['kernel_ms_per_step'])" | tee -a $O/${OUT}.txt
   done; done
 done
