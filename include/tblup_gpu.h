@@ -160,6 +160,8 @@ int tblup_eval_folds_device(tblup_ctx* ctx, const int* split_ids, int n_splits, 
  * (idx, offsets) pair tblup_eval_batch takes.  Equal keys are ordered by index (a
  * stable argsort), so a tie straddling the k-th position selects its largest
  * indices; with continuous keys this is the set numpy's default sort returns.
+ * Keys compare as numpy compares them: -0.0 equals +0.0, and every NaN (either
+ * sign bit, any payload) is equal to every other NaN and sorts above +inf.
  * 1 <= k_b <= min(d, 8192).  Host pointers, synchronous.
  */
 int tblup_decode_topk(tblup_ctx* ctx, const double* keys, int64_t batch, int64_t d, const int64_t* offsets,

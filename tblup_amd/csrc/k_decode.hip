@@ -23,8 +23,16 @@ namespace {
 constexpr int DTH = 1024;
 constexpr int KSORT_MAX = 8192;   // LDS sort capacity (k <= 8192)
 
+// Order-preserving uint64 image of a key, with numpy's sort order on the special values:
+// -0.0 compares equal to +0.0 (one image, so the tie goes by index), and every NaN, whatever
+// its sign bit and payload, takes one image above +inf (numpy sorts NaN last).  The smallest
+// image, -inf's, is 0x000fffffffffffff > 0 (the sample's padding slots) and the NaN image is
+// below ~0 (the bitonic sort's padding key).
 __device__ __forceinline__ uint64_t ord_key(double x) {
-  const uint64_t b = (uint64_t)__double_as_longlong(x);
+  uint64_t b = (uint64_t)__double_as_longlong(x);
+  const uint64_t mag = b & 0x7fffffffffffffffull;
+  if (mag > 0x7ff0000000000000ull) return 0xfff8000000000000ull;   // NaN of either sign
+  if (mag == 0) b = 0;                                             // -0.0 -> +0.0
   return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
 

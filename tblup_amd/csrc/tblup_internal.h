@@ -70,7 +70,9 @@ __host__ __device__ __forceinline__ int64_t snp_col(int64_t p, int64_t P) {
   p = p < 0 ? p + P : p;
   return p < 0 ? 0 : (p >= P ? P - 1 : p);
 }
-constexpr int FLAG_WRITE_LJJ = 1 << 16;   // CholLaunch::skip: also store L_JJ (debug readback only)
+// CholLaunch::skip: also store L_JJ (debug readback only).  Bits 0-18 of the mask are the ablation
+// bits of TBLUP_DBG_SKIP (bits 16-18: k_sys_tiles stores nothing); this flag must stay clear of them.
+constexpr int FLAG_WRITE_LJJ = 1 << 24;
 
 // System dimensions of one chunk.
 struct SysDims {
