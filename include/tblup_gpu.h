@@ -300,6 +300,56 @@ int tblup_mt19937_jump(const uint32_t* key, int32_t pos, uint64_t n_words, uint3
 int tblup_de_donors(int strategy, int64_t pop, int64_t L, int32_t best, uint32_t* py_mt, int32_t* py_index,
                     int32_t* donors, int64_t* fixed);
 
+/*
+ * One MDE_pBX generation (MDE_pBX.evolve, tblup/evolver.py:550-687) in two device halves with a
+ * host resolve between them.  Per individual i the reference draws
+ *   best = population[np.random.choice(q_best, 1)], parent = np.random.choice(p_best, 1)
+ * and then runs de_currenttobest_one on population[parent] (exclusive_randrange twice, randrange,
+ * np.random.rand(L)).  Legacy np.random.choice(arr, 1) takes no MT19937 word for a single-entry
+ * array and otherwise one word per attempt of `word & mask <= n - 1` (mask = 2^bit_length(n-1) - 1),
+ * so individual i's uniforms start at word 2 L i + C_i of the generation's numpy stream, C_i = the
+ * words the choices of individuals 0..i took.
+ *
+ * tblup_mde_windows (host-only): the stream offsets past 2 L i that a choice of individual i can
+ * read, [lo[i], hi[i]) -- lo[i] the certain minimum of C_{i-1}, hi[i] the expected C_i plus slack
+ * (slack < 0: six standard deviations + 16 words; slack >= 0: that many words and no deviation
+ * term, for tests that force an overflow) -- and off[i] (pop + 1 entries), where that run starts in
+ * the compact word buffer of *n_words = off[pop] words.  lo / hi / off may be NULL.
+ *
+ * tblup_mde_draws: enqueues on `stream` (NULL = the context's) the jump to every individual's
+ * window and the expansion of those runs, copies the tempered words into `words` (host, n_words as
+ * tblup_mde_windows gives for the same pop, nq, np, slack) and waits for them.  mt_key / mt_pos:
+ * numpy's state before the generation's first choice; it is not advanced.
+ *
+ * tblup_mde_resolve (host-only, no context): sequentially over i, the two choices from `words`
+ * (q_best[.] / p_best[.]: the population indices of the nq group bests and np parents to choose
+ * from), C_i into c_words[i], and python's draws on (py_mt, py_index) as tblup_de_donors makes
+ * them, with exclusions [parent_i, best_i] then a: donors[i] = (best_i, a, b), fixed[i],
+ * parent[i].  *overflow = 1 when a rejection run left its window: the outputs are then undefined
+ * and (py_mt, py_index) untouched -- the caller runs the generation on the host instead.
+ *
+ * tblup_mde_step_device_async: the step for the resolved draws, asynchronous like
+ * tblup_de_step_device_async and completed by tblup_de_state_wait (numpy's state after all
+ * 2 L pop + C_pop words): child i = DE/current-to-best/1 on row parent[i] with F[i], cr[i]
+ * (host arrays of pop), uniforms from word 2 L i + c_words[i].  It continues the last
+ * tblup_mde_draws of the same context, which must have been given the same pop, L and MT state
+ * (TBLUP_ERR_STATE otherwise); c_words must be non-decreasing and within those draws' windows
+ * (c_words[pop-1] <= hi[pop-1], as tblup_mde_resolve guarantees); one step may be pending at a
+ * time.  Needs 4 <= pop.
+ */
+int tblup_mde_windows(int64_t pop, int64_t nq, int64_t np, int32_t slack, int32_t* lo, int32_t* hi, int64_t* off,
+                      int64_t* n_words);
+int tblup_mde_draws(tblup_ctx* ctx, int64_t pop, int64_t L, int64_t nq, int64_t np, int32_t slack,
+                    const uint32_t* mt_key, int32_t mt_pos, uint32_t* words, int64_t n_words, void* stream);
+int tblup_mde_resolve(int64_t pop, int64_t L, const int32_t* q_best, int64_t nq, const int32_t* p_best, int64_t np,
+                      int32_t slack, const uint32_t* words, int64_t n_words, uint32_t* py_mt, int32_t* py_index,
+                      int32_t* parent, int32_t* donors, int64_t* fixed, int64_t* c_words, int32_t* overflow);
+int tblup_mde_step_device_async(tblup_ctx* ctx, const double* F, const double* cr, const double* d_parents,
+                                int64_t pop, int64_t L, int64_t ld, const int32_t* parent, const int32_t* donors,
+                                const int64_t* fixed, const int64_t* c_words, int clip, double clip_hi,
+                                const uint32_t* mt_key, int32_t mt_pos, double* d_children, int64_t ldc,
+                                void* stream);
+
 /* Index-error flag of the device entry points: synchronises `stream` (NULL = the context's
  * stream), sets *flag = 1 if any individual evaluated since the last call had an index
  * outside [-n_snps, n_snps) (its fitness is NaN), and clears the flag. */

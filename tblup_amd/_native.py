@@ -74,6 +74,14 @@ SIGNATURES = {
     "tblup_snp_scan": (_c.c_int, [_P, _I64P, _c.c_int64, _DP, _I64P, _I64P, _DP]),
     "tblup_mt19937_jump": (_c.c_int, [_U32P, _c.c_int32, _c.c_uint64, _U32P, _I32P]),
     "tblup_de_donors": (_c.c_int, [_c.c_int, _c.c_int64, _c.c_int64, _c.c_int32, _U32P, _I32P, _I32P, _I64P]),
+    "tblup_mde_windows": (_c.c_int, [_c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _I32P, _I32P, _I64P, _I64P]),
+    "tblup_mde_draws": (_c.c_int, [_P, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_int32, _U32P, _c.c_int32,
+                                   _U32P, _c.c_int64, _P]),
+    "tblup_mde_resolve": (_c.c_int, [_c.c_int64, _c.c_int64, _I32P, _c.c_int64, _I32P, _c.c_int64, _c.c_int32, _U32P,
+                                     _c.c_int64, _U32P, _I32P, _I32P, _I32P, _I64P, _I64P, _I32P]),
+    "tblup_mde_step_device_async": (_c.c_int, [_P, _DP, _DP, _P, _c.c_int64, _c.c_int64, _c.c_int64, _I32P, _I32P,
+                                               _I64P, _I64P, _c.c_int, _c.c_double, _U32P, _c.c_int32, _P, _c.c_int64,
+                                               _P]),
     "tblup_gather_rows": (_c.c_int, [_c.c_void_p, _c.c_void_p, _c.c_int64, _c.c_int64, _c.c_int64, _c.c_void_p,
                                      _c.c_void_p]),
 }

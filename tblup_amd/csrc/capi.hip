@@ -774,6 +774,7 @@ int tblup_ctx_destroy(tblup_ctx* c) {
   c->de_small.release();
   c->de_par.release();
   c->de_chi.release();
+  c->mde_dev.release();
   if (c->de_ev) (void)hipEventDestroy(c->de_ev);
   if (c->de_host) (void)hipHostFree(c->de_host);
   if (c->de_stage) (void)hipHostFree(c->de_stage);

@@ -139,6 +139,50 @@ static int validate_de(int strategy, int64_t pop, int64_t L, const int32_t* dono
   return 0;
 }
 
+// the jump polynomials of (L, pop) on the device (kept until another shape is asked for)
+static int de_upload_polys(tblup_ctx* c, int64_t L, int64_t pop, hipStream_t s) {
+  if (c->de_L == L && c->de_pop == pop) return 0;
+  const tblup_mt::DePolys dp = tblup_mt::de_polys(L, pop);
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int rc = dev_alloc(c, c->de_polys, dp.words.size() * 4)) return rc;
+  HIPCHK(hipMemcpy(c->de_polys.p, dp.words.data(), dp.words.size() * 4, hipMemcpyHostToDevice));
+  c->de_L = L;
+  c->de_pop = pop;
+  c->de_end_jump = dp.end_jump;
+  return 0;
+}
+
+// page-locked staging of a step's per-call arguments that outlives the call (the copy is
+// asynchronous); the previous call's copy from it finished before that call's state was fetched
+// (one step pending at a time)
+static int de_stage_reserve(tblup_ctx* c, size_t bytes, hipStream_t s) {
+  if (bytes <= c->de_stage_bytes) return 0;
+  HIPCHK(hipStreamSynchronize(s));
+  if (c->de_stage) HIPCHK(hipHostFree(c->de_stage));
+  c->de_stage = nullptr;
+  c->de_stage_bytes = 0;
+  HIPCHK(hipHostMalloc((void**)&c->de_stage, bytes, hipHostMallocDefault));
+  c->de_stage_bytes = bytes;
+  return 0;
+}
+
+// the copy of the new MT state to the host behind a step, and the event tblup_de_state_wait waits for
+static int de_state_fetch(tblup_ctx* c, const void* d_state, hipStream_t s) {
+  if (!c->de_host) HIPCHK(hipHostMalloc((void**)&c->de_host, 625 * 4, hipHostMallocDefault));
+  if (!c->de_ev) HIPCHK(hipEventCreateWithFlags(&c->de_ev, hipEventDisableTiming));
+  HIPCHK(hipMemcpyAsync(c->de_host, d_state, 624 * 4 + 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipEventRecord(c->de_ev, s));
+  c->de_pending = true;
+  return 0;
+}
+
+// smallest population the three-launch forms take (TBLUP_DE_SPLIT; default: more individuals than CUs)
+static int64_t de_split_min() {
+  static const int64_t v = getenv("TBLUP_DE_SPLIT") ? atoll(getenv("TBLUP_DE_SPLIT")) : cu_count() + 1;
+  return v;
+}
+
 // The asynchronous step, with optional per-individual strategies / F / crossover rates (host
 // arrays of pop; null: the scalars).
 static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, const double* F_i, const double* cr_i,
@@ -159,16 +203,7 @@ static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, con
   if (!d_parents || !d_children) return fail(TBLUP_ERR_ARG, "null device pointers");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  if (c->de_L != L || c->de_pop != pop) {
-    const tblup_mt::DePolys dp = tblup_mt::de_polys(L, pop);
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->de_polys, dp.words.size() * 4)) return rc;
-    HIPCHK(hipMemcpy(c->de_polys.p, dp.words.data(), dp.words.size() * 4, hipMemcpyHostToDevice));
-    c->de_L = L;
-    c->de_pop = pop;
-    c->de_end_jump = dp.end_jump;
-  }
+  if (int rc = de_upload_polys(c, L, pop, s)) return rc;
   // per-call arguments: key in, key out, pos out, donors, fixed
   const size_t o_keyo = 624 * 4, o_pos = 2 * 624 * 4, o_don = o_pos + 16, o_fix = o_don + (size_t)round_up(12 * pop, 16);
   const size_t o_str = o_fix + 8 * (size_t)pop, o_F = o_str + (size_t)round_up(4 * pop, 16), o_cr = o_F + 8 * (size_t)pop;
@@ -176,8 +211,7 @@ static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, con
   // device-only scratch of the three-launch form (large populations): base sequence + windows
   // (from more individuals than CUs: both forms need a second round of jump workgroups there, and the
   // split form's mask and stream run several per CU; TBLUP_DE_SPLIT = the smallest split population)
-  static const int64_t split_min = getenv("TBLUP_DE_SPLIT") ? atoll(getenv("TBLUP_DE_SPLIT")) : cu_count() + 1;
-  const bool split = pop >= split_min;
+  const bool split = pop >= de_split_min();
   const size_t o_scr = (size_t)round_up((int64_t)small, 256);
   const size_t need = split ? o_scr + 4 * (size_t)(DE_SEQ_SCRATCH + 624 * pop) : small;
   if (need > c->de_small.bytes) {
@@ -185,16 +219,7 @@ static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, con
     if (int rc = dev_alloc(c, c->de_small, need)) return rc;
   }
   char* base = (char*)c->de_small.p;
-  // page-locked staging that outlives this call (the copy is asynchronous); the previous call's
-  // copy from it finished before that call's state was fetched (one step pending at a time)
-  if (small > c->de_stage_bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (c->de_stage) HIPCHK(hipHostFree(c->de_stage));
-    c->de_stage = nullptr;
-    c->de_stage_bytes = 0;
-    HIPCHK(hipHostMalloc((void**)&c->de_stage, small, hipHostMallocDefault));
-    c->de_stage_bytes = small;
-  }
+  if (int rc = de_stage_reserve(c, small, s)) return rc;
   char* stage = c->de_stage;
   std::memcpy(stage, mt_key, 624 * 4);
   std::memcpy(stage + o_don, donors, 12 * pop);
@@ -210,12 +235,7 @@ static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, con
                         (int32_t*)(base + o_pos), s, strat_i ? (const int32_t*)(base + o_str) : nullptr,
                         F_i ? (const double*)(base + o_F) : nullptr, cr_i ? (const double*)(base + o_cr) : nullptr,
                         split ? (uint32_t*)(base + o_scr) : nullptr));
-  if (!c->de_host) HIPCHK(hipHostMalloc((void**)&c->de_host, 625 * 4, hipHostMallocDefault));
-  if (!c->de_ev) HIPCHK(hipEventCreateWithFlags(&c->de_ev, hipEventDisableTiming));
-  HIPCHK(hipMemcpyAsync(c->de_host, base + o_keyo, 624 * 4 + 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipEventRecord(c->de_ev, s));
-  c->de_pending = true;
-  return 0;
+  return de_state_fetch(c, base + o_keyo, s);
 }
 
 int tblup_de_step_device_async(tblup_ctx* c, int strategy, const double* d_parents, int64_t pop, int64_t L,
@@ -286,6 +306,154 @@ int tblup_de_step(tblup_ctx* c, int strategy, const double* parents, int64_t pop
     return rc;
   HIPCHK(hipMemcpy(children, c->de_chi.p, bytes, hipMemcpyDeviceToHost));
   return 0;
+}
+
+// ---- MDE_pBX generation (evolver.py:550-687): draws, host resolve, step ----
+
+static const int64_t MDE_WORDS_MAX = (int64_t)1 << 26;   // draw words of one generation (256 MiB)
+
+static int validate_mde_shape(int64_t pop, int64_t L, int64_t nq, int64_t np) {
+  if (pop < 4 || pop > 65535 || L < 1 || L > ((int64_t)1 << 31))
+    return fail(TBLUP_ERR_ARG, "need 4 <= pop <= 65535 and 1 <= L <= 2^31");
+  if (nq < 1 || nq > pop || np < 1 || np > pop) return fail(TBLUP_ERR_ARG, "choice-array sizes must be in [1, pop]");
+  return 0;
+}
+
+int tblup_mde_windows(int64_t pop, int64_t nq, int64_t np, int32_t slack, int32_t* lo, int32_t* hi, int64_t* off,
+                      int64_t* n_words) {
+  clear_error();
+  if (int rc = validate_mde_shape(pop, 1, nq, np)) return rc;
+  if (!n_words) return fail(TBLUP_ERR_ARG, "null n_words");
+  *n_words = tblup_mt::mde_windows(pop, nq, np, slack, lo, hi, off);
+  return 0;
+}
+
+int tblup_mde_draws(tblup_ctx* c, int64_t pop, int64_t L, int64_t nq, int64_t np, int32_t slack,
+                    const uint32_t* mt_key, int32_t mt_pos, uint32_t* words, int64_t n_words, void* stream) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
+  if (int rc = validate_mde_shape(pop, L, nq, np)) return rc;
+  if (!mt_key || !words) return fail(TBLUP_ERR_ARG, "null mt_key/words");
+  if (mt_pos < 0 || mt_pos > 624) return fail(TBLUP_ERR_ARG, "mt_pos must be in [0, 624]");
+  std::vector<int32_t> lo((size_t)pop), hi((size_t)pop);
+  std::vector<int64_t> off((size_t)pop + 1);
+  const int64_t total = tblup_mt::mde_windows(pop, nq, np, slack, lo.data(), hi.data(), off.data());
+  if (n_words != total) return fail(TBLUP_ERR_ARG, "n_words is not the size tblup_mde_windows gives");
+  if (total > MDE_WORDS_MAX) return fail(TBLUP_ERR_ARG, "more than 2^26 draw words: keep this generation on the host");
+  c->mde_key.clear();
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  if (int rc = de_upload_polys(c, L, pop, s)) return rc;
+  const bool split = pop >= de_split_min();
+  const size_t o_tab = 624 * 4, o_off = o_tab + (size_t)round_up(8 * pop, 16), o_words = o_off + 8 * (size_t)pop;
+  const size_t o_scr = (size_t)round_up((int64_t)(o_words + 4 * (size_t)total), 256);
+  const size_t need = split ? o_scr + 4 * (size_t)(DE_SEQ_SCRATCH + 624 * (pop + 1)) : o_scr;
+  if (need > c->mde_dev.bytes) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = dev_alloc(c, c->mde_dev, need)) return rc;
+  }
+  char* base = (char*)c->mde_dev.p;
+  std::vector<char> host(o_words);
+  std::memcpy(host.data(), mt_key, 624 * 4);
+  int32_t* tab = (int32_t*)(host.data() + o_tab);
+  for (int64_t i = 0; i < pop; ++i) tab[2 * i] = lo[i], tab[2 * i + 1] = hi[i];
+  std::memcpy(host.data() + o_off, off.data(), 8 * (size_t)pop);
+  // `host` is pageable and local: the stream is synchronised below, before it goes away
+  HIPCHK(hipMemcpyAsync(base, host.data(), o_words, hipMemcpyHostToDevice, s));
+  HIPCHK(launch_mde_draws((const uint32_t*)base, mt_pos, (const uint32_t*)c->de_polys.p, c->de_end_jump ? 1 : 0, (int)pop,
+                          (const int32_t*)(base + o_tab), (const int64_t*)(base + o_off), (uint32_t*)(base + o_words), s,
+                          split ? (uint32_t*)(base + o_scr) : nullptr));
+  if (total > 0) HIPCHK(hipMemcpyAsync(words, base + o_words, 4 * (size_t)total, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  c->mde_key.assign(mt_key, mt_key + 624);
+  c->mde_pos = mt_pos;
+  c->mde_pop = pop;
+  c->mde_L = L;
+  c->mde_scr = split ? (int64_t)o_scr : 0;
+  c->mde_cmax = hi[(size_t)pop - 1];
+  return 0;
+}
+
+int tblup_mde_resolve(int64_t pop, int64_t L, const int32_t* q_best, int64_t nq, const int32_t* p_best, int64_t np,
+                      int32_t slack, const uint32_t* words, int64_t n_words, uint32_t* py_mt, int32_t* py_index,
+                      int32_t* parent, int32_t* donors, int64_t* fixed, int64_t* c_words, int32_t* overflow) {
+  clear_error();
+  if (int rc = validate_mde_shape(pop, 1, nq, np)) return rc;
+  if (L < 1 || L >= ((int64_t)1 << 32)) return fail(TBLUP_ERR_ARG, "need 1 <= L < 2^32");
+  if (!q_best || !p_best || !words || !py_mt || !py_index || !parent || !donors || !fixed || !c_words || !overflow)
+    return fail(TBLUP_ERR_ARG, "null argument");
+  if (*py_index < 0 || *py_index > 624) return fail(TBLUP_ERR_ARG, "py_index must be in [0, 624]");
+  for (int64_t k = 0; k < nq; ++k)
+    if (q_best[k] < 0 || q_best[k] >= pop) return fail(TBLUP_ERR_ARG, "best index out of range");
+  for (int64_t k = 0; k < np; ++k)
+    if (p_best[k] < 0 || p_best[k] >= pop) return fail(TBLUP_ERR_ARG, "parent index out of range");
+  if (n_words != tblup_mt::mde_windows(pop, nq, np, slack, nullptr, nullptr, nullptr))
+    return fail(TBLUP_ERR_ARG, "n_words is not the size tblup_mde_windows gives");
+  *overflow = tblup_mt::mde_resolve(pop, L, q_best, nq, p_best, np, slack, words, py_mt, py_index, parent, donors,
+                                    fixed, c_words)
+                  ? 0
+                  : 1;
+  return 0;
+}
+
+int tblup_mde_step_device_async(tblup_ctx* c, const double* F, const double* cr, const double* d_parents, int64_t pop,
+                                int64_t L, int64_t ld, const int32_t* parent, const int32_t* donors,
+                                const int64_t* fixed, const int64_t* c_words, int clip, double clip_hi,
+                                const uint32_t* mt_key, int32_t mt_pos, double* d_children, int64_t ldc, void* stream) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
+  if (!F || !cr || !parent || !c_words) return fail(TBLUP_ERR_ARG, "null F/cr/parent/c_words");
+  if (pop < 4) return fail(TBLUP_ERR_ARG, "need 4 <= pop <= 65535 and 1 <= L <= 2^31");
+  if (int rc = validate_de(TBLUP_DE_CURRENT_TO_BEST_1, pop, L, donors, fixed, 0.0, mt_key, &mt_pos)) return rc;
+  for (int64_t i = 0; i < pop; ++i) {
+    if (!(cr[i] == cr[i])) return fail(TBLUP_ERR_ARG, "crossover rate is NaN");
+    if (parent[i] < 0 || parent[i] >= pop) return fail(TBLUP_ERR_ARG, "parent index out of range");
+    if (c_words[i] < (i ? c_words[i - 1] : 0)) return fail(TBLUP_ERR_ARG, "c_words must be non-negative and non-decreasing");
+  }
+  if (ld < L || ldc < L) return fail(TBLUP_ERR_ARG, "ld/ldc < L");
+  if (!d_parents || !d_children) return fail(TBLUP_ERR_ARG, "null device pointers");
+  if (c->mde_key.empty() || c->mde_pop != pop || c->mde_L != L || c->mde_pos != mt_pos || c->de_pop != pop ||
+      c->de_L != L || std::memcmp(c->mde_key.data(), mt_key, 624 * 4) != 0)
+    return fail(TBLUP_ERR_STATE, "no tblup_mde_draws of this population, length and MT state to continue");
+  // every workgroup walks c_words / 624 blocks forward: no more than the draws' windows can give
+  if (c_words[pop - 1] > c->mde_cmax) return fail(TBLUP_ERR_ARG, "c_words exceeds the windows of tblup_mde_draws");
+  c->mde_key.clear();   // the draws are used up, whatever happens below
+  HIPCHK(hipSetDevice(c->device));
+  hipStream_t s = stream ? (hipStream_t)stream : c->stream;
+  // per-call arguments: key in, key out, pos out, donors, fixed, F, cr, the uniforms' window offsets, targets
+  const size_t o_keyo = 624 * 4, o_pos = 2 * 624 * 4, o_don = o_pos + 16, o_fix = o_don + (size_t)round_up(12 * pop, 16);
+  const size_t o_F = o_fix + 8 * (size_t)pop, o_cr = o_F + 8 * (size_t)pop, o_f = o_cr + 8 * (size_t)pop;
+  const size_t o_tgt = o_f + 8 * (size_t)pop, small = o_tgt + 4 * (size_t)pop;
+  if (small > c->de_small.bytes) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = dev_alloc(c, c->de_small, small)) return rc;
+  }
+  char* base = (char*)c->de_small.p;
+  if (int rc = de_stage_reserve(c, small, s)) return rc;
+  char* stage = c->de_stage;
+  std::memcpy(stage, mt_key, 624 * 4);
+  std::memcpy(stage + o_don, donors, 12 * pop);
+  std::memcpy(stage + o_fix, fixed, 8 * pop);
+  std::memcpy(stage + o_F, F, 8 * pop);
+  std::memcpy(stage + o_cr, cr, 8 * pop);
+  int64_t* f_i = (int64_t*)(stage + o_f);
+  for (int64_t i = 0; i < pop; ++i) f_i[i] = c_words[i] + (i ? 2 : 0);   // windows 1.. start two words early
+  std::memcpy(stage + o_tgt, parent, 4 * pop);
+  HIPCHK(hipMemcpyAsync(base, stage, small, hipMemcpyHostToDevice, s));
+  // numpy's state after 2 L pop + C_pop words, counted from where the end window starts
+  const uint64_t fixed_words = 2 * (uint64_t)L * (uint64_t)pop;
+  const tblup_mt::EndState e = tblup_mt::end_state(mt_pos, fixed_words + (uint64_t)c_words[pop - 1]);
+  const uint64_t o_win = c->de_end_jump ? (uint64_t)mt_pos + fixed_words - 625 : 0;
+  const int end_s = (int)((uint64_t)e.s + e.o_rel - o_win);
+  HIPCHK(launch_mde_step((const uint32_t*)base, mt_pos, (const uint32_t*)c->de_polys.p, c->de_end_jump ? 1 : 0, end_s,
+                         e.pos, d_parents, ld, (const int32_t*)(base + o_don), (const int64_t*)(base + o_fix),
+                         (const double*)(base + o_F), (const double*)(base + o_cr), (const int64_t*)(base + o_f),
+                         (const int32_t*)(base + o_tgt), clip ? 1 : 0, clip_hi, L, (int)pop, d_children, ldc,
+                         (uint32_t*)(base + o_keyo), (int32_t*)(base + o_pos), s,
+                         c->mde_scr ? (uint32_t*)((char*)c->mde_dev.p + c->mde_scr) : nullptr));
+  return de_state_fetch(c, base + o_keyo, s);
 }
 
 int tblup_gather_rows(tblup_ctx* c, double* d_dst, int64_t n, int64_t L, int64_t ldd, const double* const* d_src_rows,

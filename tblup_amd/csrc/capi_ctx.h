@@ -72,6 +72,13 @@ struct tblup_ctx {
   size_t de_stage_bytes = 0;
   hipEvent_t de_ev = nullptr;    // recorded behind that state's copy
   bool de_pending = false;       // tblup_de_step_device_async issued, tblup_de_state_wait not yet called
+  // MDE_pBX (tblup_mde_draws -> tblup_mde_step_device_async): the draws' device buffer (base key,
+  // window tables, draw words, the three-launch form's sequence and windows) and what it was made for
+  DevBuf mde_dev;
+  std::vector<uint32_t> mde_key;   // the base key of the last tblup_mde_draws (empty: none to continue)
+  int32_t mde_pos = -1;
+  int64_t mde_cmax = 0;   // hi[pop - 1] of those draws' windows: no resolved C_i can exceed it
+  int64_t mde_pop = -1, mde_L = -1, mde_scr = 0;   // mde_scr: byte offset of the scratch in mde_dev, 0 = one-launch form
   size_t budget = 0;
   // profiling
   bool profiling = false;

@@ -90,6 +90,12 @@ struct DeArgs {
   const int32_t* strat_i;
   const double* F_i;
   const double* cr_i;
+  // MDE_pBX (evolver.py:550-687; the kernels' general form): individual i's uniforms start at word
+  // f_i[i] of its window (any offset: its np.random.choice draws come first), its target and the
+  // child's base are row target_i[i]; keep_end: k_de_jump leaves the end window in gwin row pop
+  const int64_t* f_i;
+  const int32_t* target_i;
+  int keep_end;
 };
 
 // 1. the sequence that continues the base window, words [0, need) of sq
@@ -165,25 +171,69 @@ __device__ __forceinline__ void de_window(const DeArgs& a, uint32_t* seq, const 
 }
 
 // the end workgroup (i = pop): numpy's (key, pos) after the generation's draws
+// (end_s <= 624 after the fixed 2L pop draws: one more block; GEN: MDE_pBX's choice words push it
+// further, and k_mde_mask runs it on 320 threads)
+template <bool GEN>
 __device__ __forceinline__ void de_end_state(const DeArgs& a, uint32_t* ring, int tid) {
-  mt_block(ring, 1, tid);
-  if (tid < MTN) a.key_out[tid] = ring[a.end_s + tid];
+  if constexpr (!GEN) {
+    mt_block(ring, 1, tid);
+    if (tid < MTN) a.key_out[tid] = ring[a.end_s + tid];
+    if (tid == 0) *a.pos_out = a.end_pos;
+    return;
+  }
+  const int last = (a.end_s + MTN - 1) / MTN;
+  for (int b = 1; b <= last; ++b) mt_block(ring, b, tid);
+  for (int t = tid; t < MTN; t += (int)blockDim.x) {
+    const int w = a.end_s + t;
+    a.key_out[t] = ring[((w / MTN) & 1) * MTN + w % MTN];
+  }
   if (tid == 0) *a.pos_out = a.end_pos;
+}
+
+// MDE_pBX, before the step: the tempered words [lo, hi) past 2Li of individual i's stream -- what
+// its np.random.choice draws can read -- from the window in ring slot 0 into out[0, hi - lo)
+template <int NTHR>
+__device__ __forceinline__ void de_draw_words(uint32_t* ring, int i, int lo, int hi, uint32_t* __restrict__ out,
+                                              int tid) {
+  static_assert(NTHR >= 227, "mt_block's widest step");
+  const int f0 = i == 0 ? 0 : 2;
+  const int w0 = lo + f0, w1 = hi + f0;
+  for (int b = 0; b * MTN < w1; ++b) {
+    if (b > 0) mt_block(ring, b, tid);
+    const uint32_t* blk = ring + (b & 1) * MTN;
+    for (int t = tid; t < MTN; t += NTHR) {
+      const int w = b * MTN + t;
+      if (w >= w0 && w < w1) out[w - w0] = mt_temper(blk[t]);
+    }
+  }
 }
 
 // 3. crossover mask, then the elementwise mutant / crossover / clip stream, NTHR threads.  The mask
 // of a segment of up to MASKW x 32 elements is built in LDS from the MT19937 words [f, f + 2L) of
 // the window in ring slot 0, one double per word pair; the segment is then streamed with every
 // thread (coalesced loads, many in flight) instead of 312 lanes per block.
-template <int NTHR>
+// GEN (MDE_pBX): the uniforms start at window word f = 624 bs + r, any r: bs whole blocks are
+// skipped, and for odd r a double's word pair is (2q - 1, 2q) of a block, its first word the
+// previous block's last for q = 0 (still in the other ring slot); the target is row target_i[i].
+template <int NTHR, bool GEN>
 __device__ __forceinline__ void de_stream(const DeArgs& a, uint32_t* ring, uint32_t* mask, int maskw, int i, int tid) {
 #pragma clang fp contract(off)   // numpy's separate multiply and add (the pragma is scoped: here, not the caller)
   static_assert(NTHR >= MTN / 2, "one thread per word pair of a block");
   const int f = i == 0 ? 0 : 2;
+  int64_t bs = 0;   // GEN: first block with uniforms, pair shift, elements' shift in that block
+  int odd = 0, h = 0;
+  if constexpr (GEN) {
+    const int64_t fg = a.f_i[i];
+    const int r = (int)(fg % MTN);
+    bs = fg / MTN;
+    odd = r & 1;
+    h = (r + odd) / 2;
+    for (int64_t bb = 1; bb <= bs; ++bb) mt_block(ring, (int)(bb & 1), tid);
+  }
   const int64_t L = a.L;
   const int strategy = a.strat_i ? a.strat_i[i] : a.strategy;
   const double F = a.F_i ? a.F_i[i] : a.F, cr = a.cr_i ? a.cr_i[i] : a.cr;
-  const double* P = a.parent + (int64_t)i * a.ldp;
+  const double* P = a.parent + (int64_t)(GEN ? a.target_i[i] : i) * a.ldp;
   double* C = a.child + (int64_t)i * a.ldc;
   const int d0 = a.donors[3 * i], d1 = a.donors[3 * i + 1], d2 = a.donors[3 * i + 2];
   const double* X0 = a.parent + (int64_t)d0 * a.ldp;
@@ -191,7 +241,7 @@ __device__ __forceinline__ void de_stream(const DeArgs& a, uint32_t* ring, uint3
   const double* X2 = a.parent + (int64_t)d2 * a.ldp;
   const int64_t fixed = a.fixed[i];
   const int64_t SEG = (int64_t)maskw * 32;
-  int64_t b = 0;                             // next ring block to consume (block 0 = the window)
+  int64_t b = bs;                            // next ring block to consume (block 0 = the window)
   for (int64_t lo = 0; lo < L; lo += SEG) {
     const int64_t hi = lo + SEG < L ? lo + SEG : L;
     __syncthreads();   // previous segment's stream has finished reading the mask
@@ -200,15 +250,17 @@ __device__ __forceinline__ void de_stream(const DeArgs& a, uint32_t* ring, uint3
     // element j = 312 b + q - f/2 comes from block b, pair q.  (A one-wave recurrence without
     // s_barrier -- a wave's LDS operations execute in order -- measured slower: 0.42 vs
     // 0.29 ms per step, its passes serialise on the LDS latency.)
-    for (; !(a.dbg & 2) && (MTN / 2) * b - f / 2 < hi; ++b) {
-      if (b > 0) mt_block(ring, (int)(b & 1), tid);
+    for (; !(a.dbg & 2) && (MTN / 2) * (b - bs) - (GEN ? h : f / 2) < hi; ++b) {
+      if (b > bs) mt_block(ring, (int)(b & 1), tid);
       const uint32_t* blk = ring + (b & 1) * MTN;
       const int q = tid;
-      const int64_t j = (MTN / 2) * b + q - f / 2;
-      const bool valid = q < MTN / 2 && !(b == 0 && q < f / 2) && j >= lo && j < hi;
+      const int64_t j = (MTN / 2) * (b - bs) + q - (GEN ? h : f / 2);
+      const bool valid = q < MTN / 2 && !(!GEN && b == 0 && q < f / 2) && j >= lo && j < hi;
       bool set = false;
       if (valid) {
-        const uint32_t w0 = mt_temper(blk[2 * q]) >> 5, w1 = mt_temper(blk[2 * q + 1]) >> 6;
+        const int i0 = 2 * q - odd;
+        const uint32_t r0 = GEN && i0 < 0 ? ring[((b + 1) & 1) * MTN + MTN - 1] : blk[i0];
+        const uint32_t w0 = mt_temper(r0) >> 5, w1 = mt_temper(blk[i0 + 1]) >> 6;
         const double u = ((double)w0 * 67108864.0 + (double)w1) / 9007199254740992.0;
         set = u < cr || j == fixed;
       }
@@ -220,7 +272,7 @@ __device__ __forceinline__ void de_stream(const DeArgs& a, uint32_t* ring, uint3
         const uint32_t wb = (uint32_t)(lane >= bit ? bal >> (lane - bit) : bal << (bit - lane));
         if (wb) atomicOr(&mask[(j - lo) >> 5], wb);
       }
-      if ((MTN / 2) * (b + 1) - f / 2 > hi) break;   // this block also feeds the next segment
+      if ((MTN / 2) * (b - bs + 1) - (GEN ? h : f / 2) > hi) break;   // this block also feeds the next segment
     }
     __syncthreads();
     constexpr int U = 4;
@@ -262,11 +314,8 @@ __device__ __forceinline__ void de_stream(const DeArgs& a, uint32_t* ring, uint3
 
 // One launch per generation (small populations): every workgroup rebuilds the sequence, jumps, and
 // streams its child with the sequence buffer as the mask.
-__global__ __launch_bounds__(DE_THREADS) void k_de_step(DeArgs a) {
-  // sequence buffer, 16-B aligned at word pos0 (sq = seq + sh) so the correlation reads b128s;
-  // the slack covers the correlation's trailing loads (bits past degree 19936 are zero)
-  __shared__ __attribute__((aligned(16))) uint32_t seq[SEQ_ALLOC];
-  __shared__ uint32_t ring[2 * MTN];
+template <bool GEN>
+__device__ __forceinline__ void de_step_body(const DeArgs a, uint32_t* seq, uint32_t* ring) {
   const int tid = threadIdx.x;
   const int i = blockIdx.x;
   const bool is_end = i == a.pop;
@@ -275,10 +324,44 @@ __global__ __launch_bounds__(DE_THREADS) void k_de_step(DeArgs a) {
   de_sequence(a.key, sq, jump ? a.pos0 + tblup_mt::MT_DEG + MTN - 1 : (i == 0 ? a.pos0 + MTN : MTN), tid);
   de_window(a, seq, sq, ring, i, is_end, jump, tid);
   if (is_end) {
-    de_end_state(a, ring, tid);
+    de_end_state<GEN>(a, ring, tid);
     return;
   }
-  de_stream<DE_THREADS>(a, ring, seq, SEQ_WORDS, i, tid);
+  de_stream<DE_THREADS, GEN>(a, ring, seq, SEQ_WORDS, i, tid);
+}
+
+__global__ __launch_bounds__(DE_THREADS) void k_de_step(DeArgs a) {
+  // sequence buffer, 16-B aligned at word pos0 (sq = seq + sh) so the correlation reads b128s;
+  // the slack covers the correlation's trailing loads (bits past degree 19936 are zero)
+  __shared__ __attribute__((aligned(16))) uint32_t seq[SEQ_ALLOC];
+  __shared__ uint32_t ring[2 * MTN];
+  de_step_body<false>(a, seq, ring);
+}
+
+// MDE_pBX, one launch: every workgroup's uniforms at its own offset f_i, target row target_i.  (The
+// jump correlation, the VALU-bound part, then runs twice per generation in this form: once in
+// k_mde_draws_fused and once here -- a window is 2.5 KB per workgroup and the whole one-launch
+// generation measures 5.9 ms at pop 256; the three-launch form keeps the windows in gwin instead.)
+__global__ __launch_bounds__(DE_THREADS) void k_mde_step(DeArgs a) {
+  __shared__ __attribute__((aligned(16))) uint32_t seq[SEQ_ALLOC];
+  __shared__ uint32_t ring[2 * MTN];
+  de_step_body<true>(a, seq, ring);
+}
+
+// MDE_pBX, before the step (small populations): workgroup i's window as k_de_step builds it, then
+// its draw words (tab[i] = lo_i, hi_i; woff[i] = their place in `words`)
+__global__ __launch_bounds__(DE_THREADS) void k_mde_draws_fused(DeArgs a, const int32_t* __restrict__ tab,
+                                                                const int64_t* __restrict__ woff,
+                                                                uint32_t* __restrict__ words) {
+  __shared__ __attribute__((aligned(16))) uint32_t seq[SEQ_ALLOC];
+  __shared__ uint32_t ring[2 * MTN];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x;
+  const bool jump = i > 0;
+  uint32_t* sq = seq + ((4 - (a.pos0 & 3)) & 3);
+  de_sequence(a.key, sq, jump ? a.pos0 + tblup_mt::MT_DEG + MTN - 1 : a.pos0 + MTN, tid);
+  de_window(a, seq, sq, ring, i, false, jump, tid);
+  de_draw_words<DE_THREADS>(ring, i, tab[2 * i], tab[2 * i + 1], words + woff[i], tid);
 }
 
 // Large populations, three launches: the base sequence once (one workgroup, into gseq), then every
@@ -308,8 +391,8 @@ __global__ __launch_bounds__(DE_THREADS) void k_de_jump(DeArgs a, const uint32_t
   for (int t = tid; t < need; t += DE_THREADS) sq[t] = gseq[t];
   __syncthreads();
   de_window(a, seq, sq, ring, i, is_end, jump, tid);
-  if (is_end) {
-    de_end_state(a, ring, tid);
+  if (is_end && !a.keep_end) {
+    de_end_state<false>(a, ring, tid);
     return;
   }
   if (tid < MTN) gwin[(int64_t)i * MTN + tid] = ring[tid];
@@ -324,7 +407,36 @@ __global__ __launch_bounds__(DE_MASK_THREADS) void k_de_mask(DeArgs a, const uin
   const int i = blockIdx.x;
   for (int t = tid; t < MTN; t += DE_MASK_THREADS) ring[t] = gwin[(int64_t)i * MTN + t];
   __syncthreads();
-  de_stream<DE_MASK_THREADS>(a, ring, mask, DE_MASK_WORDS, i, tid);
+  de_stream<DE_MASK_THREADS, false>(a, ring, mask, DE_MASK_WORDS, i, tid);
+}
+
+// MDE_pBX, three-launch form: the draw words from the windows k_de_jump left in gwin; after the
+// host has resolved the draws, the mask and stream at each individual's offset and the end state
+// from the end window (gwin row pop)
+__global__ __launch_bounds__(DE_MASK_THREADS) void k_mde_draws(const uint32_t* __restrict__ gwin,
+                                                               const int32_t* __restrict__ tab,
+                                                               const int64_t* __restrict__ woff,
+                                                               uint32_t* __restrict__ words) {
+  __shared__ uint32_t ring[2 * MTN];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x;
+  for (int t = tid; t < MTN; t += DE_MASK_THREADS) ring[t] = gwin[(int64_t)i * MTN + t];
+  __syncthreads();
+  de_draw_words<DE_MASK_THREADS>(ring, i, tab[2 * i], tab[2 * i + 1], words + woff[i], tid);
+}
+
+__global__ __launch_bounds__(DE_MASK_THREADS) void k_mde_mask(DeArgs a, const uint32_t* __restrict__ gwin) {
+  __shared__ uint32_t ring[2 * MTN];
+  __shared__ uint32_t mask[DE_MASK_WORDS];
+  const int tid = threadIdx.x;
+  const int i = blockIdx.x;
+  for (int t = tid; t < MTN; t += DE_MASK_THREADS) ring[t] = gwin[(int64_t)i * MTN + t];
+  __syncthreads();
+  if (i == a.pop) {
+    de_end_state<true>(a, ring, tid);
+    return;
+  }
+  de_stream<DE_MASK_THREADS, true>(a, ring, mask, DE_MASK_WORDS, i, tid);
 }
 
 }  // namespace
@@ -340,7 +452,7 @@ hipError_t launch_de_step(const uint32_t* key, int pos0, const uint32_t* polys, 
   constexpr int dbg = 0;
 #endif
   DeArgs a{key, pos0, polys, end_jump, end_s, end_pos, parent, ldp, donors, fixed, strategy, F, cr, clip, hi, L, pop,
-           child, ldc, key_out, pos_out, dbg, strat_i, F_i, cr_i};
+           child, ldc, key_out, pos_out, dbg, strat_i, F_i, cr_i, nullptr, nullptr, 0};
   if (scratch == nullptr) {
     hipLaunchKernelGGL(k_de_step, dim3(pop + 1), dim3(DE_THREADS), 0, s, a);
     return hipGetLastError();
@@ -352,6 +464,46 @@ hipError_t launch_de_step(const uint32_t* key, int pos0, const uint32_t* polys, 
   hipLaunchKernelGGL(k_de_jump, dim3(pop + 1), dim3(DE_THREADS), 0, s, a, gseq, gwin);
   if (hipError_t e = hipGetLastError()) return e;
   hipLaunchKernelGGL(k_de_mask, dim3(pop), dim3(DE_MASK_THREADS), 0, s, a, gwin);
+  return hipGetLastError();
+}
+
+hipError_t launch_mde_draws(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int pop,
+                            const int32_t* tab, const int64_t* woff, uint32_t* words, hipStream_t s,
+                            uint32_t* scratch) {
+  DeArgs a{};
+  a.key = key;
+  a.pos0 = pos0;
+  a.polys = polys;
+  a.end_jump = end_jump;
+  a.pop = pop;
+  a.keep_end = 1;
+  if (scratch == nullptr) {
+    hipLaunchKernelGGL(k_mde_draws_fused, dim3(pop), dim3(DE_THREADS), 0, s, a, tab, woff, words);
+    return hipGetLastError();
+  }
+  uint32_t* gseq = scratch;
+  uint32_t* gwin = scratch + DE_SEQ_SCRATCH;
+  hipLaunchKernelGGL(k_de_seq, dim3(1), dim3(DE_THREADS), 0, s, a, gseq);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_de_jump, dim3(pop + 1), dim3(DE_THREADS), 0, s, a, gseq, gwin);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_mde_draws, dim3(pop), dim3(DE_MASK_THREADS), 0, s, gwin, tab, woff, words);
+  return hipGetLastError();
+}
+
+hipError_t launch_mde_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
+                           const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed,
+                           const double* F_i, const double* cr_i, const int64_t* f_i, const int32_t* target_i, int clip,
+                           double hi, int64_t L, int pop, double* child, int64_t ldc, uint32_t* key_out,
+                           int32_t* pos_out, hipStream_t s, uint32_t* scratch) {
+  DeArgs a{key, pos0, polys, end_jump, end_s, end_pos, parent, ldp, donors, fixed, 1, 0.0, 0.0, clip, hi, L, pop,
+           child, ldc, key_out, pos_out, 0, nullptr, F_i, cr_i, f_i, target_i, 1};
+  if (scratch == nullptr) {
+    hipLaunchKernelGGL(k_mde_step, dim3(pop + 1), dim3(DE_THREADS), 0, s, a);
+    return hipGetLastError();
+  }
+  // the windows (and the end window, row pop) are the ones launch_mde_draws left in the scratch
+  hipLaunchKernelGGL(k_mde_mask, dim3(pop + 1), dim3(DE_MASK_THREADS), 0, s, a, scratch + DE_SEQ_SCRATCH);
   return hipGetLastError();
 }
 

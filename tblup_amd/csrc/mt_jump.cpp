@@ -20,6 +20,7 @@
 
 #include <immintrin.h>
 
+#include <cmath>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -400,6 +401,98 @@ void py_random_donors(uint32_t* mt, int32_t* index, int64_t pop, int64_t L, int3
     fixed[i] = g.below((uint64_t)L);
   }
   *index = g.idx;
+}
+
+// ---- MDE_pBX (evolver.py:550-687): per individual two np.random.choice(arr, 1) draws (group
+// best, parent) come before its np.random.rand(L), so individual i's uniforms start C_i words past
+// 2Li, C_i = the words the choices of individuals 0..i consumed.  Legacy np.random.choice(arr, 1) is
+// randint(0, n, 1): nothing for n == 1, else next_uint32 & mask (mask = 2^bit_length(n-1) - 1)
+// until the value is <= n - 1, one word per attempt.
+namespace {
+
+struct ChoiceStat {
+  int min;        // words a draw takes at least (0 for a single-entry array)
+  double mean;    // (mask + 1) / n
+  double var;     // of the geometric attempt count
+  uint32_t mask;
+};
+
+ChoiceStat choice_stat(int64_t n) {
+  ChoiceStat s{0, 0.0, 0.0, 0u};
+  if (n <= 1) return s;
+  uint32_t m = (uint32_t)(n - 1);
+  m |= m >> 1, m |= m >> 2, m |= m >> 4, m |= m >> 8, m |= m >> 16;
+  const double p = (double)n / ((double)m + 1.0);
+  s.min = 1;
+  s.mean = 1.0 / p;
+  s.var = (1.0 - p) / (p * p);
+  s.mask = m;
+  return s;
+}
+
+}  // namespace
+
+int64_t mde_windows(int64_t pop, int64_t nq, int64_t np, int32_t slack, int32_t* lo, int32_t* hi, int64_t* off) {
+  const ChoiceStat q = choice_stat(nq), p = choice_stat(np);
+  const int mind = q.min + p.min;
+  const double mean = q.mean + p.mean, var = q.var + p.var;
+  int64_t total = 0;
+  for (int64_t i = 0; i < pop; ++i) {
+    const double k = (double)(i + 1);
+    const int64_t l = i * mind;
+    int64_t h = slack >= 0 ? (int64_t)std::ceil(mean * k) + slack
+                           : (int64_t)std::ceil(mean * k + 6.0 * std::sqrt(var * k)) + 16;
+    if (h < l) h = l;
+    if (lo) lo[i] = (int32_t)l;
+    if (hi) hi[i] = (int32_t)h;
+    if (off) off[i] = total;
+    total += h - l;
+  }
+  if (off) off[pop] = total;
+  return total;
+}
+
+bool mde_resolve(int64_t pop, int64_t L, const int32_t* q_best, int64_t nq, const int32_t* p_best, int64_t np,
+                 int32_t slack, const uint32_t* words, uint32_t* mt, int32_t* index, int32_t* parent, int32_t* donors,
+                 int64_t* fixed, int64_t* c_words) {
+  const ChoiceStat sq = choice_stat(nq), sp = choice_stat(np);
+  std::vector<int32_t> lo((size_t)pop), hi((size_t)pop);
+  std::vector<int64_t> off((size_t)pop + 1);
+  mde_windows(pop, nq, np, slack, lo.data(), hi.data(), off.data());
+  uint32_t st[MT_N];   // python's state is written back only when every draw stayed in its window
+  std::memcpy(st, mt, sizeof(st));
+  PyMT g{st, *index};
+  int64_t C = 0;
+  for (int64_t i = 0; i < pop; ++i) {
+    const uint32_t* w = words + off[i] - lo[i];   // w[r]: the word at offset r from 2Li
+    int64_t pick[2] = {0, 0};
+    for (int d = 0; d < 2; ++d) {
+      const ChoiceStat& s = d == 0 ? sq : sp;
+      const int64_t n = d == 0 ? nq : np;
+      if (n <= 1) continue;
+      for (;;) {
+        if (C >= hi[i]) return false;
+        const uint32_t v = w[C++] & s.mask;
+        if ((int64_t)v <= n - 1) {
+          pick[d] = v;
+          break;
+        }
+      }
+    }
+    const int32_t best = q_best[pick[0]], par = p_best[pick[1]];
+    int64_t ex[3] = {par, best, 0};
+    ex[2] = g.excluding(pop, ex, 2);
+    const int64_t b = g.excluding(pop, ex, 3);
+    parent[i] = par;
+    donors[3 * i] = best;
+    donors[3 * i + 1] = (int32_t)ex[2];
+    donors[3 * i + 2] = (int32_t)b;
+    fixed[i] = g.below((uint64_t)L);
+    c_words[i] = C;
+  }
+  std::memcpy(mt, st, sizeof(st));
+  *index = g.idx;
+  return true;
 }
 
 }  // namespace tblup_mt

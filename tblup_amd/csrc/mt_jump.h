@@ -40,4 +40,21 @@ void jump_state(const uint32_t* key, int pos, uint64_t n_words, uint32_t* key_ou
 void py_random_donors(uint32_t* mt, int32_t* index, int64_t pop, int64_t L, int32_t best, int32_t* donors,
                       int64_t* fixed);
 
+// MDE_pBX (evolver.py:550-687): individual i's np.random.rand(L) starts C_i words past 2Li, C_i =
+// the words the np.random.choice draws of individuals 0..i took (group best out of nq entries, then
+// parent out of np).  mde_windows: the offsets from 2Li a choice of individual i can read,
+// [lo_i, hi_i): lo_i the certain minimum of C_{i-1}, hi_i the expected C_i plus slack (slack < 0:
+// six standard deviations + 16; slack >= 0: that many words and no deviation term -- tests), and
+// off_i (off[pop] = the return value) = where that run starts in the compact word buffer.
+int64_t mde_windows(int64_t pop, int64_t nq, int64_t np, int32_t slack, int32_t* lo, int32_t* hi, int64_t* off);
+
+// One MDE_pBX generation's draws from the tempered words of those windows: per individual the two
+// choices (q_best[.] = the group best's population index, p_best[.] = the parent's), C_i, then
+// python-`random` (mt[624], index) as evolver.py:199-203 and :76 draw it: exclusive_randrange twice
+// (exclusions [parent, best], then a), randrange(0, L); donors[i] = (best, a, b).  false when a
+// rejection run left its window: nothing is written to (mt, index) then.  Needs pop >= 4.
+bool mde_resolve(int64_t pop, int64_t L, const int32_t* q_best, int64_t nq, const int32_t* p_best, int64_t np,
+                 int32_t slack, const uint32_t* words, uint32_t* mt, int32_t* index, int32_t* parent, int32_t* donors,
+                 int64_t* fixed, int64_t* c_words);
+
 }  // namespace tblup_mt

@@ -366,6 +366,21 @@ hipError_t launch_de_step(const uint32_t* key, int pos0, const uint32_t* polys, 
 // the workgroups' windows -- the three-launch form for large populations (k_de.hip)
 constexpr int64_t DE_SEQ_SCRATCH = 624 + 19937 + 624 + 64;
 
+// MDE_pBX generation in two halves (k_de.hip).  launch_mde_draws: every individual's window, then
+// the tempered words [tab[2i], tab[2i+1]) past 2Li of its stream into words + woff[i] (what its
+// np.random.choice draws can read).  launch_mde_step, once the host has resolved the draws: the
+// step with per-individual F / cr, uniforms from window word f_i[i], target row target_i[i], and
+// the end state end_s words into the end window.  scratch (null: one launch each): as above with
+// (pop + 1) x 624 window words -- the step reads the windows the draws' launch left there.
+hipError_t launch_mde_draws(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int pop,
+                            const int32_t* tab, const int64_t* woff, uint32_t* words, hipStream_t s,
+                            uint32_t* scratch);
+hipError_t launch_mde_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
+                           const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed,
+                           const double* F_i, const double* cr_i, const int64_t* f_i, const int32_t* target_i, int clip,
+                           double hi, int64_t L, int pop, double* child, int64_t ldc, uint32_t* key_out,
+                           int32_t* pos_out, hipStream_t s, uint32_t* scratch);
+
 // ---- launcher (k_de.hip): rows from scattered device rows into one matrix (up to ROWPTRS rows
 //      per launch, source pointers in the kernel arguments) ----
 constexpr int ROWPTRS = 128;

@@ -22,9 +22,11 @@ strategy (python's random.random() < p) and crossover rate are drawn on the host
 reference's order and the step takes them per individual (tblup_de_step_device_async_mix; numpy's
 stream still holds one np.random.rand(L) per individual).  MDE_pBX (evolver.py:550-687) draws
 np.random.choice (rejection-sampled randint) between the individuals' np.random.rand(L) calls, so
-each individual's numpy stream offset depends on the draws before it; it runs its DE step on the
-host, as the reference does, with the reference's RNG consumption.
-There is no CPU fallback for the GPU steps: without the HIP library, `evolve` raises ImportError.
+each individual's numpy stream offset depends on the draws before it: the device expands the few
+stream words those draws can read, native host code resolves them in order, and the GPU step
+starts every individual's uniforms at its own offset (GpuDEStep.mde_draws; the reference's host
+loop is kept for machines without a device and as the tests' reference, see MDE_pBX).
+There is no CPU fallback for the other GPU steps: without the HIP library, `evolve` raises ImportError.
 """
 import abc
 import csv
@@ -133,12 +135,56 @@ class GpuDEStep:
         np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
         return children
 
-    def step_device(self, strategy, parents, donors, fixed, F, cr, clip, clip_hi, defer=False):
+    def mde_draws(self, pop, L, q_idx, p_idx, slack=-1):
+        """The draws of one MDE_pBX generation for numpy's and python's current global states: the
+        device expands every individual's window of numpy's stream (tblup_mde_draws), the host
+        resolves the np.random.choice draws from it and makes python's (tblup_mde_resolve).  q_idx /
+        p_idx: the population indices to choose the group best / the parent from.  Returns (parent,
+        donors, fixed, c_words) with python's `random` state advanced, numpy's untouched (the step
+        advances it).  With neither state touched: None when a rejection run left its window, False
+        when the windows exceed 2^26 words (tens of thousands of individuals with choice sizes just
+        above a power of two), before anything runs on the device."""
+        import torch
+        q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
+        p_idx = np.ascontiguousarray(p_idx, dtype=np.int32)
+        I32, I64, U32 = (ctypes.POINTER(t) for t in (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32))
+        n_words = ctypes.c_int64()
+        _native.check("tblup_mde_windows", self._lib.tblup_mde_windows(pop, len(q_idx), len(p_idx), slack, None, None,
+                                                                       None, ctypes.byref(n_words)))
+        if n_words.value > 1 << 26:
+            return False
+        words = np.empty(max(n_words.value, 1), dtype=np.uint32)
+        st, key, pos = self._rng_state()
+        ws = work_stream(self.device)
+        ws.wait_stream(torch.cuda.current_stream(ws.device))
+        _native.check("tblup_mde_draws", self._lib.tblup_mde_draws(
+            self._ctx, pop, L, len(q_idx), len(p_idx), slack, key.ctypes.data_as(U32), pos.value,
+            words.ctypes.data_as(U32), n_words.value, ctypes.c_void_p(ws.cuda_stream)))
+        version, internal, gauss = random.getstate()
+        mt = np.array(internal[:624], dtype=np.uint32)
+        idx = np.array([internal[624]], dtype=np.int32)
+        parent = np.empty(pop, dtype=np.int32)
+        donors = np.empty((pop, 3), dtype=np.int32)
+        fixed = np.empty(pop, dtype=np.int64)
+        c_words = np.empty(pop, dtype=np.int64)
+        overflow = ctypes.c_int32()
+        _native.check("tblup_mde_resolve", self._lib.tblup_mde_resolve(
+            pop, L, q_idx.ctypes.data_as(I32), len(q_idx), p_idx.ctypes.data_as(I32), len(p_idx), slack,
+            words.ctypes.data_as(U32), n_words.value, mt.ctypes.data_as(U32), idx.ctypes.data_as(I32),
+            parent.ctypes.data_as(I32), donors.ctypes.data_as(I32), fixed.ctypes.data_as(I64),
+            c_words.ctypes.data_as(I64), ctypes.byref(overflow)))
+        if overflow.value:
+            return None
+        random.setstate((version, tuple(mt.tolist()) + (int(idx[0]),), gauss))
+        return parent, donors, fixed, c_words
+
+    def step_device(self, strategy, parents, donors, fixed, F, cr, clip, clip_hi, defer=False, mde=None):
         """Same on a device tensor of parents (pop x L float64, on this device); returns the
         children as a device tensor.  Runs on torch's current stream.  defer: return
         (children, finish) without waiting for the step; finish() waits for the new MT state
         only (tblup_de_state_wait) and hands it to numpy -- call it before numpy's global RNG is
-        used again.  strategy / F / cr: scalars, or one per individual (SaDE)."""
+        used again.  strategy / F / cr: scalars, or one per individual (SaDE).  mde: (parent,
+        c_words) of mde_draws -- the MDE_pBX step that continues those draws (F / cr per individual)."""
         import torch
         pop, L = parents.shape
         donors = np.ascontiguousarray(donors, dtype=np.int32)
@@ -150,7 +196,21 @@ class GpuDEStep:
             children = torch.empty_like(parents)
         st, key, pos = self._rng_state()
         stream = ws.cuda_stream
-        if np.ndim(strategy) or np.ndim(F) or np.ndim(cr):
+        if mde is not None:
+            parent_i = np.ascontiguousarray(mde[0], dtype=np.int32)
+            c_words = np.ascontiguousarray(mde[1], dtype=np.int64)
+            F_i = np.ascontiguousarray(np.broadcast_to(F, (pop,)), dtype=np.float64)
+            cr_i = np.ascontiguousarray(np.broadcast_to(cr, (pop,)), dtype=np.float64)
+            _native.check("tblup_mde_step_device_async", self._lib.tblup_mde_step_device_async(
+                self._ctx, F_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                cr_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(parents.data_ptr()), pop, L,
+                parents.stride(0), parent_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                c_words.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 1 if clip else 0, float(clip_hi),
+                key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pos.value,
+                ctypes.c_void_p(children.data_ptr()), children.stride(0), ctypes.c_void_p(stream)))
+        elif np.ndim(strategy) or np.ndim(F) or np.ndim(cr):
             strat_i = np.ascontiguousarray(np.broadcast_to(strategy, (pop,)), dtype=np.int32)
             F_i = np.ascontiguousarray(np.broadcast_to(F, (pop,)), dtype=np.float64)
             cr_i = np.ascontiguousarray(np.broadcast_to(cr, (pop,)), dtype=np.float64)
@@ -200,9 +260,10 @@ class GpuDEStep:
 _F64 = np.dtype(np.float64)
 
 
-def _child_dtypes(genomes, donors, strategy, mi, clip):
+def _child_dtypes(genomes, donors, strategy, mi, clip, parent_of=None):
     """Per-child dtype numpy gives the reference: np.where(mask, mutant, target) (+ np.clip);
-    None when every child is float64 (the usual RandomKey case)."""
+    None when every child is float64 (the usual RandomKey case).  parent_of: child i's target is
+    genome parent_of[i] (MDE_pBX), else genome i."""
     dts = [g.dtype if isinstance(g, np.ndarray) else np.asarray(g).dtype for g in genomes]
     f64 = _F64
     if all(dt is f64 or dt == f64 for dt in dts):
@@ -210,7 +271,7 @@ def _child_dtypes(genomes, donors, strategy, mi, clip):
     out = []
     e = np.zeros(0, dtype=bool)
     for i, (x, y, z) in enumerate(donors):
-        t, a, b, c = (np.zeros(0, dtype=dts[j]) for j in (i, x, y, z))
+        t, a, b, c = (np.zeros(0, dtype=dts[j]) for j in (i if parent_of is None else parent_of[i], x, y, z))
         st = strategy[i] if np.ndim(strategy) else strategy
         m = mi[i] if np.ndim(mi) else mi
         mutant = a + m * (b - c) if st == 0 else t + m * (a - t) + m * (b - c)
@@ -497,10 +558,11 @@ class _GpuDEEvolver(Evolver):
         return self._gpu_generation(population, t, donors, fixed, self.strategy, mi, self.crossover_rate,
                                     self._clip(), members)
 
-    def _gpu_generation(self, population, t, donors, fixed, strategy, mi, cr, clip, members=None):
+    def _gpu_generation(self, population, t, donors, fixed, strategy, mi, cr, clip, members=None, mde=None):
         """The children of one generation (donors / fixed: the python-`random` draws already made;
         strategy, mi, cr: scalars or one per individual; members: _members(population) when the
-        caller has it) through the GPU DE step."""
+        caller has it) through the GPU DE step.  mde: (parent, c_words) of GpuDEStep.mde_draws --
+        child i is made from, and is a copy of, population[parent[i]] (MDE_pBX)."""
         import torch
         inds, genomes, L = members if members is not None else _members(population)
         n = len(inds)
@@ -512,16 +574,18 @@ class _GpuDEEvolver(Evolver):
                                    copy_rows=step.gather_rows)   # device-resident parents
             t = _mark(t, "ev_gather")
             children, rng_done = step.step_device(strategy, parents, donors, fixed, mi, cr, clip,
-                                                  self.dimensionality - 1, defer=True)
+                                                  self.dimensionality - 1, defer=True, mde=mde)
+            src = range(n) if mde is None else [int(j) for j in mde[0]]   # child i's base individual
             t = _mark(t, "ev_prepare_step")
             try:
                 # the children's numpy dtypes (None: all float64), while the step runs
-                dtypes = _child_dtypes(genomes, donors, strategy, mi, clip)
+                dtypes = _child_dtypes(genomes, donors, strategy, mi, clip, None if mde is None else src)
                 # the population's evaluator (tblup_amd) may start evaluating the children on the GPU
                 # now, while their genomes cross to the host (BlupParallelEvaluator._speculate)
                 evaluator = getattr(population, "evaluator", None)
                 spec = getattr(evaluator, "_speculate", None)
-                speculated = bool(spec is not None and dtypes is None and spec(inds, children, population.generation))
+                bases = inds if mde is None else [inds[j] for j in src]
+                speculated = bool(spec is not None and dtypes is None and spec(bases, children, population.generation))
                 t = _mark(t, "ev_speculate")
                 # float64 children: one DMA into a page-locked block whose rows become the children's
                 # genomes (views: no host copy); otherwise chunks, each followed by an event, so the
@@ -556,7 +620,7 @@ class _GpuDEEvolver(Evolver):
                 rng_done()   # numpy's global state after the step's np.random.rand draws
         t = _mark(t, "ev_transfer_issue")
         # the candidates (new uids, the parent's other attributes) while the transfer runs
-        next_pop = [_copy_individual(population[i]) for i in range(n)]
+        next_pop = [_copy_individual(population[j]) for j in src]
         t = _mark(t, "ev_candidates")
         if (shared is not None or block_rows) and all(_assigns_genome(c) for c in next_pop):
             # whole-block rows: every child is bound to its row (a view: nothing reads the values),
@@ -842,19 +906,36 @@ class SaDE(AdaptiveEvolver, _GpuDEEvolver):
         return self._gpu_generation(population, t, donors, fixed, strategies, f, crs, self.clip, members)
 
 
-class MDE_pBX(AdaptiveEvolver):
-    """MDE_pBX (Islam et al. 2012; evolver.py:550-687), the DE step on the host.
+class MDE_pBX(AdaptiveEvolver, _GpuDEEvolver):
+    """MDE_pBX (Islam et al. 2012; evolver.py:550-687), its generation on the host or on the GPU.
 
     Each individual draws its group best and its parent with np.random.choice -- rejection-sampled
     integers, a data-dependent number of MT19937 words -- between the individuals' np.random.rand(L)
-    calls, so an individual's numpy stream offset depends on every draw before it and cannot be
-    jumped to in parallel as the GPU step does.  The generation therefore runs as the reference's
-    loop: the same draws in the same order, DE/current-to-best/1 with the chosen best and parent,
-    binary crossover, optional clip."""
+    calls, so individual i's uniforms start 2Li + C_i words into the generation's numpy stream, C_i
+    the words the choices of individuals 0..i took.  The host loop (_host_current_to_best) is the
+    reference's: the same draws in the same order, DE/current-to-best/1 with the chosen best and
+    parent, binary crossover, optional clip.  The device generation (GpuDEStep.mde_draws, then
+    _gpu_generation) jumps to every individual's fixed offset 2Li on the GPU, expands the few words
+    past it that the choices can read, resolves the choices, C_i and python's draws sequentially in
+    native host code, and runs the step with each individual's uniforms at its own offset; the
+    children then live in the DeviceKeyStore like the other strategies'.  Same bits either way
+    (tests/test_gpu_mde.py).
+
+    Which one runs: `device_step` (True / False; None: the environment's TBLUP_MDE_PBX = "device" /
+    "host", else DEVICE_DEFAULT).  The host loop always runs when no HIP device is visible, for
+    pop < 4 (the reference's assertion is raised there), and for a generation whose rejection run
+    leaves its window (MDE_pBX.fallbacks counts those; TBLUP_MDE_SLACK >= 0 sets the window slack in
+    words, for tests), and for a population whose draw windows would exceed 2^26 words
+    (MDE_pBX.oversize counts those generations: every one of such a run).  The device generation is the default: 5.9 against 98 ms per generation at
+    pop 256, 22 against 401 ms at pop 1024 (L = 50 000, tools/de_bench.py mde_pbx; PERFLOG.md)."""
 
     f_scale = 0.1
     cr_std = 0.1
     group_q = 0.15
+    DEVICE_DEFAULT = True
+    device_step = None
+    fallbacks = 0   # generations that fell back to the host loop on a window overflow
+    oversize = 0    # generations kept on the host loop because their draw windows are too large
 
     def __init__(self, dimensionality, generations, clip=True):
         AdaptiveEvolver.__init__(self)
@@ -917,7 +998,49 @@ class MDE_pBX(AdaptiveEvolver):
     def recalculate_p(self, population):
         self.p = ceil((len(population) / 2) * (1 - (population.generation / self.g_max)))
 
+    _HAS_DEVICE = None
+
+    def _on_device(self, n):
+        mode = self.device_step
+        if mode is None:
+            env = os.environ.get("TBLUP_MDE_PBX", "")
+            mode = True if env == "device" else False if env == "host" else self.DEVICE_DEFAULT
+        if not mode or n < 4 or n > 65535:
+            return False
+        if MDE_pBX._HAS_DEVICE is None:
+            try:
+                MDE_pBX._HAS_DEVICE = _native.device_count() >= 1
+            except (ImportError, _native.TblupError):
+                MDE_pBX._HAS_DEVICE = False
+        return MDE_pBX._HAS_DEVICE
+
+    def _device_generation(self, population, t, q_best, p_best):
+        """The generation through the GPU step; None (no RNG state touched) to run the host loop."""
+        members = _members(population)
+        n, L = len(members[0]), members[2]
+        if L < 1 or L > 1 << 31:
+            return None
+        first = {}
+        for j, x in enumerate(population.population):   # population.index(best), evolver.py:194
+            first.setdefault(id(x), j)
+        q_idx = [first[id(population[int(q)])] for q in q_best]
+        slack = int(os.environ.get("TBLUP_MDE_SLACK", "-1"))
+        drawn = GpuDEStep.get(self.device).mde_draws(n, L, q_idx, p_best, slack)
+        if drawn is None:
+            MDE_pBX.fallbacks += 1
+            return None
+        if drawn is False:
+            MDE_pBX.oversize += 1
+            return None
+        parent, donors, fixed, c_words = drawn
+        fs = np.array([float(f) for f in self.fs[:n]], dtype=np.float64)
+        crs = np.array([float(c) for c in self.crs[:n]], dtype=np.float64)
+        return self._gpu_generation(population, t, donors, fixed, _native.DE_STRATEGY["de_currenttobest_1"], fs, crs,
+                                    self.clip, members, mde=(parent, c_words))
+
     def evolve(self, population):
+        import time
+        t = time.perf_counter()
         self.recalculate_cr_m()
         self.recalculate_f_m()
         self.recalculate_p(population)
@@ -926,6 +1049,10 @@ class MDE_pBX(AdaptiveEvolver):
         q_best = order[-int(len(population) * self.group_q):]
         p_best = order[-self.p:]
         n = len(population)
+        if self._on_device(n):
+            out = self._device_generation(population, t, q_best, p_best)
+            if out is not None:
+                return out
         out = []
         for i in range(n):
             best = population[np.random.choice(q_best, 1).item()]
