@@ -119,7 +119,49 @@ int tblup_eval_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const int
                      int64_t batch, double h2, int branch, double* fitness, double* ebv);
 
 /*
- * Same computation on device-resident inputs/outputs, enqueued on `stream`
+ * Taking the fitted model out.  The reference ends a blup() call with one number; the model it
+ * fitted on the way is the clf of snp_blup (evaluator.py:311-312: coef_, intercept_, and the 2p it
+ * subtracted, :304-309) or, under gblup, the all-animal `prediction` of evaluator.py:284 that it
+ * indexes by the validation rows and drops (:286).  Both are, for selected columns idx[0..k)
+ * (duplicates kept, each occurrence its own column, as data[:, indices]),
+ *   EBV_t(a) = intercept[t] + sum_j (x[a, idx_j] - center[j]) * effects[t][j]
+ * with center[j] = 2 p_j, the exact allele count of column j over the branch's reference rows (all
+ * n animals for gblup, utils.py:7-18; the train rows for snp, evaluator.py:304) divided once by
+ * their number; effects = the solved beta (SNP form: Ridge's primal coef_) or W_T^T alpha / d
+ * (kernel form: gblup, and the snp branch's dual Ridge when k > n_T), W = A - 2p, d = 2 sum p(1-p),
+ * (K_TT + lambda I) alpha = y_T - mu; intercept = 0 (gblup) or the split's mean(y_T) (snp).
+ *
+ * tblup_fit_batch: tblup_eval_batch plus the model of every individual.  idx / offsets / h2 /
+ * branch, the index rules and errors and the chunking by TBLUP_WORKSPACE_MB are tblup_eval_batch's.
+ *   fitness   : optional out (may be NULL), batch doubles, bit-identical to tblup_eval_batch's
+ *   intercept : out, batch x n_traits
+ *   center    : out, offsets[batch] doubles, indexed like idx
+ *   effects   : out, n_traits x offsets[batch], trait-major planes each indexed like idx
+ * An individual whose solve yields NaN (a monomorphic panel: d = 0) gets NaN effects; that is not
+ * an error.  The effects are the same bits under every TBLUP_SOLVE_CHAIN / TBLUP_SOLVE_PULL
+ * setting.  Host pointers, synchronous.
+ */
+int tblup_fit_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                    double h2, int branch, double* fitness, double* intercept, double* center, double* effects);
+
+/*
+ * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
+ * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
+ * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a
+ * DE / decode-only context).  Models are portable between contexts: predicting newly genotyped
+ * candidates means a context on their genotype matrix (same SNP columns) and the same model.
+ * idx follows tblup_eval_batch's index rules (negative indices wrap, TBLUP_ERR_INDEX outside
+ * [-n_snps, n_snps)); intercept / center / effects are laid out as tblup_fit_batch writes them.
+ * Every animal's sum over j runs in list order in one chain, so the same call gives the same bits
+ * twice and an animal's EBV depends neither on n_pred nor on its position in `animals`.
+ * Host pointers, synchronous.
+ */
+int tblup_predict_batch(tblup_ctx* ctx, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                        const int64_t* offsets, int64_t batch, const double* intercept, const double* center,
+                        const double* effects, int64_t n_traits, double* ebv);
+
+/*
+ * tblup_eval_batch's computation on device-resident inputs/outputs, enqueued on `stream`
  * (a hipStream_t; NULL = the context's own stream) without synchronising.
  * d_idx / d_offsets / d_fitness / d_ebv are device pointers on the
  * context's device; h_offsets is the same batch+1 offsets on the host (used

@@ -7,9 +7,11 @@ include/tblup_gpu.h (libtblup_gpu.so, built in-tree under tblup_amd/lib/).
 from .evaluator import (BlupParallelEvaluator, Evaluator, InterGCVBlupParallelEvaluator,
                         IntraGCVBlupParallelEvaluator, MonteCarloCVBlupParallelEvaluator, ParallelEvaluator,
                         SNPRemovalHandler, get_evaluator)
+from .model import PanelModel
 
 __all__ = [
     "Evaluator", "ParallelEvaluator", "BlupParallelEvaluator", "InterGCVBlupParallelEvaluator",
     "IntraGCVBlupParallelEvaluator", "MonteCarloCVBlupParallelEvaluator", "SNPRemovalHandler", "get_evaluator",
+    "PanelModel",
 ]
 __version__ = "0.1.0"

@@ -39,6 +39,9 @@ SIGNATURES = {
     "tblup_set_traits": (_c.c_int, [_P, _DP, _c.c_int64]),
     "tblup_get_traits": (_c.c_int, [_P, _I64P]),
     "tblup_eval_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP, _DP]),
+    "tblup_fit_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP, _DP, _DP, _DP]),
+    "tblup_predict_batch": (_c.c_int, [_P, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _DP, _DP, _DP, _c.c_int64,
+                                       _DP]),
     "tblup_eval_batch_device": (_c.c_int, [_P, _c.c_int, _P, _P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _P, _P,
                                            _P]),
     "tblup_eval_folds": (_c.c_int, [_P, _I32P, _c.c_int, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP]),

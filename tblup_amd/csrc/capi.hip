@@ -3,6 +3,7 @@
 //
 // Pipeline per chunk of B individuals (one HIP stream, no host syncs inside):
 //   k_indiv_stats -> k_gather -> k_grm -> for J: (k_chol_diag, k_chol_offdiag) -> k_solve
+//   (tblup_fit_batch: -> k_effects, on the factor and z the pipeline leaves in the workspace)
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -294,7 +295,7 @@ bool use_last_term(const tblup_ctx* c, const SysDims& sd, int64_t B) { return la
 inline bool lt_bit(uint32_t m, int J) { return J < 32 ? ((m >> J) & 1u) != 0 : m == ~1u; }
 
 size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv) {
+                   bool with_ebv, bool with_model = false) {
   size_t s = 0;
   auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
   add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
@@ -320,6 +321,8 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
   add((size_t)B * 8);                                           // fitness
   add(with_ebv ? (size_t)B * d.nt * d.nV * 8 : 0);              // ebv
   add((size_t)sum_k * 8 + (size_t)(B + 1) * 8);                 // idx, off
+  add(with_model ? (size_t)sum_k * 8 : 0);                      // the fitted models' centres
+  add(with_model ? (size_t)d.nt * sum_k * 8 : 0);               // and effects (tblup_fit_batch)
   return s + 4096;
 }
 
@@ -405,7 +408,7 @@ FoldTab single_fold(const Split& sp, int64_t B) {
 int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& sd, hipStream_t s,
               const int64_t* d_idx, const int64_t* d_off, const int64_t* h_off, int64_t B, double h2,
               int branch, Carve& cv, double* d_fit, double* d_ebv, int stop_stage, double** K_out,
-              double** z_out, const FoldTab* ftp = nullptr) {
+              double** z_out, const FoldTab* ftp = nullptr, CholLaunch* cl_out = nullptr) {
   const FoldTab ft = ftp ? *ftp : single_fold(sp, B);
   const bool redo = stop_stage == 3;
   const bool chain = stop_stage != 4 && use_chain(c, sd, B, d.nt);
@@ -486,6 +489,7 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
   cl.kd = kdb;
   cl.sys_st = c->sys_st;
   cl.padskip = (sd.form == FORM_PRIMAL && sd.pad_first) ? 1 : 0;
+  if (cl_out) *cl_out = cl;   // the chunk's buffers, for a launch after the pipeline (launch_effects)
   const double T3 = (double)TILE * TILE * TILE;
   // profiling only: room for one record per Cholesky workgroup of this chunk
   uint64_t* wgt = nullptr;
@@ -918,6 +922,15 @@ static int validate_batch(tblup_ctx* c, int branch, double h2, const int64_t* of
 
 int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
                      double h2, int branch, double* fitness, double* ebv) {
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, ebv, nullptr);
+}
+
+}  // extern "C"
+
+// tblup_eval_batch, and with `fo` tblup_fit_batch (capi_model.hip): the same chunks through the same
+// pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
+int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                                double h2, int branch, double* fitness, double* ebv, const FitOut* fo) {
   g_err.clear();
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
@@ -937,13 +950,13 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
     int64_t b1 = b0, sum_k = 0;
     while (b1 < batch) {
       const int64_t k = offsets[b1 + 1] - offsets[b1];
-      if (b1 > b0 && chunk_bytes(c, d, sd, b1 + 1 - b0, sum_k + k, want_ebv) > c->budget) break;
+      if (b1 > b0 && chunk_bytes(c, d, sd, b1 + 1 - b0, sum_k + k, want_ebv, fo != nullptr) > c->budget) break;
       if (b1 - b0 >= 65535) break;
       sum_k += k;
       ++b1;
     }
     const int64_t B = b1 - b0;
-    const size_t need = chunk_bytes(c, d, sd, B, sum_k, want_ebv);
+    const size_t need = chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (int rc = dev_alloc(c, c->ws, need)) return rc;
     Carve cv{(char*)c->ws.p};
@@ -951,6 +964,8 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
     int64_t* d_off = cv.take<int64_t>((size_t)B + 1);
     double* d_fit = cv.take<double>((size_t)B);
     double* d_ebv = want_ebv ? cv.take<double>((size_t)B * d.nt * d.nV) : nullptr;
+    double* d_cen = fo ? cv.take<double>((size_t)sum_k) : nullptr;
+    double* d_eff = fo ? cv.take<double>((size_t)d.nt * sum_k) : nullptr;
     std::vector<int64_t> hoff(B + 1);
     for (int64_t b = 0; b <= B; ++b) hoff[b] = offsets[b0 + b] - offsets[b0];
     HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, c->stream));
@@ -959,10 +974,20 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
     for (int pass = 0;; ++pass) {
       // pass 1: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
       Carve cvp = cv0;
+      CholLaunch cl{};
       if (int rc = run_chunk(c, *sp, d, sd, c->stream, d_idx, d_off, hoff.data(), B, h2, branch, cvp, d_fit, d_ebv,
-                             pass ? 3 : 0, nullptr, nullptr))
+                             pass ? 3 : 0, nullptr, nullptr, nullptr, fo ? &cl : nullptr))
         return rc;
       const int32_t seq = c->last_chain_seq;
+      if (fo && pass == 0) {
+        // neither solve kernel writes L, the diagonal inverses or z: the effects do not wait for the
+        // chained solve's verdict (a recovery pass re-solves for the fitness only)
+        HIPCHK(launch_effects(cl, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, c->stream));
+        HIPCHK(hipMemcpyAsync(fo->center + offsets[b0], d_cen, (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
+        for (int t = 0; t < d.nt; ++t)
+          HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
+                                (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
+      }
       HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
       if (want_ebv)
         HIPCHK(hipMemcpyAsync(ebv + b0 * d.nt * d.nV, d_ebv, (size_t)B * d.nt * d.nV * 8, hipMemcpyDeviceToHost,
@@ -975,9 +1000,18 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
     }
     b0 = b1;
   }
+  if (fo) {
+    // intercept: the split's mean(y_T) the evaluation uses under snp, 0 under gblup (evaluator.py:257 dispatch)
+    for (int64_t b = 0; b < batch; ++b) {
+      const int mode = branch ? branch : (offsets[b + 1] - offsets[b] > c->n ? 1 : 2);
+      for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = mode == 2 ? sp->meanyT[t] : 0.0;
+    }
+  }
   if (c->profiling) return drain_events(c);
   return 0;
 }
+
+extern "C" {
 
 int tblup_eval_batch_device(tblup_ctx* c, int split_id, const int64_t* d_idx, const int64_t* d_offsets,
                             const int64_t* h_offsets, int64_t batch, double h2, int branch, double* d_fitness,

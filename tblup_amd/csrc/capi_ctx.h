@@ -137,4 +137,14 @@ int dev_alloc(tblup_ctx* c, DevBuf& b, size_t bytes);
 void dev_free(tblup_ctx* c, DevBuf& b);
 int check_ctx(tblup_ctx* c);
 void clear_error();
+// Host outputs of tblup_fit_batch (capi_model.hip): intercept [batch][nt], center [offsets[batch]],
+// effects [nt][offsets[batch]].
+struct FitOut {
+  double* intercept;
+  double* center;
+  double* effects;
+};
+// tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual
+int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                    int branch, double* fitness, double* ebv, const FitOut* fo);
 }  // namespace tblup_capi

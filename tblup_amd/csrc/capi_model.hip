@@ -1,0 +1,116 @@
+// C ABI of libtblup_gpu.so, taking the fitted model out (include/tblup_gpu.h): tblup_fit_batch
+// (the evaluation's chunks plus one k_effects launch each) and tblup_predict_batch (k_predict).
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "capi_ctx.h"
+
+using namespace tblup;
+using namespace tblup_capi;
+
+extern "C" {
+
+int tblup_fit_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                    int branch, double* fitness, double* intercept, double* center, double* effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (batch > 0 && (!intercept || !center || !effects)) return fail(TBLUP_ERR_ARG, "null intercept/center/effects");
+  std::vector<double> fit_local;
+  if (!fitness && batch > 0) {
+    fit_local.resize((size_t)batch);
+    fitness = fit_local.data();
+  }
+  const FitOut fo{intercept, center, effects};
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, &fo);
+}
+
+int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                        const int64_t* offsets, int64_t batch, const double* intercept, const double* center,
+                        const double* effects, int64_t n_traits, double* ebv) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (n_traits < 1 || n_traits > MAXT) return fail(TBLUP_ERR_ARG, "need 1 <= n_traits <= 4");
+  if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
+  if (batch == 0 || n_pred == 0) return 0;
+  if (!animals || !idx || !offsets || !intercept || !center || !effects || !ebv)
+    return fail(TBLUP_ERR_ARG, "null predict arguments");
+  if (offsets[0] != 0) return fail(TBLUP_ERR_ARG, "offsets[0] must be 0");
+  for (int64_t b = 0; b < batch; ++b)
+    if (offsets[b + 1] - offsets[b] < 1) return fail(TBLUP_ERR_ARG, "every model needs k >= 1 indices");
+  const int64_t total = offsets[batch];
+  for (int64_t i = 0; i < total; ++i)
+    if (idx[i] < -c->P || idx[i] >= c->P)
+      return fail(TBLUP_ERR_INDEX, "index " + std::to_string(idx[i]) + " is out of bounds for axis 1 with size " +
+                                       std::to_string(c->P));
+  std::vector<int32_t> a32((size_t)n_pred);
+  for (int64_t i = 0; i < n_pred; ++i) {
+    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
+    a32[i] = (int32_t)animals[i];
+  }
+  HIPCHK(hipSetDevice(c->device));
+  const int nt = (int)n_traits;
+  // device bytes of models [b0, b1) (every buffer rounded up to 256 B)
+  auto bytes_of = [&](int64_t B, int64_t sum_k) {
+    size_t s = 0;
+    auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
+    add((size_t)n_pred * 4);
+    add((size_t)sum_k * 8);
+    add((size_t)(B + 1) * 8);
+    add((size_t)B * nt * 8);
+    add((size_t)sum_k * 8);
+    add((size_t)nt * sum_k * 8);
+    add((size_t)B * nt * n_pred * 8);
+    return s + 256;
+  };
+  const int64_t nblk = (n_pred + 255) / 256;
+  int64_t b0 = 0;
+  while (b0 < batch) {
+    // models per chunk: within the workspace budget (TBLUP_WORKSPACE_MB) and one launch's grid
+    int64_t b1 = b0, sum_k = 0;
+    while (b1 < batch) {
+      const int64_t k = offsets[b1 + 1] - offsets[b1];
+      if (b1 > b0 && (bytes_of(b1 + 1 - b0, sum_k + k) > c->budget || (b1 + 1 - b0) * nblk > 0x7fffffff)) break;
+      sum_k += k;
+      ++b1;
+    }
+    const int64_t B = b1 - b0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (int rc = dev_alloc(c, c->ws, bytes_of(B, sum_k))) return rc;
+    char* base = (char*)c->ws.p;
+    size_t used = 0;
+    auto take = [&](size_t bytes) {
+      char* p = base + used;
+      used = (size_t)round_up((int64_t)(used + bytes), 256);
+      return p;
+    };
+    int32_t* d_an = (int32_t*)take((size_t)n_pred * 4);
+    int64_t* d_idx = (int64_t*)take((size_t)sum_k * 8);
+    int64_t* d_off = (int64_t*)take((size_t)(B + 1) * 8);
+    double* d_int = (double*)take((size_t)B * nt * 8);
+    double* d_cen = (double*)take((size_t)sum_k * 8);
+    double* d_eff = (double*)take((size_t)nt * sum_k * 8);
+    double* d_ebv = (double*)take((size_t)B * nt * n_pred * 8);
+    if (used > c->ws.bytes) return fail(TBLUP_ERR_STATE, "internal error: predict buffers overrun the workspace");
+    std::vector<int64_t> hoff((size_t)B + 1);
+    for (int64_t b = 0; b <= B; ++b) hoff[b] = offsets[b0 + b] - offsets[b0];
+    hipStream_t s = c->stream;
+    HIPCHK(hipMemcpyAsync(d_an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_off, hoff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_int, intercept + b0 * nt, (size_t)B * nt * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(d_cen, center + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
+    for (int t = 0; t < nt; ++t)
+      HIPCHK(hipMemcpyAsync(d_eff + (int64_t)t * sum_k, effects + (int64_t)t * total + offsets[b0], (size_t)sum_k * 8,
+                            hipMemcpyHostToDevice, s));
+    HIPCHK(launch_predict((const int8_t*)c->geno_sm.p, c->n, c->P, d_an, n_pred, d_idx, d_off, B, d_int, d_cen, d_eff,
+                          sum_k, nt, d_ebv, s));
+    HIPCHK(hipMemcpyAsync(ebv + b0 * nt * n_pred, d_ebv, (size_t)B * nt * n_pred * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // hoff and the host buffers are borrowed until here
+    b0 = b1;
+  }
+  return 0;
+}
+
+}  // extern "C"

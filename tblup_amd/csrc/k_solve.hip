@@ -828,4 +828,130 @@ hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitne
   }
 }
 
+// ===========================================================================
+// The fitted model (tblup_fit_batch): a launch of its own after the chunk's pipeline, one
+// 1024-thread workgroup per individual, reading the L tiles, the diagonal inverses and z that the
+// pipeline left in the workspace -- the state k_solve reads, untouched by either solve kernel, so
+// the effects are the same bits under every TBLUP_SOLVE_CHAIN / TBLUP_SOLVE_PULL setting.
+//   alpha = L^{-T} z                      k_solve's back substitution, block row by block row
+//   SNP form:    effects_j = alpha[pad + j]                    (sklearn Ridge's coef_, evaluator.py:311-312)
+//   kernel form: effects_j = sum_t (a_tj - c_j) alpha_t / d    (W_T^T alpha / d: G[:, T] Ginv y_T of
+//                evaluator.py:284 = W (W_T^T alpha) / d; the snp branch's dual Ridge when k > n_T)
+//   center_j = c_j = m_j / N, m the exact allele count over the branch's N reference rows
+// Kernel form: one thread per selected SNP walks the split's 2-bit packed row of that SNP (animal
+// 4q + i at bits 2i of byte q) over the train animals in order, 16 per 32-bit word, in one fma chain
+// per trait -- a fixed order per SNP; a wave reads the same alpha_t from LDS (a broadcast) and its
+// 64 rows' loads are independent, so the 1024 threads' loads overlap.  (A wave per SNP with a
+// butterfly over its lanes waited out one dependent row load per SNP: 345 us against the solve's
+// 118 us at 32 individuals of k = 1500, n_T = 768.)
+template <int NTR>
+__global__ __launch_bounds__(NTH) void k_effects(CholLaunch c, const int32_t* __restrict__ csA,
+                                                 double* __restrict__ center, double* __restrict__ effects,
+                                                 int64_t plane) {
+  extern __shared__ double dyn[];  // alpha[nt][ns]
+  __shared__ double vsh[MAXT][TPAD];
+  const int64_t nT = c.d.nT, ns = c.sd.ns;
+  const int NT = c.sd.NT;
+  constexpr int nt = NTR;
+  double* alpha = dyn;
+  const int t = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const double* Lb = c.L + b * l_stride(NT);
+  const double* Db = c.Dinv + b * (int64_t)NT * NPACK * BLKD;
+  const double* sc = c.scal + b * SCAL;
+  const int fo = fold_of(c.ft, b);
+  const int rc = t >> 3, seg = t & 7;
+  for (int64_t i = t; i < nt * ns; i += NTH) alpha[i] = c.z[b * nt * ns + i];
+  __syncthreads();
+  for (int I = NT - 1; I >= 0; --I) {
+    double s[NTR] = {};
+    for (int J = NT - 1; J > I; --J) {
+      const double* row0 = Lb + ((int64_t)J * NT + I) * TILE * TILE + rc * TILE + 2 * seg;
+      v2d x0[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) x0[e] = *reinterpret_cast<const v2d*>(row0 + 16 * e);
+      double p[NTR];
+      tile_row_partial<NTR>(x0, alpha + J * TILE, ns, seg, p);
+#pragma unroll
+      for (int tr = 0; tr < NTR; ++tr) s[tr] += p[tr];
+    }
+    v2d xr[8];
+    const bool xrow = xrow_load(Db + (int64_t)I * NPACK * BLKD, rc, seg, xr);
+#pragma unroll
+    for (int tr = 0; tr < NTR; ++tr)
+      if (seg == 0) vsh[tr][vpi(rc)] = alpha[tr * ns + (int64_t)I * TILE + rc] - s[tr];
+    __syncthreads();
+    double s2[NTR];
+    xrow_apply<NTR>(xr, xrow, rc, seg, vsh, s2);
+#pragma unroll
+    for (int tr = 0; tr < NTR; ++tr)
+      if (seg == 0) alpha[tr * ns + I * TILE + rc] = s2[tr];
+    __syncthreads();
+  }
+
+  const int64_t kk = (int64_t)sc[SC_K], o0 = c.off[b];
+  const bool gblup = (int)sc[SC_MODE] == 1;
+  const int32_t* cs = gblup ? csA : c.ft.csT[fo];
+  const double N = gblup ? (double)c.d.n : (double)nT;
+  if (c.sd.form == FORM_PRIMAL) {
+    const int64_t pad = (int64_t)sc[SC_PAD];
+    for (int64_t j = t; j < kk; j += NTH) {
+      center[o0 + j] = (double)cs[snp_col(c.idx[o0 + j], c.d.P)] / N;
+#pragma unroll
+      for (int tr = 0; tr < NTR; ++tr) effects[tr * plane + o0 + j] = alpha[tr * ns + pad + j];
+    }
+    return;
+  }
+  const double dd = sc[SC_D];
+  const int64_t nwf = nT / 16;   // whole 32-bit words of a packed row (16 train animals each)
+  for (int64_t j = t; j < kk; j += NTH) {
+    const int64_t col = snp_col(c.idx[o0 + j], c.d.P);
+    const double cj = (double)cs[col] / N;
+    const uint32_t* row = reinterpret_cast<const uint32_t*>(c.ft.gpk[fo] + col * c.gpk_row);
+    double acc[NTR] = {};
+#pragma unroll 4
+    for (int64_t w = 0; w < nwf; ++w) {
+      const uint32_t x = row[w];
+#pragma unroll
+      for (int i = 0; i < 16; ++i) {
+        const double a = (double)((x >> (2 * i)) & 3u) - cj;
+#pragma unroll
+        for (int tr = 0; tr < NTR; ++tr) acc[tr] = __builtin_fma(a, alpha[tr * ns + 16 * w + i], acc[tr]);
+      }
+    }
+    if (16 * nwf < nT) {   // the row's last train animals (the row itself is padded to 128 animals)
+      const uint32_t x = row[nwf];
+      for (int64_t r = 16 * nwf; r < nT; ++r) {
+        const double a = (double)((x >> (2 * (r & 15))) & 3u) - cj;
+#pragma unroll
+        for (int tr = 0; tr < NTR; ++tr) acc[tr] = __builtin_fma(a, alpha[tr * ns + r], acc[tr]);
+      }
+    }
+    center[o0 + j] = cj;
+#pragma unroll
+    for (int tr = 0; tr < NTR; ++tr) effects[tr * plane + o0 + j] = acc[tr] / dd;
+  }
+}
+
+hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
+                          hipStream_t s) {
+  const size_t shm = (size_t)c.d.nt * (size_t)c.sd.ns * sizeof(double);
+  if (shm > 150 * 1024) return hipErrorInvalidValue;   // (k_solve's own LDS bound is tighter)
+  auto launch = [&](const void* fn, auto kernel) -> hipError_t {
+    if (shm > 64 * 1024) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c.B), dim3(NTH), shm, s, c, csA, center, effects, plane);
+    return hipGetLastError();
+  };
+  switch (c.d.nt) {
+    case 1: return launch((const void*)k_effects<1>, k_effects<1>);
+    case 2: return launch((const void*)k_effects<2>, k_effects<2>);
+    case 3: return launch((const void*)k_effects<3>, k_effects<3>);
+    case 4: return launch((const void*)k_effects<4>, k_effects<4>);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 }  // namespace tblup

@@ -351,6 +351,23 @@ constexpr int CHAIN_ERR_RING = 64;
 enum { ST_INDEX = 0, ST_SOLVE = 1, ST_WORDS = 2 };
 __host__ __device__ inline int64_t chain_flags(int NT) { return (int64_t)NT * (NT + 2); }
 hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitness, double* ebv, hipStream_t s);
+// The fitted model of every individual of a chunk (k_effects, k_solve.hip), from the factor, the
+// diagonal inverses and z that the chunk's pipeline left in the workspace (what launch_solve reads):
+// center[off[b] + j] = 2 p_j of selected SNP j (the exact allele count over the branch's reference
+// rows -- csA over all n animals for gblup, the split's counts for snp -- divided once by their
+// number) and effects[t * plane + off[b] + j], trait-major planes.  SNP form: the solved beta without
+// its padding rows; kernel form: W_T^T alpha / d over the split's 2-bit packed rows.
+hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
+                          hipStream_t s);
+
+// ---- launcher (k_model.hip): EBVs of any animals of the panel from fitted models ----
+// ebv[(m * nt + t) * n_pred + v] = intercept[m * nt + t] + sum_j (x[animals[v], idx_j] - center_j)
+// effects[t * plane + j], j = off[m] .. off[m + 1] in that order for every animal (the same bits
+// wherever the animal stands in the list).  geno_sm: int8 [P][n]; indices wrap as snp_col.
+hipError_t launch_predict(const int8_t* geno_sm, int64_t n, int64_t P, const int32_t* animals, int64_t n_pred,
+                          const int64_t* idx, const int64_t* off, int64_t B, const double* intercept,
+                          const double* center, const double* effects, int64_t plane, int nt, double* ebv,
+                          hipStream_t s);
 
 // ---- launcher (k_decode.hip): RandomKey genome decode, top-k of each key row ----
 hipError_t launch_decode_topk(const double* keys, int64_t B, int64_t d, int64_t ld, const int64_t* off, int64_t* out,

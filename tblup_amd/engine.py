@@ -158,6 +158,61 @@ class GpuBlupEngine:
                 _ptr(ebv, ctypes.c_double) if return_ebv else None))
         return (fit, ebv) if return_ebv else fit
 
+    # ------------------------------------------------------- taking the model out
+    def fit(self, genomes, train, valid, h2, branch="auto"):
+        """evaluate() plus what it fitted: one PanelModel per selected-index set (tblup_fit_batch),
+        whose `fitness` is evaluate()'s value bit for bit.  Out-of-range indices raise
+        TblupIndexError; a degenerate panel gives NaN effects, not an error."""
+        from .model import PanelModel
+        self._settle()
+        sid = self.split_id(train, valid)
+        idx, offsets = concat_genomes(genomes)
+        B, nt, total = len(genomes), self.n_traits, int(offsets[-1])
+        fit = np.empty(B, dtype=np.float64)
+        intercept = np.empty((B, nt), dtype=np.float64)
+        center = np.empty(total, dtype=np.float64)
+        effects = np.empty((nt, total), dtype=np.float64)
+        if B:
+            _native.check("tblup_fit_batch", self._lib.tblup_fit_batch(
+                self._ctx, sid, _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64), B, float(h2),
+                _native.BRANCH[branch], _ptr(fit, ctypes.c_double), _ptr(intercept, ctypes.c_double),
+                _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double)))
+        wrapped = np.where(idx < 0, idx + self.n_snps, idx)
+        models = []
+        for b in range(B):
+            lo, hi = int(offsets[b]), int(offsets[b + 1])
+            fitted = branch if branch != "auto" else ("gblup" if hi - lo > self.n_animals else "snp")
+            models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
+                                     fit[b]))
+        return models
+
+    def predict(self, models, animals):
+        """EBVs of `animals` (row ids of this engine's panel: any order, repeats allowed, no split
+        needed) under each PanelModel (tblup_predict_batch): (len(models), n_traits, len(animals)),
+        the trait axis dropped for one trait as evaluate(return_ebv=True) shapes its output.  An
+        animal's EBV does not depend on its position in the list."""
+        self._settle()
+        models = list(models)
+        an = _as_int64(animals)
+        if an.ndim != 1:
+            raise ValueError("animals must be a 1-D list of row ids")
+        nt = models[0].n_traits if models else self.n_traits
+        if any(m.n_traits != nt for m in models):
+            raise ValueError("models of one call must have the same number of traits")
+        idx, offsets = concat_genomes([m.indices for m in models])
+        B, total = len(models), int(offsets[-1])
+        out = np.empty((B, nt, len(an)), dtype=np.float64)
+        if B and len(an):
+            intercept = np.ascontiguousarray(np.stack([m.intercept for m in models]))
+            center = np.ascontiguousarray(np.concatenate([m.center for m in models]))
+            effects = np.ascontiguousarray(np.concatenate([m.effects for m in models], axis=1))
+            assert effects.shape == (nt, total)
+            _native.check("tblup_predict_batch", self._lib.tblup_predict_batch(
+                self._ctx, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64),
+                B, _ptr(intercept, ctypes.c_double), _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double),
+                nt, _ptr(out, ctypes.c_double)))
+        return out[:, 0, :] if nt == 1 else out
+
     def evaluate_folds(self, genomes, splits, h2, branch="auto"):
         """Every genome against each (train, valid) split in one call (tblup_eval_folds: the
         splits' evaluations back to back on the GPU, one round trip): (n_splits, B) fitness, row f

@@ -376,6 +376,39 @@ class BlupParallelEvaluator(ParallelEvaluator):
                 genomes.append(np.union1d(indv.genome, np.array([])).astype(int))
         return list(self._fitness(genomes, train, self.testing_indices))
 
+    def fit_models(self, population, final=True, train=None, valid=None):
+        """The fitted model (tblup_amd.model.PanelModel) of every individual, in population order.
+
+        final=True is evaluate_testing's set-up -- train = T u V, valid = the testing animals, the
+        genome merged with the removed SNPs -- so each model's `fitness` is evaluate_testing's value
+        bit for bit; final=False fits on the evaluator's own (training, validation) split and the
+        plain genome.  Explicit `train` / `valid` override either side of the split.
+        Draws no RNG and uses no collective: under torch.distributed every rank fits the population
+        it is given (call it on one rank, or with that rank's share)."""
+        if self.engine is None:
+            raise AttributeError("Workers are not set up.")
+        genomes = []
+        for indv in population:
+            if not final:
+                genomes.append(np.asarray(indv.genome))
+            elif self.snp_remover is not None:
+                genomes.append(self.snp_remover.combine_with_removed(indv.genome))
+            else:
+                genomes.append(np.union1d(indv.genome, np.array([])).astype(int))
+        if train is None:
+            train = (np.concatenate((self.training_indices, self.validation_indices)) if final
+                     else self.training_indices)
+        if valid is None:
+            valid = self.testing_indices if final else self.validation_indices
+        return self.engine.fit(genomes, train, valid, self.h2)
+
+    def predict(self, models, animals):
+        """EBVs of `animals` (row ids of the evaluator's data, any order, in or out of any split)
+        under each model: GpuBlupEngine.predict.  No RNG, no collective."""
+        if self.engine is None:
+            raise AttributeError("Workers are not set up.")
+        return self.engine.predict(models, animals)
+
 
 class InterGCVBlupParallelEvaluator(BlupParallelEvaluator):
     """Validation fold rotates with the generation (evaluator.py:434-491)."""

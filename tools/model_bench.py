@@ -1,0 +1,166 @@
+"""Timings of the model export (tblup_fit_batch / tblup_predict_batch); no thresholds, the
+numbers go to PERFLOG.md.  One JSON line per part:
+
+  fit      config 2 (2000 x 50k, k = 1000, 256 individuals, n_T 1280, n_V 320): fit against evaluate
+           in one process, alternated, each call timed as the synchronous entry it is (wall clock
+           around a call that ends in the stream's synchronisation; medians over --reps)
+  predict  the 256 fitted models for all 2000 animals: time, and bytes/s over the bytes k_predict
+           must read (batch x k x n genotype bytes) against the 8 TB/s HBM figure
+  dual     a config-4-shaped small stand-in in the kernel form (1200 x 20k, k = 1500 > n: gblup,
+           n_T 768, 32 individuals): fit against evaluate, predict for all animals
+  --stats CSV   the k_effects / k_predict share of a `rocprofv3 --kernel-trace --stats` run of
+           `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
+
+    python tools/model_bench.py [--only fit,predict,dual] [--reps 7]
+    rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
+    python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_GBS = 8000.0   # the microarchitecture guide's HBM figure (bench.py PEAKS)
+
+
+def workload(n, P, k, pop, nT, nV, seed=1234):
+    rng = np.random.default_rng(seed)
+    maf = rng.uniform(0.05, 0.5, size=P)
+    geno = rng.binomial(2, maf, size=(n, P)).astype(np.int8)
+    pheno = rng.standard_normal(n)
+    perm = rng.permutation(n)
+    if k <= P:
+        genomes = [rng.choice(P, k, replace=False) for _ in range(pop)]
+    else:
+        genomes = [rng.integers(0, P, k) for _ in range(pop)]
+    return geno, pheno, perm[:nT], perm[nT:nT + nV], genomes
+
+
+def med_ms(ts):
+    return round(float(np.median(ts)) * 1e3, 4)
+
+
+def fit_vs_eval(eng, genomes, T, V, reps):
+    """Alternated evaluate / fit calls on one engine; returns (models, stats)."""
+    te, tf = [], []
+    models = None
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        fit = eng.evaluate(genomes, T, V, 0.4)
+        t1 = time.perf_counter()
+        models = eng.fit(genomes, T, V, 0.4)
+        t2 = time.perf_counter()
+        if r >= 2:
+            te.append(t1 - t0)
+            tf.append(t2 - t1)
+    assert np.array_equal(fit, [m.fitness for m in models], equal_nan=True)
+    return models, {"evaluate_ms": med_ms(te), "fit_ms": med_ms(tf), "extra_ms": round(med_ms(tf) - med_ms(te), 4),
+                    "evaluate_ms_all": [round(x * 1e3, 3) for x in te], "fit_ms_all": [round(x * 1e3, 3) for x in tf],
+                    "note": "fit includes building the PanelModel objects and the D2H copy of the effects"}
+
+
+def fit_raw(eng, genomes, T, V, reps):
+    """The C entries alone (no PanelModel objects): tblup_eval_batch against tblup_fit_batch."""
+    import ctypes
+    from tblup_amd.engine import concat_genomes, _ptr
+    from tblup_amd import _native
+    sid = eng.split_id(T, V)
+    idx, off = concat_genomes(genomes)
+    B, total = len(genomes), int(off[-1])
+    fit = np.empty(B)
+    icp, cen, eff = np.empty((B, eng.n_traits)), np.empty(total), np.empty((eng.n_traits, total))
+    dp, ip = ctypes.c_double, ctypes.c_int64
+    te, tf = [], []
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        _native.check("tblup_eval_batch", eng._lib.tblup_eval_batch(eng._ctx, sid, _ptr(idx, ip), _ptr(off, ip), B, 0.4, 0,
+                                                                    _ptr(fit, dp), None))
+        t1 = time.perf_counter()
+        _native.check("tblup_fit_batch", eng._lib.tblup_fit_batch(eng._ctx, sid, _ptr(idx, ip), _ptr(off, ip), B, 0.4, 0,
+                                                                  _ptr(fit, dp), _ptr(icp, dp), _ptr(cen, dp), _ptr(eff, dp)))
+        t2 = time.perf_counter()
+        if r >= 2:
+            te.append(t1 - t0)
+            tf.append(t2 - t1)
+    return {"eval_batch_ms": med_ms(te), "fit_batch_ms": med_ms(tf), "extra_ms": round(med_ms(tf) - med_ms(te), 4),
+            "eval_batch_ms_all": [round(x * 1e3, 3) for x in te], "fit_batch_ms_all": [round(x * 1e3, 3) for x in tf]}
+
+
+def predict_all(eng, models, n, reps):
+    an = np.arange(n)
+    ts = []
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        out = eng.predict(models, an)
+        t1 = time.perf_counter()
+        if r >= 2:
+            ts.append(t1 - t0)
+    k = sum(len(m.indices) for m in models)
+    must = float(k) * n                      # genotype bytes the kernel must read
+    s = float(np.median(ts))
+    return out, {"predict_ms": med_ms(ts), "predict_ms_all": [round(x * 1e3, 3) for x in ts],
+                 "bytes_must_read": must, "gbs_call": round(must / s / 1e9, 1),
+                 "frac_hbm_call": round(must / s / 1e9 / HBM_GBS, 4),
+                 "note": "the call includes the H2D copy of the models and the D2H copy of the EBVs; "
+                         "the kernel alone: --stats"}
+
+
+def stats_share(path):
+    rows = list(csv.DictReader(open(path)))
+    tot = sum(float(r["TotalDurationNs"]) for r in rows)
+    out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
+    for r in rows:
+        name = r["Name"]
+        for key in ("k_effects", "k_predict", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+            if key + "<" in name or key + "(" in name:
+                e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
+                e["calls"] += int(r["Calls"])
+                e["total_ms"] = round(e["total_ms"] + float(r["TotalDurationNs"]) / 1e6, 4)
+    for e in out["kernels"].values():
+        e["avg_us"] = round(e["total_ms"] * 1e3 / max(e["calls"], 1), 2)
+        e["share"] = round(e["total_ms"] * 1e6 / tot, 5)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", default="fit,predict,dual")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--stats", default=None, help="kernel_stats CSV of a rocprofv3 --kernel-trace --stats run")
+    args = ap.parse_args()
+    if args.stats:
+        print(json.dumps(stats_share(args.stats)))
+        return
+    parts = set(args.only.split(","))
+    from tblup_amd.engine import GpuBlupEngine
+    if parts & {"fit", "predict"}:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            models, st = fit_vs_eval(eng, genomes, T, V, args.reps)
+            if "fit" in parts:
+                print(json.dumps({"part": "fit", "config": "config2", **st, "c_abi": fit_raw(eng, genomes, T, V, args.reps)}))
+            if "predict" in parts:
+                out, sp = predict_all(eng, models, n, args.reps)
+                host = models[0].predict(geno)
+                sp["max_rel_vs_numpy_model0"] = float(np.max(np.abs(out[0] - host)) / np.max(np.abs(host)))
+                print(json.dumps({"part": "predict", "config": "config2", "models": pop, "k": k, "animals": n, **sp}))
+    if "dual" in parts:
+        n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            models, st = fit_vs_eval(eng, genomes, T, V, args.reps)
+            _, sp = predict_all(eng, models, n, args.reps)
+            print(json.dumps({"part": "dual", "config": "config4-shaped stand-in: %d x %d, k=%d (gblup), n_T=%d, pop %d"
+                              % (n, P, k, nT, pop), **st, "c_abi": fit_raw(eng, genomes, T, V, args.reps), "predict": sp}))
+
+
+if __name__ == "__main__":
+    main()
