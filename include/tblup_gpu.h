@@ -145,6 +145,39 @@ int tblup_fit_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const int6
                     double h2, int branch, double* fitness, double* intercept, double* center, double* effects);
 
 /*
+ * Reliabilities of the predicted breeding values: tblup_fit_batch plus, for each of `n_pred` animals
+ * of the context's panel under each of the `batch` models, the squared accuracy of its genomic value
+ * g_a = w_a . beta (r^2 = 1 - PEV / (sigma_g^2 K_aa)).  With A the gathered columns idx[0..k)
+ * (duplicates kept), c = 2p the exact allele count over the branch's N reference rows divided once by
+ * N (all n animals for gblup -- the reference's make_grm centres over every row, candidates included
+ * -- and the train rows for snp), d = 2 sum p(1-p), lambda = (1-h2)/h2, w_a = A[a] - c, K = W W^T / d:
+ *   rel(a) = k_aT^T (K_TT + lambda I)^{-1} k_Ta / K_aa,  k_Ta = W_T w_a / d, K_aa = w_a.w_a / d   (kernel form)
+ *   rel(a) = 1 - lambda w_a^T (C + lambda I)^{-1} w_a / (w_a.w_a),  C = W_T^T W_T / d            (SNP form)
+ * -- equal by the Woodbury identity; the library evaluates whichever form the batch's systems were
+ * factored in.  The model is the reference's own: beta ~ N(0, sigma_g^2 / d I), e ~ N(0, sigma_e^2 I),
+ * sigma_e^2 / sigma_g^2 = lambda; the snp branch's intercept mean(y_T) is taken as known (its
+ * uncertainty is not in the PEV).  No phenotype and no variance component enters: with several traits
+ * (one factor, shared h2) it is one number per (model, animal).
+ *   animals     : n_pred row ids in [0, n), any order, repeats allowed, any or no split role
+ *                 (TBLUP_ERR_ARG outside the range)
+ *   fitness     : optional out (may be NULL), bit-identical to tblup_eval_batch's
+ *   intercept / center / effects : optional as a triple -- all NULL: reliabilities only; all given:
+ *                 tblup_fit_batch's outputs, bit for bit; anything else is TBLUP_ERR_ARG
+ *   reliability : out, batch x n_pred
+ * n_pred == 0 or batch == 0 returns 0 and writes nothing; a context without a panel gives
+ * TBLUP_ERR_STATE; idx / offsets / h2 / branch, the index rules (TBLUP_ERR_INDEX) and the chunking are
+ * tblup_eval_batch's.  d = 0 (a monomorphic panel) or K_aa = 0 gives NaN, not an error.
+ * The Cholesky factor (k x k or n_T x n_T doubles per model) is not portable and is dropped with the
+ * chunk, so reliabilities are produced here, at fit time: for newly genotyped candidates use a context
+ * whose panel holds them as extra rows (they need not be in any split).
+ * An animal's value depends neither on n_pred, nor on its position in `animals`, nor on the chunking
+ * (TBLUP_WORKSPACE_MB), and the same call gives the same bits twice.  Host pointers, synchronous.
+ */
+int tblup_reliability_batch(tblup_ctx* ctx, int split_id, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                            const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                            double* intercept, double* center, double* effects, double* reliability);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

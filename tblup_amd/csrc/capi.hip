@@ -294,8 +294,16 @@ bool use_last_term(const tblup_ctx* c, const SysDims& sd, int64_t B) { return la
 // there the all-launches mask (~1u, J >= 1) keeps its meaning while a sparse mask names none
 inline bool lt_bit(uint32_t m, int J) { return J < 32 ? ((m >> J) & 1u) != 0 : m == ~1u; }
 
+// k_reliab keeps a slab's right-hand sides in LDS (else in workspace slices, reliab_slabs at a time)
+bool reliab_in_lds(const tblup_ctx* c, const SysDims& sd) { return c->reliab_lds && reliab_lds(sd); }
+// slabs of the animal list per k_reliab launch: all of them, or what a quarter of the workspace budget
+// (at most RELIAB_SCRATCH) holds of their workspace slices -- never less than one slab per model
+int64_t rel_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_rel) {
+  return reliab_slabs(sd, B, n_rel, reliab_in_lds(c, sd), std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(c->budget / 4)));
+}
+
 size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv, bool with_model = false) {
+                   bool with_ebv, bool with_model = false, int64_t n_rel = 0) {
   size_t s = 0;
   auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
   add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
@@ -323,6 +331,12 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
   add((size_t)sum_k * 8 + (size_t)(B + 1) * 8);                 // idx, off
   add(with_model ? (size_t)sum_k * 8 : 0);                      // the fitted models' centres
   add(with_model ? (size_t)d.nt * sum_k * 8 : 0);               // and effects (tblup_fit_batch)
+  if (n_rel > 0) {                                              // tblup_reliability_batch:
+    add((size_t)n_rel * 4);                                     // the animal list
+    add((size_t)B * n_rel * 8);                                 // the reliabilities
+    add(reliab_in_lds(c, sd) ? 0                                // right-hand sides / V of one launch's slabs
+                             : (size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W * 8);
+  }
   return s + 4096;
 }
 
@@ -716,6 +730,7 @@ int tblup_ctx_create(const int8_t* geno, int64_t n, int64_t P, int layout, const
   if (const char* e = getenv("TBLUP_DIAG_D")) c->diag_d = std::max(-1, std::min(1, atoi(e)));
   if (const char* e = getenv("TBLUP_DIAG_E")) c->diag_e = std::max(-1, std::min(2, atoi(e)));
   if (const char* e = getenv("TBLUP_PAD_FIRST")) c->pad_first = atoi(e) != 0;
+  if (const char* e = getenv("TBLUP_RELIAB_LDS")) c->reliab_lds = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_NRS")) c->nrs = (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4) ? atoi(e) : 0;
   if (const char* e = getenv("TBLUP_CHAIN_DEBUG")) {
     int sp = 0, dl = 0, sh = 0;
@@ -930,7 +945,8 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
 // tblup_eval_batch, and with `fo` tblup_fit_batch (capi_model.hip): the same chunks through the same
 // pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
 int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
-                                double h2, int branch, double* fitness, double* ebv, const FitOut* fo) {
+                                double h2, int branch, double* fitness, double* ebv, const FitOut* fo,
+                                const RelOut* ro) {
   g_err.clear();
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
@@ -943,20 +959,22 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
   HostEntry he(c);
   const EvalDims d = dims_of(c, *sp);
   const bool want_ebv = ebv != nullptr;
+  const int64_t n_rel = ro ? ro->n_pred : 0;
   const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
+  const bool rel_lds = reliab_in_lds(c, sd);
   int64_t b0 = 0;
   while (b0 < batch) {
     // grow the chunk while it fits the workspace budget
     int64_t b1 = b0, sum_k = 0;
     while (b1 < batch) {
       const int64_t k = offsets[b1 + 1] - offsets[b1];
-      if (b1 > b0 && chunk_bytes(c, d, sd, b1 + 1 - b0, sum_k + k, want_ebv, fo != nullptr) > c->budget) break;
+      if (b1 > b0 && chunk_bytes(c, d, sd, b1 + 1 - b0, sum_k + k, want_ebv, fo != nullptr, n_rel) > c->budget) break;
       if (b1 - b0 >= 65535) break;
       sum_k += k;
       ++b1;
     }
     const int64_t B = b1 - b0;
-    const size_t need = chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr);
+    const size_t need = chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (int rc = dev_alloc(c, c->ws, need)) return rc;
     Carve cv{(char*)c->ws.p};
@@ -966,17 +984,23 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
     double* d_ebv = want_ebv ? cv.take<double>((size_t)B * d.nt * d.nV) : nullptr;
     double* d_cen = fo ? cv.take<double>((size_t)sum_k) : nullptr;
     double* d_eff = fo ? cv.take<double>((size_t)d.nt * sum_k) : nullptr;
+    int32_t* d_an = n_rel ? cv.take<int32_t>((size_t)n_rel) : nullptr;
+    double* d_rel = n_rel ? cv.take<double>((size_t)B * n_rel) : nullptr;
+    double* d_vscr = (n_rel && !rel_lds)
+                         ? cv.take<double>((size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W)
+                         : nullptr;
     std::vector<int64_t> hoff(B + 1);
     for (int64_t b = 0; b <= B; ++b) hoff[b] = offsets[b0 + b] - offsets[b0];
     HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(d_off, hoff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (n_rel) HIPCHK(hipMemcpyAsync(d_an, ro->animals, (size_t)n_rel * 4, hipMemcpyHostToDevice, c->stream));
     const Carve cv0 = cv;
     for (int pass = 0;; ++pass) {
       // pass 1: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
       Carve cvp = cv0;
       CholLaunch cl{};
       if (int rc = run_chunk(c, *sp, d, sd, c->stream, d_idx, d_off, hoff.data(), B, h2, branch, cvp, d_fit, d_ebv,
-                             pass ? 3 : 0, nullptr, nullptr, nullptr, fo ? &cl : nullptr))
+                             pass ? 3 : 0, nullptr, nullptr, nullptr, (fo || n_rel) ? &cl : nullptr))
         return rc;
       const int32_t seq = c->last_chain_seq;
       if (fo && pass == 0) {
@@ -987,6 +1011,13 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
         for (int t = 0; t < d.nt; ++t)
           HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
                                 (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
+      }
+      if (n_rel && pass == 0) {
+        // like the effects: L, the diagonal inverses, u and the scalars only, so no wait for the solve
+        HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, d_an, n_rel, rel_lds,
+                             rel_slabs(c, sd, B, n_rel), d_vscr, d_rel, c->stream));
+        HIPCHK(hipMemcpyAsync(ro->reliability + b0 * n_rel, d_rel, (size_t)B * n_rel * 8, hipMemcpyDeviceToHost,
+                              c->stream));
       }
       HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
       if (want_ebv)

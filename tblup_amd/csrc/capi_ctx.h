@@ -120,6 +120,9 @@ struct tblup_ctx {
   // SNP form: the padding rows (ns - k) lead the system, so the contractions over block column 0
   // skip them (TBLUP_PAD_FIRST=0: trailing padding, equal up to rounding -- a test knob).
   int pad_first = 1;
+  // TBLUP_RELIAB_LDS=0: k_reliab keeps its right-hand sides in the workspace at every system size (what
+  // it does above 1024 rows anyway; the same bits -- a test knob)
+  int reliab_lds = 1;
   std::vector<int64_t> fold_hoff;   // host offsets of the last fold-fused chunk (host-side shapes only)
   DevBuf chain;          // its flags [B][chain_flags(NT)], the expiry ring [CHAIN_ERR_RING] and one
                          // scratch word (zeroed when allocated)
@@ -144,7 +147,15 @@ struct FitOut {
   double* center;
   double* effects;
 };
-// tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual
+// Host output of tblup_reliability_batch: reliability [batch][n_pred] of the listed panel rows
+// (already checked against [0, n))
+struct RelOut {
+  const int32_t* animals;
+  int64_t n_pred;
+  double* reliability;
+};
+// tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual;
+// ro != null: also the reliabilities of ro's animals under every individual's model
 int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
-                    int branch, double* fitness, double* ebv, const FitOut* fo);
+                    int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr);
 }  // namespace tblup_capi

@@ -25,6 +25,34 @@ int tblup_fit_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_
   return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, &fo);
 }
 
+int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                            const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                            double* intercept, double* center, double* effects, double* reliability) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
+  const bool any = intercept || center || effects;
+  if (any && !(intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
+  std::vector<int32_t> a32((size_t)n_pred);
+  for (int64_t i = 0; i < n_pred; ++i) {
+    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
+    a32[i] = (int32_t)animals[i];
+  }
+  if (batch == 0 || n_pred == 0) return 0;
+  if (!reliability) return fail(TBLUP_ERR_ARG, "null reliability");
+  std::vector<double> fit_local;
+  if (!fitness) {
+    fit_local.resize((size_t)batch);
+    fitness = fit_local.data();
+  }
+  const FitOut fo{intercept, center, effects};
+  const RelOut ro{a32.data(), n_pred, reliability};
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, any ? &fo : nullptr, &ro);
+}
+
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,
                         const int64_t* offsets, int64_t batch, const double* intercept, const double* center,
                         const double* effects, int64_t n_traits, double* ebv) {

@@ -1,0 +1,306 @@
+// Reliabilities of predicted breeding values (tblup_reliability_batch): for every listed animal a of
+// the panel, from the Cholesky factor L L^T and the inverted diagonal tiles X_J = L_JJ^{-1} that the
+// chunk's pipeline left in the workspace (what k_effects reads; neither solve kernel writes them),
+//   kernel form  rel(a) = |L^{-1} k_Ta|^2 / K_aa,            k_Ta = W_T w_a / d, K_aa = w_a.w_a / d
+//   SNP form     rel(a) = 1 - lambda |L^{-1} w_a|^2 / (w_a.w_a)
+// with w_a = A[a] - c the animal's centred row over the model's SNPs (the two are equal by the
+// Woodbury identity).  No phenotype and no variance component enters.
+//
+// One 512-thread workgroup per (model, slab of RW = 16 listed animals); workgroups are independent
+// (no flags, no hand-offs, every loop bounded by the system's shape).
+//   phase 1: the slab's right-hand sides R [ns][16] into V.  SNP form: gathered from the SNP-major
+//     int8 panel and centred with the centre k_effects writes; w_a.w_a in one fma chain in list order.
+//     Kernel form: the exact counts (A_T A_a^T)_ta on int8 MFMA (v_mfma_i32_16x16x64_i8) -- the train
+//     rows from the chunk's 2-bit packed panel (unpack16), the animals' genotypes gathered into LDS in
+//     the same byte order -- then (G_ta - (u_t + u_a)/N + q/N^2)/d in fp64; u_a and G_aa are exact
+//     integer sums.
+//   phase 2: blocked forward substitution with 16 right-hand sides on fp64 MFMA
+//     (v_mfma_f64_16x16x4_f64), block row by block row: V_J = X_J (R_J - sum_{L<J} L_JL V_L); wave q
+//     owns rows 16q .. 16q+15 of the block row, one accumulator chain over L = J0 .. J-1 and the rows
+//     of each tile in order (L read once per slab, from L2: a model's slabs run on one XCD), then
+//     over the blocks s = 0 .. q of X_J.  Every lane adds the squares of
+//     its four rows of V_J to one running sum; the 32 partial sums of an animal are added in a fixed
+//     order at the end.
+// So an animal's value is a function of its genotypes and the system alone: not of n_pred, of its
+// place in the list, of its slab or of the chunking.
+// V lives in LDS when ns x 16 doubles fit beside the staging buffers (ns <= 1024), else in a
+// workspace slice of the workgroup's own -- the same arithmetic in the same order.
+#include <algorithm>
+
+#include "i8_tile.h"
+
+namespace tblup {
+
+namespace {
+
+constexpr int RTH = 512;          // 8 waves
+constexpr int RKC = 1024;         // kernel form: SNPs per LDS stage of the animals' genotypes
+constexpr int RKS = RKC + 16;     // its row stride (bytes): 16 animals' 16-B reads on distinct banks
+constexpr int RPARTS = RTH / RELIAB_W;
+constexpr int RSTEP = 64;         // rows of L per step of the substitution's chain (16 MFMAs)
+
+template <int FORM, bool VLDS>
+__global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __restrict__ geno,
+                                                const int32_t* __restrict__ csA,
+                                                const int32_t* __restrict__ animals, int64_t n_pred, int64_t slab0,
+                                                int64_t nslab, double* __restrict__ vscr,
+                                                double* __restrict__ rel) {
+  extern __shared__ __attribute__((aligned(16))) double dyn[];
+  __shared__ double nrm[RTH];
+  __shared__ double den[RELIAB_W];   // SNP form: w_a.w_a; kernel form: K_aa
+  constexpr int W = RELIAB_W;
+  const int t = threadIdx.x, l = t & 63, q = __builtin_amdgcn_readfirstlane(t >> 6), lc = l & 15, lg = l >> 4;
+  // consecutive slabs of a model on one XCD, so that its L tiles are shared in that XCD's L2 (speed only)
+  const int64_t blk = xcd_remap(blockIdx.x, gridDim.x);
+  const int64_t b = blk / nslab, sl = slab0 + blk % nslab;
+  const int64_t ns = c.sd.ns, n = c.d.n, P = c.d.P;
+  const int NT = c.sd.NT;
+  double* V;
+  if constexpr (VLDS) V = dyn;
+  else V = vscr + (int64_t)blockIdx.x * ns * W;
+  const double* sc = c.scal + b * SCAL;
+  const double lam = sc[SC_LAM], dd = sc[SC_D], invd = sc[SC_INVD];
+  const int64_t kk = (int64_t)sc[SC_K], pad = (int64_t)sc[SC_PAD], nrow = (int64_t)sc[SC_NROW];
+  const bool gblup = (int)sc[SC_MODE] == 1;
+  const int fo = fold_of(c.ft, b);
+  const int32_t* cs = gblup ? csA : c.ft.csT[fo];
+  const double N = gblup ? (double)n : (double)c.d.nT;
+  const int64_t o0 = c.off[b];
+  // block rows that hold real system rows (the rest is identity padding with zero right-hand sides)
+  const int J0 = (int)(pad / TILE), J1 = (int)((pad + nrow + TILE - 1) / TILE);
+  // phase 1 thread map: animal ta of the slab, part tp of RPARTS
+  const int ta = t & (W - 1), tp = t / W;
+  const int64_t va = sl * W + ta;
+  const int64_t an = va < n_pred ? animals[va] : animals[0];
+
+  if constexpr (FORM == FORM_PRIMAL) {
+    // (every row loads -- a padding row the first SNP's values, then dropped -- so that the unrolled
+    // loop's loads are in flight together)
+#pragma unroll 8
+    for (int64_t r = (int64_t)J0 * TILE + tp; r < (int64_t)J1 * TILE; r += RPARTS) {
+      const bool real = sys_real(r, pad, nrow);
+      const int64_t col = snp_col(c.idx[o0 + (real ? r - pad : 0)], P);
+      const double x = (double)geno[col * n + an] - (double)cs[col] / N;
+      V[r * W + ta] = real ? x : 0.0;
+    }
+    __syncthreads();
+    if (t < W) {
+      double ww = 0.0;
+#pragma unroll 8
+      for (int64_t j = 0; j < kk; ++j) {
+        const double x = V[(pad + j) * W + t];
+        ww = __builtin_fma(x, x, ww);
+      }
+      den[t] = ww;
+    }
+  } else {
+    __shared__ __attribute__((aligned(16))) int8_t ab[W * RKS];
+    __shared__ long long ired[2][W][RPARTS];
+    __shared__ double ua_s[W];
+    const uint8_t* pb = c.panel + b * c.pstride;
+    const int64_t pk_row = (c.sd.cblk + 3) / 4 * 64;   // dual_pk_row
+    const int64_t nrb = (int64_t)J1 * (TILE / 16);   // 16-row blocks of the real block rows
+    long long iu = 0, ig = 0;
+    for (int64_t k0 = 0; k0 < kk; k0 += RKC) {
+      const int kc = (int)min((int64_t)RKC, kk - k0);
+      const int kc64 = (kc + KBLK - 1) / KBLK * KBLK;
+      for (int jj = tp; jj < kc64; jj += RPARTS) {
+        int g = 0;
+        if (jj < kc) {
+          const int64_t col = snp_col(c.idx[o0 + k0 + jj], P);
+          g = geno[col * n + an];
+          iu += (long long)g * cs[col];
+          ig += (long long)g * g;
+        }
+        // unpack16's order: byte m of dword e of a 16-SNP group is its SNP 4m + e
+        const int e16 = jj & 15;
+        ab[ta * RKS + (jj & ~15) + 4 * (e16 & 3) + (e16 >> 2)] = (int8_t)g;
+      }
+      __syncthreads();
+      for (int64_t rb = q; rb < nrb; rb += RTH / 64) {
+        v4i acc = {0, 0, 0, 0};
+        const uint8_t* prow = pb + (16 * rb + lc) * pk_row + k0 / 4 + 4 * lg;
+        for (int kb = 0; kb < kc64 / KBLK; ++kb) {
+          const v4i a = unpack16(*reinterpret_cast<const uint32_t*>(prow + 16 * kb));
+          const v4i bv = *reinterpret_cast<const v4i*>(ab + lc * RKS + KBLK * kb + 16 * lg);
+          acc = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bv, acc, 0, 0, 0);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int64_t vi = (16 * rb + 4 * lg + r) * W + lc;
+          V[vi] = (k0 == 0 ? 0.0 : V[vi]) + (double)acc[r];   // exact integers
+        }
+      }
+      __syncthreads();
+    }
+    ired[0][ta][tp] = iu;
+    ired[1][ta][tp] = ig;
+    __syncthreads();
+    const double sa = sc[SC_SA], cN = sc[SC_CN];
+    if (t < W) {
+      long long su = 0, sg = 0;
+      for (int p = 0; p < RPARTS; ++p) {
+        su += ired[0][t][p];
+        sg += ired[1][t][p];
+      }
+      const double ua = (double)su;
+      ua_s[t] = ua;
+      den[t] = ((double)sg - (ua + ua) * sa + cN) * invd;
+    }
+    __syncthreads();
+    const double* ub = c.u + b * c.sd.prow;
+    const double ua = ua_s[lc];
+    for (int64_t rb = q; rb < nrb; rb += RTH / 64) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int64_t row = 16 * rb + 4 * lg + r;
+        const int64_t vi = row * W + lc;
+        V[vi] = row < nrow ? (V[vi] - (ub[row] + ua) * sa + cN) * invd : 0.0;
+      }
+    }
+  }
+  __syncthreads();
+
+  // phase 2: V_J = X_J (R_J - sum_{L<J} L_JL V_L)
+  const double* Lb = c.L + b * l_stride(NT);
+  const double* Db = c.Dinv + b * (int64_t)NT * NPACK * BLKD;
+  double nacc = 0.0;
+  // The tiles (J, Lc), Lc = 0 .. J-1, lie back to back and each holds L_JL^T (element [cc][r] =
+  // L_JL[r][cc]), so row kx = 128 Lc + cc of that run holds column kx of block row J: one chain over
+  // kx in order, RSTEP rows per step, through a ring of three register sets -- two steps' L values are
+  // in flight while a step's MFMAs run, and the first two steps of block row J + 1 (which need no V)
+  // are issued before block row J's barriers.  The zero rows of V that lead the system are skipped in
+  // whole steps.
+  constexpr int NA = RSTEP / 4;
+  const double* lrow = Lb + 16 * q + lc;
+  const double* vcol = V + lc;
+  const int ks = (int)(pad / RSTEP) * RSTEP;
+  double a0[NA], a1[NA], a2[NA];
+  auto lda = [&](double (&a)[NA], int k) {
+#pragma unroll
+    for (int e = 0; e < NA; ++e) a[e] = lrow[(int64_t)(k + 4 * e + lg) * TILE];
+  };
+  auto prime = [&](int Jn) {
+    lrow = Lb + (int64_t)Jn * NT * TILE * TILE + 16 * q + lc;
+    if (ks < Jn * TILE) lda(a0, ks);
+    if (ks + RSTEP < Jn * TILE) lda(a1, ks + RSTEP);
+  };
+  prime(J0);
+  for (int J = J0; J < J1; ++J) {
+    v4d acc = {0.0, 0.0, 0.0, 0.0};
+    // X_J's blocks (q, s), s = 0 .. q, of this wave through a ring of four register sets, the first
+    // four in flight under the chain below: stored block (q, s) element [r][cc] = X[16q + cc][16s + r]
+    const double* xq = Db + (int64_t)J * NPACK * BLKD + pk(q, 0);
+    double xr[4][4];
+    auto ldx = [&](double (&x)[4], int s) {
+#pragma unroll
+      for (int k4 = 0; k4 < 4; ++k4) x[k4] = xq[s * BLKD + bo(4 * k4 + lg, lc)];
+    };
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      if (i <= q) ldx(xr[i], i);
+    {
+      const int ke = J * TILE;
+      auto mm = [&](const double (&a)[NA], int k) {
+#pragma unroll
+        for (int e = 0; e < NA; ++e)
+          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[e], vcol[(int64_t)(k + 4 * e + lg) * W], acc, 0, 0, 0);
+      };
+      for (int k = ks; k < ke; k += 3 * RSTEP) {
+        if (k + 2 * RSTEP < ke) lda(a2, k + 2 * RSTEP);
+        mm(a0, k);
+        if (k + RSTEP < ke) {
+          if (k + 3 * RSTEP < ke) lda(a0, k + 3 * RSTEP);
+          mm(a1, k + RSTEP);
+        }
+        if (k + 2 * RSTEP < ke) {
+          if (k + 4 * RSTEP < ke) lda(a1, k + 4 * RSTEP);
+          mm(a2, k + 2 * RSTEP);
+        }
+      }
+    }
+    if (J + 1 < J1) prime(J + 1);
+    double* vj = V + ((int64_t)J * TILE) * W;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int i = (16 * q + lg + 4 * r) * W + lc;
+      vj[i] = vj[i] - acc[r];
+    }
+    __syncthreads();
+    v4d acc2 = {0.0, 0.0, 0.0, 0.0};
+    for (int s0 = 0; s0 <= q; s0 += 4) {
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int s = s0 + i;
+        if (s <= q) {
+#pragma unroll
+          for (int k4 = 0; k4 < 4; ++k4)
+            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xr[i][k4], vj[(16 * s + 4 * k4 + lg) * W + lc], acc2, 0, 0, 0);
+          if (s + 4 <= q) ldx(xr[i], s + 4);
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      vj[(16 * q + lg + 4 * r) * W + lc] = acc2[r];
+      nacc = __builtin_fma(acc2[r], acc2[r], nacc);
+    }
+    __syncthreads();
+  }
+  nrm[t] = nacc;
+  __syncthreads();
+  if (t < W && sl * W + t < n_pred) {
+    double s2 = 0.0;
+    for (int w = 0; w < RTH / 64; ++w)
+      for (int g = 0; g < 4; ++g) s2 += nrm[64 * w + 16 * g + t];
+    double r;
+    if constexpr (FORM == FORM_PRIMAL) r = 1.0 - lam * s2 / den[t];
+    else r = s2 / den[t];
+    if (dd == 0.0 || den[t] == 0.0 || sc[SC_BAD] != 0.0) r = __builtin_nan("");
+    rel[b * n_pred + sl * W + t] = r;
+  }
+}
+
+}  // namespace
+
+bool reliab_lds(const SysDims& sd) { return sd.ns * RELIAB_W * 8 <= RELIAB_LDS_V; }
+
+int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int64_t aim) {
+  const int64_t nslab = (n_pred + RELIAB_W - 1) / RELIAB_W;
+  int64_t S = nslab;
+  if (!lds) S = std::min(S, std::max<int64_t>(1, aim / (B * sd.ns * RELIAB_W * 8)));
+  return std::max<int64_t>(1, std::min(S, (int64_t)0x7fffffff / std::max<int64_t>(B, 1)));
+}
+
+hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
+                         int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s) {
+  if (c.B < 1 || n_pred < 1) return hipSuccess;
+  if (lds && !reliab_lds(c.sd)) return hipErrorInvalidValue;
+  if ((!lds && !vscr) || S < 1 || c.B * S > 0x7fffffff) return hipErrorInvalidValue;
+  const int64_t nslab = (n_pred + RELIAB_W - 1) / RELIAB_W;
+  const size_t shm = lds ? (size_t)c.sd.ns * RELIAB_W * 8 : 0;
+  auto launch = [&](const void* fn, auto kernel) -> hipError_t {
+    if (shm > 32 * 1024) {
+      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+      if (e != hipSuccess) return e;
+    }
+    for (int64_t s0 = 0; s0 < nslab; s0 += S) {
+      const int64_t sn = std::min(S, nslab - s0);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)(c.B * sn)), dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn,
+                         vscr, rel);
+      hipError_t e = hipGetLastError();
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  };
+  const int sel = (c.sd.form == FORM_PRIMAL ? 2 : 0) + (lds ? 1 : 0);
+  switch (sel) {
+    case 0: return launch((const void*)k_reliab<FORM_DUAL, false>, k_reliab<FORM_DUAL, false>);
+    case 1: return launch((const void*)k_reliab<FORM_DUAL, true>, k_reliab<FORM_DUAL, true>);
+    case 2: return launch((const void*)k_reliab<FORM_PRIMAL, false>, k_reliab<FORM_PRIMAL, false>);
+    default: return launch((const void*)k_reliab<FORM_PRIMAL, true>, k_reliab<FORM_PRIMAL, true>);
+  }
+}
+
+}  // namespace tblup

@@ -360,6 +360,22 @@ hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitne
 hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
                           hipStream_t s);
 
+// ---- launcher (k_reliab.hip): reliabilities of any animals of the panel from a chunk's factor ----
+// rel[b * n_pred + v] for animal animals[v] (a row of geno_sm, int8 [P][n]) under model b of the chunk
+// whose pipeline left L, Dinv, u, scal (and, kernel form, the packed panel) in c: one workgroup per
+// (model, slab of RELIAB_W listed animals), a blocked forward substitution on fp64 MFMA.  lds: the
+// slab's ns x RELIAB_W right-hand sides live in LDS (reliab_lds); else in vscr, ns x RELIAB_W doubles
+// for each of the B x S workgroups of one launch (the list is walked S slabs at a time, in several
+// launches when S = reliab_slabs(aim bytes of slices) is below the list's slabs).
+// The same bits either way, and for an animal wherever it stands in the list.
+constexpr int RELIAB_W = 16;
+constexpr int64_t RELIAB_LDS_V = 128 * 1024;          // bytes of LDS for V beside the staging buffers
+constexpr int64_t RELIAB_SCRATCH = 64ll << 20;        // aim of the workspace slices' size (>= one slab per model)
+bool reliab_lds(const SysDims& sd);
+int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int64_t aim);
+hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
+                         int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s);
+
 // ---- launcher (k_model.hip): EBVs of any animals of the panel from fitted models ----
 // ebv[(m * nt + t) * n_pred + v] = intercept[m * nt + t] + sum_j (x[animals[v], idx_j] - center_j)
 // effects[t * plane + j], j = off[m] .. off[m + 1] in that order for every animal (the same bits

@@ -159,12 +159,20 @@ class GpuBlupEngine:
         return (fit, ebv) if return_ebv else fit
 
     # ------------------------------------------------------- taking the model out
-    def fit(self, genomes, train, valid, h2, branch="auto"):
+    def fit(self, genomes, train, valid, h2, branch="auto", reliability_of=None):
         """evaluate() plus what it fitted: one PanelModel per selected-index set (tblup_fit_batch),
         whose `fitness` is evaluate()'s value bit for bit.  Out-of-range indices raise
-        TblupIndexError; a degenerate panel gives NaN effects, not an error."""
+        TblupIndexError; a degenerate panel gives NaN effects, not an error.
+        reliability_of: a list of animals (row ids of the panel) -- the return value is then
+        (models, reliabilities) from one pass (tblup_reliability_batch), the models bit-identical to
+        fit()'s and the (len(genomes), len(animals)) array to reliability()'s."""
         from .model import PanelModel
         self._settle()
+        an = None
+        if reliability_of is not None:
+            an = _as_int64(reliability_of)
+            if an.ndim != 1:
+                raise ValueError("reliability_of must be a 1-D list of row ids")
         sid = self.split_id(train, valid)
         idx, offsets = concat_genomes(genomes)
         B, nt, total = len(genomes), self.n_traits, int(offsets[-1])
@@ -172,7 +180,14 @@ class GpuBlupEngine:
         intercept = np.empty((B, nt), dtype=np.float64)
         center = np.empty(total, dtype=np.float64)
         effects = np.empty((nt, total), dtype=np.float64)
-        if B:
+        rel = None if an is None else np.empty((B, len(an)), dtype=np.float64)
+        if B and an is not None and len(an):
+            _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
+                self._ctx, sid, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64),
+                _ptr(offsets, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], _ptr(fit, ctypes.c_double),
+                _ptr(intercept, ctypes.c_double), _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double),
+                _ptr(rel, ctypes.c_double)))
+        elif B:
             _native.check("tblup_fit_batch", self._lib.tblup_fit_batch(
                 self._ctx, sid, _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64), B, float(h2),
                 _native.BRANCH[branch], _ptr(fit, ctypes.c_double), _ptr(intercept, ctypes.c_double),
@@ -184,7 +199,31 @@ class GpuBlupEngine:
             fitted = branch if branch != "auto" else ("gblup" if hi - lo > self.n_animals else "snp")
             models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
                                      fit[b]))
-        return models
+        return models if an is None else (models, rel)
+
+    def reliability(self, genomes, train, valid, h2, animals, branch="auto"):
+        """Reliability (squared accuracy, 1 - PEV / (sigma_g^2 K_aa)) of the genomic value of each of
+        `animals` (row ids of this engine's panel: any order, repeats allowed, any or no split role)
+        under the model each selected-index set fits on (train, valid): an ndarray
+        (len(genomes), len(animals)) from tblup_reliability_batch (include/tblup_gpu.h has the
+        definition).  It needs no phenotype: with several traits it is still one number per (model,
+        animal).  The snp branch's intercept is taken as known.  The factor behind it is not kept, so
+        candidates must be rows of this engine's panel.  A degenerate panel gives NaN; an animal's
+        value does not depend on the list it comes in."""
+        self._settle()
+        an = _as_int64(animals)
+        if an.ndim != 1:
+            raise ValueError("animals must be a 1-D list of row ids")
+        sid = self.split_id(train, valid)
+        idx, offsets = concat_genomes(genomes)
+        B = len(genomes)
+        rel = np.empty((B, len(an)), dtype=np.float64)
+        if B and len(an):
+            _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
+                self._ctx, sid, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64),
+                _ptr(offsets, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], None, None, None, None,
+                _ptr(rel, ctypes.c_double)))
+        return rel
 
     def predict(self, models, animals):
         """EBVs of `animals` (row ids of this engine's panel: any order, repeats allowed, no split

@@ -376,15 +376,8 @@ class BlupParallelEvaluator(ParallelEvaluator):
                 genomes.append(np.union1d(indv.genome, np.array([])).astype(int))
         return list(self._fitness(genomes, train, self.testing_indices))
 
-    def fit_models(self, population, final=True, train=None, valid=None):
-        """The fitted model (tblup_amd.model.PanelModel) of every individual, in population order.
-
-        final=True is evaluate_testing's set-up -- train = T u V, valid = the testing animals, the
-        genome merged with the removed SNPs -- so each model's `fitness` is evaluate_testing's value
-        bit for bit; final=False fits on the evaluator's own (training, validation) split and the
-        plain genome.  Explicit `train` / `valid` override either side of the split.
-        Draws no RNG and uses no collective: under torch.distributed every rank fits the population
-        it is given (call it on one rank, or with that rank's share)."""
+    def _model_setup(self, population, final, train, valid):
+        """Genomes and split of fit_models / reliability: final=True is evaluate_testing's set-up."""
         if self.engine is None:
             raise AttributeError("Workers are not set up.")
         genomes = []
@@ -400,7 +393,31 @@ class BlupParallelEvaluator(ParallelEvaluator):
                      else self.training_indices)
         if valid is None:
             valid = self.testing_indices if final else self.validation_indices
-        return self.engine.fit(genomes, train, valid, self.h2)
+        return genomes, train, valid
+
+    def fit_models(self, population, final=True, train=None, valid=None, reliability_of=None):
+        """The fitted model (tblup_amd.model.PanelModel) of every individual, in population order.
+
+        final=True is evaluate_testing's set-up -- train = T u V, valid = the testing animals, the
+        genome merged with the removed SNPs -- so each model's `fitness` is evaluate_testing's value
+        bit for bit; final=False fits on the evaluator's own (training, validation) split and the
+        plain genome.  Explicit `train` / `valid` override either side of the split.
+        reliability_of: a list of animals -- returns (models, reliabilities) from the same pass
+        (GpuBlupEngine.fit).
+        Draws no RNG and uses no collective: under torch.distributed every rank fits the population
+        it is given (call it on one rank, or with that rank's share)."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        if reliability_of is None:
+            return self.engine.fit(genomes, train, valid, self.h2)
+        return self.engine.fit(genomes, train, valid, self.h2, reliability_of=reliability_of)
+
+    def reliability(self, population, animals, final=True, train=None, valid=None):
+        """Reliabilities of the genomic values of `animals` (row ids of the evaluator's data, in or out
+        of any split) under every individual's model, (len(population), len(animals)):
+        GpuBlupEngine.reliability with fit_models' split and genome conventions.  No RNG, no
+        collective: under torch.distributed every rank computes what it is given."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
     def predict(self, models, animals):
         """EBVs of `animals` (row ids of the evaluator's data, any order, in or out of any split)

@@ -8,10 +8,14 @@ numbers go to PERFLOG.md.  One JSON line per part:
            must read (batch x k x n genotype bytes) against the 8 TB/s HBM figure
   dual     a config-4-shaped small stand-in in the kernel form (1200 x 20k, k = 1500 > n: gblup,
            n_T 768, 32 individuals): fit against evaluate, predict for all animals
-  --stats CSV   the k_effects / k_predict share of a `rocprofv3 --kernel-trace --stats` run of
+  reliability  config 2 again: reliabilities of all 2000 animals under the 256 models
+           (tblup_reliability_batch) against fit and evaluate from the same process, alternated; the
+           derived fp64 MFMA floor of k_reliab (batch x n_pred x ns^2 flop over the measured 72.7 TF/s
+           peak); and one kernel-form shape (the `dual` stand-in, all 1200 animals)
+  --stats CSV   the k_effects / k_predict / k_reliab share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -112,13 +116,43 @@ def predict_all(eng, models, n, reps):
                          "the kernel alone: --stats"}
 
 
+F64_MFMA_TFS = 72.7   # measured fp64 MFMA peak (README, profiles/r02f_mfma_peak.json)
+
+
+def reliability_all(eng, genomes, T, V, n, ns, reps):
+    """reliability() for the whole herd against fit() and evaluate(), alternated on one engine."""
+    an = np.arange(n)
+    te, tf, tr = [], [], []
+    rel = None
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        eng.evaluate(genomes, T, V, 0.4)
+        t1 = time.perf_counter()
+        eng.fit(genomes, T, V, 0.4)
+        t2 = time.perf_counter()
+        rel = eng.reliability(genomes, T, V, 0.4, an)
+        t3 = time.perf_counter()
+        if r >= 2:
+            te.append(t1 - t0)
+            tf.append(t2 - t1)
+            tr.append(t3 - t2)
+    flop = float(len(genomes)) * n * ns * ns
+    return {"evaluate_ms": med_ms(te), "fit_ms": med_ms(tf), "reliability_ms": med_ms(tr),
+            "extra_ms_over_evaluate": round(med_ms(tr) - med_ms(te), 4),
+            "reliability_ms_all": [round(x * 1e3, 3) for x in tr], "k_reliab_flop": flop,
+            "k_reliab_floor_ms": round(flop / (F64_MFMA_TFS * 1e12) * 1e3, 3),
+            "rel_min": float(np.nanmin(rel)), "rel_max": float(np.nanmax(rel)), "finite": bool(np.all(np.isfinite(rel))),
+            "note": "the call is the whole evaluation plus k_reliab and the D2H copy of the reliabilities; "
+                    "the kernel alone: --stats; the floor is derived (flop / measured fp64 MFMA peak)"}
+
+
 def stats_share(path):
     rows = list(csv.DictReader(open(path)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
     for r in rows:
         name = r["Name"]
-        for key in ("k_effects", "k_predict", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_effects", "k_predict", "k_reliab", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -152,6 +186,19 @@ def main():
                 host = models[0].predict(geno)
                 sp["max_rel_vs_numpy_model0"] = float(np.max(np.abs(out[0] - host)) / np.max(np.abs(host)))
                 print(json.dumps({"part": "predict", "config": "config2", "models": pop, "k": k, "animals": n, **sp}))
+    if "reliability" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            st = reliability_all(eng, genomes, T, V, n, 1024, args.reps)
+            print(json.dumps({"part": "reliability", "config": "config2", "models": pop, "k": k, "animals": n,
+                              "form": "snp", "ns": 1024, **st}))
+        n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            st = reliability_all(eng, genomes, T, V, n, 768, args.reps)
+            print(json.dumps({"part": "reliability", "config": "config4-shaped stand-in: %d x %d, k=%d (gblup), n_T=%d"
+                              % (n, P, k, nT), "models": pop, "k": k, "animals": n, "form": "kernel", "ns": 768, **st}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
