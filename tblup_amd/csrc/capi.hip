@@ -51,8 +51,68 @@ void dev_free(tblup_ctx* c, DevBuf& b) {
   b.release();
 }
 
+void Split::release(tblup_ctx* c) {
+  for (DevBuf* b : {&gpk, &colsumT, &xty, &yT, &yV, &ymu}) dev_free(c, *b);
+}
+
 int check_ctx(tblup_ctx* c) {
   if (!c) return fail(TBLUP_ERR_ARG, "null context");
+  return 0;
+}
+
+int ws_check(const tblup_ctx* c, const Carve& cv) {
+  if (cv.base >= (char*)c->ws.p && cv.base + cv.used <= (char*)c->ws.p + c->ws.bytes) return 0;
+  return fail(TBLUP_ERR_STATE, "internal error: workspace carve of " + std::to_string(cv.used) +
+                                   " bytes overruns the " + std::to_string(c->ws.bytes) + "-byte workspace");
+}
+
+int check_indices(const tblup_ctx* c, const int64_t* idx, int64_t count) {
+  for (int64_t i = 0; i < count; ++i)
+    if (idx[i] < -c->P || idx[i] >= c->P)
+      return fail(TBLUP_ERR_INDEX, "index " + std::to_string(idx[i]) + " is out of bounds for axis 1 with size " +
+                                       std::to_string(c->P));
+  return 0;
+}
+
+int check_counts(const int64_t* offsets, int64_t batch, const char* who) {
+  for (int64_t b = 0; b < batch; ++b)
+    if (offsets[b + 1] - offsets[b] < 1) return fail(TBLUP_ERR_ARG, std::string("every ") + who + " needs k >= 1 indices");
+  return 0;
+}
+
+int for_each_chunk(tblup_ctx* c, const int64_t* offsets, int64_t batch, int64_t max_B, const ChunkBytes& bytes,
+                   const std::function<int(const Chunk&)>& body) {
+  std::vector<int64_t> hoff;
+  int64_t b0 = 0;
+  while (b0 < batch) {
+    // grow the chunk while it fits the workspace budget and one launch's grid
+    int64_t b1 = b0, sum_k = 0;
+    hoff.assign(1, 0);
+    while (b1 < batch) {
+      const int64_t k = offsets[b1 + 1] - offsets[b1];
+      hoff.push_back(sum_k + k);
+      if (b1 > b0 && (bytes(hoff.data(), b1 + 1 - b0, sum_k + k) > c->budget || b1 + 1 - b0 > max_B)) {
+        hoff.pop_back();
+        break;
+      }
+      sum_k += k;
+      ++b1;
+    }
+    const int64_t B = b1 - b0;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (int rc = dev_alloc(c, c->ws, bytes(hoff.data(), B, sum_k))) return rc;
+    if (int rc = body(Chunk{b0, B, sum_k, hoff.data()})) return rc;
+    b0 = b1;
+  }
+  return 0;
+}
+
+int upload_chunk(tblup_ctx* c, Carve& cv, const int64_t* idx, const int64_t* offsets, const Chunk& ck, int64_t** d_idx,
+                 int64_t** d_off) {
+  *d_idx = cv.take<int64_t>((size_t)ck.sum_k);
+  *d_off = cv.take<int64_t>((size_t)ck.B + 1);
+  HIPCHK(hipMemcpyAsync(*d_idx, idx + offsets[ck.b0], (size_t)ck.sum_k * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(*d_off, ck.hoff, (size_t)(ck.B + 1) * 8, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 
@@ -106,18 +166,6 @@ int timed(tblup_ctx* c, hipStream_t s, int cls, double flops, double bytes, F&& 
   }
   return 0;
 }
-
-struct Carve {
-  char* base;
-  size_t used = 0;
-  template <typename T>
-  T* take(size_t count) {
-    used = round_up((int64_t)used, 256);
-    T* p = reinterpret_cast<T*>(base + used);
-    used += count * sizeof(T);
-    return p;
-  }
-};
 
 // TBLUP_DBG_SKIP (phase ablation, results wrong when set): honoured by diagnostic builds only
 // (tools/ab_build_defs.sh 'diag=-DTBLUP_DIAG_BUILD'); the production library ignores it
@@ -340,12 +388,6 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
   return s + 4096;
 }
 
-// Form of the per-individual system for a batch.  The SNP-space (primal) form is what
-// sklearn's Ridge solves when k <= n_T (_ridge.py _solve_cholesky: X^T X + alpha I); it is
-// used when every individual takes the snp branch and it gives no more 128-row tiles than the
-// kernel form.  pref: 0 auto, 1 force dual, 2 force primal (snp batches only).
-SysDims choose_sys(const tblup_ctx* c, const EvalDims& d, const int64_t* h_off, int64_t B, int branch, int pref);
-
 EvalDims dims_of(const tblup_ctx* c, const Split& sp) {
   EvalDims d;
   d.n = c->n;
@@ -361,6 +403,10 @@ EvalDims dims_of(const tblup_ctx* c, const Split& sp) {
   return d;
 }
 
+// Form of the per-individual system for a batch.  The SNP-space (primal) form is what
+// sklearn's Ridge solves when k <= n_T (_ridge.py _solve_cholesky: X^T X + alpha I); it is
+// used when every individual takes the snp branch and it gives no more 128-row tiles than the
+// kernel form.  pref: 0 auto, 1 force dual, 2 force primal (snp batches only).
 SysDims choose_sys(const tblup_ctx* c, const EvalDims& d, const int64_t* h_off, int64_t B, int branch, int pref) {
   int64_t max_k = 1;
   bool all_snp = true;
@@ -391,42 +437,73 @@ SysDims choose_sys(const tblup_ctx* c, const EvalDims& d, const int64_t* h_off, 
   return sd;
 }
 
-// Every buffer carved so far lies inside the workspace (checked before the launches that use
-// them: a sizing mistake fails the call instead of faulting the GPU)
-int ws_check(const tblup_ctx* c, const Carve& cv) {
-  if (cv.base >= (char*)c->ws.p && cv.base + cv.used <= (char*)c->ws.p + c->ws.bytes) return 0;
-  return fail(TBLUP_ERR_STATE, "internal error: workspace carve of " + std::to_string(cv.used) +
-                                   " bytes overruns the " + std::to_string(c->ws.bytes) + "-byte workspace");
+void set_fold(FoldTab& ft, int64_t f, const Split& sp) {
+  ft.gpk[f] = (const uint8_t*)sp.gpk.p;
+  ft.csT[f] = (const int32_t*)sp.colsumT.p;
+  ft.xty[f] = (const double*)sp.xty.p;
+  ft.yV[f] = (const double*)sp.yV.p;
+  ft.yT[f] = (const double*)sp.yT.p;
+  ft.ymu[f] = (const double*)sp.ymu.p;
 }
 
 FoldTab single_fold(const Split& sp, int64_t B) {
   FoldTab ft{};
   ft.bpf = std::max<int64_t>(B, 1);
   ft.nf = 1;
-  ft.gpk[0] = (const uint8_t*)sp.gpk.p;
-  ft.csT[0] = (const int32_t*)sp.colsumT.p;
-  ft.xty[0] = (const double*)sp.xty.p;
-  ft.yV[0] = (const double*)sp.yV.p;
-  ft.yT[0] = (const double*)sp.yT.p;
-  ft.ymu[0] = (const double*)sp.ymu.p;
+  set_fold(ft, 0, sp);
   return ft;
 }
 
-// Enqueue the full pipeline for one chunk whose idx/off already sit in device memory.  ftp: the
-// systems' splits when they are not all sp (fold-fused evaluation; sp is then fold 0).
-// stop_stage: 0 the whole pipeline; 1 / 2 debug readbacks (K, L); 3 the solve only, through the
-// one-workgroup k_solve, on the factor an earlier run_chunk of the same chunk left in the same
-// carve (host entries, after that run's chained solve gave up a wait: bit-identical results);
-// 4 the whole pipeline with the one-workgroup k_solve instead of the chained solve (a per-call
-// choice: the context's policy is not touched).
-int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& sd, hipStream_t s,
-              const int64_t* d_idx, const int64_t* d_off, const int64_t* h_off, int64_t B, double h2,
-              int branch, Carve& cv, double* d_fit, double* d_ebv, int stop_stage, double** K_out,
-              double** z_out, const FoldTab* ftp = nullptr, CholLaunch* cl_out = nullptr) {
-  const FoldTab ft = ftp ? *ftp : single_fold(sp, B);
-  const bool redo = stop_stage == 3;
-  const bool chain = stop_stage != 4 && use_chain(c, sd, B, d.nt);
-  c->last_chain_seq = 0;
+enum class ChunkMode {
+  Full,        // the whole pipeline
+  DebugK,      // debug readback: the pipeline up to the full K block (k_grm)
+  DebugL,      // debug readback: the pipeline up to the factor L and z
+  SolveOnly,   // the solve only, through the one-workgroup k_solve, on the factor an earlier run_chunk
+               // of the same chunk left in the same carve (host entries, after that run's chained
+               // solve gave up a wait: bit-identical results)
+  NoChain,     // the whole pipeline with the one-workgroup k_solve instead of the chained solve (a
+               // per-call choice: the context's policy is not touched)
+};
+
+// One chunk whose idx/off already sit in device memory, as run_chunk enqueues it.  An entry fixes the
+// first six members once (ChunkReq rq{sp, d, sd, s, h2, branch}: six distinct types); the chunk's
+// pointers, B and the mode are set by name.
+struct ChunkReq {
+  const Split* sp;
+  EvalDims d;
+  SysDims sd;
+  hipStream_t s;
+  double h2;
+  int branch;
+  const int64_t *d_idx = nullptr, *d_off = nullptr;
+  const int64_t* h_off = nullptr;   // host copy of the offsets (work accounting and shapes)
+  int64_t B = 0;
+  double* d_fit = nullptr;       // [B] fitness
+  double* d_ebv = nullptr;       // [B][nt][nV], if wanted
+  const FoldTab* ft = nullptr;   // the systems' splits when they are not all sp (fold-fused evaluation;
+                                 // sp is then fold 0)
+  ChunkMode mode = ChunkMode::Full;
+};
+
+struct ChunkRes {
+  int32_t chain_seq = 0;    // seq of the chained solve this run enqueued, 0 if none
+  double* K = nullptr;      // debug readbacks: the K block (DebugK), else the factor L
+  double* z = nullptr;
+  CholLaunch cl{};          // the chunk's buffers, for a launch after the pipeline (launch_effects)
+};
+
+// Enqueue the pipeline for one chunk (no host synchronisation unless the chain flags must grow).
+int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
+  const EvalDims& d = rq.d;
+  const SysDims& sd = rq.sd;
+  const hipStream_t s = rq.s;
+  const int64_t *d_idx = rq.d_idx, *d_off = rq.d_off, *h_off = rq.h_off, B = rq.B;
+  res = ChunkRes{};
+  CholLaunch& cl = res.cl;
+  cl.ft = rq.ft ? *rq.ft : single_fold(*rq.sp, B);
+  const FoldTab& ft = cl.ft;
+  const bool redo = rq.mode == ChunkMode::SolveOnly;
+  const bool chain = rq.mode != ChunkMode::NoChain && use_chain(c, sd, B, d.nt);
   double grm_flops = 0.0, gather_bytes = 0.0, stats_bytes = 0.0;
   const double tri = (double)d.nT * (d.nT + 1) / 2.0 + (double)d.nV * d.nT;
   for (int64_t b = 0; b < B; ++b) {
@@ -447,7 +524,7 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
   double* rhs = cv.take<double>((size_t)B * d.nt * sd.ns);
   double* Sp = cv.take<double>((size_t)B * TBLUP_NSLOT * 36 * 256);
   // (kernel-form fold chunks read their counts from the shared A_R A_R^T instead)
-  const bool use_st = sys_tiles(c, d, sd) && stop_stage != 1 && !ft.gsh;
+  const bool use_st = sys_tiles(c, d, sd) && rq.mode != ChunkMode::DebugK && !ft.gsh;
   // diagonal system tiles: fp64 K_JJ + lambda I (with k_sys_tiles: J < 2 only, the diagonal
   // kernel's direct reads) and, with k_sys_tiles, the exact int16 counts of J >= 2 (the D-units')
   double* Kdg = cv.take<double>((size_t)B * sd.NT * NPACK * BLKD);
@@ -457,6 +534,14 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
   double* Qb = use_last_term(c, sd, B) ? cv.take<double>((size_t)B * NPACK * BLKD) : nullptr;
   const bool fold_share = use_st && sd.form == FORM_PRIMAL && ft.nf > 1 && ft.share;   // k_sys_tiles_folds
   if (int rc = ws_check(c, cv)) return rc;
+  // the launches' arguments, by name (cl.ft above; wgt, q and stats change from launch to launch)
+  cl.d = d; cl.sd = sd; cl.B = B; cl.off = rq.d_off; cl.idx = rq.d_idx;
+  cl.L = L; cl.Dinv = Dinv; cl.z = z; cl.w = wv; cl.rhs = rhs; cl.S = Sp; cl.u = u; cl.scal = scal;
+  cl.Kd = Kdg; cl.kd = kdb; cl.kc = kcb; cl.part = Pp; cl.q = Qb;
+  cl.yT = (const double*)rq.sp->yT.p; cl.panel = panel; cl.pstride = pstride; cl.gs_row = d.nRp; cl.gpk_row = d.nRp / 4;
+  cl.skip = dbg_skip(c) | (rq.mode == ChunkMode::DebugL ? FLAG_WRITE_LJJ : 0);
+  cl.padskip = (sd.form == FORM_PRIMAL && sd.pad_first) ? 1 : 0;
+  cl.sys_st = c->sys_st;
   std::vector<OffPlan> plan(sd.NT);
   for (int J = 0; J < sd.NT; ++J) {
     plan[J] = plan_of(c, B, sd.NT, J, use_st);
@@ -465,16 +550,12 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
   const int32_t* csA = (const int32_t*)c->colsum_all.p;
   // the scalars formed after k_sys_tiles_st / k_sys_tiles_folds, in their K_JJ epilogue launch (one
   // launch less; neither reads a scalar), else by k_indiv_stats first
-  CholLaunch probe{};
-  probe.B = B;
-  probe.sd = sd;
-  probe.sys_st = c->sys_st;
-  const bool fuse_stats = !redo && use_st && sd.form == FORM_PRIMAL && (fold_share || sys_tiles_grid(probe) > 0);
-  const StatsFuse sf{csA, d.n, d.nT, branch, h2, (int32_t*)c->status.p + ST_INDEX, scal, u, rhs};
+  const bool fuse_stats = !redo && use_st && sd.form == FORM_PRIMAL && (fold_share || sys_tiles_grid(cl) > 0);
+  const StatsFuse sf{csA, d.n, d.nT, rq.branch, rq.h2, (int32_t*)c->status.p + ST_INDEX, scal, u, rhs};
   int rc = 0;
   if (!redo && !fuse_stats)
     rc = timed(c, s, KC_STATS, 2.0 * (double)h_off[B], stats_bytes, [&] {
-      return launch_indiv_stats(d_idx, d_off, B, ft, csA, d, sd, branch, h2, scal, u, rhs,
+      return launch_indiv_stats(d_idx, d_off, B, ft, csA, d, sd, rq.branch, rq.h2, scal, u, rhs,
                                 (int32_t*)c->status.p + ST_INDEX, s);
     });
   if (rc) return rc;
@@ -485,25 +566,18 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
     });
     if (rc) return rc;
   }
-  if (z_out) *z_out = z;
-  if (stop_stage == 1) {
+  res.z = z;
+  if (rq.mode == ChunkMode::DebugK) {
     // parity readback only: the full K_{R,T} block of the unified form (k_grm); the
     // production path never materialises K (the Cholesky kernels rebuild each tile)
     double* K = cv.take<double>((size_t)B * d.nRp * d.nTp);
     if (int rc2 = ws_check(c, cv)) return rc2;
-    if (K_out) *K_out = K;
+    res.K = K;
     const double kbytes = (double)B * ((double)d.nT * d.nT / 2.0 + (double)d.nV * d.nT) * 8.0;
     return timed(c, s, KC_GRM, grm_flops, kbytes + gather_bytes / 2.0,
                  [&] { return launch_grm(panel, pstride, pk_row, d_off, u, scal, d, B, K, s); });
   }
-  if (K_out) *K_out = L;
-  CholLaunch cl{d, sd, B, L, Dinv, z, wv, rhs, Sp, Kdg, (const double*)sp.yT.p, panel, pstride, d_off, d_idx,
-                d.nRp, d.nRp / 4, ft, u, scal, dbg_skip(c) | (stop_stage == 2 ? FLAG_WRITE_LJJ : 0), nullptr, kcb,
-                Pp, Qb};
-  cl.kd = kdb;
-  cl.sys_st = c->sys_st;
-  cl.padskip = (sd.form == FORM_PRIMAL && sd.pad_first) ? 1 : 0;
-  if (cl_out) *cl_out = cl;   // the chunk's buffers, for a launch after the pipeline (launch_effects)
+  res.K = L;
   const double T3 = (double)TILE * TILE * TILE;
   // profiling only: room for one record per Cholesky workgroup of this chunk
   uint64_t* wgt = nullptr;
@@ -517,27 +591,26 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
     wgt = (uint64_t*)c->wgt.p;
     c->wgt_used = 0;
   }
+  auto trace = [&](int64_t n) {   // the next launch writes its n records behind those so far
+    cl.wgt = wgt + c->wgt_used * WGT_REC;
+    c->wgt_used += n;
+  };
   const double kbar = B > 0 ? (double)h_off[B] / (double)B : 0.0;
   const double cbar = (sd.form == FORM_PRIMAL) ? (double)d.nT : kbar;   // contraction length
-  if (redo) {
-  } else if (use_st) {
+  if (!redo && use_st) {
     // every system tile (I >= J) in one int8 launch: int ops 2 x 128^2 x n_T per tile
     const double ntri = (double)sd.NT * (sd.NT + 1) / 2.0;
     const double fg = (double)B * ntri * 2.0 * 128.0 * 128.0 * cbar;
     const double nd8 = std::min(sd.NT, 2);   // diagonal tiles stored as fp64 (the rest as int16 counts)
     const double bg = (double)B * ((ntri - sd.NT) * KC_TILE * 2.0 + (sd.NT - nd8) * KD_TILE * 2.0 + nd8 * KD_TILE * 8.0);
-    if (wgt) {
-      cl.wgt = wgt + c->wgt_used * WGT_REC;
-      const int64_t sg = fold_share ? -(B * sd.NT * (sd.NT + 1) / 2) : sys_tiles_grid(cl);
-      c->wgt_used += sg > 0 ? sg : -sg;
-    }
+    if (wgt) trace(fold_share ? B * sd.NT * (sd.NT + 1) / 2 : std::abs(sys_tiles_grid(cl)));
     cl.stats = fuse_stats ? &sf : nullptr;
     rc = timed(c, s, KC_GRM, fg, bg + (fuse_stats ? stats_bytes : 0.0), [&] {
       return fold_share ? launch_sys_tiles_folds(cl, s) : launch_sys_tiles(cl, s);
     });
     cl.stats = nullptr;
     if (rc) return rc;
-  } else {
+  } else if (!redo) {
     if (ft.gsh) {
       // kernel-form folds: every individual's A_R A_R^T once (int ops 2 x nRp^2 x k / 2 + the diagonal tiles)
       const double NR = (double)(d.nRp / TILE);
@@ -570,10 +643,7 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
                       (double)p.ne * 2.0 * T3;
     const double bd = Bd * (TILE * TILE * lt_d * 8.0 + 2.0 * TILE * TILE * 8.0) +
                       (p.ndd ? 2.0 * Bd * TILE * TILE * jt * 8.0 : 0.0) + (double)p.ne * 3.0 * TILE * TILE * 8.0;
-    if (wgt) {
-      cl.wgt = wgt + c->wgt_used * WGT_REC;
-      c->wgt_used += B * (1 + p.ndd) + p.ne + DTR_RECS;
-    }
+    if (wgt) trace(B * (1 + p.ndd) + p.ne + DTR_RECS);
     cl.q = qd ? Qb : nullptr;   // diagonal J: its last term from launch J-1
     rc = timed(c, s, KC_DIAG, fd, bd, [&] { return launch_chol_diag(cl, J, p, s); });
     cl.q = qo ? Qb : nullptr;   // off-diagonal J: the last term of diagonal J+1
@@ -588,15 +658,12 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
       const double bo = Bd * p.nI * (TILE * TILE * lt * 8.0 + TILE * TILE * 8.0) +
                         Bd * p.nP * (2.0 * TILE * TILE * jt * 8.0 + TILE * TILE * 8.0) +
                         (p.nds ? 2.0 * Bd * TILE * TILE * jt * 8.0 : 0.0);
-      if (wgt) {
-        cl.wgt = wgt + c->wgt_used * WGT_REC;
-        c->wgt_used += offdiag_grid(p, B);
-      }
+      if (wgt) trace(offdiag_grid(p, B));
       rc = timed(c, s, KC_OFFDIAG, fo, bo, [&] { return launch_chol_offdiag(cl, J, p, s); });
       if (rc) return rc;
     }
   }
-  if (stop_stage == 2) return 0;
+  if (rq.mode == ChunkMode::DebugL) return 0;
   const double fs = (double)B * (2.0 * (double)sd.ns * sd.ns / 2.0 + 2.0 * kbar * (double)(d.nT + d.nV) + 10.0 * d.nV);
   const double bs = (double)B * (((double)sd.ns * sd.ns / 2.0 + (double)sd.NT * TILE * TILE) * 8.0 +
                                  kbar * (double)(d.nT + d.nV));
@@ -621,7 +688,7 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
     ch.err = ring + ch.seq % CHAIN_ERR_RING;
     // host entries recover from their ring slot (chain_expired); device entries raise the status word
     ch.expired = c->host_entry ? ring + CHAIN_ERR_RING : (int32_t*)c->status.p + ST_SOLVE;
-    c->last_chain_seq = ch.seq;
+    res.chain_seq = ch.seq;
     ch.mode = c->chain_sync;
     // pull units for one trait (several traits: their registers spill at two units per CU)
     ch.pull = c->solve_pull == 1 || (c->solve_pull < 0 && d.nt == 1);
@@ -633,26 +700,51 @@ int run_chunk(tblup_ctx* c, const Split& sp, const EvalDims& d, const SysDims& s
       ch.delay = c->chain_dbg_delay;
     }
     chp = &ch;
-    if (wgt) {
-      cl.wgt = wgt + c->wgt_used * WGT_REC;
-      c->wgt_used += B * sd.NT;
-    }
+    if (wgt) trace(B * sd.NT);
   }
-  rc = timed(c, s, KC_SOLVE, fs, bs, [&] { return launch_solve(cl, chp, d_fit, d_ebv, s); });
-  return rc;
+  return timed(c, s, KC_SOLVE, fs, bs, [&] { return launch_solve(cl, chp, rq.d_fit, rq.d_ebv, s); });
 }
 
-// Host entries, after the chunk's stream synchronisation: whether the chained solve `seq` (0: none)
-// gave up a wait.  Its ring slot holds seq exactly then (slots of other calls hold their own seqs).
-int chain_expired(tblup_ctx* c, int32_t seq, bool* out) {
+// Host entries, after the chunk's stream synchronisation: whether one of the chained solves `seqs`
+// (0: none) gave up a wait.  Its ring slot holds seq exactly then (slots of other calls hold their own seqs).
+int chain_expired(tblup_ctx* c, const std::vector<int32_t>& seqs, bool* out) {
   *out = false;
-  if (seq <= 0 || !c->chain.p) return 0;
-  const int32_t* ring = (const int32_t*)c->chain.p + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
-  int32_t v = 0;
-  HIPCHK(hipMemcpyAsync(&v, ring + seq % CHAIN_ERR_RING, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  *out = v == seq;
+  for (int32_t seq : seqs) {
+    if (seq <= 0 || !c->chain.p) continue;
+    const int32_t* ring = (const int32_t*)c->chain.p + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
+    int32_t v = 0;
+    HIPCHK(hipMemcpyAsync(&v, ring + seq % CHAIN_ERR_RING, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = *out || v == seq;
+  }
   return 0;
+}
+
+// A host entry's chunk with recovery.  enqueue(redo, seqs) enqueues one pass on the context's stream --
+// its launches and the copies of the results to the host -- and lists the chained solves it enqueued.
+// Pass 0 (redo false) is the chunk as usual; when one of its chained solves gave up a wait, the pass
+// is enqueued once more with redo set (the entry solves through k_solve then) and the chunk counted.
+template <typename Enqueue>
+int run_recovering(tblup_ctx* c, Enqueue&& enqueue) {
+  std::vector<int32_t> seqs;
+  for (int pass = 0;; ++pass) {
+    seqs.clear();
+    if (int rc = enqueue(pass != 0, seqs)) return rc;
+    HIPCHK(hipStreamSynchronize(c->stream));
+    bool any = false;
+    if (int rc = chain_expired(c, seqs, &any)) return rc;
+    if (!any) return 0;
+    ++c->chain_recoveries;
+  }
+}
+
+// Device entries: the workspace grown to `need` bytes.  Large enough already: no synchronisation (the
+// entries are asynchronous); else it may still be in use by earlier work on either stream.
+int ensure_ws(tblup_ctx* c, hipStream_t s, size_t need) {
+  if (need <= c->ws.bytes) return 0;
+  HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return dev_alloc(c, c->ws, need);
 }
 
 // Marks a synchronous entry for its duration: its chained solves write their expiry to the ring
@@ -772,28 +864,10 @@ int tblup_ctx_destroy(tblup_ctx* c) {
     (void)hipEventDestroy(p.b);
   }
   for (auto e : c->event_pool) (void)hipEventDestroy(e);
-  for (auto& kv : c->splits) {
-    kv.second->gpk.release();
-    kv.second->colsumT.release();
-    kv.second->xty.release();
-    kv.second->yT.release();
-    kv.second->yV.release();
-    kv.second->ymu.release();
-  }
-  c->geno_sm.release();
-  c->colsum_all.release();
-  c->status.release();
-  c->scratch.release();
-  c->ws.release();
-  c->wgt.release();
-  c->chain.release();
-  c->dec_keys.release();
-  c->dec_idx.release();
-  c->de_polys.release();
-  c->de_small.release();
-  c->de_par.release();
-  c->de_chi.release();
-  c->mde_dev.release();
+  for (auto& kv : c->splits) kv.second->release(c);
+  for (DevBuf* b : {&c->geno_sm, &c->colsum_all, &c->status, &c->scratch, &c->ws, &c->wgt, &c->chain, &c->dec_keys,
+                    &c->dec_idx, &c->de_polys, &c->de_small, &c->de_par, &c->de_chi, &c->mde_dev})
+    b->release();
   if (c->de_ev) (void)hipEventDestroy(c->de_ev);
   if (c->de_host) (void)hipHostFree(c->de_host);
   if (c->de_stage) (void)hipHostFree(c->de_stage);
@@ -857,15 +931,7 @@ int tblup_set_split(tblup_ctx* c, int split_id, const int64_t* train, int64_t nT
                             (const double*)sp->yT.p, (const double*)sp->ymu.p, nt, (uint8_t*)sp->gpk.p, (int32_t*)sp->colsumT.p, (double*)sp->xty.p, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   dev_free(c, rm);
-  auto it = c->splits.find(split_id);
-  if (it != c->splits.end()) {
-  dev_free(c, it->second->gpk);
-    dev_free(c, it->second->colsumT);
-    dev_free(c, it->second->xty);
-    dev_free(c, it->second->yT);
-    dev_free(c, it->second->yV);
-    dev_free(c, it->second->ymu);
-  }
+  if (Split* old = find_split(c, split_id)) old->release(c);
   c->splits[split_id] = std::move(sp);
   return 0;
 }
@@ -877,14 +943,7 @@ int tblup_set_traits(tblup_ctx* c, const double* pheno, int64_t n_traits) {
   if (!pheno || n_traits < 1 || n_traits > MAXT) return fail(TBLUP_ERR_ARG, "need 1 <= n_traits <= 4 and phenotypes");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (auto& kv : c->splits) {   // splits hold per-trait phenotype vectors
-    dev_free(c, kv.second->gpk);
-    dev_free(c, kv.second->colsumT);
-    dev_free(c, kv.second->xty);
-    dev_free(c, kv.second->yT);
-    dev_free(c, kv.second->yV);
-    dev_free(c, kv.second->ymu);
-  }
+  for (auto& kv : c->splits) kv.second->release(c);   // splits hold per-trait phenotype vectors
   c->splits.clear();
   c->nt = (int)n_traits;
   c->pheno.assign(pheno, pheno + c->n * n_traits);
@@ -903,23 +962,8 @@ int tblup_drop_split(tblup_ctx* c, int split_id) {
   if (it == c->splits.end()) return fail(TBLUP_ERR_ARG, "unknown split id");
   HIPCHK(hipSetDevice(c->device));
   HIPCHK(hipStreamSynchronize(c->stream));
-  dev_free(c, it->second->gpk);
-  dev_free(c, it->second->colsumT);
-  dev_free(c, it->second->xty);
-  dev_free(c, it->second->yT);
-  dev_free(c, it->second->yV);
-  dev_free(c, it->second->ymu);
+  it->second->release(c);
   c->splits.erase(it);
-  return 0;
-}
-
-// numpy's fancy-index bound (the reference's data[:, indices], evaluator.py:275/298):
-// -P <= i < P is valid (negatives wrap, on the device); anything else is numpy's IndexError.
-static int check_indices(const tblup_ctx* c, const int64_t* idx, int64_t count) {
-  for (int64_t i = 0; i < count; ++i)
-    if (idx[i] < -c->P || idx[i] >= c->P)
-      return fail(TBLUP_ERR_INDEX, "index " + std::to_string(idx[i]) + " is out of bounds for axis 1 with size " +
-                                       std::to_string(c->P));
   return 0;
 }
 
@@ -928,10 +972,8 @@ static int validate_batch(tblup_ctx* c, int branch, double h2, const int64_t* of
   if (!(h2 > 0.0) || !(h2 <= 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1]");
   if (batch < 0) return fail(TBLUP_ERR_ARG, "negative batch");
   if (batch > 0 && !offsets) return fail(TBLUP_ERR_ARG, "null offsets");
-  for (int64_t b = 0; b < batch; ++b)
-    if (offsets[b + 1] - offsets[b] < 1) return fail(TBLUP_ERR_ARG, "every individual needs k >= 1 indices");
+  if (int rc = check_counts(offsets, batch, "individual")) return rc;
   if (batch > 0 && offsets[0] != 0) return fail(TBLUP_ERR_ARG, "offsets[0] must be 0");
-  (void)c;
   return 0;
 }
 
@@ -962,24 +1004,15 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
   const int64_t n_rel = ro ? ro->n_pred : 0;
   const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
   const bool rel_lds = reliab_in_lds(c, sd);
-  int64_t b0 = 0;
-  while (b0 < batch) {
-    // grow the chunk while it fits the workspace budget
-    int64_t b1 = b0, sum_k = 0;
-    while (b1 < batch) {
-      const int64_t k = offsets[b1 + 1] - offsets[b1];
-      if (b1 > b0 && chunk_bytes(c, d, sd, b1 + 1 - b0, sum_k + k, want_ebv, fo != nullptr, n_rel) > c->budget) break;
-      if (b1 - b0 >= 65535) break;
-      sum_k += k;
-      ++b1;
-    }
-    const int64_t B = b1 - b0;
-    const size_t need = chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel);
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->ws, need)) return rc;
+  ChunkReq rq{sp, d, sd, c->stream, h2, branch};
+  const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
+    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel);
+  };
+  const int rc = for_each_chunk(c, offsets, batch, 65535, bytes, [&](const Chunk& ck) -> int {
+    const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
     Carve cv{(char*)c->ws.p};
-    int64_t* d_idx = cv.take<int64_t>((size_t)sum_k);
-    int64_t* d_off = cv.take<int64_t>((size_t)B + 1);
+    int64_t *d_idx, *d_off;
+    if (int rc = upload_chunk(c, cv, idx, offsets, ck, &d_idx, &d_off)) return rc;
     double* d_fit = cv.take<double>((size_t)B);
     double* d_ebv = want_ebv ? cv.take<double>((size_t)B * d.nt * d.nV) : nullptr;
     double* d_cen = fo ? cv.take<double>((size_t)sum_k) : nullptr;
@@ -989,33 +1022,29 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
     double* d_vscr = (n_rel && !rel_lds)
                          ? cv.take<double>((size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W)
                          : nullptr;
-    std::vector<int64_t> hoff(B + 1);
-    for (int64_t b = 0; b <= B; ++b) hoff[b] = offsets[b0 + b] - offsets[b0];
-    HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_off, hoff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, c->stream));
     if (n_rel) HIPCHK(hipMemcpyAsync(d_an, ro->animals, (size_t)n_rel * 4, hipMemcpyHostToDevice, c->stream));
-    const Carve cv0 = cv;
-    for (int pass = 0;; ++pass) {
-      // pass 1: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
-      Carve cvp = cv0;
-      CholLaunch cl{};
-      if (int rc = run_chunk(c, *sp, d, sd, c->stream, d_idx, d_off, hoff.data(), B, h2, branch, cvp, d_fit, d_ebv,
-                             pass ? 3 : 0, nullptr, nullptr, nullptr, (fo || n_rel) ? &cl : nullptr))
-        return rc;
-      const int32_t seq = c->last_chain_seq;
-      if (fo && pass == 0) {
+    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
+    rq.d_fit = d_fit; rq.d_ebv = d_ebv;
+    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+      // redo: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
+      Carve cvp = cv;
+      rq.mode = redo ? ChunkMode::SolveOnly : ChunkMode::Full;
+      ChunkRes res;
+      if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+      seqs.push_back(res.chain_seq);
+      if (fo && !redo) {
         // neither solve kernel writes L, the diagonal inverses or z: the effects do not wait for the
         // chained solve's verdict (a recovery pass re-solves for the fitness only)
-        HIPCHK(launch_effects(cl, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, c->stream));
+        HIPCHK(launch_effects(res.cl, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, c->stream));
         HIPCHK(hipMemcpyAsync(fo->center + offsets[b0], d_cen, (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
         for (int t = 0; t < d.nt; ++t)
           HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
                                 (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
       }
-      if (n_rel && pass == 0) {
+      if (n_rel && !redo) {
         // like the effects: L, the diagonal inverses, u and the scalars only, so no wait for the solve
-        HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, d_an, n_rel, rel_lds,
-                             rel_slabs(c, sd, B, n_rel), d_vscr, d_rel, c->stream));
+        HIPCHK(launch_reliab(res.cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, d_an, n_rel,
+                             rel_lds, rel_slabs(c, sd, B, n_rel), d_vscr, d_rel, c->stream));
         HIPCHK(hipMemcpyAsync(ro->reliability + b0 * n_rel, d_rel, (size_t)B * n_rel * 8, hipMemcpyDeviceToHost,
                               c->stream));
       }
@@ -1023,14 +1052,10 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
       if (want_ebv)
         HIPCHK(hipMemcpyAsync(ebv + b0 * d.nt * d.nV, d_ebv, (size_t)B * d.nt * d.nV * 8, hipMemcpyDeviceToHost,
                               c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      bool expired = false;
-      if (int rc = chain_expired(c, seq, &expired)) return rc;
-      if (!expired) break;
-      ++c->chain_recoveries;
-    }
-    b0 = b1;
-  }
+      return 0;
+    });
+  });
+  if (rc) return rc;
   if (fo) {
     // intercept: the split's mean(y_T) the evaluation uses under snp, 0 under gblup (evaluator.py:257 dispatch)
     for (int64_t b = 0; b < batch; ++b) {
@@ -1038,8 +1063,7 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
       for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = mode == 2 ? sp->meanyT[t] : 0.0;
     }
   }
-  if (c->profiling) return drain_events(c);
-  return 0;
+  return c->profiling ? drain_events(c) : 0;
 }
 
 extern "C" {
@@ -1059,16 +1083,13 @@ int tblup_eval_batch_device(tblup_ctx* c, int split_id, const int64_t* d_idx, co
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const EvalDims d = dims_of(c, *sp);
   const SysDims sd = choose_sys(c, d, h_offsets, batch, branch, c->form_pref);
-  const size_t need = chunk_bytes(c, d, sd, batch, 0, false);
-  if (need > c->ws.bytes) {
-    // the workspace may still be in use by earlier work on either stream
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->ws, need)) return rc;
-  }
+  if (int rc = ensure_ws(c, s, chunk_bytes(c, d, sd, batch, 0, false))) return rc;
   Carve cv{(char*)c->ws.p};
-  return run_chunk(c, *sp, d, sd, s, d_idx, d_offsets, h_offsets, batch, h2, branch, cv, d_fitness, d_ebv, 0, nullptr,
-                   nullptr);
+  ChunkReq rq{sp, d, sd, s, h2, branch};
+  rq.d_idx = d_idx; rq.d_off = d_offsets; rq.h_off = h_offsets; rq.B = batch;
+  rq.d_fit = d_fitness; rq.d_ebv = d_ebv;
+  ChunkRes res;
+  return run_chunk(c, rq, cv, res);
 }
 
 // IntraGCV's k folds (evaluator.py:509-537) or any set of splits: every individual against every
@@ -1113,12 +1134,13 @@ static size_t gshare_bytes(const std::vector<Split*>& sps, int64_t B) {
 }
 
 // The fused chunk: the index lists replicated per fold (F x sum_k, device to device), the fused
-// offsets built on the device, then run_chunk over F x B systems.
-static int run_folds_fused(tblup_ctx* c, const std::vector<Split*>& sps, const SysDims& sd, hipStream_t s,
-                           const int64_t* d_idx, const int64_t* d_off, const int64_t* h_off, int64_t B, double h2, int branch, Carve& cv,
-                           double* d_fit, int stop_stage = 0) {
-  const int64_t F = (int64_t)sps.size(), FB = F * B, sum_k = h_off[B];
-  const EvalDims d = dims_of(c, *sps[0]);
+// offsets built on the device, then run_chunk over F x B systems.  rq: the chunk of B individuals as
+// for fold 0 alone (sd: the folds' common shape; d_fit: [F][B]).
+static int run_folds_fused(tblup_ctx* c, const std::vector<Split*>& sps, ChunkReq rq, Carve& cv, ChunkRes& res) {
+  const int64_t B = rq.B, F = (int64_t)sps.size(), FB = F * B, sum_k = rq.h_off[B];
+  const int64_t *d_idx = rq.d_idx, *d_off = rq.d_off, *h_off = rq.h_off;
+  const SysDims& sd = rq.sd;
+  const hipStream_t s = rq.s;
   int64_t* idx_f = cv.take<int64_t>((size_t)(F * sum_k));
   int64_t* off_f = cv.take<int64_t>((size_t)FB + 1);
   std::vector<int64_t>& ho = c->fold_hoff;   // host copy (run_chunk's work accounting and shapes)
@@ -1134,45 +1156,41 @@ static int run_folds_fused(tblup_ctx* c, const std::vector<Split*>& sps, const S
   ft.nf = (int)F;
   ft.share = c->fold_share;
   for (int64_t f = 1; f < F; ++f) ft.share = ft.share && sps[f]->rows == sps[0]->rows;
-  if (fold_gshare(c, sps, sd) && stop_stage != 3) {
-    // the fold row maps: system row r of fold f -> fold 0's split row of the same animal
+  if (fold_gshare(c, sps, sd)) {
     const int64_t nRp = sps[0]->nRp, nTp = sps[0]->nTp, nT = sps[0]->nT;
-    std::unordered_map<int64_t, int32_t> pos0;
-    pos0.reserve((size_t)(sps[0]->nT + sps[0]->nV) * 2);
-    for (int64_t i = 0; i < sps[0]->nT; ++i) pos0[sps[0]->train[i]] = (int32_t)i;
-    for (int64_t j = 0; j < sps[0]->nV; ++j) pos0[sps[0]->valid[j]] = (int32_t)(nTp + j);
-    std::vector<int32_t>& hm = c->gmap_host;
-    HIPCHK(hipStreamSynchronize(s));   // the previous chunk's map copy may still read hm
-    hm.assign((size_t)(F * nTp), -1);
-    for (int64_t f = 0; f < F; ++f)
-      for (int64_t r = 0; r < nT; ++r) {
-        const auto it = pos0.find(sps[f]->train[r]);
-        if (it == pos0.end()) return fail(TBLUP_ERR_STATE, "internal error: fold rows are not one animal set");
-        hm[(size_t)(f * nTp + r)] = it->second;
-      }
-    ft.gsh = cv.take<int32_t>((size_t)(B * nRp * nRp));
+    int32_t* gsh = cv.take<int32_t>((size_t)(B * nRp * nRp));
     int32_t* dmap = cv.take<int32_t>((size_t)(F * nTp));
     if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpyAsync(dmap, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, s));
-    ft.gmap = dmap;
-    ft.gsh_ld = nRp;
-    ft.gmap_ld = nTp;
-  } else if (fold_gshare(c, sps, sd)) {
-    // the solve-only re-run: the counts are not read again, but the carve must match the first pass
-    const int64_t nRp = sps[0]->nRp, nTp = sps[0]->nTp;
-    cv.take<int32_t>((size_t)(B * nRp * nRp));
-    cv.take<int32_t>((size_t)(F * nTp));
+    // (the solve-only re-run does not read the counts again, but its carve must match the first pass)
+    if (rq.mode != ChunkMode::SolveOnly) {
+      // the fold row maps: system row r of fold f -> fold 0's split row of the same animal
+      std::unordered_map<int64_t, int32_t> pos0;
+      pos0.reserve((size_t)(sps[0]->nT + sps[0]->nV) * 2);
+      for (int64_t i = 0; i < sps[0]->nT; ++i) pos0[sps[0]->train[i]] = (int32_t)i;
+      for (int64_t j = 0; j < sps[0]->nV; ++j) pos0[sps[0]->valid[j]] = (int32_t)(nTp + j);
+      std::vector<int32_t>& hm = c->gmap_host;
+      HIPCHK(hipStreamSynchronize(s));   // the previous chunk's map copy may still read hm
+      hm.assign((size_t)(F * nTp), -1);
+      for (int64_t f = 0; f < F; ++f)
+        for (int64_t r = 0; r < nT; ++r) {
+          const auto it = pos0.find(sps[f]->train[r]);
+          if (it == pos0.end()) return fail(TBLUP_ERR_STATE, "internal error: fold rows are not one animal set");
+          hm[(size_t)(f * nTp + r)] = it->second;
+        }
+      HIPCHK(hipMemcpyAsync(dmap, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, s));
+      ft.gsh = gsh;
+      ft.gmap = dmap;
+      ft.gsh_ld = nRp;
+      ft.gmap_ld = nTp;
+    }
   }
-  for (int64_t f = 0; f < F; ++f) {
-    ft.gpk[f] = (const uint8_t*)sps[f]->gpk.p;
-    ft.csT[f] = (const int32_t*)sps[f]->colsumT.p;
-    ft.xty[f] = (const double*)sps[f]->xty.p;
-    ft.yV[f] = (const double*)sps[f]->yV.p;
-    ft.yT[f] = (const double*)sps[f]->yT.p;
-    ft.ymu[f] = (const double*)sps[f]->ymu.p;
-  }
-  return run_chunk(c, *sps[0], d, sd, s, idx_f, off_f, ho.data(), FB, h2, branch, cv, d_fit, nullptr, stop_stage,
-                   nullptr, nullptr, &ft);
+  for (int64_t f = 0; f < F; ++f) set_fold(ft, f, *sps[f]);
+  rq.d_idx = idx_f;
+  rq.d_off = off_f;
+  rq.h_off = ho.data();
+  rq.B = FB;
+  rq.ft = &ft;
+  return run_chunk(c, rq, cv, res);
 }
 
 // workspace of a fused chunk: its replicated index lists and the diagonal tiles' counts included,
@@ -1194,6 +1212,25 @@ static int validate_splits(tblup_ctx* c, const int* split_ids, int n_splits, std
   return 0;
 }
 
+// One chunk against every split on rq's stream: fused (fsd: the folds' common shape) through one launch
+// sequence, else split by split, every split reusing the workspace after `head` in stream order.
+// rq: the chunk, its mode and d_fit [F][B]; seqs: the chained solves enqueued.
+static int run_folds(tblup_ctx* c, const std::vector<Split*>& sps, ChunkReq rq, bool fused, const SysDims& fsd,
+                     const Carve& head, std::vector<int32_t>& seqs) {
+  double* const d_fit = rq.d_fit;
+  for (size_t f = 0; f < (fused ? 1 : sps.size()); ++f) {
+    Carve cv = head;
+    ChunkRes res;
+    rq.sp = sps[f];
+    rq.d = dims_of(c, *sps[f]);
+    rq.sd = fused ? fsd : choose_sys(c, rq.d, rq.h_off, rq.B, rq.branch, c->form_pref);
+    rq.d_fit = d_fit + (int64_t)f * rq.B;
+    if (int rc = fused ? run_folds_fused(c, sps, rq, cv, res) : run_chunk(c, rq, cv, res)) return rc;
+    seqs.push_back(res.chain_seq);
+  }
+  return 0;
+}
+
 int tblup_eval_folds_device(tblup_ctx* c, const int* split_ids, int n_splits, const int64_t* d_idx,
                             const int64_t* d_offsets, const int64_t* h_offsets, int64_t batch, double h2, int branch,
                             double* d_fitness, void* stream) {
@@ -1208,35 +1245,19 @@ int tblup_eval_folds_device(tblup_ctx* c, const int* split_ids, int n_splits, co
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   SysDims fsd{};
-  const bool fused = fold_fusable(c, sps, h_offsets, batch, branch, fsd) &&
-                     fused_bytes(c, sps, fsd, batch, h_offsets[batch]) <= c->budget;
-  size_t need = 0;
-  if (fused) {
-    need = fused_bytes(c, sps, fsd, batch, h_offsets[batch]);
-  } else {
-    for (int f = 0; f < n_splits; ++f) {
-      const EvalDims d = dims_of(c, *sps[f]);
-      need = std::max(need, chunk_bytes(c, d, choose_sys(c, d, h_offsets, batch, branch, c->form_pref), batch, 0, false));
-    }
-  }
-  if (need > c->ws.bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->ws, need)) return rc;
-  }
-  if (fused) {
-    Carve cv{(char*)c->ws.p};
-    return run_folds_fused(c, sps, fsd, s, d_idx, d_offsets, h_offsets, batch, h2, branch, cv, d_fitness);
-  }
-  for (int f = 0; f < n_splits; ++f) {
+  size_t need = fold_fusable(c, sps, h_offsets, batch, branch, fsd) ? fused_bytes(c, sps, fsd, batch, h_offsets[batch]) : 0;
+  const bool fused = need > 0 && need <= c->budget;
+  if (!fused) need = 0;   // split by split: the largest split's chunk
+  for (int f = 0; !fused && f < n_splits; ++f) {
     const EvalDims d = dims_of(c, *sps[f]);
-    const SysDims sd = choose_sys(c, d, h_offsets, batch, branch, c->form_pref);
-    Carve cv{(char*)c->ws.p};
-    if (int rc = run_chunk(c, *sps[f], d, sd, s, d_idx, d_offsets, h_offsets, batch, h2, branch, cv,
-                           d_fitness + (int64_t)f * batch, nullptr, 0, nullptr, nullptr))
-      return rc;
+    need = std::max(need, chunk_bytes(c, d, choose_sys(c, d, h_offsets, batch, branch, c->form_pref), batch, 0, false));
   }
-  return 0;
+  if (int rc = ensure_ws(c, s, need)) return rc;
+  ChunkReq rq{nullptr, {}, {}, s, h2, branch};   // run_folds sets the split, its dims and the system shape
+  rq.d_idx = d_idx; rq.d_off = d_offsets; rq.h_off = h_offsets; rq.B = batch;
+  rq.d_fit = d_fitness;
+  std::vector<int32_t> seqs;   // device entry: an expiry raises the status word instead
+  return run_folds(c, sps, rq, fused, fsd, Carve{(char*)c->ws.p}, seqs);
 }
 
 int tblup_eval_folds(tblup_ctx* c, const int* split_ids, int n_splits, const int64_t* idx, const int64_t* offsets,
@@ -1251,84 +1272,42 @@ int tblup_eval_folds(tblup_ctx* c, const int* split_ids, int n_splits, const int
   if (int rc = check_indices(c, idx, offsets[batch])) return rc;
   HIPCHK(hipSetDevice(c->device));
   HostEntry he(c);
-  std::vector<EvalDims> ds(n_splits);
-  for (int f = 0; f < n_splits; ++f) ds[f] = dims_of(c, *sps[f]);
-  auto fold_bytes = [&](const int64_t* off, int64_t B, int64_t sum_k) {
+  // the form is chosen per chunk, from the candidate's own offsets
+  const ChunkBytes fold_bytes = [&](const int64_t* off, int64_t B, int64_t sum_k) {
     size_t m = 0;
-    for (int f = 0; f < n_splits; ++f)
-      m = std::max(m, chunk_bytes(c, ds[f], choose_sys(c, ds[f], off, B, branch, c->form_pref), B, sum_k, false));
+    for (const Split* sp : sps) {
+      const EvalDims d = dims_of(c, *sp);
+      m = std::max(m, chunk_bytes(c, d, choose_sys(c, d, off, B, branch, c->form_pref), B, sum_k, false));
+    }
     SysDims fsd{};
     if (fold_fusable(c, sps, off, B, branch, fsd)) m = std::max(m, fused_bytes(c, sps, fsd, B, sum_k));
     return m + (size_t)n_splits * B * 8 + 256;
   };
-  int64_t b0 = 0;
-  while (b0 < batch) {
-    int64_t b1 = b0, sum_k = 0;
-    std::vector<int64_t> hoff(1, 0);
-    while (b1 < batch) {
-      const int64_t k = offsets[b1 + 1] - offsets[b1];
-      hoff.push_back(hoff.back() + k);
-      if (b1 > b0 && fold_bytes(hoff.data(), b1 + 1 - b0, sum_k + k) > c->budget) {
-        hoff.pop_back();
-        break;
-      }
-      if (b1 - b0 >= 65535) {
-        hoff.pop_back();
-        break;
-      }
-      sum_k += k;
-      ++b1;
-    }
-    const int64_t B = b1 - b0;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->ws, fold_bytes(hoff.data(), B, sum_k))) return rc;
+  ChunkReq rq{nullptr, {}, {}, c->stream, h2, branch};   // run_folds sets the split, its dims and the system shape
+  const int rc = for_each_chunk(c, offsets, batch, 65535, fold_bytes, [&](const Chunk& ck) -> int {
+    const int64_t B = ck.B;
     Carve head{(char*)c->ws.p};
-    int64_t* d_idx = head.take<int64_t>((size_t)sum_k);
-    int64_t* d_off = head.take<int64_t>((size_t)B + 1);
+    int64_t *d_idx, *d_off;
+    if (int rc = upload_chunk(c, head, idx, offsets, ck, &d_idx, &d_off)) return rc;
     double* d_fit = head.take<double>((size_t)n_splits * B);
-    HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d_off, hoff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
+    rq.d_fit = d_fit;
     SysDims fsd{};
-    const bool fused = fold_fusable(c, sps, hoff.data(), B, branch, fsd);
-    for (int pass = 0;; ++pass) {
-      // pass 1 after a chained solve gave up a wait: fused, the same factor solved by k_solve; split
+    const bool fused = fold_fusable(c, sps, ck.hoff, B, branch, fsd);
+    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+      // redo, after a chained solve gave up a wait: fused, the same factor solved by k_solve; split
       // by split (the folds reuse one workspace, so the earlier folds' factors are gone), every fold
       // again with the chained solve off -- bit-identical either way
-      std::vector<int32_t> seqs;
-      if (fused) {
-        Carve cv = head;
-        if (int rc = run_folds_fused(c, sps, fsd, c->stream, d_idx, d_off, hoff.data(), B, h2, branch, cv, d_fit,
-                                     pass ? 3 : 0))
-          return rc;
-        seqs.push_back(c->last_chain_seq);
-      } else {
-        for (int f = 0; f < n_splits; ++f) {
-          Carve cv = head;   // every fold reuses the same workspace after the inputs, in stream order
-          const SysDims sd = choose_sys(c, ds[f], hoff.data(), B, branch, c->form_pref);
-          // the recovery pass runs every fold with k_solve (stop_stage 4: a per-call choice)
-          if (int rc = run_chunk(c, *sps[f], ds[f], sd, c->stream, d_idx, d_off, hoff.data(), B, h2, branch, cv,
-                                 d_fit + (int64_t)f * B, nullptr, pass ? 4 : 0, nullptr, nullptr))
-            return rc;
-          seqs.push_back(c->last_chain_seq);
-        }
-      }
+      rq.mode = !redo ? ChunkMode::Full : fused ? ChunkMode::SolveOnly : ChunkMode::NoChain;
+      if (int rc = run_folds(c, sps, rq, fused, fsd, head, seqs)) return rc;
       for (int f = 0; f < n_splits; ++f)
-        HIPCHK(hipMemcpyAsync(fitness + (int64_t)f * batch + b0, d_fit + (int64_t)f * B, (size_t)B * 8,
+        HIPCHK(hipMemcpyAsync(fitness + (int64_t)f * batch + ck.b0, d_fit + (int64_t)f * B, (size_t)B * 8,
                               hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      bool any = false;
-      for (int32_t q : seqs) {
-        bool e = false;
-        if (int rc = chain_expired(c, q, &e)) return rc;
-        any = any || e;
-      }
-      if (!any) break;
-      ++c->chain_recoveries;
-    }
-    b0 = b1;
-  }
-  if (c->profiling) return drain_events(c);
-  return 0;
+      return 0;
+    });
+  });
+  if (rc) return rc;
+  return c->profiling ? drain_events(c) : 0;
 }
 
 int tblup_set_profiling(tblup_ctx* c, int enable) {
@@ -1379,19 +1358,19 @@ int tblup_debug_grm(tblup_ctx* c, int split_id, const int64_t* idx, int64_t k, d
   HIPCHK(hipStreamSynchronize(c->stream));
   if (int rc = dev_alloc(c, c->ws, chunk_bytes(c, d, sd, 1, k, false) + (size_t)d.nRp * d.nTp * 8 + 4096)) return rc;
   Carve cv{(char*)c->ws.p};
-  int64_t* d_idx = cv.take<int64_t>((size_t)k);
-  int64_t* d_off = cv.take<int64_t>(2);
+  int64_t *d_idx, *d_off;
+  if (int rc = upload_chunk(c, cv, idx, offs, Chunk{0, 1, k, offs}, &d_idx, &d_off)) return rc;
   double* d_fit = cv.take<double>(1);
-  HIPCHK(hipMemcpyAsync(d_idx, idx, (size_t)k * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(d_off, offs, 16, hipMemcpyHostToDevice, c->stream));
-  double *K = nullptr, *z = nullptr;
-  if (int rc = run_chunk(c, *sp, d, sd, c->stream, d_idx, d_off, offs, 1, h2, branch, cv, d_fit, nullptr, stage,
-                         &K, &z))
-    return rc;
+  ChunkReq rq{sp, d, sd, c->stream, h2, branch};
+  rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = offs; rq.B = 1;
+  rq.d_fit = d_fit;
+  rq.mode = stage == 1 ? ChunkMode::DebugK : ChunkMode::DebugL;
+  ChunkRes res;
+  if (int rc = run_chunk(c, rq, cv, res)) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
   const int64_t rows = (stage == 1) ? d.nRp : d.nTp;
   std::vector<double> full((size_t)rows * d.nTp);
-  HIPCHK(hipMemcpy(full.data(), K, full.size() * 8, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(full.data(), res.K, full.size() * 8, hipMemcpyDeviceToHost));
   const int64_t nR = d.nT + d.nV;
   if (stage == 2) {
     // Lt tiles: tile (I, J) at ((I*NT + J) * 128*128), element [j][i] = L[128I+i][128J+j]
@@ -1410,11 +1389,10 @@ int tblup_debug_grm(tblup_ctx* c, int split_id, const int64_t* idx, int64_t k, d
   }
   if (z_out) {
     std::vector<double> zz(d.nTp);   // trait 0
-    HIPCHK(hipMemcpy(zz.data(), z, (size_t)d.nTp * 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(zz.data(), res.z, (size_t)d.nTp * 8, hipMemcpyDeviceToHost));
     std::memcpy(z_out, zz.data(), (size_t)d.nT * 8);
   }
-  if (c->profiling) return drain_events(c);
-  return 0;
+  return c->profiling ? drain_events(c) : 0;
 }
 
 int tblup_grm(tblup_ctx* c, const int64_t* idx, int64_t k, double* G) {

@@ -1,6 +1,7 @@
 // Internal to libtblup_gpu.so's C-ABI translation units (capi.hip, capi_aux.hip): the context
 // (struct tblup_ctx of include/tblup_gpu.h), its device buffers and the error / allocation helpers.
 #pragma once
+#include <functional>
 #include <map>
 #include <memory>
 #include <string>
@@ -8,6 +9,8 @@
 
 #include "../../include/tblup_gpu.h"
 #include "tblup_internal.h"
+
+struct tblup_ctx;
 
 namespace tblup_capi {
 
@@ -37,6 +40,7 @@ struct Split {
   std::vector<int64_t> train, valid;   // the split's animal lists in system-row order
   std::vector<double> meanyT;   // [nt]
   DevBuf gpk, colsumT, xty, yT, yV, ymu;
+  void release(tblup_ctx* c);   // frees the six device buffers (dev_free: the context's memory accounting)
 };
 
 enum { KC_STATS = 0, KC_GATHER, KC_GRM, KC_DIAG, KC_OFFDIAG, KC_SOLVE };
@@ -127,7 +131,6 @@ struct tblup_ctx {
   DevBuf chain;          // its flags [B][chain_flags(NT)], the expiry ring [CHAIN_ERR_RING] and one
                          // scratch word (zeroed when allocated)
   int32_t chain_seq = 0; // flag value of the last chained solve
-  int32_t last_chain_seq = 0;   // seq of the chained solve the last run_chunk enqueued, 0 if none
   bool host_entry = false;      // a synchronous entry is running: its chained solves recover on expiry
   int64_t chain_recoveries = 0; // chunks whose expired chained solve was re-run through k_solve
   // debug knob (TBLUP_CHAIN_DEBUG="spin,delay,shots"): the next `shots` chained solves poll at
@@ -140,6 +143,45 @@ int dev_alloc(tblup_ctx* c, DevBuf& b, size_t bytes);
 void dev_free(tblup_ctx* c, DevBuf& b);
 int check_ctx(tblup_ctx* c);
 void clear_error();
+
+// Buffers of a chunk, taken in order from the workspace (each starts on a 256-byte boundary)
+struct Carve {
+  char* base;
+  size_t used = 0;
+  template <typename T>
+  T* take(size_t count) {
+    used = round_up((int64_t)used, 256);
+    T* p = reinterpret_cast<T*>(base + used);
+    used += count * sizeof(T);
+    return p;
+  }
+};
+// Every buffer carved so far lies inside the workspace (checked before the launches that use
+// them: a sizing mistake fails the call instead of faulting the GPU)
+int ws_check(const tblup_ctx* c, const Carve& cv);
+// numpy's fancy-index bound (the reference's data[:, indices], evaluator.py:275/298):
+// -P <= i < P is valid (negatives wrap, on the device); anything else is numpy's IndexError.
+int check_indices(const tblup_ctx* c, const int64_t* idx, int64_t count);
+// every one of the batch's index lists is non-empty ("every <who> needs k >= 1 indices")
+int check_counts(const int64_t* offsets, int64_t batch, const char* who);
+
+// The host entries' chunk loop.  Individuals [b0, b0 + B) of the batch: sum_k indices, hoff their
+// B + 1 offsets rebased to 0 (valid until the body returns).
+struct Chunk {
+  int64_t b0, B, sum_k;
+  const int64_t* hoff;
+};
+// workspace bytes of a candidate chunk (its rebased offsets, B, sum_k)
+using ChunkBytes = std::function<size_t(const int64_t* hoff, int64_t B, int64_t sum_k)>;
+// Runs `body` on each chunk of the batch in turn.  A chunk grows while its bytes fit the context's
+// budget (TBLUP_WORKSPACE_MB) and max_B individuals (one launch's grid); its first individual always
+// fits.  Before the body: the context's stream synchronised, the workspace grown to the chunk's bytes.
+int for_each_chunk(tblup_ctx* c, const int64_t* offsets, int64_t batch, int64_t max_B, const ChunkBytes& bytes,
+                   const std::function<int(const Chunk&)>& body);
+// The chunk's index list and offsets carved next from cv and their upload enqueued on the context's stream
+int upload_chunk(tblup_ctx* c, Carve& cv, const int64_t* idx, const int64_t* offsets, const Chunk& ck,
+                 int64_t** d_idx, int64_t** d_off);
+
 // Host outputs of tblup_fit_batch (capi_model.hip): intercept [batch][nt], center [offsets[batch]],
 // effects [nt][offsets[batch]].
 struct FitOut {

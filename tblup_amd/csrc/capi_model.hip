@@ -65,13 +65,9 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
   if (!animals || !idx || !offsets || !intercept || !center || !effects || !ebv)
     return fail(TBLUP_ERR_ARG, "null predict arguments");
   if (offsets[0] != 0) return fail(TBLUP_ERR_ARG, "offsets[0] must be 0");
-  for (int64_t b = 0; b < batch; ++b)
-    if (offsets[b + 1] - offsets[b] < 1) return fail(TBLUP_ERR_ARG, "every model needs k >= 1 indices");
+  if (int rc = check_counts(offsets, batch, "model")) return rc;
   const int64_t total = offsets[batch];
-  for (int64_t i = 0; i < total; ++i)
-    if (idx[i] < -c->P || idx[i] >= c->P)
-      return fail(TBLUP_ERR_INDEX, "index " + std::to_string(idx[i]) + " is out of bounds for axis 1 with size " +
-                                       std::to_string(c->P));
+  if (int rc = check_indices(c, idx, total)) return rc;
   std::vector<int32_t> a32((size_t)n_pred);
   for (int64_t i = 0; i < n_pred; ++i) {
     if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
@@ -80,7 +76,7 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
   HIPCHK(hipSetDevice(c->device));
   const int nt = (int)n_traits;
   // device bytes of models [b0, b1) (every buffer rounded up to 256 B)
-  auto bytes_of = [&](int64_t B, int64_t sum_k) {
+  const ChunkBytes bytes_of = [&](const int64_t*, int64_t B, int64_t sum_k) {
     size_t s = 0;
     auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
     add((size_t)n_pred * 4);
@@ -92,41 +88,22 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
     add((size_t)B * nt * n_pred * 8);
     return s + 256;
   };
+  // models per chunk: within the workspace budget (TBLUP_WORKSPACE_MB) and one launch's grid,
+  // B * nblk <= 0x7fffffff
   const int64_t nblk = (n_pred + 255) / 256;
-  int64_t b0 = 0;
-  while (b0 < batch) {
-    // models per chunk: within the workspace budget (TBLUP_WORKSPACE_MB) and one launch's grid
-    int64_t b1 = b0, sum_k = 0;
-    while (b1 < batch) {
-      const int64_t k = offsets[b1 + 1] - offsets[b1];
-      if (b1 > b0 && (bytes_of(b1 + 1 - b0, sum_k + k) > c->budget || (b1 + 1 - b0) * nblk > 0x7fffffff)) break;
-      sum_k += k;
-      ++b1;
-    }
-    const int64_t B = b1 - b0;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (int rc = dev_alloc(c, c->ws, bytes_of(B, sum_k))) return rc;
-    char* base = (char*)c->ws.p;
-    size_t used = 0;
-    auto take = [&](size_t bytes) {
-      char* p = base + used;
-      used = (size_t)round_up((int64_t)(used + bytes), 256);
-      return p;
-    };
-    int32_t* d_an = (int32_t*)take((size_t)n_pred * 4);
-    int64_t* d_idx = (int64_t*)take((size_t)sum_k * 8);
-    int64_t* d_off = (int64_t*)take((size_t)(B + 1) * 8);
-    double* d_int = (double*)take((size_t)B * nt * 8);
-    double* d_cen = (double*)take((size_t)sum_k * 8);
-    double* d_eff = (double*)take((size_t)nt * sum_k * 8);
-    double* d_ebv = (double*)take((size_t)B * nt * n_pred * 8);
-    if (used > c->ws.bytes) return fail(TBLUP_ERR_STATE, "internal error: predict buffers overrun the workspace");
-    std::vector<int64_t> hoff((size_t)B + 1);
-    for (int64_t b = 0; b <= B; ++b) hoff[b] = offsets[b0 + b] - offsets[b0];
+  return for_each_chunk(c, offsets, batch, 0x7fffffff / nblk, bytes_of, [&](const Chunk& ck) -> int {
+    const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
+    Carve cv{(char*)c->ws.p};
+    int32_t* d_an = cv.take<int32_t>((size_t)n_pred);
+    int64_t *d_idx, *d_off;
+    if (int rc = upload_chunk(c, cv, idx, offsets, ck, &d_idx, &d_off)) return rc;
+    double* d_int = cv.take<double>((size_t)B * nt);
+    double* d_cen = cv.take<double>((size_t)sum_k);
+    double* d_eff = cv.take<double>((size_t)nt * sum_k);
+    double* d_ebv = cv.take<double>((size_t)B * nt * n_pred);
+    if (ws_check(c, cv)) return fail(TBLUP_ERR_STATE, "internal error: predict buffers overrun the workspace");
     hipStream_t s = c->stream;
     HIPCHK(hipMemcpyAsync(d_an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_off, hoff.data(), (size_t)(B + 1) * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_int, intercept + b0 * nt, (size_t)B * nt * 8, hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(d_cen, center + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
     for (int t = 0; t < nt; ++t)
@@ -135,10 +112,9 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
     HIPCHK(launch_predict((const int8_t*)c->geno_sm.p, c->n, c->P, d_an, n_pred, d_idx, d_off, B, d_int, d_cen, d_eff,
                           sum_k, nt, d_ebv, s));
     HIPCHK(hipMemcpyAsync(ebv + b0 * nt * n_pred, d_ebv, (size_t)B * nt * n_pred * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));   // hoff and the host buffers are borrowed until here
-    b0 = b1;
-  }
-  return 0;
+    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    return 0;
+  });
 }
 
 }  // extern "C"

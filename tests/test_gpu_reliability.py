@@ -282,6 +282,30 @@ def test_e_solve_kernels_are_identical(gpu):
         np.testing.assert_array_equal(val[1], base[1])
 
 
+def test_e_forced_expiry_keeps_models_and_reliabilities(gpu):
+    """fit(reliability_of=) on a context whose first chained solve gives up a wait
+    (TBLUP_CHAIN_DEBUG="1000,20000,1"): the effects and reliability launches run once, beside the
+    first pass, and the recovery pass re-solves for the fitness only -- models, fitnesses and
+    reliabilities bit-equal to a clean context's, chain_recoveries = 1.  SNP form with three tile
+    columns (k in 257..331 on split (257, 70)), so that a wait can expire."""
+    pn = Q.panel()
+    T, V = pn["splits"][257, 70]
+    rng = np.random.default_rng(331257)
+    genomes = [rng.choice(P, int(k), replace=False) for k in rng.integers(257, 332, 4)]
+    an = HERD[::-3].copy()
+    with _engine(pn["geno"], pn["pheno"]) as e:
+        ref_models, ref_rel = e.fit(genomes, T, V, H2, reliability_of=an)
+        assert e.chain_recoveries() == 0
+    with _engine(pn["geno"], pn["pheno"], {"TBLUP_CHAIN_DEBUG": "1000,20000,1"}) as e:
+        models, rel = e.fit(genomes, T, V, H2, reliability_of=an)
+        rec = e.chain_recoveries()
+    print("\nforced expiry in fit(reliability_of=): chain_recoveries", rec)
+    _same_models(models, ref_models)
+    np.testing.assert_array_equal(rel, ref_rel)
+    assert np.all(np.isfinite(ref_rel)) and np.all(np.isfinite([m.fitness for m in ref_models]))
+    assert rec == 1
+
+
 def test_e_one_pass_outputs(eng):
     """fit(reliability_of=) returns fit()'s models and reliability()'s array, bit for bit; the entry's
     fitness is evaluate()'s."""

@@ -301,3 +301,70 @@ def test_sys_tiles_persistent_bit_identical(panel, ks, B):
     for i in (0, B - 1):
         f, _ = O.blup_grm_form(genomes[i], p["T"], p["V"], p["geno"], p["pheno"], 0.4)
         assert abs(st[0][i] - f) <= FIT_ATOL, i
+
+
+# ---------------------------------------------------------------------------------------------
+# The host entries' chunk loops on the small panel of tests/model_ref.py (331 animals x 600 SNPs).
+# TBLUP_WORKSPACE_MB=1: with two or more tile columns two individuals' factors alone
+# (2 x (4 x 128 KiB + 4 KiB)) exceed the budget and the first individual of a chunk is always
+# accepted, so every individual is a chunk of its own.
+# ---------------------------------------------------------------------------------------------
+def _small_folds(animals, F=3):
+    """F folds over `animals` (permuted once): fold f validates on part f and trains on the rest."""
+    parts = np.array_split(np.random.default_rng(17).permutation(animals), F)
+    return [(np.concatenate([parts[g] for g in range(F) if g != f]), parts[f]) for f in range(F)]
+
+
+@pytest.mark.parametrize("case", ["fused", "unfused", "ragged"])
+def test_chunked_folds_are_identical(gpu, case):
+    """evaluate_folds under TBLUP_WORKSPACE_MB=1 (one individual per chunk) against the default
+    budget, bit for bit, and every row against that split's own evaluate.  Three equal folds of
+    330 animals (train 220: two tile columns) fused and with TBLUP_FOLD_FUSE=0; a ragged fold set
+    over all 331 animals (always split by split).  An SNP-form batch (k = 63 / 129 / 200 and the
+    negative-index genome) and a kernel-form batch (k = 400 and 332: gblup; k = 300: the snp branch
+    above the folds' 256 padded train rows).  tblup_eval_folds chooses the form per chunk, so every
+    genome of a batch takes its batch's form when alone too: a batch mixing k = 129 with k = 400
+    runs k = 129 in the kernel form whole and in the SNP form chunked, equal only up to rounding."""
+    from tblup_amd.engine import GpuBlupEngine
+    from tests import model_ref as R
+    pn = R.panel()
+    folds = _small_folds(331 if case == "ragged" else 330)
+    assert (len({len(t) for t, _ in folds}) == 1) == (case != "ragged")
+    env = {"TBLUP_FOLD_FUSE": "0"} if case == "unfused" else {}
+    k300 = np.random.default_rng(300).choice(R.N_SNPS, 300, replace=False)
+    batches = [[pn["genomes"][k] for k in (63, 129, 200, "neg")], [pn["genomes"][400], k300, pn["genomes"][332]]]
+    with _env(env):
+        with GpuBlupEngine(pn["geno"], pn["pheno"], device=0) as eng:
+            ref = [eng.evaluate_folds(b, folds, R.H2) for b in batches]
+            for b, r in zip(batches, ref):
+                assert r.shape == (3, len(b)) and np.all(np.isfinite(r))
+                for f, (t, v) in enumerate(folds):
+                    np.testing.assert_array_equal(r[f], eng.evaluate(b, t, v, R.H2))
+    with _env(dict(env, TBLUP_WORKSPACE_MB="1")):
+        with GpuBlupEngine(pn["geno"], pn["pheno"], device=0) as eng:
+            for b, r in zip(batches, ref):
+                np.testing.assert_array_equal(eng.evaluate_folds(b, folds, R.H2), r)
+
+
+def test_chunked_call_recovers_in_every_chunk(gpu):
+    """TBLUP_WORKSPACE_MB=1 with TBLUP_CHAIN_DEBUG="1000,20000,2": three SNP-form genomes on split
+    (257, 70) are three chunks, and the chained solves of the first two give up a wait -- each chunk
+    is re-solved on its own (chain_recoveries = 2) and the call returns a clean context's bits.
+    k in 257..331: three tile columns, so that the late producer unit has a consumer."""
+    from tblup_amd.engine import GpuBlupEngine
+    from tests import model_ref as R
+    pn = R.panel()
+    T, V = pn["splits"][257, 70]
+    rng = np.random.default_rng(257331)
+    genomes = [rng.choice(R.N_SNPS, int(k), replace=False) for k in rng.integers(257, 332, 3)]
+    with GpuBlupEngine(pn["geno"], pn["pheno"], device=0) as eng:
+        ref = eng.evaluate(genomes, T, V, R.H2, return_ebv=True)
+        assert eng.chain_recoveries() == 0
+    with _env({"TBLUP_WORKSPACE_MB": "1", "TBLUP_CHAIN_DEBUG": "1000,20000,2"}):
+        with GpuBlupEngine(pn["geno"], pn["pheno"], device=0) as eng:
+            got = eng.evaluate(genomes, T, V, R.H2, return_ebv=True)
+            rec = eng.chain_recoveries()
+    print("\nchunked recovery: chain_recoveries", rec)
+    np.testing.assert_array_equal(got[0], ref[0])
+    np.testing.assert_array_equal(got[1], ref[1])
+    assert rec == 2
