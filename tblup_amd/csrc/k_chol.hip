@@ -7,13 +7,19 @@
 //             scikit-learn 1.7.2 _ridge.py _solve_cholesky[_kernel])
 // by one Cholesky factorisation per individual, batched over the population.
 // For each tile column J:
-//   k_chol_diag    (one WG per individual): K_JJ (int8 MFMA) - sum_L L_JL L_JL^T (fp64 MFMA
-//                  SYRK on the lower blocks), blocked 16x16 factorisation, blocked inverse
+//   k_chol_diag    (one WG per individual): K_JJ - sum_L L_JL L_JL^T (fp64 MFMA SYRK on the
+//                  lower blocks), blocked 16x16 factorisation, blocked inverse
 //                  X_J = L_JJ^{-1}, forward-substitution block z_J = X_J (y_J - mu - w_J)
 //   k_chol_offdiag (one WG per individual x tile row I > J), all transposes in registers:
-//                  T^T = K_JI - sum_L L_JL L_IL^T  (int8 MFMA for K, fp64 MFMA, acc = T^T)
+//                  T^T = K_JI - sum_L L_JL L_IL^T  (fp64 MFMA, acc = T^T)
 //                  L_IJ^T = X_J T^T               (acc of T^T is the B operand directly)
 //                  w_I += L_IJ z_J                (forward-substitution partial sums)
+// Where K comes from: by default the exact integer counts of every system tile are formed on FP4
+// MFMA before the column loop (k_systiles.hip) and the units here only turn them into fp64 K where
+// they read them (kc_issue / k_acc, kd_load / kd_block; layout: chol_dev.h).  Without those counts
+// (one tile, counts past int16, the kernel form with TBLUP_DUAL_ST=0 or with shared fold counts) the
+// int8 MFMA rings of this file form them: k_diag_grm8 and diag_grm_tile for K_JJ, k_acc's own int8
+// phase for K_JI, k_gshare for the shared counts.
 //
 // Storage of L ("Lt"): tile-contiguous and transposed.  Tile (I, J), I >= J, of matrix b
 // is 128x128 doubles at L + ((b*NT + I)*NT + J)*128*128 with Lt[j][i] = L[128I+i][128J+j],
@@ -26,8 +32,7 @@
 // Reading the i8 16x16x64 A rows through the permutation pi(rho) = (rho>>2) + 4(rho&3)
 // makes its accumulator land in the f64 C layout, so the exact integer GRM counts
 // become the fp64 accumulators of the Cholesky GEMM without any data movement.
-#include "i8_tile.h"
-#include "k_stats.h"
+#include "chol_dev.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -51,52 +56,17 @@ constexpr int NSLOT = TBLUP_NSLOT;
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
 
-// (glds16_asm, the stage rings' LDS-DMA as inline asm: tblup_internal.h)
-#ifndef TBLUP_AB_ASM_SYRK   // A/B builds only (tools/ab_build_defs.sh): the SYRK ring's DMA as inline asm
-#define TBLUP_AB_ASM_SYRK 1
-#endif
-#ifndef TBLUP_AB_ASM_GEMM1   // the GEMM1 ring's DMA as inline asm
-#define TBLUP_AB_ASM_GEMM1 1
-#endif
+// (glds16_asm, the stage rings' LDS-DMA as inline asm -- the SYRK, GEMM1 and integer-count rings all
+// use it: tblup_internal.h)
 // Non-temporal result stores (round 5): the L tiles of the T-units, the partial sums (P- / E-units),
 // the diagonal targets S and last terms Q -- each read by a later launch, none by this one (the
 // last-term read-back aside), and every line a kernel leaves dirty in L2 is written back at its
 // end (the kernel boundary).  Interleaved A/B at config 2 (profiles/r05_nt_store_ab.txt): both on
 // +0.9% at pop 256 (off-diagonal 1.611 -> 1.594 ms), +1.0% at 128, +0.9% at 64 (the L tiles alone:
-// -0.3% at 64).  TBLUP_AB_NT_*: A/B builds only (tools/ab_build_defs.sh).
-#ifndef TBLUP_AB_NT_L
-#define TBLUP_AB_NT_L 1
-#endif
-#ifndef TBLUP_AB_NT_PART
-#define TBLUP_AB_NT_PART 1
-#endif
-#ifndef TBLUP_AB_NT_X   // the diagonal kernel's X_J (Dinv) stores
-#define TBLUP_AB_NT_X 0
-#endif
-#ifndef TBLUP_AB_NT_PLD   // the partial sums' and S's loads non-temporal (each read once; A/B:
-#define TBLUP_AB_NT_PLD 1    // +0.7% at pop 128, +0.15% at 256, profiles/r05_nt_store_ab.txt)
-#endif
-#ifndef TBLUP_AB_NT_KD   // the K_JJ + lambda I tiles J < 2 of the system-tile epilogue
-#define TBLUP_AB_NT_KD 0
-#endif
-template <bool NT>
-__device__ __forceinline__ void st64(double* p, double v) {
-  if constexpr (NT)
-    __builtin_nontemporal_store(v, p);
-  else
-    *p = v;
-}
-#ifndef TBLUP_AB_ASM_I8   // the integer-count rings' DMA (int8 / packed tiles, per-tile system tiles) as inline asm
-#define TBLUP_AB_ASM_I8 1
-#endif
-// one ring DMA: inline asm (A) or the builtin
-template <bool A>
-__device__ __forceinline__ void ring_glds(const void* g, void* lds) {
-  if constexpr (A)
-    glds16_asm(g, lds);
-  else
-    __builtin_amdgcn_global_load_lds(g, (lds_ptr_t)lds, 16, 0, 0);
-}
+// -0.3% at 64).  The partial sums' and S's loads are non-temporal too (each read once; A/B: +0.7% at
+// pop 128, +0.15% at 256, same file).  The diagonal kernel's X_J (Dinv) stores and the system-tile
+// epilogue's K_JJ + lambda I tiles J < 2 stay plain stores.  (Where a store's address goes into a
+// local `d` first, that is the evaluation order of the measured builds: address, then value.)
 
 // Stage image [16 k][128 x] of an Lt tile: 16-B chunk p of row k holds source chunk
 // p ^ 8(k&1), so the fragment pattern (16 x in one k row, the next k in lanes 16-31)
@@ -105,10 +75,8 @@ __device__ __forceinline__ int lt_off(int k, int x) { return k * TILE + 2 * ((x 
 
 // ---- int8 GRM tile in the f64 accumulator layout (offdiag) ----
 // cnt[cb][ib] = sum_s A[16cb + pi-row][s] B[32w + 16ib + col][s] with A = panel rows of tile J
-// (c) and B = panel rows of tile I (i).  Panel tiles [128 rows][64 B]; A chunk swizzle
-// (row>>2)&3 and B chunk swizzle (row>>2)&2 keep both ds_read_b128 patterns conflict-free.
-__device__ __forceinline__ int i8off_a(int row, int c) { return row * 64 + 16 * (c ^ ((row >> 2) & 3)); }
-__device__ __forceinline__ int i8off_b(int row, int c) { return row * 64 + 16 * (c ^ ((row >> 2) & 2)); }
+// (c) and B = panel rows of tile I (i).  Panel tiles [128 rows][64 B], chunks swizzled (i8off_a /
+// i8off_b, chol_dev.h).
 
 // ---- SYRK restricted to the 36 lower 16x16 blocks (diag kernel), A = Lt tiles (J, L) ----
 __host__ __device__ constexpr int tri_q(int e) {
@@ -282,47 +250,8 @@ __device__ __forceinline__ void factor16(double* D, double* X, int l, uint64_t* 
 
 }  // namespace
 
-// Per-launch arguments shared by the two Cholesky kernels.
-struct CholArgs {
-  double* L;                // Lt tiles [B][NT][NT][128*128]
-  double* Dinv;             // [B][NT][36 packed 16x16 blocks] X = L_JJ^{-1}
-  double* z;                // [B][nt][ns]
-  double* w;                // [B][nt][ns] forward-substitution partial sums
-  double* S;                // [B][2][36*256] K_JJ - sum_{L<J-1} L_JL L_JL^T, slot J&1
-  double* Kd;               // [B][NT][36*256] GRM diagonal tiles (k_diag_grm)
-  const double* yT;         // [nt][ytp] dual right-hand sides (y_T - mu, on the fly)
-  const double* rhs;        // [B][nt][ns] primal right-hand sides
-  const uint8_t* panel;     // [B] x pstride: kernel form, prow packed animal rows of pstride / prow bytes
-  int64_t pstride;
-  const double* u;          // [B][prow]
-  const double* scal;       // [B][SCAL]
-  int64_t ns, prow;         // padded system size, panel rows per contraction block
-  int form;
-  // primal form: rows read in place from the split's 2-bit packed SNP-major matrix
-  // (row P is zero; ft.gpk of the system's split)
-  const int64_t* idx;
-  const int64_t* off;
-  int64_t gs_row, P;
-  int64_t ytp;              // yT stride (nTp)
-  int nt;                   // traits (right-hand sides)
-  int NT, J;
-  int skip;                 // diagnostic ablation mask (TBLUP_DBG_SKIP); 0 in production
-  uint64_t* wgt;            // workgroup trace records (TBLUP_WG_TRACE), null in production
-  uint64_t* dtr;            // diagonal launch: phase timestamps of workgroup 0 (TBLUP_WG_TRACE), else null
-  const int16_t* kc;        // off-diagonal system-tile counts (k_sys_tiles, either form), else null
-  double* part;             // [2][B][NT][128*128] off-diagonal partial sums K - sum_{L<J-1} (acc layout), slot J&1
-  double* q;                // last-term mode: [B][NPACK*BLKD] L_{J,J-1} L_{J,J-1}^T, from launch J-1's tile (J, J-1)
-  int64_t B;                // individuals in the chunk
-  FoldTab ft;               // each system's split (ymu, packed rows)
-  int padskip;              // contractions over block column 0 skip the leading padding rows (SNP form)
-  int padfirst;             // SNP form: padding rows lead (SC_PAD = ns - k)
-  int16_t* kd;              // with k_sys_tiles: the diagonal tiles' exact counts for J >= 2 (KD_TILE
-                            // each; the D-units form K_JJ + lambda I where they read it, kd_block); Kd then
-                            // holds J < 2 only (the diagonal kernel's direct reads)
-};
-
 // K_JJ + lambda I (identity on padding rows) of packed lower block e of individual b's diagonal tile J,
-// from its exact counts (k_sys_tiles), minus sub (may be null), into the packed-block image dst: the
+// from its exact counts (the system-tile launches, k_systiles.hip), minus sub (may be null), into the packed-block image dst: the
 // f64 MFMA C layout, element (16 q + (l >> 4) + 4 r, 16 s + (l & 15)) of the tile at
 // dst[pk(q, s) + bo((l >> 4) + 4 r, l & 15)], q / s the block's row / column.  cv: the block's
 // counts (int2 load issued by the caller).  (v - 0.0 == v exactly, so sub = 0 stores K itself.)
@@ -332,16 +261,14 @@ __device__ __forceinline__ void kd_block(const CholArgs& a, int64_t b, int J, in
   const double* sc = a.scal + b * SCAL;
   const double sa = sc[SC_SA], cN = sc[SC_CN], invd = sc[SC_INVD], lam = sc[SC_LAM], sm = sc[SC_SM];
   const int64_t nrow = (int64_t)sc[SC_NROW], pad = (int64_t)sc[SC_PAD];
-  int q = 0;
-  while ((q + 1) * (q + 2) / 2 <= e) ++q;
-  const int sb = e - q * (q + 1) / 2;
+  int q, sb;
+  tri_decode(e, q, sb);
   const int64_t j0 = (int64_t)J * TILE;
   const double* ub = a.u + b * a.prow + j0;
   const int il = 16 * sb + (l & 15);
   const int64_t gj = j0 + il;
   const double uj = ub[il];
-  const int32_t c4[4] = {(int32_t)(int16_t)(cv.x & 0xffff), (int32_t)(int16_t)(cv.x >> 16),
-                         (int32_t)(int16_t)(cv.y & 0xffff), (int32_t)(int16_t)(cv.y >> 16)};
+  const v4i c4 = unpack_counts4(cv);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int cl = 16 * q + (l >> 4) + 4 * r;
@@ -349,22 +276,13 @@ __device__ __forceinline__ void kd_block(const CholArgs& a, int64_t b, int J, in
     const double kv = grm_value(c4[r], ub[cl], uj, sa, cN, invd, sm);
     const double v = (sys_real(gi, pad, nrow) && sys_real(gj, pad, nrow)) ? kv + ((gi == gj) ? lam : 0.0)
                                                                          : ((gi == gj) ? 1.0 : 0.0);
-    st64<TBLUP_AB_NT_PART>(dst + pk(q, sb) + bo((l >> 4) + 4 * r, l & 15), v - sub[r]);
+    double* d = dst + pk(q, sb) + bo((l >> 4) + 4 * r, l & 15);
+    __builtin_nontemporal_store(v - sub[r], d);
   }
-}
-// The exact count tiles are written once (k_sys_tiles) and read once (the unit that forms their K):
-// non-temporal accesses, so that 235 MB of them a step do not push the Lt tiles out of the caches
-__device__ __forceinline__ int2 nt_load2(const int16_t* p) {
-  const long long v = __builtin_nontemporal_load(reinterpret_cast<const long long*>(p));
-  return int2{(int)(unsigned)(v & 0xffffffffll), (int)(v >> 32)};
-}
-__device__ __forceinline__ void nt_store2(int16_t* p, int2 v) {
-  __builtin_nontemporal_store((long long)(((unsigned long long)(unsigned)v.y << 32) | (unsigned)v.x),
-                              reinterpret_cast<long long*>(p));
 }
 __device__ __forceinline__ int2 kd_load(const CholArgs& a, int64_t b, int J, int e) {
   const int l = threadIdx.x & 63;
-  return nt_load2(a.kd + ((b * a.NT + J) * KD_TILE) + (e * 64 + l) * 4);
+  return nt_load2(a.kd + kd_tile(a.NT, b, J) + (e * 64 + l) * 4);
 }
 
 // Leading contraction rows of block column 0 that a GEMM1 / SYRK run starting at L = 0 skips:
@@ -386,52 +304,6 @@ __device__ __forceinline__ void factor16_any(const CholArgs& a, double* D, doubl
 __device__ __forceinline__ void dstamp(const CholArgs& a, int slot) {
   if (a.dtr && blockIdx.x == 0 && (threadIdx.x & 63) == 0)
     a.dtr[(threadIdx.x >> 6) * 64 + slot] = __builtin_amdgcn_s_memrealtime();
-}
-
-// Profiling only: workgroup start / end timestamps (s_memrealtime, 100 MHz) of a launch.
-struct WgTrace {
-  uint64_t* rec;
-  uint64_t t0;
-  uint64_t ph;   // up to three phase marks of wave 0 (10-ns ticks from the start, 16 bits each)
-  __device__ __forceinline__ explicit WgTrace(uint64_t* base) : rec(nullptr), t0(0), ph(0) {
-    if (base) {
-      rec = base + (int64_t)blockIdx.x * WGT_REC;
-      t0 = __builtin_amdgcn_s_memrealtime();
-    }
-  }
-  __device__ __forceinline__ void mark(int k) {
-    if (!rec) return;
-    const uint64_t d = __builtin_amdgcn_s_memrealtime() - t0;
-    ph |= (d < 0xffff ? d : 0xffff) << (16 * k);
-  }
-  __device__ __forceinline__ void done(int kind, int J, int I, int64_t b) {
-    if (!rec) return;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const uint64_t t1 = __builtin_amdgcn_s_memrealtime();
-      rec[0] = t0;
-      rec[1] = t1;
-      rec[2] = ((uint64_t)kind << 56) | ((uint64_t)I << 40) | (uint64_t)b;
-      rec[3] = (uint64_t)J | (ph << 16);
-    }
-  }
-};
-
-// Packed panel row of system row r of individual b (kernel form: the gathered animal rows,
-// dual_pk_row = pstride / prow bytes each; stage kb at + 16 kb, as row_packed's)
-__device__ __forceinline__ const uint8_t* row_dpk(const CholArgs& a, int64_t b, int64_t r) {
-  return a.panel + b * a.pstride + r * (a.pstride / a.prow);
-}
-// Packed split row of system row r (primal: row r holds selected SNP r - pad; padding rows -> the
-// zero row P; stage kb at + 16 kb).
-__device__ __forceinline__ const uint8_t* row_packed(const CholArgs& a, int64_t b, int64_t r) {
-  const int64_t o0 = a.off[b], k = a.off[b + 1] - o0;
-  const int64_t pad = a.padfirst ? a.ns - k : 0;   // = SC_PAD, without a dependent scal load
-  int64_t p = a.P;
-  if (sys_real(r, pad, k)) {
-    p = snp_col(a.idx[o0 + r - pad], a.P);
-  }
-  return a.ft.gpk[fold_of(a.ft, b)] + p * a.gs_row;
 }
 
 // Kernel form, folds sharing one animal set (FoldTab::gsh): the exact count A_r . A_c of system
@@ -484,8 +356,8 @@ __device__ __forceinline__ void i8_tt8_pk64(const uint8_t* sa, const uint8_t* sb
   constexpr int TB = TILE * 64;
   auto issue = [&](int64_t st) {
     uint8_t* slot = lds + (int)(st % D) * 2 * TB;
-    ring_glds<TBLUP_AB_ASM_I8>(sa + st * 64, slot + w * 1024);
-    ring_glds<TBLUP_AB_ASM_I8>(sb + st * 64, slot + TB + w * 1024);
+    glds16_asm(sa + st * 64, slot + w * 1024);
+    glds16_asm(sb + st * 64, slot + TB + w * 1024);
   };
   for (int64_t st = 0; st < D - 1 && st < nst; ++st) issue(st);
   const int rho = l & 15, prow = (rho >> 2) + 4 * (rho & 3), ch = l >> 4;
@@ -551,8 +423,8 @@ __device__ __forceinline__ void i8_tt2d_pk64(const uint8_t* sa, const uint8_t* s
       for (int h = 0; h < 2; ++h) {
         const int64_t hs = 2 * st + h;
         if (hs < nh) {
-          ring_glds<TBLUP_AB_ASM_I8>(sa + hs * 64, slot + h * 2 * TB + w * 1024);
-          ring_glds<TBLUP_AB_ASM_I8>(sb + hs * 64, slot + h * 2 * TB + TB + w * 1024);
+          glds16_asm(sa + hs * 64, slot + h * 2 * TB + w * 1024);
+          glds16_asm(sb + hs * 64, slot + h * 2 * TB + TB + w * 1024);
         }
       }
     };
@@ -641,11 +513,7 @@ __device__ __forceinline__ void gemm1_a32(const double* __restrict__ ltJ, const 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int k = 4 * w + e;
-      if constexpr (TBLUP_AB_ASM_GEMM1)
-        glds16_asm(ltJ + src + k * TILE + 2 * (l ^ (8 * (k & 1))), slot + k * TILE);
-      else
-        __builtin_amdgcn_global_load_lds(ltJ + src + k * TILE + 2 * (l ^ (8 * (k & 1))), (lds_ptr_t)(slot + k * TILE),
-                                         16, 0, 0);
+      glds16_asm(ltJ + src + k * TILE + 2 * (l ^ (8 * (k & 1))), slot + k * TILE);
     }
   };
   const double* bcol = ltI + 16 * w + (l & 15) + (l >> 4) * TILE;
@@ -762,11 +630,7 @@ __device__ __forceinline__ void syrk_lower8_32(const double* __restrict__ src, i
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const int k = 4 * w + e;
-      if constexpr (TBLUP_AB_ASM_SYRK)
-        glds16_asm(src + (int64_t)s * AS + k * TILE + 2 * (l ^ (8 * (k & 1))), slot + k * TILE);
-      else
-        __builtin_amdgcn_global_load_lds(src + (int64_t)s * AS + k * TILE + 2 * (l ^ (8 * (k & 1))),
-                                         (lds_ptr_t)(slot + k * TILE), 16, 0, 0);
+      glds16_asm(src + (int64_t)s * AS + k * TILE + 2 * (l ^ (8 * (k & 1))), slot + k * TILE);
     }
   };
   issue(s0);
@@ -831,7 +695,8 @@ __device__ __forceinline__ void store_syrk_blocks(double* dst, const double* bas
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int o = pk(q, sb) + bo((l >> 4) + 4 * r, l & 15);
-        st64<TBLUP_AB_NT_PART>(dst + o, base ? base[o] - acc[i][r] : acc[i][r]);
+        double* d = dst + o;
+        __builtin_nontemporal_store(base ? base[o] - acc[i][r] : acc[i][r], d);
       }
     }
   }
@@ -982,7 +847,7 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
 #pragma unroll
     for (int e = 0; e < NPACK * BLKD / 2 / DTHR; ++e) {   // 9 x 16 B per thread
       const int chunk = (e * DW + w) * 64;
-      __builtin_amdgcn_global_load_lds(src + 2 * (chunk + l), (lds_ptr_t)(Tp + 2 * chunk), 16, 0, TBLUP_AB_NT_PLD ? 2 : 0);
+      __builtin_amdgcn_global_load_lds(src + 2 * (chunk + l), (lds_ptr_t)(Tp + 2 * chunk), 16, 0, 2);   // aux 2: non-temporal
     }
     if (J > L0 && a.q != nullptr) {
       // last-term mode: Q = L_{J,J-1} L_{J,J-1}^T came with launch J-1's tile (J, J-1)
@@ -1125,10 +990,7 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
       const int g = 2 * k, blk = g >> 8, o = g & 255, r = o >> 4;
       const int c0 = 2 * (((o & 15) >> 1) ^ ((r >> 1) & 7));
       const double* xb = Xp + blk * BLKD;
-      if constexpr (TBLUP_AB_NT_X)
-        __builtin_nontemporal_store(v2d{xb[bo(c0, r)], xb[bo(c0 + 1, r)]}, reinterpret_cast<v2d*>(Xg + g));
-      else
-        *reinterpret_cast<v2d*>(Xg + g) = v2d{xb[bo(c0, r)], xb[bo(c0 + 1, r)]};
+      *reinterpret_cast<v2d*>(Xg + g) = v2d{xb[bo(c0, r)], xb[bo(c0 + 1, r)]};
     }
   }
   if (a.skip & FLAG_WRITE_LJJ) {
@@ -1154,7 +1016,7 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
 // ---------------------------------------------------------------------------
 // Off-diagonal launch of column J: one 8-wave workgroup per unit, two per CU (LDS <= 72 KiB).
 //   T-unit, tile (I, J), I > J:
-//     0. acc = K_JI in the f64 accumulator layout: from k_sys_tiles' counts (either form) or int8
+//     0. acc = K_JI in the f64 accumulator layout: from the system-tile launches' counts (either form) or int8
 //        MFMA here (rows permuted so the counts land in the f64 layout) -- or, when launch J-1 ran
 //        ahead, its partial sum K_JI - sum_{L<J-1} L_JL L_IL^T
 //     1. acc -= sum_{L} L_JL L_IL^T over the L < J not summed yet   (acc = T^T, wave w: its 16 i)
@@ -1166,12 +1028,11 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
 // ---------------------------------------------------------------------------
 
 // K_{I,Jt} (the T^T layout of tile (I, Jt)) for the NCB row blocks from cb0: exact counts of
-// k_sys_tiles (loads issued by kc_issue) or, NCB = 8 only, the int8 tile here.
+// the system-tile launches (loads issued by kc_issue) or, NCB = 8 only, the int8 tile here.
 template <int NCB>
 __device__ __forceinline__ void kc_issue(const CholArgs& a, int64_t b, int I, int Jt, int cb0, int2 (&kcv)[NCB]) {
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int NT = a.NT;
-  const int16_t* kt = a.kc + ((b * (NT * (NT - 1) / 2)) + I * (I - 1) / 2 + Jt) * KC_TILE + w * 8 * 64 * 4;
+  const int16_t* kt = a.kc + kc_tile(a.NT, b, I, Jt) + w * 8 * 64 * 4;
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) kcv[cb] = nt_load2(kt + ((cb0 + cb) * 64 + l) * 4);
 }
@@ -1217,6 +1078,7 @@ __device__ __forceinline__ void k_acc(const CholArgs& a, int64_t b, int I, int J
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb) {
+      // (written out, not unpack_counts4: with it the compiler reorders k_chol_diag's register setup)
       const int32_t c4[4] = {(int32_t)(int16_t)(kcv[cb].x & 0xffff), (int32_t)(int16_t)(kcv[cb].x >> 16),
                              (int32_t)(int16_t)(kcv[cb].y & 0xffff), (int32_t)(int16_t)(kcv[cb].y >> 16)};
 #pragma unroll
@@ -1242,8 +1104,8 @@ __device__ __forceinline__ void k_acc(const CholArgs& a, int64_t b, int I, int J
       // 2-bit packed rows of either form: the SNP form's split rows, the kernel form's gathered panel
       const int row = 16 * w + (l >> 2), pos = l & 3;
       const bool pf = a.form == FORM_PRIMAL;
-      const uint8_t* sa = (pf ? row_packed(a, b, j0 + row) : row_dpk(a, b, j0 + row)) + 16 * (pos ^ ((row >> 2) & 3));
-      const uint8_t* sb = (pf ? row_packed(a, b, i0 + row) : row_dpk(a, b, i0 + row)) + 16 * (pos ^ ((row >> 2) & 2));
+      const uint8_t* sa = (pf ? row_packed(a, b, j0 + row) : row_dpk(a, b, j0 + row)) + pk_swz_a(row, pos);
+      const uint8_t* sb = (pf ? row_packed(a, b, i0 + row) : row_dpk(a, b, i0 + row)) + pk_swz_b(row, pos);
       i8_tt2d_pk64<4>(sa, sb, nblk, lds8, cnt);
     } else {
 #pragma unroll
@@ -1287,13 +1149,8 @@ __device__ __forceinline__ void part_unit(const CholArgs& a, int64_t b, int I, i
 #pragma unroll
   for (int cb = 0; cb < NCB; ++cb) {
     v2d* d = reinterpret_cast<v2d*>(pd + ((cb0 + cb) * 64 + l) * 4);
-    if constexpr (TBLUP_AB_NT_PART) {
-      __builtin_nontemporal_store(v2d{acc[cb][0], acc[cb][1]}, d);
-      __builtin_nontemporal_store(v2d{acc[cb][2], acc[cb][3]}, d + 1);
-    } else {
-      d[0] = v2d{acc[cb][0], acc[cb][1]};
-      d[1] = v2d{acc[cb][2], acc[cb][3]};
-    }
+    __builtin_nontemporal_store(v2d{acc[cb][0], acc[cb][1]}, d);
+    __builtin_nontemporal_store(v2d{acc[cb][2], acc[cb][3]}, d + 1);
   }
 }
 
@@ -1314,8 +1171,7 @@ __device__ __forceinline__ void tile_unit(const CholArgs& a, int64_t b, int I, i
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
       const v2d* s2 = reinterpret_cast<const v2d*>(pd + (cb * 64 + l) * 4);
-      const v2d lo = TBLUP_AB_NT_PLD ? __builtin_nontemporal_load(s2) : s2[0];
-      const v2d hi = TBLUP_AB_NT_PLD ? __builtin_nontemporal_load(s2 + 1) : s2[1];
+      const v2d lo = __builtin_nontemporal_load(s2), hi = __builtin_nontemporal_load(s2 + 1);
       acc[cb] = v4d{lo[0], lo[1], hi[0], hi[1]};
     }
   } else if (a.kc) {
@@ -1371,7 +1227,8 @@ __device__ __forceinline__ void tile_unit(const CholArgs& a, int64_t b, int I, i
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int jl = 16 * jb + (l >> 4) + 4 * r, il = 16 * w + (l & 15);
-      st64<TBLUP_AB_NT_L>(Lout + jl * TILE + il, o[r]);
+      double* d = Lout + jl * TILE + il;
+      __builtin_nontemporal_store(o[r], d);
 #pragma unroll
       for (int tr = 0; tr < NTR; ++tr) wacc[tr] += o[r] * zj_sh[tr][jl];
     }
@@ -1419,8 +1276,7 @@ __device__ __forceinline__ void e_unit(const CholArgs& a, int64_t b, int I, int 
 #pragma unroll
     for (int cb = 0; cb < 8; ++cb) {
       const v2d* s2 = reinterpret_cast<const v2d*>(pd + (cb * 64 + l) * 4);
-      const v2d lo = TBLUP_AB_NT_PLD ? __builtin_nontemporal_load(s2) : s2[0];
-      const v2d hi = TBLUP_AB_NT_PLD ? __builtin_nontemporal_load(s2 + 1) : s2[1];
+      const v2d lo = __builtin_nontemporal_load(s2), hi = __builtin_nontemporal_load(s2 + 1);
       acc[cb] = v4d{lo[0], lo[1], hi[0], hi[1]};
     }
   } else {
@@ -1437,13 +1293,8 @@ __device__ __forceinline__ void e_unit(const CholArgs& a, int64_t b, int I, int 
 #pragma unroll
   for (int cb = 0; cb < 8; ++cb) {
     v2d* d = reinterpret_cast<v2d*>(pd + (cb * 64 + l) * 4);
-    if constexpr (TBLUP_AB_NT_PART) {
-      __builtin_nontemporal_store(v2d{acc[cb][0], acc[cb][1]}, d);
-      __builtin_nontemporal_store(v2d{acc[cb][2], acc[cb][3]}, d + 1);
-    } else {
-      d[0] = v2d{acc[cb][0], acc[cb][1]};
-      d[1] = v2d{acc[cb][2], acc[cb][3]};
-    }
+    __builtin_nontemporal_store(v2d{acc[cb][0], acc[cb][1]}, d);
+    __builtin_nontemporal_store(v2d{acc[cb][2], acc[cb][3]}, d + 1);
   }
 }
 
@@ -1511,8 +1362,8 @@ __device__ __forceinline__ void diag_grm_tile(const CholArgs& a, int64_t b, int 
   } else {
     // 2-bit packed rows: the SNP form's split rows, the kernel form's gathered panel
     const uint8_t* rp = a.form == FORM_PRIMAL ? row_packed(a, b, j0 + row) : row_dpk(a, b, j0 + row);
-    const uint8_t* sa = rp + 16 * (pos ^ ((row >> 2) & 3));
-    const uint8_t* sb = rp + 16 * (pos ^ ((row >> 2) & 2));
+    const uint8_t* sa = rp + pk_swz_a(row, pos);
+    const uint8_t* sb = rp + pk_swz_b(row, pos);
     switch (wc) {   // wave-uniform: one instantiation per column block
       case 0: i8_tt8_pk64<4, 0>(sa, sb, nblk, lds, cnt); break;
       case 1: i8_tt8_pk64<4, 1>(sa, sb, nblk, lds, cnt); break;
@@ -1622,614 +1473,6 @@ __global__ __launch_bounds__(OTH, 4) void k_chol_offdiag(CholArgs a, OffPlan p) 
   tr.done(WGT_KJJ, a.J, 2 + (int)(lg % nJ), lg / nJ);
 }
 
-// ===========================================================================
-// SNP form: every system tile (I >= J) of the batch in one launch, before the column loop:
-// C = A B^T over the n_T train animals on FP4 MFMA (16x16x128, e2m1 operands, fp32 accumulate),
-// 2-bit packed split rows read in place.  Genotype code g read as an e2m1 nibble is g / 2 (0, 0.5,
-// 1.0), so a packed dword's even fields become nibbles by x & 0x33333333 and its odd fields by
-// (x >> 2) & 0x33333333 -- 3 VALU ops per 16 animals into 2 operand dwords (the int8 form spent 7
-// per 16 animals) -- and both operands carry the E8M0 scale 2.0; the counts (<= 4 n_T < 2^24)
-// accumulate exactly in fp32 at twice the int8 rate.  The animals' order inside k is the same for A and B, so A B^T is unchanged.
-// 4 waves per workgroup; wave (qr, qc) computes a 64 x 64 quadrant = 4 x 4 blocks; 256-animal
-// stages through a 3-deep LDS-DMA ring (48 KiB, three workgroups per CU).  A rows are read
-// through pi(rho) so the counts land in the f64 accumulator layout.  Off-diagonal tiles store
-// the exact counts as int16 where the off-diagonal kernel's lanes read them (kc, see
-// tblup_internal.h); diagonal tiles store the exact counts of their 36 lower blocks the same way
-// (kd: 18 KiB a tile instead of 72 KiB of fp64 K_JJ + lambda I -- the diagonal kernel and the
-// D-units form those values where they read them, kd_block).  (Rows stored as nibbles -- twice the
-// bytes, no unpack -- measured no faster: those loads then bound the launch.)
-// ===========================================================================
-constexpr int STW = 4;   // waves per system-tile workgroup
-
-// K_JJ + lambda I (identity on padding rows) from a diagonal tile's accumulators (exact counts in
-// fp32) as packed fp64 blocks into Kd: the tiles J < 2, which the diagonal kernel reads directly
-// (sc / ub: the system's scalars and tile J's centring sums -- scal / u, or their LDS copies)
-__device__ __forceinline__ void sys_diag_epilogue_src(const CholArgs& a, const v4f (&cnt)[4][4], int64_t b, int J, int qr,
-                                                      int qc, int l, const double* sc, const double* ub) {
-  const int64_t j0 = (int64_t)J * TILE;
-  const double sa_ = sc[SC_SA], cN = sc[SC_CN], invd = sc[SC_INVD], lam = sc[SC_LAM], sm = sc[SC_SM];
-  const int64_t nrow = (int64_t)sc[SC_NROW], pad = (int64_t)sc[SC_PAD];
-  double* Kd = a.Kd + (b * a.NT + J) * (int64_t)NPACK * BLKD;
-  // every centring sum this lane needs, loaded before the first store (Kd and u are both double
-  // pointers: loads interleaved with the stores were issued one after another, ~47 us a launch)
-  double ur[4][4], uc[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) ur[m][r] = ub[16 * (4 * qr + m) + (l >> 4) + 4 * r];
-#pragma unroll
-  for (int n = 0; n < 4; ++n) uc[n] = ub[16 * (4 * qc + n) + (l & 15)];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const int cb = 4 * qr + m, ib = 4 * qc + n;
-      if (cb < ib) continue;
-      const int il = 16 * ib + (l & 15);
-      const int64_t gj = j0 + il;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int cl = 16 * cb + (l >> 4) + 4 * r;
-        const int64_t gi = j0 + cl;
-        const double kv = grm_value((int32_t)cnt[m][n][r], ur[m][r], uc[n], sa_, cN, invd, sm);
-        const double v = (sys_real(gi, pad, nrow) && sys_real(gj, pad, nrow)) ? kv + ((gi == gj) ? lam : 0.0)
-                                                                              : ((gi == gj) ? 1.0 : 0.0);
-        st64<TBLUP_AB_NT_KD>(Kd + pk(cb, ib) + bo(cl & 15, il & 15), v);
-      }
-    }
-}
-__device__ __forceinline__ void sys_diag_epilogue_inl(const CholArgs& a, const v4f (&cnt)[4][4], int64_t b, int J, int qr,
-                                                      int qc, int l) {
-  sys_diag_epilogue_src(a, cnt, b, J, qr, qc, l, a.scal + b * SCAL, a.u + b * a.prow + (int64_t)J * TILE);
-}
-__device__ void sys_diag_epilogue(const CholArgs& a, const v4f (&cnt)[4][4], int64_t b, int J, int qr, int qc, int l);
-
-// a diagonal tile's counts as int16 (diag): its 36 lower blocks (cb >= ib) only, packed block
-// e = cb (cb + 1) / 2 + ib, lane order of the f64 C layout (kd_load / kd_block read them); an
-// off-diagonal tile's: store_counts16's layout
-// The super-tile kernel's counted ring waits (k_sys_tiles_st) leave the VMEM ops younger than the
-// stage they wait for outstanding: ST_STAGE_OPS LDS-DMA loads per lane for each later stage (issue():
-// two rows x A and B) and, after a unit of two off-diagonal tiles, this function's stores -- one 8-B
-// store per 16 x 16 block of the wave's 4 x 4 quadrant (all 16 off the diagonal: addresses 512 B
-// apart within a lane, never merged).  A count above the real number only waits for more.
-constexpr int ST_STAGE_OPS = 4;
-constexpr int ST_TILE_STORES = 4 * 4;
-constexpr int ST_UNIT_STORES = 2 * ST_TILE_STORES;
-static_assert(2 * ST_STAGE_OPS + ST_UNIT_STORES < 64, "vmcnt holds 6 bits");
-__device__ __forceinline__ void store_counts16_any(int16_t* kt, const v4f (&cnt)[4][4], int qr, int qc, int l,
-                                                   bool diag) {
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const int cb = 4 * qr + m, ib = 4 * qc + n;
-      if (diag && cb < ib) continue;
-      const v4f c = cnt[m][n];
-      const int2 packed = {(int)((uint32_t)((int)c[0] & 0xffff) | ((uint32_t)(int)c[1] << 16)),
-                           (int)((uint32_t)((int)c[2] & 0xffff) | ((uint32_t)(int)c[3] << 16))};
-      nt_store2(kt + ((diag ? cb * (cb + 1) / 2 + ib : ib * 8 + cb) * 64 + l) * 4, packed);
-    }
-}
-
-// two packed dwords (32 animals) -> one fp4 MFMA operand (even fields, odd fields of each): the
-// 2-bit code g lands in the low half of a nibble, e2m1 value g / 2 (0, 0.5 subnormal, 1.0), and
-// the E8M0 operand scales 2.0 (128) restore g -- 3 VALU ops per packed dword instead of 4
-__device__ __forceinline__ v4i fp4_operand(uint32_t x0, uint32_t x1) {
-  constexpr uint32_t M = 0x33333333u;
-  return v4i{(int)(x0 & M), (int)((x0 >> 2) & M), (int)(x1 & M), (int)((x1 >> 2) & M)};
-}
-// the scaled f8f6f4 MFMA with fp4 operands in 4 VGPRs each (the clang builtin types them as 8 VGPRs,
-// the upper half unused by fp4 -- 32 more VGPRs and a zeroing move per operand)
-__device__ v4f mfma_fp4_16x16x128(v4i a, v4i b, v4f c, int cbsz, int blgp, int opsel_a, int scale_a, int opsel_b,
-                                  int scale_b) __asm("llvm.amdgcn.mfma.scale.f32.16x16x128.f8f6f4.v4i32.v4i32");
-
-template <bool DUAL>   // kernel form: the gathered panel's packed animal rows
-__global__ __launch_bounds__(64 * STW, 2) void k_sys_tiles(CholArgs a, int16_t* kc, int ntri) {
-  constexpr int D = 3;                 // 64-B stages (256 animals) in the LDS ring (48 KiB: 3 workgroups per CU)
-  constexpr int TB = TILE * 64;        // one operand image of a stage: 8 KiB
-  __shared__ __attribute__((aligned(16))) uint8_t lds[D * 2 * TB];   // 64 KiB
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, qr = w >> 1, qc = w & 1;
-  WgTrace tr(a.wgt);
-  const int64_t lg = xcd_remap(blockIdx.x, gridDim.x);   // an individual's tiles on one XCD
-  const int64_t b = lg / ntri;
-  const int t = (int)(lg % ntri);
-  int I = 0;
-  while ((I + 1) * (I + 2) / 2 <= t) ++I;
-  const int J = t - I * (I + 1) / 2;
-  const bool compute = (I != J) || (qr >= qc);   // diagonal tile: the upper quadrant is never read
-  const int64_t i0 = (int64_t)I * TILE, j0 = (int64_t)J * TILE;
-  const double* sc = a.scal + b * SCAL;
-  const int64_t nblk = (int64_t)sc[SC_CBLK];
-  const int64_t nst = (nblk + 3) >> 2;
-  const int tail_ch = (int)(nblk & 3);
-  // loader: wave w fills rows 16 (2w + h) + (l >> 2), h = 0, 1, of both operand images
-  const uint8_t* sa[2];
-  const uint8_t* sb[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = 16 * (2 * w + h) + (l >> 2), pos = l & 3;
-    sa[h] = (DUAL ? row_dpk(a, b, j0 + row) : row_packed(a, b, j0 + row)) + 16 * (pos ^ ((row >> 2) & 3));
-    sb[h] = (DUAL ? row_dpk(a, b, i0 + row) : row_packed(a, b, i0 + row)) + 16 * (pos ^ ((row >> 2) & 2));
-  }
-  auto issue = [&](int64_t st) {
-    uint8_t* slot = lds + (int)(st % D) * 2 * TB;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      ring_glds<TBLUP_AB_ASM_I8>(sa[h] + st * 64, slot + (2 * w + h) * 1024);
-      ring_glds<TBLUP_AB_ASM_I8>(sb[h] + st * 64, slot + TB + (2 * w + h) * 1024);
-    }
-  };
-  v4f cnt[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) cnt[m][n] = v4f{0.f, 0.f, 0.f, 0.f};
-  for (int64_t st = 0; st < D - 1 && st < nst; ++st) issue(st);
-  const int rho = l & 15, prow = (rho >> 2) + 4 * (rho & 3), ch = l >> 4;
-  for (int64_t st = 0; st < nst; ++st) {
-    if (st + D - 2 < nst) {
-      asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * 4) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    if (st + D - 1 < nst) issue(st + D - 1);
-    if (compute && !(a.skip & (1 << 18))) {
-      const uint8_t* As = lds + (int)(st % D) * 2 * TB;
-      const uint8_t* Bs = As + TB;
-      const bool ztail = (st == nst - 1 && tail_ch != 0 && ch >= tail_ch);   // past the training animals
-      uint4 aq[4], bq[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        aq[m] = *reinterpret_cast<const uint4*>(As + i8off_a(16 * (4 * qr + m) + prow, ch));
-        bq[m] = *reinterpret_cast<const uint4*>(Bs + i8off_b(16 * (4 * qc + m) + rho, ch));
-        if (ztail) bq[m] = uint4{0u, 0u, 0u, 0u};
-      }
-#pragma unroll
-      for (int s2 = 0; s2 < 2; ++s2) {
-        v4i av[4], bv[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          av[m] = s2 == 0 ? fp4_operand(aq[m].x, aq[m].y) : fp4_operand(aq[m].z, aq[m].w);
-          bv[m] = s2 == 0 ? fp4_operand(bq[m].x, bq[m].y) : fp4_operand(bq[m].z, bq[m].w);
-        }
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n)   // cbsz = blgp = 4: A, B in fp4; E8M0 scales 128 = 2.0
-            cnt[m][n] = mfma_fp4_16x16x128(av[m], bv[n], cnt[m][n], 4, 4, 0, 128, 0, 128);
-      }
-    }
-  }
-  if (compute && I == J && J < 2 && !(a.skip & (1 << 17)))
-    sys_diag_epilogue(a, cnt, b, J, qr, qc, l);   // read directly by the diagonal kernel
-  else if (compute && !(a.skip & (I != J ? 1 << 16 : 1 << 17)))
-    store_counts16_any(I != J ? kc + ((b * (a.NT * (a.NT - 1) / 2)) + I * (I - 1) / 2 + J) * KC_TILE
-                              : a.kd + (b * a.NT + J) * KD_TILE,
-                       cnt, qr, qc, l, I == J);
-  tr.done(WGT_SYS, J, I, b);
-}
-
-// Persistent super-tile form of k_sys_tiles (large batches, sys_tiles_grid): one 8-wave workgroup
-// per CU walks a contiguous run of units, a unit being a 256 x 256 super-tile = the 2 x 2 tiles
-// (I0 + ti, J0 + tj), I0 = 2 SI, J0 = 2 SJ, SI >= SJ, of one individual (10 units at NT = 8 instead
-// of 36 tile workgroups).  Per 256-animal stage a unit loads 2 x 256 rows (32 KiB: half the bytes
-// per tile of the single-tile form) and runs 64 MFMAs per wave: wave (tj, qr, qc) accumulates
-// quadrant (qr, qc) of tiles (I0, J0 + tj) and (I0 + 1, J0 + tj) (A fragments shared).  The
-// 3-deep LDS-DMA ring runs on across unit boundaries (the next unit's first stages load while
-// this one's last stage computes and its counts are stored), so the per-tile prologue and store
-// latency of 36 short workgroups is paid once per run.  Row addresses come from a per-individual
-// row table in LDS (no global load whose use would drain the ring).  The same exact fp32 counts as
-// k_sys_tiles (every partial sum an integer below 2^24), stored to the same places.
-constexpr int SPW = 8;                 // waves per super-tile workgroup
-constexpr int SP_MAXIND = 64;          // individuals in one workgroup's run (sys_tiles_grid checks)
-
-#ifndef TBLUP_AB_SYS_ST_MIN   // A/B builds only (tools/ab_build_defs.sh)
-#define TBLUP_AB_SYS_ST_MIN 4
-#endif
-#ifndef TBLUP_AB_SP_D
-#define TBLUP_AB_SP_D 3
-#endif
-static_assert(TBLUP_AB_SP_D >= 3 && TBLUP_AB_SP_D <= 4, "ring waits are written for 1-2 stages ahead");
-constexpr int64_t SYS_ST_MIN = TBLUP_AB_SYS_ST_MIN;   // auto: at least this many units per CU
-
-template <bool DUAL>   // kernel form: the gathered panel's packed animal rows
-__global__ __launch_bounds__(64 * SPW, 1) void k_sys_tiles_st(CholArgs a, int16_t* kc, int nsu, int nunits) {
-  constexpr int D = TBLUP_AB_SP_D;     // stages in the ring
-  constexpr int TB2 = 2 * TILE * 64;   // one 256-row operand image of a stage: 16 KiB
-  __shared__ __attribute__((aligned(16))) uint8_t lds[D * 2 * TB2];   // 96 KiB at D = 3
-  __shared__ int32_t rowtab[SP_ROWTAB];
-  __shared__ int32_t cblk_tab[SP_MAXIND];   // contraction blocks of the run's individuals (SNP form:
-                                            // n_Tp / 64 each, SC_CBLK -- not read from scal, so this
-                                            // launch may precede the scalars' k_stats_diag_counts)
-  const int t = threadIdx.x, l = t & 63, w = t >> 6;
-  const int tj = w >> 2, qr = (w >> 1) & 1, qc = w & 1;
-  const int NT = a.NT;
-  WgTrace tr(a.wgt);
-  const int u0 = (int)((int64_t)blockIdx.x * nunits / gridDim.x), u1 = (int)((int64_t)(blockIdx.x + 1) * nunits / gridDim.x);
-  const int b_first = u0 / nsu;
-  const int rho = l & 15, prow = (rho >> 2) + 4 * (rho & 3), ch = l >> 4;
-  const int pos = l & 3;
-  // super-tile s of the lower triangle (row-major): SI, SJ
-  auto unit_tiles = [&](int u, int& b, int& I0, int& J0) __attribute__((always_inline)) {
-    b = __builtin_amdgcn_readfirstlane(u / nsu);
-    const int s = __builtin_amdgcn_readfirstlane(u % nsu);
-    int SI = 0;
-    while ((SI + 1) * (SI + 2) / 2 <= s) ++SI;
-    I0 = 2 * SI;
-    J0 = 2 * (s - SI * (SI + 1) / 2);
-  };
-  // the row table of individual b: packed row index of each of its ns system rows (row P: zero)
-  int tab_b = -1;
-  auto load_rowtab = [&](int b) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const int64_t o0 = a.off[b], k = a.off[b + 1] - o0;
-    const int64_t pad = a.padfirst ? a.ns - k : 0;
-    const int nrt = 2 * TILE * ((NT + 1) / 2);   // rows a super-tile reads (ns rounded up to 256)
-    if constexpr (!DUAL) {
-      for (int r = t; r < nrt; r += 64 * SPW)
-        rowtab[r] = (int32_t)(r < a.ns && sys_real(r, pad, k) ? snp_col(a.idx[o0 + r - pad], a.P) : a.P);
-    } else {   // kernel form: the panel's own rows (past ns: any row -- those tiles are not stored)
-      for (int r = t; r < nrt; r += 64 * SPW) rowtab[r] = r < a.ns ? r : 0;
-    }
-    __syncthreads();
-    tab_b = b;
-  };
-  // issue cursor: the unit and stage whose loads go out next, and its row pointers
-  int iu = u0, ib = 0;
-  int ist = 0, inst = 0;
-  int ra[2], rb[2];                    // packed rows of this lane's A / B loads (h = 0, 1)
-  const uint8_t* gbase = nullptr;
-  const int64_t gsr = DUAL ? a.pstride / a.prow : a.gs_row;   // packed row bytes
-  const int offa[2] = {16 * (pos ^ (((l >> 2) >> 2) & 3)), 16 * (pos ^ (((16 + (l >> 2)) >> 2) & 3))};
-  const int offb[2] = {16 * (pos ^ (((l >> 2) >> 2) & 2)), 16 * (pos ^ (((16 + (l >> 2)) >> 2) & 2))};
-  auto setup_issue = [&]() __attribute__((always_inline)) {
-    int I0, J0;
-    unit_tiles(iu, ib, I0, J0);
-    if (ib != tab_b) load_rowtab(ib);
-    inst = (cblk_tab[ib - b_first] + 3) >> 2;
-    gbase = DUAL ? a.panel + ib * a.pstride : a.ft.gpk[fold_of(a.ft, ib)];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int row = 16 * (2 * w + h) + (l >> 2);
-      ra[h] = rowtab[J0 * TILE + row];
-      rb[h] = rowtab[I0 * TILE + row];
-    }
-    ist = 0;
-  };
-  // issue one stage into ring slot g % D and advance the cursor (false: nothing left)
-  auto issue = [&](int g) __attribute__((always_inline)) {
-    if (iu >= u1) return;
-    uint8_t* slot = lds + (g % D) * 2 * TB2;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      glds16_asm(gbase + (int64_t)ra[h] * gsr + (offa[h] + ist * 64), slot + (2 * w + h) * 1024);
-      glds16_asm(gbase + (int64_t)rb[h] * gsr + (offb[h] + ist * 64), slot + TB2 + (2 * w + h) * 1024);
-    }
-    if (++ist == inst && ++iu < u1) setup_issue();
-  };
-  if (u0 >= u1) return;
-  const int nind = (u1 - 1) / nsu - b_first + 1;
-  if (t < nind) {   // kernel form: the individual's k SNPs
-    const int64_t bt = b_first + t;
-    cblk_tab[t] = (int32_t)(DUAL ? (a.off[bt + 1] - a.off[bt] + KBLK - 1) / KBLK : a.ytp / KBLK);
-  }
-  __syncthreads();
-  setup_issue();
-  // total stages of the run (the units of one individual share its stage count)
-  int nstages = 0;
-  for (int u = u0; u < u1;) {
-    const int b = u / nsu, ue = min(u1, (b + 1) * nsu);
-    nstages += (ue - u) * ((cblk_tab[b - b_first] + 3) >> 2);
-    u = ue;
-  }
-  for (int g = 0; g < D - 1; ++g) issue(g);
-
-  v4f cnt[2][4][4];
-#pragma unroll
-  for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-    for (int m = 0; m < 4; ++m)
-#pragma unroll
-      for (int n = 0; n < 4; ++n) cnt[ti][m][n] = v4f{0.f, 0.f, 0.f, 0.f};
-  // compute cursor
-  int cu = u0, cb_ = 0;
-  int cI0 = 0, cJ0 = 0, cst = 0;
-  unit_tiles(cu, cb_, cI0, cJ0);
-  int cnblk = cblk_tab[cb_ - b_first];
-  int cnst = (int)((cnblk + 3) >> 2);
-  bool stored_full = false;   // the previous stage ended a unit whose every wave stored 32 count pairs
-  for (int g = 0; g < nstages; ++g) {
-    // stage g's loads done: the younger ops are the 4 loads of each stage issued after it (up to
-    // D - 2) and the stores of the unit that ended last stage (32 per wave after a full
-    // off-diagonal super-tile: 16 8-B stores per tile whose addresses lie 512 B apart within a
-    // lane, so none can be merged; any other unit: waited for)
-    const int ahead = min(D - 2, nstages - 1 - g);   // stages issued after stage g
-    if (ahead >= 2) {
-      if (stored_full)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ST_STAGE_OPS + ST_UNIT_STORES) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(2 * ST_STAGE_OPS) : "memory");
-    } else if (ahead == 1) {
-      if (stored_full)
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(ST_STAGE_OPS + ST_UNIT_STORES) : "memory");
-      else
-        asm volatile("s_waitcnt vmcnt(%0)" ::"i"(ST_STAGE_OPS) : "memory");
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    __builtin_amdgcn_s_barrier();
-    issue(g + D - 1);
-    const int J0t = cJ0 + tj;
-    bool comp[2];
-#pragma unroll
-    for (int ti = 0; ti < 2; ++ti) {
-      const int I = cI0 + ti;
-      comp[ti] = I < NT && J0t < NT && (I > J0t || (I == J0t && qr >= qc));
-    }
-    if ((comp[0] || comp[1]) && !(a.skip & (1 << 18))) {
-      const uint8_t* As = lds + (g % D) * 2 * TB2;
-      const uint8_t* Bs = As + TB2;
-      const int tail_ch = (int)(cnblk & 3);
-      const bool ztail = (cst == cnst - 1 && tail_ch != 0 && ch >= tail_ch);   // past the training animals
-      uint4 aq[4];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) aq[m] = *reinterpret_cast<const uint4*>(As + i8off_a(TILE * tj + 16 * (4 * qr + m) + prow, ch));
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti) {
-        if (!comp[ti]) continue;
-        uint4 bq[4];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) {
-          bq[n] = *reinterpret_cast<const uint4*>(Bs + i8off_b(TILE * ti + 16 * (4 * qc + n) + rho, ch));
-          if (ztail) bq[n] = uint4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          v4i av[4];
-#pragma unroll
-          for (int m = 0; m < 4; ++m) av[m] = s2 == 0 ? fp4_operand(aq[m].x, aq[m].y) : fp4_operand(aq[m].z, aq[m].w);
-#pragma unroll
-          for (int n = 0; n < 4; ++n) {
-            const v4i bv = s2 == 0 ? fp4_operand(bq[n].x, bq[n].y) : fp4_operand(bq[n].z, bq[n].w);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)   // cbsz = blgp = 4: A, B in fp4; E8M0 scales 128 = 2.0
-              cnt[ti][m][n] = mfma_fp4_16x16x128(av[m], bv, cnt[ti][m][n], 4, 4, 0, 128, 0, 128);
-          }
-        }
-      }
-    }
-    stored_full = false;
-    if (++cst == cnst) {
-      // the unit's epilogue: its tiles' counts (diagonal tiles J < 2 too: k_sys_diag_counts forms
-      // their K_JJ + lambda I afterwards -- the fp64 epilogue here would spill the accumulators)
-      stored_full = cI0 != cJ0 && cI0 + 1 < NT && !(a.skip & (1 << 16));
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti) {
-        const int I = cI0 + ti;
-        if (!comp[ti]) continue;
-        if (!(a.skip & (I != J0t ? 1 << 16 : 1 << 17))) {
-          store_counts16_any(I != J0t ? kc + ((int64_t)cb_ * (NT * (NT - 1) / 2) + I * (I - 1) / 2 + J0t) * KC_TILE
-                                      : a.kd + ((int64_t)cb_ * NT + J0t) * KD_TILE,
-                             cnt[ti], qr, qc, l, I == J0t);
-        }
-      }
-#pragma unroll
-      for (int ti = 0; ti < 2; ++ti)
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-          for (int n = 0; n < 4; ++n) cnt[ti][m][n] = v4f{0.f, 0.f, 0.f, 0.f};
-      if (++cu < u1) {
-        unit_tiles(cu, cb_, cI0, cJ0);
-        cnblk = cblk_tab[cb_ - b_first];
-        cnst = (int)((cnblk + 3) >> 2);
-      }
-      cst = 0;
-    }
-  }
-  tr.done(WGT_SYS, 0, 0, u0 / nsu);
-}
-
-// Fold-fused evaluation with shared counts (IntraGCV's folds, tblup_eval_folds*): when every fold's
-// training rows R_f and validation rows V_f make up the same multiset T_all, C_{R_f} = C_{T_all} -
-// C_{V_f}.  One workgroup per (individual b, tile) accumulates C_{T_all} over fold 0's rows
-// [0, nRp) (train, zero padding, validation, zero padding), then for f = 0 .. F-1 adds C_{V_{f-1}}
-// back (f > 0) and subtracts C_{V_f} -- the A operand negated through the e2m1 sign bits -- and
-// stores system f * B + b's tile after each subtraction.  The stage sequence runs through one
-// 3-deep LDS-DMA ring across these segments.  Every partial sum is an exact integer in fp32, so
-// the tiles equal k_sys_tiles' per-fold ones bit for bit; contraction (nRp + (2F - 1) nVp) / (F nTp)
-// of the per-fold launch's (config 2, 5 folds of 256: 14 stages of 256 animals instead of 20).
-__global__ __launch_bounds__(64 * STW, 2) void k_sys_tiles_folds(CholArgs a, int16_t* kc, int ntri) {
-  constexpr int D = 3;
-  constexpr int TB = TILE * 64;
-  __shared__ __attribute__((aligned(16))) uint8_t lds[D * 2 * TB];
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, qr = w >> 1, qc = w & 1;
-  WgTrace tr(a.wgt);
-  const int64_t lg = xcd_remap(blockIdx.x, gridDim.x);
-  const int64_t b = lg / ntri;   // individual: system b of fold 0
-  const int t = (int)(lg % ntri);
-  int I = 0;
-  while ((I + 1) * (I + 2) / 2 <= t) ++I;
-  const int J = t - I * (I + 1) / 2;
-  const bool compute = (I != J) || (qr >= qc);
-  const int64_t i0 = (int64_t)I * TILE, j0 = (int64_t)J * TILE;
-  const int F = a.ft.nf;
-  const int64_t bpf = a.ft.bpf;
-  const int64_t vbyte = a.ytp / 4;                           // validation rows start (nTp animals)
-  const int64_t nblkA = a.gs_row / 16, nsA = (nblkA + 3) >> 2;   // all nRp animals, 64 per block
-  const int64_t nblkV = nblkA - a.ytp / 64, nsV = (nblkV + 3) >> 2;
-  const int64_t nst = nsA + (2 * F - 1) * nsV;
-  // the same SNP rows in every fold's layout: per-lane row offsets, fold bases per stage
-  int64_t oa[2], ob[2];
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int row = 16 * (2 * w + h) + (l >> 2), pos = l & 3;
-    oa[h] = (row_packed(a, b, j0 + row) - a.ft.gpk[0]) + 16 * (pos ^ ((row >> 2) & 3));
-    ob[h] = (row_packed(a, b, i0 + row) - a.ft.gpk[0]) + 16 * (pos ^ ((row >> 2) & 2));
-  }
-  // stage g -> segment k (0: T_all of fold 0, 2f + 1: minus V_f, 2f + 2: plus V_f) and its stage
-  auto seg_of = [&](int64_t g, int& k, int64_t& st) {
-    if (g < nsA) {
-      k = 0;
-      st = g;
-    } else {
-      k = 1 + (int)((g - nsA) / nsV);
-      st = (g - nsA) % nsV;
-    }
-  };
-  auto issue = [&](int64_t g) __attribute__((always_inline)) {
-    int k;
-    int64_t st;
-    seg_of(g, k, st);
-    const uint8_t* base = a.ft.gpk[k == 0 ? 0 : (k - 1) >> 1] + (k == 0 ? 0 : vbyte) + st * 64;
-    uint8_t* slot = lds + (int)(g % D) * 2 * TB;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      ring_glds<TBLUP_AB_ASM_I8>(base + oa[h], slot + (2 * w + h) * 1024);
-      ring_glds<TBLUP_AB_ASM_I8>(base + ob[h], slot + TB + (2 * w + h) * 1024);
-    }
-  };
-  v4f cnt[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) cnt[m][n] = v4f{0.f, 0.f, 0.f, 0.f};
-  for (int64_t g = 0; g < D - 1 && g < nst; ++g) issue(g);
-  const int rho = l & 15, prow = (rho >> 2) + 4 * (rho & 3), ch = l >> 4;
-  int64_t g = 0;
-  for (int k = 0; k < 2 * F; ++k) {
-    const int64_t ns_k = k == 0 ? nsA : nsV;
-    const int tail_ch = (int)((k == 0 ? nblkA : nblkV) & 3);
-    const int neg = (k & 1) ? (int)0x88888888u : 0;   // e2m1 sign bits: subtract this segment
-    for (int64_t st = 0; st < ns_k; ++st, ++g) {
-      if (g + D - 2 < nst) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"((D - 2) * 4) : "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      if (g + D - 1 < nst) issue(g + D - 1);
-      if (compute) {
-        const uint8_t* As = lds + (int)(g % D) * 2 * TB;
-        const uint8_t* Bs = As + TB;
-        const bool ztail = (st == ns_k - 1 && tail_ch != 0 && ch >= tail_ch);   // past the segment's rows
-        uint4 aq[4], bq[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-          aq[m] = *reinterpret_cast<const uint4*>(As + i8off_a(16 * (4 * qr + m) + prow, ch));
-          bq[m] = *reinterpret_cast<const uint4*>(Bs + i8off_b(16 * (4 * qc + m) + rho, ch));
-          if (ztail) bq[m] = uint4{0u, 0u, 0u, 0u};
-        }
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-          v4i av[4], bv[4];
-#pragma unroll
-          for (int m = 0; m < 4; ++m) {
-            av[m] = s2 == 0 ? fp4_operand(aq[m].x, aq[m].y) : fp4_operand(aq[m].z, aq[m].w);
-            av[m] |= neg;
-            bv[m] = s2 == 0 ? fp4_operand(bq[m].x, bq[m].y) : fp4_operand(bq[m].z, bq[m].w);
-          }
-#pragma unroll
-          for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n)
-              cnt[m][n] = mfma_fp4_16x16x128(av[m], bv[n], cnt[m][n], 4, 4, 0, 128, 0, 128);
-        }
-      }
-    }
-    if (!(k & 1) || !compute) continue;
-    const int64_t s = (int64_t)((k - 1) >> 1) * bpf + b;   // C_{T_all} - C_{V_f}: system f * B + b
-    store_counts16_any(I != J ? kc + ((s * (a.NT * (a.NT - 1) / 2)) + I * (I - 1) / 2 + J) * KC_TILE
-                              : a.kd + (s * a.NT + J) * KD_TILE,
-                       cnt, qr, qc, l, I == J);
-  }
-  tr.done(WGT_SYS, J, I, b);
-}
-
-
-__device__ void sys_diag_epilogue(const CholArgs& a, const v4f (&cnt)[4][4], int64_t b, int J, int qr, int qc,
-                                  int l) {
-  sys_diag_epilogue_inl(a, cnt, b, J, qr, qc, l);
-}
-
-// fold-fused chunks (k_sys_tiles_folds stores every diagonal tile's counts): K_JJ + lambda I of the
-// tiles J < 2 into Kd, one 4-wave workgroup per (system, J)
-__global__ __launch_bounds__(64 * STW) void k_sys_diag_counts(CholArgs a) {
-  const int l = threadIdx.x & 63, w = threadIdx.x >> 6, qr = w >> 1, qc = w & 1;
-  const int64_t s = blockIdx.x >> 1;
-  const int J = (int)(blockIdx.x & 1);
-  if (qr < qc || J >= a.NT) return;   // the upper quadrant is never read
-  const int16_t* kt = a.kd + (s * a.NT + J) * KD_TILE;
-  v4f cnt[4][4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const int cb = 4 * qr + m, ib = 4 * qc + n;
-      int2 p = {0, 0};
-      if (cb >= ib) p = *reinterpret_cast<const int2*>(kt + ((cb * (cb + 1) / 2 + ib) * 64 + l) * 4);
-      cnt[m][n] = v4f{(float)(int16_t)(p.x & 0xffff), (float)(int16_t)(p.x >> 16), (float)(int16_t)(p.y & 0xffff),
-                      (float)(int16_t)(p.y >> 16)};
-    }
-  sys_diag_epilogue_inl(a, cnt, s, J, qr, qc, l);
-}
-
-// k_sys_tiles_st chunks: k_sys_diag_counts with the per-individual scalars formed here (the same
-// stats_wg code as k_indiv_stats) instead of in a launch before the system tiles -- one launch less
-// on the chain.  Workgroup (b, J < 2): stats_wg (workgroup J = 0 also stores scal), tile
-// J's centring sums into LDS, then the epilogue from the LDS copies; the u / rhs rows are split
-// between the two workgroups.
-__global__ __launch_bounds__(64 * STW) void k_stats_diag_counts(CholArgs a, StatsFuse x) {
-  static_assert(64 * STW == STATS_THREADS, "stats_wg runs on the workgroup's 256 threads");
-  __shared__ StatsShared sh;
-  __shared__ double u_sh[TILE];
-  const int t = threadIdx.x, l = t & 63, w = t >> 6, qr = w >> 1, qc = w & 1;
-  const int64_t b = blockIdx.x >> 1;
-  const int J = (int)(blockIdx.x & 1);
-  const bool tile = qr >= qc && J < a.NT;   // the upper quadrant is never read
-  // the counts first: their loads overlap the scalars' reduction
-  v4f cnt[4][4];
-  const int16_t* kt = a.kd + (b * a.NT + J) * KD_TILE;
-#pragma unroll
-  for (int m = 0; m < 4; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) {
-      const int cb = 4 * qr + m, ib = 4 * qc + n;
-      int2 p = {0, 0};
-      if (tile && cb >= ib) p = *reinterpret_cast<const int2*>(kt + ((cb * (cb + 1) / 2 + ib) * 64 + l) * 4);
-      cnt[m][n] = v4f{(float)(int16_t)(p.x & 0xffff), (float)(int16_t)(p.x >> 16), (float)(int16_t)(p.y & 0xffff),
-                      (float)(int16_t)(p.y >> 16)};
-    }
-  // u_a = s_a of tile J's rows (stats_wg's u values, gathered here before its reduction so that
-  // these loads overlap it)
-  if (t < TILE) {
-    const int64_t o0 = a.off[b], k = a.off[b + 1] - o0;
-    const int64_t pad = a.padfirst ? a.ns - k : 0;
-    const int64_t r = (int64_t)J * TILE + t;
-    const int32_t* csT = a.ft.csT[fold_of(a.ft, b)];
-    u_sh[t] = (r < a.ns && sys_real(r, pad, k)) ? (double)csT[snp_col(a.idx[o0 + r - pad], a.P)] : 0.0;
-  }
-  // (stats_wg's barriers also publish u_sh)
-  stats_wg(a.idx, a.off, a.ft, x.csA, x.n, x.nT, a.ytp, a.P, a.form, a.ns, a.padfirst, a.nt, x.branch, x.h2, b,
-           J == 0 ? x.scal : nullptr, x.err, sh);
-  if (tile) sys_diag_epilogue_src(a, cnt, b, J, qr, qc, l, sh.sc, u_sh);
-  // then the u / rhs rows, split between the individual's two workgroups (their stores overlap the
-  // epilogue's)
-  const int64_t half = (a.ns / 2 + 63) & ~(int64_t)63;
-  stats_rows(a.idx, a.off, a.ft, a.P, a.ns, a.padfirst, a.nt, b, x.u, x.rhs, sh, J == 0 ? 0 : half,
-             J == 0 ? half : a.ns);
-}
-
-static CholArgs make_args(const CholLaunch& c, int J) {
-  CholArgs a{c.L, c.Dinv, c.z, c.w, c.S, c.Kd, c.yT, c.rhs, c.panel, c.pstride, c.u, c.scal, c.sd.ns,
-             c.sd.prow, c.sd.form, c.idx, c.off, c.gpk_row, c.d.P, c.d.nTp, c.d.nt, c.sd.NT, J, c.skip,
-             c.wgt, nullptr, c.kc, c.part, c.q, c.B, c.ft, c.padskip,
-             (c.sd.form == FORM_PRIMAL && c.sd.pad_first) ? 1 : 0, c.kd};
-  return a;
-}
-
 int cu_count() {
   static int n = 0;
   if (n <= 0) {
@@ -2239,58 +1482,6 @@ int cu_count() {
       n = 256;
   }
   return n;
-}
-
-int64_t sys_tiles_grid(const CholLaunch& c) {
-  const int64_t ntri = (int64_t)c.sd.NT * (c.sd.NT + 1) / 2;
-  const int64_t NS = (c.sd.NT + 1) / 2, units = c.B * (NS * (NS + 1) / 2);
-  const int64_t cus = cu_count();
-  const bool st = c.sys_st > 0 || (c.sys_st < 0 && units >= SYS_ST_MIN * cus);
-  const int64_t grid = std::min(units, cus);
-  const int64_t nsu = NS * (NS + 1) / 2, per = (units + grid - 1) / grid;
-  if (!st || c.sd.ns > SP_ROWTAB || per / nsu + 2 > SP_MAXIND) return -(c.B * ntri);
-  return grid;
-}
-
-hipError_t launch_sys_tiles(const CholLaunch& c, hipStream_t s) {
-  CholArgs a = make_args(c, 0);
-  const int ntri = c.sd.NT * (c.sd.NT + 1) / 2;
-  const int64_t grid = sys_tiles_grid(c);
-  if (grid > 0) {
-    const int NS = (c.sd.NT + 1) / 2;
-    if (c.sd.form == FORM_PRIMAL)
-      hipLaunchKernelGGL(k_sys_tiles_st<false>, dim3((unsigned)grid), dim3(64 * SPW), 0, s, a, c.kc, NS * (NS + 1) / 2,
-                         (int)(c.B * (NS * (NS + 1) / 2)));
-    else
-      hipLaunchKernelGGL(k_sys_tiles_st<true>, dim3((unsigned)grid), dim3(64 * SPW), 0, s, a, c.kc, NS * (NS + 1) / 2,
-                         (int)(c.B * (NS * (NS + 1) / 2)));
-    if (hipError_t e = hipGetLastError()) return e;
-    a.wgt = nullptr;
-    if (c.stats)
-      hipLaunchKernelGGL(k_stats_diag_counts, dim3((unsigned)(c.B * 2)), dim3(64 * STW), 0, s, a, *c.stats);
-    else
-      hipLaunchKernelGGL(k_sys_diag_counts, dim3((unsigned)(c.B * 2)), dim3(64 * STW), 0, s, a);
-  } else {
-    if (c.stats) return hipErrorInvalidValue;   // the per-tile kernel reads the scalars
-    if (c.sd.form == FORM_PRIMAL)
-      hipLaunchKernelGGL(k_sys_tiles<false>, dim3((unsigned)(c.B * ntri)), dim3(64 * STW), 0, s, a, c.kc, ntri);
-    else
-      hipLaunchKernelGGL(k_sys_tiles<true>, dim3((unsigned)(c.B * ntri)), dim3(64 * STW), 0, s, a, c.kc, ntri);
-  }
-  return hipGetLastError();
-}
-
-hipError_t launch_sys_tiles_folds(const CholLaunch& c, hipStream_t s) {
-  CholArgs a = make_args(c, 0);
-  const int ntri = c.sd.NT * (c.sd.NT + 1) / 2;
-  hipLaunchKernelGGL(k_sys_tiles_folds, dim3((unsigned)(c.ft.bpf * ntri)), dim3(64 * STW), 0, s, a, c.kc, ntri);
-  if (hipError_t e = hipGetLastError()) return e;
-  a.wgt = nullptr;
-  if (c.stats)   // k_sys_tiles_folds reads no scalar either
-    hipLaunchKernelGGL(k_stats_diag_counts, dim3((unsigned)(c.B * 2)), dim3(64 * STW), 0, s, a, *c.stats);
-  else
-    hipLaunchKernelGGL(k_sys_diag_counts, dim3((unsigned)(c.B * 2)), dim3(64 * STW), 0, s, a);
-  return hipGetLastError();
 }
 
 __global__ __launch_bounds__(OTH, 2) void k_diag_grm8(CholArgs a, int nJ) {
@@ -2316,17 +1507,15 @@ __global__ __launch_bounds__(OTH, 2) void k_gshare(CholArgs a, int NR) {
   const int64_t ntp = (int64_t)NR * (NR + 1) / 2;
   const int64_t lg = xcd_remap(blockIdx.x, gridDim.x);   // an individual's tiles on one XCD
   const int64_t b = lg / ntp;
-  const int tp = (int)(lg % ntp);
-  int I = 0;
-  while ((I + 1) * (I + 2) / 2 <= tp) ++I;
-  const int J = tp - I * (I + 1) / 2;
+  int I, J;
+  tri_decode((int)(lg % ntp), I, J);
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t i0 = (int64_t)I * TILE, j0 = (int64_t)J * TILE;
   const int row = 16 * w + (l >> 2), pos = l & 3;
   const int64_t nblk = (int64_t)a.scal[b * SCAL + SC_CBLK];
   v4i cnt[8];
-  i8_tt8_pk64<4>(row_dpk(a, b, j0 + row) + 16 * (pos ^ ((row >> 2) & 3)),
-                 row_dpk(a, b, i0 + row) + 16 * (pos ^ ((row >> 2) & 2)), nblk, lds, cnt);
+  i8_tt8_pk64<4>(row_dpk(a, b, j0 + row) + pk_swz_a(row, pos), row_dpk(a, b, i0 + row) + pk_swz_b(row, pos), nblk, lds,
+                 cnt);
   const int64_t ld = a.ft.gsh_ld;
   int32_t* G = a.ft.gsh + b * ld * ld;
   const int64_t ic = i0 + 16 * w + (l & 15);

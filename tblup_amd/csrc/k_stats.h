@@ -1,6 +1,6 @@
 // Per-individual scalars of one system, for one 256-thread workgroup: k_indiv_stats (k_prep.hip) and
 // the SNP-form launch that forms K_JJ + lambda I of the tiles J < 2 after k_sys_tiles_st
-// (k_stats_diag_counts, k_chol.hip) run this same code, so the scalars are the same bits either way.
+// (k_stats_diag_counts, k_systiles.hip) run this same code, so the scalars are the same bits either way.
 //
 // Reference behaviour restated (ianwhale/tblup): allele frequency p = column mean / 2 over ALL rows for
 // gblup (utils.py:14 via evaluator.py:275) and over TRAIN rows for snp_blup (evaluator.py:304);

@@ -185,7 +185,7 @@ hipError_t launch_gather(const FoldTab& ft, const int64_t* idx, const int64_t* o
 hipError_t launch_grm(const uint8_t* panel, int64_t panel_stride, int64_t pk_row, const int64_t* off, const double* u,
                       const double* scal, const EvalDims& d, int64_t B, double* K, hipStream_t s);
 
-// ---- launchers (k_chol.hip, k_solve.hip) ----
+// ---- launchers (k_chol.hip, k_systiles.hip, k_solve.hip) ----
 // SNP form with k_sys_tiles_st (which reads no scalar): k_indiv_stats' inputs and outputs, when the
 // scalars are formed in the launch after the system tiles (k_stats_diag_counts, fused with the
 // K_JJ + lambda I epilogue of the tiles J < 2) instead of in a launch of their own before them
@@ -202,10 +202,7 @@ struct StatsFuse {
 // 4 KiB between individuals' Lt tiles, so the same tile of different individuals does not start on the
 // same HBM channel offset: off-diagonal -5 us at pop 128, solve -1% (A/B, profiles/r06_lpad_ab.txt;
 // 64 KiB was slower, 260 KiB even)
-#ifndef TBLUP_AB_LPAD   // A/B builds (tools/ab_build_defs.sh): doubles of padding between individuals' L
-#define TBLUP_AB_LPAD 512
-#endif
-constexpr int64_t L_PAD = TBLUP_AB_LPAD;
+constexpr int64_t L_PAD = 512;   // doubles of padding between individuals' L
 // doubles from one individual's Lt tiles to the next's
 __host__ __device__ inline int64_t l_stride(int NT) { return (int64_t)NT * NT * TILE * TILE + L_PAD; }
 struct CholLaunch {
@@ -244,6 +241,7 @@ struct CholLaunch {
 // k_sys_tiles output: per individual NT(NT-1)/2 off-diagonal tiles (I > J, t = I(I-1)/2 + J) of
 // 128 x 128 int16 counts, in the order the off-diagonal kernel's lanes read them:
 // [column block ib][row block cb][lane][4].  Exact while n_T <= 8191 (counts <= 4 n_T).
+// (Tile offsets, both sides: kc_tile / kd_tile, chol_dev.h.)
 constexpr int64_t KC_TILE = (int64_t)TILE * TILE;
 constexpr int64_t KD_TILE = (int64_t)NPACK * BLKD;   // diagonal tile counts: the 36 lower 16x16 blocks
 constexpr int64_t KC_MAX_NT = 8191;
@@ -287,10 +285,7 @@ constexpr int64_t AHEAD_SLOTS = 256;
 // launches still grow); every J (TBLUP_DIAG_D=1): diagonal +100 us at pop 128
 constexpr int64_t DD_MIN_B = 64;
 constexpr int64_t DD_MAX_B = 128;
-#ifndef TBLUP_AB_DD_MAX_J   // A/B builds only (tools/ab_build_defs.sh)
-#define TBLUP_AB_DD_MAX_J 3
-#endif
-constexpr int DD_MAX_J = TBLUP_AB_DD_MAX_J;
+constexpr int DD_MAX_J = 3;
 // diag_e: E-units in the diagonal launch, -1 auto (one per CU the launch's other workgroups leave
 // idle, ncu - B (1 + ndd), up to the column's tiles; so none at B >= ncu), 0 never, 1 every tile of
 // the column (tests), 2 only columns covered whole
@@ -307,7 +302,7 @@ hipError_t launch_chol_offdiag(const CholLaunch& c, int J, const OffPlan& p, hip
 hipError_t launch_diag_grm(const CholLaunch& c, hipStream_t s);
 // kernel form, shared fold counts: A_R A_R^T of every individual (FoldTab::gsh) from fold 0's panels
 hipError_t launch_gshare(const CholLaunch& c, hipStream_t s);
-// SNP form: every (I >= J) system tile of the batch on FP4 MFMA in one launch -- off-diagonal
+// k_systiles.hip, either form: every (I >= J) system tile of the batch on FP4 MFMA in one launch -- off-diagonal
 // counts into c.kc, diagonal tiles' counts into c.kd (replaces launch_diag_grm and the int8 phase
 // of the off-diagonal tiles)
 hipError_t launch_sys_tiles(const CholLaunch& c, hipStream_t s);

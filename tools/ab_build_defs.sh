@@ -1,5 +1,6 @@
 # A/B builds of the working tree with compile-time overrides: one library per NAME=DEFINES pair.
-#   usage: bash tools/ab_build_defs.sh 'j2=-DTBLUP_AB_DD_MAX_J=2' 'j4=-DTBLUP_AB_DD_MAX_J=4' ...
+#   usage: bash tools/ab_build_defs.sh 'a=-DSOME_SWITCH=1' 'b=-DSOME_SWITCH=2' ...
+# (for a switch that the sources guard with #ifndef; the settled ones are plain constants now)
 # -> ab/<NAME>.so (run with TBLUP_GPU_LIB=ab/<NAME>.so; tools/ab_env.sh runs ab/<NAME>.so for NAME=...)
 set -e
 cd "$(dirname "$0")/.."
