@@ -6,6 +6,7 @@ fallback: if the library is missing, `load()` raises ImportError.
 """
 import ctypes
 import os
+import random
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TBLUP_GPU_LIB", os.path.join(_HERE, "lib", "libtblup_gpu.so"))
@@ -141,6 +142,27 @@ def check(fn_name, rc):
         msg = load().tblup_last_error().decode(errors="replace")
         raise (TblupIndexError if rc == ERR_INDEX else TblupError)(fn_name, rc, msg)
     return rc
+
+
+_PTR = {"float64": _DP, "int32": _I32P, "int64": _I64P, "uint32": _U32P, "uint64": _c.POINTER(_c.c_uint64)}
+
+
+def ptr(a):
+    """The typed pointer to a numpy array's data, by its dtype (KeyError for one the ABI does not take)."""
+    return a.ctypes.data_as(_PTR[a.dtype.name])
+
+
+def py_random_state():
+    """CPython's `random` state as the native entries take it: (mt uint32[624], index int32[1])."""
+    import numpy as np
+    internal = random.getstate()[1]
+    return np.array(internal[:624], dtype=np.uint32), np.array([internal[624]], dtype=np.int32)
+
+
+def set_py_random_state(mt, index):
+    """Write (mt, index) back; the version and the gauss carry-over stay as they are."""
+    version, _, gauss = random.getstate()
+    random.setstate((version, tuple(mt.tolist()) + (int(index[0]),), gauss))
 
 
 def device_count():

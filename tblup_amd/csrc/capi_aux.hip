@@ -153,20 +153,6 @@ static int de_upload_polys(tblup_ctx* c, int64_t L, int64_t pop, hipStream_t s) 
   return 0;
 }
 
-// page-locked staging of a step's per-call arguments that outlives the call (the copy is
-// asynchronous); the previous call's copy from it finished before that call's state was fetched
-// (one step pending at a time)
-static int de_stage_reserve(tblup_ctx* c, size_t bytes, hipStream_t s) {
-  if (bytes <= c->de_stage_bytes) return 0;
-  HIPCHK(hipStreamSynchronize(s));
-  if (c->de_stage) HIPCHK(hipHostFree(c->de_stage));
-  c->de_stage = nullptr;
-  c->de_stage_bytes = 0;
-  HIPCHK(hipHostMalloc((void**)&c->de_stage, bytes, hipHostMallocDefault));
-  c->de_stage_bytes = bytes;
-  return 0;
-}
-
 // the copy of the new MT state to the host behind a step, and the event tblup_de_state_wait waits for
 static int de_state_fetch(tblup_ctx* c, const void* d_state, hipStream_t s) {
   if (!c->de_host) HIPCHK(hipHostMalloc((void**)&c->de_host, 625 * 4, hipHostMallocDefault));
@@ -183,59 +169,120 @@ static int64_t de_split_min() {
   return v;
 }
 
-// The asynchronous step, with optional per-individual strategies / F / crossover rates (host
-// arrays of pop; null: the scalars).
+// What every entry that runs DE kernels on the context checks first.
+static int de_enter(tblup_ctx* c) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
+  return 0;
+}
+
+// ... and what the two step entries check last, behind their own arguments (the reports keep their order)
+static int check_de_rows(int64_t L, int64_t ld, int64_t ldc, const double* d_parents, const double* d_children) {
+  if (ld < L || ldc < L) return fail(TBLUP_ERR_ARG, "ld/ldc < L");
+  if (!d_parents || !d_children) return fail(TBLUP_ERR_ARG, "null device pointers");
+  return 0;
+}
+
+// Byte layout of a step's per-call block, staged page-locked and copied to de_small in one piece:
+// key in, key out, pos out, donors, fixed, then the arrays of pop elements that the form take()s.
+struct DeStage {
+  static constexpr size_t key_out = 624 * 4, pos_out = 2 * 624 * 4, donors = pos_out + 16;
+  size_t fixed, end;
+  char *dev = nullptr, *host = nullptr;   // de_stage_open
+  explicit DeStage(int64_t pop) : fixed(donors + (size_t)round_up(12 * pop, 16)), end(fixed + 8 * (size_t)pop) {}
+  size_t take(size_t bytes) {
+    const size_t o = end;
+    end += bytes;
+    return o;
+  }
+};
+
+// de_small of at least dev_bytes (the stream waits only when it grows) and the page-locked stage of
+// st.end bytes, the common prefix in it and in the request; the caller adds its arrays to st.host and
+// copies st.end bytes to st.dev.  The stage outlives the call (the copy is asynchronous); the previous
+// call's copy from it finished before that call's state was fetched (one step pending at a time).
+static int de_stage_open(tblup_ctx* c, DeStage& st, size_t dev_bytes, int64_t pop, const uint32_t* mt_key,
+                         const int32_t* donors, const int64_t* fixed, DeArgs& a, hipStream_t s) {
+  if (dev_bytes > c->de_small.bytes) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (int rc = dev_alloc(c, c->de_small, dev_bytes)) return rc;
+  }
+  if (st.end > c->de_stage_bytes) {
+    HIPCHK(hipStreamSynchronize(s));
+    if (c->de_stage) HIPCHK(hipHostFree(c->de_stage));
+    c->de_stage = nullptr;
+    c->de_stage_bytes = 0;
+    HIPCHK(hipHostMalloc((void**)&c->de_stage, st.end, hipHostMallocDefault));
+    c->de_stage_bytes = st.end;
+  }
+  st.dev = (char*)c->de_small.p;
+  st.host = c->de_stage;
+  std::memcpy(st.host, mt_key, 624 * 4);
+  std::memcpy(st.host + st.donors, donors, 12 * pop);
+  std::memcpy(st.host + st.fixed, fixed, 8 * pop);
+  a.key = (const uint32_t*)st.dev;
+  a.donors = (const int32_t*)(st.dev + st.donors);
+  a.fixed = (const int64_t*)(st.dev + st.fixed);
+  a.key_out = (uint32_t*)(st.dev + st.key_out);
+  a.pos_out = (int32_t*)(st.dev + st.pos_out);
+  a.polys = (const uint32_t*)c->de_polys.p;
+  a.end_jump = c->de_end_jump ? 1 : 0;
+  return 0;
+}
+
+// The asynchronous step.  strat_i / F_i / cr_i: host arrays of pop, all three (tblup_de_step_device_async_mix)
+// or none (the scalars).
 static int de_step_async(tblup_ctx* c, int strategy, const int32_t* strat_i, const double* F_i, const double* cr_i,
                          const double* d_parents, int64_t pop, int64_t L, int64_t ld, const int32_t* donors,
                          const int64_t* fixed, double F, double cr, int clip, double clip_hi, const uint32_t* mt_key,
                          int32_t mt_pos, double* d_children, int64_t ldc, void* stream) {
-  clear_error();
-  if (int rc = check_ctx(c)) return rc;
-  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
-  int32_t* const mt_pos_in = &mt_pos;
-  if (int rc = validate_de(strategy, pop, L, donors, fixed, cr, mt_key, mt_pos_in)) return rc;
+  if (int rc = de_enter(c)) return rc;
+  DeArgs a = {};
+  a.strategy = strategy, a.F = F, a.cr = cr;
+  // With per-individual arrays no kernel reads the scalars: element 0 stands in them so that
+  // validate_de sees something valid (read only for a non-empty population; it rejects pop < 1).
+  if (strat_i) {
+    const bool any = pop >= 1;
+    a.strategy = any ? strat_i[0] : TBLUP_DE_RAND_1, a.F = any ? F_i[0] : 0.0, a.cr = any ? cr_i[0] : 0.0;
+  }
+  if (int rc = validate_de(a.strategy, pop, L, donors, fixed, a.cr, mt_key, &mt_pos)) return rc;
   for (int64_t i = 0; strat_i && i < pop; ++i)
     if (strat_i[i] != TBLUP_DE_RAND_1 && strat_i[i] != TBLUP_DE_CURRENT_TO_BEST_1)
       return fail(TBLUP_ERR_ARG, "unknown DE strategy");
   for (int64_t i = 0; cr_i && i < pop; ++i)
     if (!(cr_i[i] == cr_i[i])) return fail(TBLUP_ERR_ARG, "crossover rate is NaN");
-  if (ld < L || ldc < L) return fail(TBLUP_ERR_ARG, "ld/ldc < L");
-  if (!d_parents || !d_children) return fail(TBLUP_ERR_ARG, "null device pointers");
+  if (int rc = check_de_rows(L, ld, ldc, d_parents, d_children)) return rc;
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   if (int rc = de_upload_polys(c, L, pop, s)) return rc;
-  // per-call arguments: key in, key out, pos out, donors, fixed
-  const size_t o_keyo = 624 * 4, o_pos = 2 * 624 * 4, o_don = o_pos + 16, o_fix = o_don + (size_t)round_up(12 * pop, 16);
-  const size_t o_str = o_fix + 8 * (size_t)pop, o_F = o_str + (size_t)round_up(4 * pop, 16), o_cr = o_F + 8 * (size_t)pop;
-  const size_t small = o_cr + 8 * (size_t)pop;
+  DeStage st(pop);
+  const size_t o_str = st.take((size_t)round_up(4 * pop, 16)), o_F = st.take(8 * (size_t)pop),
+               o_cr = st.take(8 * (size_t)pop);
   // device-only scratch of the three-launch form (large populations): base sequence + windows
   // (from more individuals than CUs: both forms need a second round of jump workgroups there, and the
   // split form's mask and stream run several per CU; TBLUP_DE_SPLIT = the smallest split population)
   const bool split = pop >= de_split_min();
-  const size_t o_scr = (size_t)round_up((int64_t)small, 256);
-  const size_t need = split ? o_scr + 4 * (size_t)(DE_SEQ_SCRATCH + 624 * pop) : small;
-  if (need > c->de_small.bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (int rc = dev_alloc(c, c->de_small, need)) return rc;
+  const size_t o_scr = (size_t)round_up((int64_t)st.end, 256);
+  if (int rc = de_stage_open(c, st, split ? o_scr + 4 * (size_t)(DE_SEQ_SCRATCH + 624 * pop) : st.end, pop, mt_key,
+                             donors, fixed, a, s))
+    return rc;
+  if (strat_i) {
+    std::memcpy(st.host + o_str, strat_i, 4 * pop);
+    std::memcpy(st.host + o_F, F_i, 8 * pop);
+    std::memcpy(st.host + o_cr, cr_i, 8 * pop);
+    a.strat_i = (const int32_t*)(st.dev + o_str);
+    a.F_i = (const double*)(st.dev + o_F), a.cr_i = (const double*)(st.dev + o_cr);
   }
-  char* base = (char*)c->de_small.p;
-  if (int rc = de_stage_reserve(c, small, s)) return rc;
-  char* stage = c->de_stage;
-  std::memcpy(stage, mt_key, 624 * 4);
-  std::memcpy(stage + o_don, donors, 12 * pop);
-  std::memcpy(stage + o_fix, fixed, 8 * pop);
-  if (strat_i) std::memcpy(stage + o_str, strat_i, 4 * pop);
-  if (F_i) std::memcpy(stage + o_F, F_i, 8 * pop);
-  if (cr_i) std::memcpy(stage + o_cr, cr_i, 8 * pop);
-  HIPCHK(hipMemcpyAsync(base, stage, small, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(st.dev, st.host, st.end, hipMemcpyHostToDevice, s));
   const tblup_mt::EndState e = tblup_mt::end_state(mt_pos, 2 * (uint64_t)L * (uint64_t)pop);
-  HIPCHK(launch_de_step((const uint32_t*)base, mt_pos, (const uint32_t*)c->de_polys.p, c->de_end_jump ? 1 : 0, e.s,
-                        e.pos, d_parents, ld, (const int32_t*)(base + o_don), (const int64_t*)(base + o_fix), strategy,
-                        F, cr, clip ? 1 : 0, clip_hi, L, (int)pop, d_children, ldc, (uint32_t*)(base + o_keyo),
-                        (int32_t*)(base + o_pos), s, strat_i ? (const int32_t*)(base + o_str) : nullptr,
-                        F_i ? (const double*)(base + o_F) : nullptr, cr_i ? (const double*)(base + o_cr) : nullptr,
-                        split ? (uint32_t*)(base + o_scr) : nullptr));
-  return de_state_fetch(c, base + o_keyo, s);
+  a.pos0 = mt_pos, a.end_s = e.s, a.end_pos = e.pos;
+  a.parent = d_parents, a.ldp = ld;
+  a.child = d_children, a.ldc = ldc;
+  a.clip = clip ? 1 : 0, a.hi = clip_hi;
+  a.L = L, a.pop = (int)pop;
+  HIPCHK(launch_de_step(a, split ? (uint32_t*)(st.dev + o_scr) : nullptr, s));
+  return de_state_fetch(c, st.dev + st.key_out, s);
 }
 
 int tblup_de_step_device_async(tblup_ctx* c, int strategy, const double* d_parents, int64_t pop, int64_t L,
@@ -254,12 +301,8 @@ int tblup_de_step_device_async_mix(tblup_ctx* c, const int32_t* strategies, cons
     clear_error();
     return fail(TBLUP_ERR_ARG, "null strategies/F/cr");
   }
-  // element 0 is read only for a non-empty population (validate_de rejects pop < 1); the scalar
-  // slots are placeholders when per-individual arrays are given
-  const bool any = pop >= 1;
-  return de_step_async(c, any ? strategies[0] : TBLUP_DE_RAND_1, strategies, F, cr, d_parents, pop, L, ld, donors,
-                       fixed, any ? F[0] : 0.0, any ? cr[0] : 0.0, clip, clip_hi, mt_key, mt_pos, d_children, ldc,
-                       stream);
+  return de_step_async(c, TBLUP_DE_RAND_1, strategies, F, cr, d_parents, pop, L, ld, donors, fixed, 0.0, 0.0, clip,
+                       clip_hi, mt_key, mt_pos, d_children, ldc, stream);
 }
 
 int tblup_de_state_wait(tblup_ctx* c, uint32_t* mt_key, int32_t* mt_pos) {
@@ -330,9 +373,7 @@ int tblup_mde_windows(int64_t pop, int64_t nq, int64_t np, int32_t slack, int32_
 
 int tblup_mde_draws(tblup_ctx* c, int64_t pop, int64_t L, int64_t nq, int64_t np, int32_t slack,
                     const uint32_t* mt_key, int32_t mt_pos, uint32_t* words, int64_t n_words, void* stream) {
-  clear_error();
-  if (int rc = check_ctx(c)) return rc;
-  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
+  if (int rc = de_enter(c)) return rc;
   if (int rc = validate_mde_shape(pop, L, nq, np)) return rc;
   if (!mt_key || !words) return fail(TBLUP_ERR_ARG, "null mt_key/words");
   if (mt_pos < 0 || mt_pos > 624) return fail(TBLUP_ERR_ARG, "mt_pos must be in [0, 624]");
@@ -361,9 +402,11 @@ int tblup_mde_draws(tblup_ctx* c, int64_t pop, int64_t L, int64_t nq, int64_t np
   std::memcpy(host.data() + o_off, off.data(), 8 * (size_t)pop);
   // `host` is pageable and local: the stream is synchronised below, before it goes away
   HIPCHK(hipMemcpyAsync(base, host.data(), o_words, hipMemcpyHostToDevice, s));
-  HIPCHK(launch_mde_draws((const uint32_t*)base, mt_pos, (const uint32_t*)c->de_polys.p, c->de_end_jump ? 1 : 0, (int)pop,
-                          (const int32_t*)(base + o_tab), (const int64_t*)(base + o_off), (uint32_t*)(base + o_words), s,
-                          split ? (uint32_t*)(base + o_scr) : nullptr));
+  DeArgs a = {};
+  a.key = (const uint32_t*)base, a.pos0 = mt_pos, a.pop = (int)pop;
+  a.polys = (const uint32_t*)c->de_polys.p, a.end_jump = c->de_end_jump ? 1 : 0;
+  HIPCHK(launch_mde_draws(a, (const int32_t*)(base + o_tab), (const int64_t*)(base + o_off),
+                          (uint32_t*)(base + o_words), split ? (uint32_t*)(base + o_scr) : nullptr, s));
   if (total > 0) HIPCHK(hipMemcpyAsync(words, base + o_words, 4 * (size_t)total, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   c->mde_key.assign(mt_key, mt_key + 624);
@@ -401,9 +444,7 @@ int tblup_mde_step_device_async(tblup_ctx* c, const double* F, const double* cr,
                                 int64_t L, int64_t ld, const int32_t* parent, const int32_t* donors,
                                 const int64_t* fixed, const int64_t* c_words, int clip, double clip_hi,
                                 const uint32_t* mt_key, int32_t mt_pos, double* d_children, int64_t ldc, void* stream) {
-  clear_error();
-  if (int rc = check_ctx(c)) return rc;
-  if (c->de_pending) return fail(TBLUP_ERR_STATE, "the previous DE step's state was not fetched (tblup_de_state_wait)");
+  if (int rc = de_enter(c)) return rc;
   if (!F || !cr || !parent || !c_words) return fail(TBLUP_ERR_ARG, "null F/cr/parent/c_words");
   if (pop < 4) return fail(TBLUP_ERR_ARG, "need 4 <= pop <= 65535 and 1 <= L <= 2^31");
   if (int rc = validate_de(TBLUP_DE_CURRENT_TO_BEST_1, pop, L, donors, fixed, 0.0, mt_key, &mt_pos)) return rc;
@@ -412,8 +453,7 @@ int tblup_mde_step_device_async(tblup_ctx* c, const double* F, const double* cr,
     if (parent[i] < 0 || parent[i] >= pop) return fail(TBLUP_ERR_ARG, "parent index out of range");
     if (c_words[i] < (i ? c_words[i - 1] : 0)) return fail(TBLUP_ERR_ARG, "c_words must be non-negative and non-decreasing");
   }
-  if (ld < L || ldc < L) return fail(TBLUP_ERR_ARG, "ld/ldc < L");
-  if (!d_parents || !d_children) return fail(TBLUP_ERR_ARG, "null device pointers");
+  if (int rc = check_de_rows(L, ld, ldc, d_parents, d_children)) return rc;
   if (c->mde_key.empty() || c->mde_pop != pop || c->mde_L != L || c->mde_pos != mt_pos || c->de_pop != pop ||
       c->de_L != L || std::memcmp(c->mde_key.data(), mt_key, 624 * 4) != 0)
     return fail(TBLUP_ERR_STATE, "no tblup_mde_draws of this population, length and MT state to continue");
@@ -422,38 +462,30 @@ int tblup_mde_step_device_async(tblup_ctx* c, const double* F, const double* cr,
   c->mde_key.clear();   // the draws are used up, whatever happens below
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  // per-call arguments: key in, key out, pos out, donors, fixed, F, cr, the uniforms' window offsets, targets
-  const size_t o_keyo = 624 * 4, o_pos = 2 * 624 * 4, o_don = o_pos + 16, o_fix = o_don + (size_t)round_up(12 * pop, 16);
-  const size_t o_F = o_fix + 8 * (size_t)pop, o_cr = o_F + 8 * (size_t)pop, o_f = o_cr + 8 * (size_t)pop;
-  const size_t o_tgt = o_f + 8 * (size_t)pop, small = o_tgt + 4 * (size_t)pop;
-  if (small > c->de_small.bytes) {
-    HIPCHK(hipStreamSynchronize(s));
-    if (int rc = dev_alloc(c, c->de_small, small)) return rc;
-  }
-  char* base = (char*)c->de_small.p;
-  if (int rc = de_stage_reserve(c, small, s)) return rc;
-  char* stage = c->de_stage;
-  std::memcpy(stage, mt_key, 624 * 4);
-  std::memcpy(stage + o_don, donors, 12 * pop);
-  std::memcpy(stage + o_fix, fixed, 8 * pop);
-  std::memcpy(stage + o_F, F, 8 * pop);
-  std::memcpy(stage + o_cr, cr, 8 * pop);
-  int64_t* f_i = (int64_t*)(stage + o_f);
+  DeStage st(pop);   // + F, cr, the uniforms' window offsets, targets
+  const size_t o_F = st.take(8 * (size_t)pop), o_cr = st.take(8 * (size_t)pop), o_f = st.take(8 * (size_t)pop),
+               o_tgt = st.take(4 * (size_t)pop);
+  DeArgs a = {};
+  if (int rc = de_stage_open(c, st, st.end, pop, mt_key, donors, fixed, a, s)) return rc;
+  std::memcpy(st.host + o_F, F, 8 * pop);
+  std::memcpy(st.host + o_cr, cr, 8 * pop);
+  int64_t* f_i = (int64_t*)(st.host + o_f);
   for (int64_t i = 0; i < pop; ++i) f_i[i] = c_words[i] + (i ? 2 : 0);   // windows 1.. start two words early
-  std::memcpy(stage + o_tgt, parent, 4 * pop);
-  HIPCHK(hipMemcpyAsync(base, stage, small, hipMemcpyHostToDevice, s));
+  std::memcpy(st.host + o_tgt, parent, 4 * pop);
+  HIPCHK(hipMemcpyAsync(st.dev, st.host, st.end, hipMemcpyHostToDevice, s));
   // numpy's state after 2 L pop + C_pop words, counted from where the end window starts
   const uint64_t fixed_words = 2 * (uint64_t)L * (uint64_t)pop;
   const tblup_mt::EndState e = tblup_mt::end_state(mt_pos, fixed_words + (uint64_t)c_words[pop - 1]);
   const uint64_t o_win = c->de_end_jump ? (uint64_t)mt_pos + fixed_words - 625 : 0;
-  const int end_s = (int)((uint64_t)e.s + e.o_rel - o_win);
-  HIPCHK(launch_mde_step((const uint32_t*)base, mt_pos, (const uint32_t*)c->de_polys.p, c->de_end_jump ? 1 : 0, end_s,
-                         e.pos, d_parents, ld, (const int32_t*)(base + o_don), (const int64_t*)(base + o_fix),
-                         (const double*)(base + o_F), (const double*)(base + o_cr), (const int64_t*)(base + o_f),
-                         (const int32_t*)(base + o_tgt), clip ? 1 : 0, clip_hi, L, (int)pop, d_children, ldc,
-                         (uint32_t*)(base + o_keyo), (int32_t*)(base + o_pos), s,
-                         c->mde_scr ? (uint32_t*)((char*)c->mde_dev.p + c->mde_scr) : nullptr));
-  return de_state_fetch(c, base + o_keyo, s);
+  a.pos0 = mt_pos, a.end_s = (int)((uint64_t)e.s + e.o_rel - o_win), a.end_pos = e.pos;
+  a.parent = d_parents, a.ldp = ld;
+  a.child = d_children, a.ldc = ldc;
+  a.clip = clip ? 1 : 0, a.hi = clip_hi;
+  a.L = L, a.pop = (int)pop;
+  a.F_i = (const double*)(st.dev + o_F), a.cr_i = (const double*)(st.dev + o_cr);
+  a.f_i = (const int64_t*)(st.dev + o_f), a.target_i = (const int32_t*)(st.dev + o_tgt);
+  HIPCHK(launch_mde_step(a, c->mde_scr ? (uint32_t*)((char*)c->mde_dev.p + c->mde_scr) : nullptr, s));
+  return de_state_fetch(c, st.dev + st.key_out, s);
 }
 
 int tblup_gather_rows(tblup_ctx* c, double* d_dst, int64_t n, int64_t L, int64_t ldd, const double* const* d_src_rows,

@@ -63,41 +63,6 @@ __device__ __forceinline__ void mt_block(uint32_t* ring, int b, int tid) {
   __syncthreads();
 }
 
-struct DeArgs {
-  const uint32_t* key;     // numpy key[624] at the generation's first draw
-  int pos0;                // numpy pos (0..624)
-  const uint32_t* polys;   // [pop][624]: row i-1 -> individual i >= 1; row pop-1 -> end state
-  int end_jump;            // end window by polys[pop-1] (else the base key itself)
-  int end_s, end_pos;      // numpy key = end ring words [end_s, end_s + 624), pos = end_pos
-  const double* parent;    // [pop][ldp]
-  int64_t ldp;
-  const int32_t* donors;   // [pop][3]
-  const int64_t* fixed;    // [pop]
-  int strategy;            // 0 rand/1, 1 current-to-best/1
-  double F, cr;
-  int clip;
-  double hi;               // clip upper bound (dimensionality - 1)
-  int64_t L;               // genome length
-  int pop;
-  double* child;           // [pop][ldc]
-  int64_t ldc;
-  uint32_t* key_out;       // [624]
-  int32_t* pos_out;
-  int dbg;                 // phase-ablation timing only (env TBLUP_DE_DBG, diagnostic builds; results wrong):
-                           // 1 no jump correlation, 2 no mask recurrence, 4 no stream
-  // per-individual strategy / F / crossover rate ([pop] each; null: the scalars above) -- SaDE
-  // (evolver.py:407-547): each individual's strategy by python's random.random() < p, its own cr
-  const int32_t* strat_i;
-  const double* F_i;
-  const double* cr_i;
-  // MDE_pBX (evolver.py:550-687; the kernels' general form): individual i's uniforms start at word
-  // f_i[i] of its window (any offset: its np.random.choice draws come first), its target and the
-  // child's base are row target_i[i]; keep_end: k_de_jump leaves the end window in gwin row pop
-  const int64_t* f_i;
-  const int32_t* target_i;
-  int keep_end;
-};
-
 // 1. the sequence that continues the base window, words [0, need) of sq
 __device__ __forceinline__ void de_sequence(const uint32_t* key, uint32_t* sq, int need, int tid) {
   for (int t = tid; t < MTN; t += DE_THREADS) sq[t] = key[t];
@@ -439,71 +404,57 @@ __global__ __launch_bounds__(DE_MASK_THREADS) void k_mde_mask(DeArgs a, const ui
   de_stream<DE_MASK_THREADS, true>(a, ring, mask, DE_MASK_WORDS, i, tid);
 }
 
+// the three-launch forms' first two launches: the base sequence into the scratch, then every
+// workgroup's window (and the end workgroup's) behind it
+hipError_t launch_windows(const DeArgs& a, uint32_t* scratch, hipStream_t s) {
+  hipLaunchKernelGGL(k_de_seq, dim3(1), dim3(DE_THREADS), 0, s, a, scratch);
+  if (hipError_t e = hipGetLastError()) return e;
+  hipLaunchKernelGGL(k_de_jump, dim3(a.pop + 1), dim3(DE_THREADS), 0, s, a, scratch, scratch + DE_SEQ_SCRATCH);
+  return hipGetLastError();
+}
+
 }  // namespace
 
-hipError_t launch_de_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
-                          const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed, int strategy,
-                          double F, double cr, int clip, double hi, int64_t L, int pop, double* child, int64_t ldc,
-                          uint32_t* key_out, int32_t* pos_out, hipStream_t s, const int32_t* strat_i,
-                          const double* F_i, const double* cr_i, uint32_t* scratch) {
+hipError_t launch_de_step(const DeArgs& req, uint32_t* scratch, hipStream_t s) {
+  DeArgs a = req;
+  a.keep_end = 0;
 #ifdef TBLUP_DIAG_BUILD   // phase ablation (results wrong when set): diagnostic builds only
   static const int dbg = getenv("TBLUP_DE_DBG") ? atoi(getenv("TBLUP_DE_DBG")) : 0;
-#else
-  constexpr int dbg = 0;
+  a.dbg = dbg;
 #endif
-  DeArgs a{key, pos0, polys, end_jump, end_s, end_pos, parent, ldp, donors, fixed, strategy, F, cr, clip, hi, L, pop,
-           child, ldc, key_out, pos_out, dbg, strat_i, F_i, cr_i, nullptr, nullptr, 0};
   if (scratch == nullptr) {
-    hipLaunchKernelGGL(k_de_step, dim3(pop + 1), dim3(DE_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_de_step, dim3(a.pop + 1), dim3(DE_THREADS), 0, s, a);
     return hipGetLastError();
   }
-  uint32_t* gseq = scratch;
-  uint32_t* gwin = scratch + DE_SEQ_SCRATCH;
-  hipLaunchKernelGGL(k_de_seq, dim3(1), dim3(DE_THREADS), 0, s, a, gseq);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(k_de_jump, dim3(pop + 1), dim3(DE_THREADS), 0, s, a, gseq, gwin);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(k_de_mask, dim3(pop), dim3(DE_MASK_THREADS), 0, s, a, gwin);
+  if (hipError_t e = launch_windows(a, scratch, s)) return e;
+  hipLaunchKernelGGL(k_de_mask, dim3(a.pop), dim3(DE_MASK_THREADS), 0, s, a, scratch + DE_SEQ_SCRATCH);
   return hipGetLastError();
 }
 
-hipError_t launch_mde_draws(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int pop,
-                            const int32_t* tab, const int64_t* woff, uint32_t* words, hipStream_t s,
-                            uint32_t* scratch) {
-  DeArgs a{};
-  a.key = key;
-  a.pos0 = pos0;
-  a.polys = polys;
-  a.end_jump = end_jump;
-  a.pop = pop;
+hipError_t launch_mde_draws(const DeArgs& req, const int32_t* tab, const int64_t* woff, uint32_t* words,
+                            uint32_t* scratch, hipStream_t s) {
+  DeArgs a = req;
   a.keep_end = 1;
   if (scratch == nullptr) {
-    hipLaunchKernelGGL(k_mde_draws_fused, dim3(pop), dim3(DE_THREADS), 0, s, a, tab, woff, words);
+    hipLaunchKernelGGL(k_mde_draws_fused, dim3(a.pop), dim3(DE_THREADS), 0, s, a, tab, woff, words);
     return hipGetLastError();
   }
-  uint32_t* gseq = scratch;
-  uint32_t* gwin = scratch + DE_SEQ_SCRATCH;
-  hipLaunchKernelGGL(k_de_seq, dim3(1), dim3(DE_THREADS), 0, s, a, gseq);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(k_de_jump, dim3(pop + 1), dim3(DE_THREADS), 0, s, a, gseq, gwin);
-  if (hipError_t e = hipGetLastError()) return e;
-  hipLaunchKernelGGL(k_mde_draws, dim3(pop), dim3(DE_MASK_THREADS), 0, s, gwin, tab, woff, words);
+  if (hipError_t e = launch_windows(a, scratch, s)) return e;
+  hipLaunchKernelGGL(k_mde_draws, dim3(a.pop), dim3(DE_MASK_THREADS), 0, s, scratch + DE_SEQ_SCRATCH, tab, woff,
+                     words);
   return hipGetLastError();
 }
 
-hipError_t launch_mde_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
-                           const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed,
-                           const double* F_i, const double* cr_i, const int64_t* f_i, const int32_t* target_i, int clip,
-                           double hi, int64_t L, int pop, double* child, int64_t ldc, uint32_t* key_out,
-                           int32_t* pos_out, hipStream_t s, uint32_t* scratch) {
-  DeArgs a{key, pos0, polys, end_jump, end_s, end_pos, parent, ldp, donors, fixed, 1, 0.0, 0.0, clip, hi, L, pop,
-           child, ldc, key_out, pos_out, 0, nullptr, F_i, cr_i, f_i, target_i, 1};
+hipError_t launch_mde_step(const DeArgs& req, uint32_t* scratch, hipStream_t s) {
+  DeArgs a = req;
+  a.strategy = 1;   // current-to-best/1 with the chosen best and parent
+  a.keep_end = 1;
   if (scratch == nullptr) {
-    hipLaunchKernelGGL(k_mde_step, dim3(pop + 1), dim3(DE_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_mde_step, dim3(a.pop + 1), dim3(DE_THREADS), 0, s, a);
     return hipGetLastError();
   }
   // the windows (and the end window, row pop) are the ones launch_mde_draws left in the scratch
-  hipLaunchKernelGGL(k_mde_mask, dim3(pop + 1), dim3(DE_MASK_THREADS), 0, s, a, scratch + DE_SEQ_SCRATCH);
+  hipLaunchKernelGGL(k_mde_mask, dim3(a.pop + 1), dim3(DE_MASK_THREADS), 0, s, a, scratch + DE_SEQ_SCRATCH);
   return hipGetLastError();
 }
 

@@ -384,30 +384,57 @@ hipError_t launch_predict(const int8_t* geno_sm, int64_t n, int64_t P, const int
 hipError_t launch_decode_topk(const double* keys, int64_t B, int64_t d, int64_t ld, const int64_t* off, int64_t* out,
                               hipStream_t s);
 
-// ---- launcher (k_de.hip): one DE generation (mutation + binary crossover + clip) per individual ----
-hipError_t launch_de_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
-                          const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed, int strategy,
-                          double F, double cr, int clip, double hi, int64_t L, int pop, double* child, int64_t ldc,
-                          uint32_t* key_out, int32_t* pos_out, hipStream_t s, const int32_t* strat_i = nullptr,
-                          const double* F_i = nullptr, const double* cr_i = nullptr, uint32_t* scratch = nullptr);
-// scratch (null: one launch, k_de_step): DE_SEQ_SCRATCH words for the base sequence + pop x 624 for
-// the workgroups' windows -- the three-launch form for large populations (k_de.hip)
+// ---- launchers (k_de.hip): one DE generation (mutation + binary crossover + clip) per individual ----
+// The request, and the kernels' by-value argument: every pointer is device memory.  The caller
+// value-initialises it and fills what its form reads by name; dbg, keep_end and MDE_pBX's strategy
+// are the launchers'.
+struct DeArgs {
+  const uint32_t* key;     // numpy key[624] at the generation's first draw
+  int pos0;                // numpy pos (0..624)
+  const uint32_t* polys;   // [pop][624]: row i-1 -> individual i >= 1; row pop-1 -> end state
+  int end_jump;            // end window by polys[pop-1] (else the base key itself)
+  int end_s, end_pos;      // numpy key = end ring words [end_s, end_s + 624), pos = end_pos
+  const double* parent;    // [pop][ldp]
+  int64_t ldp;
+  const int32_t* donors;   // [pop][3]
+  const int64_t* fixed;    // [pop]
+  int strategy;            // 0 rand/1, 1 current-to-best/1
+  double F, cr;
+  int clip;
+  double hi;               // clip upper bound (dimensionality - 1)
+  int64_t L;               // genome length
+  int pop;
+  double* child;           // [pop][ldc]
+  int64_t ldc;
+  uint32_t* key_out;       // [624]
+  int32_t* pos_out;
+  int dbg;                 // phase-ablation timing only (env TBLUP_DE_DBG, diagnostic builds; results wrong):
+                           // 1 no jump correlation, 2 no mask recurrence, 4 no stream
+  // per-individual strategy / F / crossover rate ([pop] each; null: the scalars above) -- SaDE
+  // (evolver.py:407-547): each individual's strategy by python's random.random() < p, its own cr
+  const int32_t* strat_i;
+  const double* F_i;
+  const double* cr_i;
+  // MDE_pBX (evolver.py:550-687; the kernels' general form): individual i's uniforms start at word
+  // f_i[i] of its window (any offset: its np.random.choice draws come first), its target and the
+  // child's base are row target_i[i]; keep_end: k_de_jump leaves the end window in gwin row pop
+  const int64_t* f_i;
+  const int32_t* target_i;
+  int keep_end;
+};
+// scratch (null: one launch): DE_SEQ_SCRATCH words for the base sequence, then 624 per window (pop of
+// them; MDE_pBX pop + 1) -- the three-launch form for populations larger than the CU count
 constexpr int64_t DE_SEQ_SCRATCH = 624 + 19937 + 624 + 64;
-
-// MDE_pBX generation in two halves (k_de.hip).  launch_mde_draws: every individual's window, then
-// the tempered words [tab[2i], tab[2i+1]) past 2Li of its stream into words + woff[i] (what its
-// np.random.choice draws can read).  launch_mde_step, once the host has resolved the draws: the
-// step with per-individual F / cr, uniforms from window word f_i[i], target row target_i[i], and
-// the end state end_s words into the end window.  scratch (null: one launch each): as above with
-// (pop + 1) x 624 window words -- the step reads the windows the draws' launch left there.
-hipError_t launch_mde_draws(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int pop,
-                            const int32_t* tab, const int64_t* woff, uint32_t* words, hipStream_t s,
-                            uint32_t* scratch);
-hipError_t launch_mde_step(const uint32_t* key, int pos0, const uint32_t* polys, int end_jump, int end_s, int end_pos,
-                           const double* parent, int64_t ldp, const int32_t* donors, const int64_t* fixed,
-                           const double* F_i, const double* cr_i, const int64_t* f_i, const int32_t* target_i, int clip,
-                           double hi, int64_t L, int pop, double* child, int64_t ldc, uint32_t* key_out,
-                           int32_t* pos_out, hipStream_t s, uint32_t* scratch);
+// the classic step: everything above f_i
+hipError_t launch_de_step(const DeArgs& a, uint32_t* scratch, hipStream_t s);
+// MDE_pBX in two halves.  The draws read key, pos0, polys, end_jump and pop: every individual's
+// window, then the tempered words [tab[2i], tab[2i+1]) past 2Li of its stream into words + woff[i]
+// (what its np.random.choice draws can read).  The step, once the host has resolved them: F_i, cr_i,
+// f_i and target_i per individual, the end state end_s words into the end window; with scratch it
+// reads the windows the draws' launch left there.
+hipError_t launch_mde_draws(const DeArgs& a, const int32_t* tab, const int64_t* woff, uint32_t* words,
+                            uint32_t* scratch, hipStream_t s);
+hipError_t launch_mde_step(const DeArgs& a, uint32_t* scratch, hipStream_t s);
 
 // ---- launcher (k_de.hip): rows from scattered device rows into one matrix (up to ROWPTRS rows
 //      per launch, source pointers in the kernel arguments) ----

@@ -14,14 +14,11 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _native
+from ._native import ptr as _ptr
 
 
 def _as_int64(a):
     return np.ascontiguousarray(np.asarray(a, dtype=np.int64))
-
-
-def _ptr(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
 
 
 def validate_genotypes(data):
@@ -82,13 +79,12 @@ class GpuBlupEngine:
         self.n_animals, self.n_snps, self.device = n, n_snps, int(device)
         ctx = ctypes.c_void_p()
         _native.check("tblup_ctx_create", self._lib.tblup_ctx_create(
-            geno.ctypes.data_as(ctypes.c_void_p), n, n_snps, layout, _ptr(pheno, ctypes.c_double), self.device,
-            ctypes.byref(ctx)))
+            geno.ctypes.data_as(ctypes.c_void_p), n, n_snps, layout, _ptr(pheno), self.device, ctypes.byref(ctx)))
         self._ctx = ctx
         if self.n_traits > 1:
             mt = np.ascontiguousarray(labels)
             _native.check("tblup_set_traits", self._lib.tblup_set_traits(
-                self._ctx, _ptr(mt, ctypes.c_double), self.n_traits))
+                self._ctx, _ptr(mt), self.n_traits))
         self._splits = OrderedDict()   # key -> (split_id, n_valid)
         self._next_split = 0
         self._pending = None           # (event, keep-alive) of asynchronous work using the workspace
@@ -125,7 +121,7 @@ class GpuBlupEngine:
         sid = self._next_split
         self._next_split += 1
         _native.check("tblup_set_split", self._lib.tblup_set_split(
-            self._ctx, sid, _ptr(t, ctypes.c_int64), len(t), _ptr(v, ctypes.c_int64), len(v)))
+            self._ctx, sid, _ptr(t), len(t), _ptr(v), len(v)))
         self._splits[key] = (sid, len(v))
         return sid
 
@@ -153,9 +149,8 @@ class GpuBlupEngine:
         ebv = np.empty(shape, dtype=np.float64) if return_ebv else None
         if B:
             _native.check("tblup_eval_batch", self._lib.tblup_eval_batch(
-                self._ctx, sid, _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64), B, float(h2),
-                _native.BRANCH[branch], _ptr(fit, ctypes.c_double),
-                _ptr(ebv, ctypes.c_double) if return_ebv else None))
+                self._ctx, sid, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit),
+                _ptr(ebv) if return_ebv else None))
         return (fit, ebv) if return_ebv else fit
 
     # ------------------------------------------------------- taking the model out
@@ -183,15 +178,12 @@ class GpuBlupEngine:
         rel = None if an is None else np.empty((B, len(an)), dtype=np.float64)
         if B and an is not None and len(an):
             _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
-                self._ctx, sid, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64),
-                _ptr(offsets, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], _ptr(fit, ctypes.c_double),
-                _ptr(intercept, ctypes.c_double), _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double),
-                _ptr(rel, ctypes.c_double)))
+                self._ctx, sid, _ptr(an), len(an), _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch],
+                _ptr(fit), _ptr(intercept), _ptr(center), _ptr(effects), _ptr(rel)))
         elif B:
             _native.check("tblup_fit_batch", self._lib.tblup_fit_batch(
-                self._ctx, sid, _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64), B, float(h2),
-                _native.BRANCH[branch], _ptr(fit, ctypes.c_double), _ptr(intercept, ctypes.c_double),
-                _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double)))
+                self._ctx, sid, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit),
+                _ptr(intercept), _ptr(center), _ptr(effects)))
         wrapped = np.where(idx < 0, idx + self.n_snps, idx)
         models = []
         for b in range(B):
@@ -220,9 +212,8 @@ class GpuBlupEngine:
         rel = np.empty((B, len(an)), dtype=np.float64)
         if B and len(an):
             _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
-                self._ctx, sid, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64),
-                _ptr(offsets, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], None, None, None, None,
-                _ptr(rel, ctypes.c_double)))
+                self._ctx, sid, _ptr(an), len(an), _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], None,
+                None, None, None, _ptr(rel)))
         return rel
 
     def predict(self, models, animals):
@@ -247,9 +238,8 @@ class GpuBlupEngine:
             effects = np.ascontiguousarray(np.concatenate([m.effects for m in models], axis=1))
             assert effects.shape == (nt, total)
             _native.check("tblup_predict_batch", self._lib.tblup_predict_batch(
-                self._ctx, _ptr(an, ctypes.c_int64), len(an), _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64),
-                B, _ptr(intercept, ctypes.c_double), _ptr(center, ctypes.c_double), _ptr(effects, ctypes.c_double),
-                nt, _ptr(out, ctypes.c_double)))
+                self._ctx, _ptr(an), len(an), _ptr(idx), _ptr(offsets), B, _ptr(intercept), _ptr(center), _ptr(effects),
+                nt, _ptr(out)))
         return out[:, 0, :] if nt == 1 else out
 
     def evaluate_folds(self, genomes, splits, h2, branch="auto"):
@@ -263,8 +253,8 @@ class GpuBlupEngine:
         fit = np.empty((len(sids), B), dtype=np.float64)
         if B:
             _native.check("tblup_eval_folds", self._lib.tblup_eval_folds(
-                self._ctx, _ptr(sids, ctypes.c_int32), len(sids), _ptr(idx, ctypes.c_int64),
-                _ptr(offsets, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], _ptr(fit, ctypes.c_double)))
+                self._ctx, _ptr(sids), len(sids), _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch],
+                _ptr(fit)))
         return fit
 
     def evaluate_folds_device(self, split_ids, d_idx_ptr, d_off_ptr, h_offsets, h2, d_fit_ptr, stream_ptr=None,
@@ -274,9 +264,9 @@ class GpuBlupEngine:
         sids = np.ascontiguousarray(split_ids, dtype=np.int32)
         h_off = _as_int64(h_offsets)
         _native.check("tblup_eval_folds_device", self._lib.tblup_eval_folds_device(
-            self._ctx, _ptr(sids, ctypes.c_int32), len(sids), ctypes.c_void_p(d_idx_ptr), ctypes.c_void_p(d_off_ptr),
-            _ptr(h_off, ctypes.c_int64), len(h_off) - 1, float(h2), _native.BRANCH[branch],
-            ctypes.c_void_p(d_fit_ptr), ctypes.c_void_p(stream_ptr) if stream_ptr else None))
+            self._ctx, _ptr(sids), len(sids), ctypes.c_void_p(d_idx_ptr), ctypes.c_void_p(d_off_ptr), _ptr(h_off),
+            len(h_off) - 1, float(h2), _native.BRANCH[branch], ctypes.c_void_p(d_fit_ptr),
+            ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def evaluate_device(self, split_id, d_idx_ptr, d_off_ptr, h_offsets, h2, d_fit_ptr, d_ebv_ptr=None,
                         stream_ptr=None, branch="auto"):
@@ -285,9 +275,8 @@ class GpuBlupEngine:
         h_off = _as_int64(h_offsets)
         B = len(h_off) - 1
         _native.check("tblup_eval_batch_device", self._lib.tblup_eval_batch_device(
-            self._ctx, split_id, ctypes.c_void_p(d_idx_ptr), ctypes.c_void_p(d_off_ptr),
-            _ptr(h_off, ctypes.c_int64), B, float(h2), _native.BRANCH[branch], ctypes.c_void_p(d_fit_ptr),
-            ctypes.c_void_p(d_ebv_ptr) if d_ebv_ptr else None,
+            self._ctx, split_id, ctypes.c_void_p(d_idx_ptr), ctypes.c_void_p(d_off_ptr), _ptr(h_off), B, float(h2),
+            _native.BRANCH[branch], ctypes.c_void_p(d_fit_ptr), ctypes.c_void_p(d_ebv_ptr) if d_ebv_ptr else None,
             ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def index_error(self, stream_ptr=None):
@@ -355,7 +344,7 @@ class GpuBlupEngine:
         idx = np.empty(int(offsets[-1]), dtype=np.int64)
         if B:
             _native.check("tblup_decode_topk", self._lib.tblup_decode_topk(
-                self._ctx, _ptr(kk, ctypes.c_double), B, d, _ptr(offsets, ctypes.c_int64), _ptr(idx, ctypes.c_int64)))
+                self._ctx, _ptr(kk), B, d, _ptr(offsets), _ptr(idx)))
         return idx, offsets
 
     def decode_randkey_device(self, d_keys_ptr, B, d, ld, d_off_ptr, h_offsets, d_idx_ptr, stream_ptr=None):
@@ -363,7 +352,7 @@ class GpuBlupEngine:
         self._settle()
         h_off = _as_int64(h_offsets)
         _native.check("tblup_decode_topk_device", self._lib.tblup_decode_topk_device(
-            self._ctx, ctypes.c_void_p(d_keys_ptr), B, d, ld, ctypes.c_void_p(d_off_ptr), _ptr(h_off, ctypes.c_int64),
+            self._ctx, ctypes.c_void_p(d_keys_ptr), B, d, ld, ctypes.c_void_p(d_off_ptr), _ptr(h_off),
             ctypes.c_void_p(d_idx_ptr), ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def grm(self, indices=None):
@@ -372,8 +361,8 @@ class GpuBlupEngine:
         self._settle()
         idx = _as_int64(np.arange(self.n_snps) if indices is None else indices)
         G = np.empty((self.n_animals, self.n_animals), dtype=np.float64)
-        _native.check("tblup_grm", self._lib.tblup_grm(self._ctx, _ptr(idx, ctypes.c_int64), len(idx),
-                                                       _ptr(G, ctypes.c_double)))
+        _native.check("tblup_grm", self._lib.tblup_grm(self._ctx, _ptr(idx), len(idx),
+                                                       _ptr(G)))
         return G
 
     def snp_scan(self, rows, yc):
@@ -387,8 +376,7 @@ class GpuBlupEngine:
         sxx = np.empty(self.n_snps, dtype=np.int64)
         sxy = np.empty(self.n_snps, dtype=np.float64)
         _native.check("tblup_snp_scan", self._lib.tblup_snp_scan(
-            self._ctx, _ptr(r, ctypes.c_int64), len(r), _ptr(y, ctypes.c_double), _ptr(sx, ctypes.c_int64),
-            _ptr(sxx, ctypes.c_int64), _ptr(sxy, ctypes.c_double)))
+            self._ctx, _ptr(r), len(r), _ptr(y), _ptr(sx), _ptr(sxx), _ptr(sxy)))
         return sx, sxx, sxy
 
     def decode_randkey_tensor(self, keys, d, lengths):
@@ -422,8 +410,7 @@ class GpuBlupEngine:
         fit = np.empty(B, dtype=np.float64)
         if B:
             _native.check("tblup_eval_batch", self._lib.tblup_eval_batch(
-                self._ctx, sid, _ptr(idx, ctypes.c_int64), _ptr(offsets, ctypes.c_int64), B, float(h2),
-                _native.BRANCH[branch], _ptr(fit, ctypes.c_double), None))
+                self._ctx, sid, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit), None))
         return fit
 
     def debug_grm(self, indices, train, valid, h2, branch="auto", stage=1):
@@ -435,8 +422,7 @@ class GpuBlupEngine:
         out = np.empty((nT + nV, nT), dtype=np.float64)
         z = np.empty(nT, dtype=np.float64)
         _native.check("tblup_debug_grm", self._lib.tblup_debug_grm(
-            self._ctx, sid, _ptr(idx, ctypes.c_int64), len(idx), float(h2), _native.BRANCH[branch], int(stage),
-            _ptr(out, ctypes.c_double), _ptr(z, ctypes.c_double)))
+            self._ctx, sid, _ptr(idx), len(idx), float(h2), _native.BRANCH[branch], int(stage), _ptr(out), _ptr(z)))
         return out, z
 
     def eval_keys_async(self, keys, lengths, train, valid, h2):
@@ -488,8 +474,7 @@ class GpuBlupEngine:
         fl = np.zeros(n)
         by = np.zeros(n)
         _native.check("tblup_get_profile", self._lib.tblup_get_profile(
-            self._ctx, _ptr(ms, ctypes.c_double), _ptr(la, ctypes.c_int64), _ptr(fl, ctypes.c_double),
-            _ptr(by, ctypes.c_double)))
+            self._ctx, _ptr(ms), _ptr(la), _ptr(fl), _ptr(by)))
         return {name: {"ms": float(ms[i]), "launches": int(la[i]), "flops": float(fl[i]), "bytes": float(by[i])}
                 for i, name in enumerate(_native.KCLASS_NAMES)}
 
@@ -503,7 +488,7 @@ class GpuBlupEngine:
         raw = np.zeros((n.value, 4), dtype=np.uint64)
         if n.value:
             _native.check("tblup_get_wg_trace", self._lib.tblup_get_wg_trace(
-                self._ctx, raw.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n.value, ctypes.byref(n)))
+                self._ctx, _ptr(raw), n.value, ctypes.byref(n)))
         if raw_out:
             return raw
         out = np.zeros(len(raw), dtype=[("start", "f8"), ("end", "f8"), ("kind", "i4"), ("J", "i4"), ("I", "i4"),

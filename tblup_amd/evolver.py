@@ -74,17 +74,13 @@ def _native_donors(strategy, n, L, best=-1):
     stay in python (n < 4 raises the reference's assertion there; n > 65535 or L >= 2^32)."""
     if n < 4 or n > 65535 or L >= 1 << 32:
         return None
-    version, internal, gauss = random.getstate()
-    mt = np.array(internal[:624], dtype=np.uint32)
-    idx = np.array([internal[624]], dtype=np.int32)
+    mt, idx = _native.py_random_state()
     donors = np.empty((n, 3), dtype=np.int32)
     fixed = np.empty(n, dtype=np.int64)
-    lib = _native.load()
-    _native.check("tblup_de_donors", lib.tblup_de_donors(
-        strategy, n, L, best, mt.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-        idx.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-        fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
-    random.setstate((version, tuple(mt.tolist()) + (int(idx[0]),), gauss))
+    ptr = _native.ptr
+    _native.check("tblup_de_donors", _native.load().tblup_de_donors(
+        strategy, n, L, best, ptr(mt), ptr(idx), ptr(donors), ptr(fixed)))
+    _native.set_py_random_state(mt, idx)
     return donors, fixed
 
 
@@ -126,12 +122,10 @@ class GpuDEStep:
         fixed = np.ascontiguousarray(fixed, dtype=np.int64)
         st, key, pos = self._rng_state()
         children = np.empty_like(parents)
+        ptr = _native.ptr
         _native.check("tblup_de_step", self._lib.tblup_de_step(
-            self._ctx, int(strategy), parents.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), pop, L,
-            donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-            float(F), float(cr), 1 if clip else 0, float(clip_hi),
-            key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(pos),
-            children.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+            self._ctx, int(strategy), ptr(parents), pop, L, ptr(donors), ptr(fixed), float(F), float(cr),
+            1 if clip else 0, float(clip_hi), ptr(key), ctypes.byref(pos), ptr(children)))
         np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
         return children
 
@@ -147,7 +141,7 @@ class GpuDEStep:
         import torch
         q_idx = np.ascontiguousarray(q_idx, dtype=np.int32)
         p_idx = np.ascontiguousarray(p_idx, dtype=np.int32)
-        I32, I64, U32 = (ctypes.POINTER(t) for t in (ctypes.c_int32, ctypes.c_int64, ctypes.c_uint32))
+        ptr = _native.ptr
         n_words = ctypes.c_int64()
         _native.check("tblup_mde_windows", self._lib.tblup_mde_windows(pop, len(q_idx), len(p_idx), slack, None, None,
                                                                        None, ctypes.byref(n_words)))
@@ -158,24 +152,20 @@ class GpuDEStep:
         ws = work_stream(self.device)
         ws.wait_stream(torch.cuda.current_stream(ws.device))
         _native.check("tblup_mde_draws", self._lib.tblup_mde_draws(
-            self._ctx, pop, L, len(q_idx), len(p_idx), slack, key.ctypes.data_as(U32), pos.value,
-            words.ctypes.data_as(U32), n_words.value, ctypes.c_void_p(ws.cuda_stream)))
-        version, internal, gauss = random.getstate()
-        mt = np.array(internal[:624], dtype=np.uint32)
-        idx = np.array([internal[624]], dtype=np.int32)
+            self._ctx, pop, L, len(q_idx), len(p_idx), slack, ptr(key), pos.value, ptr(words), n_words.value,
+            ctypes.c_void_p(ws.cuda_stream)))
+        mt, idx = _native.py_random_state()
         parent = np.empty(pop, dtype=np.int32)
         donors = np.empty((pop, 3), dtype=np.int32)
         fixed = np.empty(pop, dtype=np.int64)
         c_words = np.empty(pop, dtype=np.int64)
         overflow = ctypes.c_int32()
         _native.check("tblup_mde_resolve", self._lib.tblup_mde_resolve(
-            pop, L, q_idx.ctypes.data_as(I32), len(q_idx), p_idx.ctypes.data_as(I32), len(p_idx), slack,
-            words.ctypes.data_as(U32), n_words.value, mt.ctypes.data_as(U32), idx.ctypes.data_as(I32),
-            parent.ctypes.data_as(I32), donors.ctypes.data_as(I32), fixed.ctypes.data_as(I64),
-            c_words.ctypes.data_as(I64), ctypes.byref(overflow)))
+            pop, L, ptr(q_idx), len(q_idx), ptr(p_idx), len(p_idx), slack, ptr(words), n_words.value, ptr(mt),
+            ptr(idx), ptr(parent), ptr(donors), ptr(fixed), ptr(c_words), ctypes.byref(overflow)))
         if overflow.value:
             return None
-        random.setstate((version, tuple(mt.tolist()) + (int(idx[0]),), gauss))
+        _native.set_py_random_state(mt, idx)
         return parent, donors, fixed, c_words
 
     def step_device(self, strategy, parents, donors, fixed, F, cr, clip, clip_hi, defer=False, mde=None):
@@ -195,45 +185,31 @@ class GpuDEStep:
         with torch.cuda.stream(ws):
             children = torch.empty_like(parents)
         st, key, pos = self._rng_state()
-        stream = ws.cuda_stream
+        ptr = _native.ptr
+
+        def each(x, dtype):   # one value per individual
+            return np.ascontiguousarray(np.broadcast_to(x, (pop,)), dtype=dtype)
+        # every entry's arguments from the parents on: (..., donors, fixed) and (clip, ..., stream)
+        rows = (ctypes.c_void_p(parents.data_ptr()), pop, L, parents.stride(0))
+        tail = (1 if clip else 0, float(clip_hi), ptr(key), pos.value, ctypes.c_void_p(children.data_ptr()),
+                children.stride(0), ctypes.c_void_p(ws.cuda_stream))
         if mde is not None:
             parent_i = np.ascontiguousarray(mde[0], dtype=np.int32)
             c_words = np.ascontiguousarray(mde[1], dtype=np.int64)
-            F_i = np.ascontiguousarray(np.broadcast_to(F, (pop,)), dtype=np.float64)
-            cr_i = np.ascontiguousarray(np.broadcast_to(cr, (pop,)), dtype=np.float64)
+            F_i, cr_i = each(F, np.float64), each(cr, np.float64)
             _native.check("tblup_mde_step_device_async", self._lib.tblup_mde_step_device_async(
-                self._ctx, F_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                cr_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ctypes.c_void_p(parents.data_ptr()), pop, L,
-                parents.stride(0), parent_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
-                c_words.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 1 if clip else 0, float(clip_hi),
-                key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pos.value,
-                ctypes.c_void_p(children.data_ptr()), children.stride(0), ctypes.c_void_p(stream)))
+                self._ctx, ptr(F_i), ptr(cr_i), *rows, ptr(parent_i), ptr(donors), ptr(fixed), ptr(c_words), *tail))
         elif np.ndim(strategy) or np.ndim(F) or np.ndim(cr):
-            strat_i = np.ascontiguousarray(np.broadcast_to(strategy, (pop,)), dtype=np.int32)
-            F_i = np.ascontiguousarray(np.broadcast_to(F, (pop,)), dtype=np.float64)
-            cr_i = np.ascontiguousarray(np.broadcast_to(cr, (pop,)), dtype=np.float64)
+            strat_i, F_i, cr_i = each(strategy, np.int32), each(F, np.float64), each(cr, np.float64)
             _native.check("tblup_de_step_device_async_mix", self._lib.tblup_de_step_device_async_mix(
-                self._ctx, strat_i.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                F_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), cr_i.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                ctypes.c_void_p(parents.data_ptr()), pop, L, parents.stride(0),
-                donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 1 if clip else 0, float(clip_hi),
-                key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pos.value,
-                ctypes.c_void_p(children.data_ptr()), children.stride(0), ctypes.c_void_p(stream)))
+                self._ctx, ptr(strat_i), ptr(F_i), ptr(cr_i), *rows, ptr(donors), ptr(fixed), *tail))
         else:
             _native.check("tblup_de_step_device_async", self._lib.tblup_de_step_device_async(
-                self._ctx, int(strategy), ctypes.c_void_p(parents.data_ptr()), pop, L, parents.stride(0),
-                donors.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
-                fixed.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), float(F), float(cr), 1 if clip else 0,
-                float(clip_hi), key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), pos.value,
-                ctypes.c_void_p(children.data_ptr()), children.stride(0), ctypes.c_void_p(stream)))
+                self._ctx, int(strategy), *rows, ptr(donors), ptr(fixed), float(F), float(cr), *tail))
         cur.wait_stream(ws)   # later caller work on the children is ordered behind the step
 
         def finish():
-            _native.check("tblup_de_state_wait", self._lib.tblup_de_state_wait(
-                self._ctx, key.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(pos)))
+            _native.check("tblup_de_state_wait", self._lib.tblup_de_state_wait(self._ctx, ptr(key), ctypes.byref(pos)))
             np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
 
         if defer:
@@ -619,6 +595,12 @@ class _GpuDEEvolver(Evolver):
             finally:
                 rng_done()   # numpy's global state after the step's np.random.rand draws
         t = _mark(t, "ev_transfer_issue")
+
+        def rows_landed():   # the whole block (one event); every rank's shard of a shared one
+            events[-1].synchronize()
+            if shared is not None:
+                import torch.distributed as dist
+                dist.barrier()
         # the candidates (new uids, the parent's other attributes) while the transfer runs
         next_pop = [_copy_individual(population[j]) for j in src]
         t = _mark(t, "ev_candidates")
@@ -632,20 +614,12 @@ class _GpuDEEvolver(Evolver):
             t = _mark(t, "ev_bind_record")
             _BLOCKS.compact(inds, store)
             t = _mark(t, "ev_compact")
-            events[-1].synchronize()
-            if shared is not None:
-                import torch.distributed as dist
-                dist.barrier()   # every rank's shard of the rows has landed
+            rows_landed()
             _mark(t, "ev_rows_landed")
             return next_pop
-        if shared is not None:
-            events[-1].synchronize()
-            import torch.distributed as dist
-            dist.barrier()   # every rank's shard of the rows has landed
-            arrays = _BLOCKS.rows(shared)
-        elif block_rows:
-            events[-1].synchronize()
-            arrays = _BLOCKS.rows(host.numpy())
+        if shared is not None or block_rows:
+            rows_landed()
+            arrays = _BLOCKS.rows(shared if shared is not None else host.numpy())
         else:
             # an own array per child; float64 rows go into page-locked buffers from torch's caching
             # host allocator, which hands back the buffers of dead genomes: no page faults on the copy

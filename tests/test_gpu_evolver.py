@@ -4,6 +4,8 @@ import hashlib
 import os
 from copy import deepcopy
 import random
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -13,6 +15,8 @@ from tests.helpers import CoevoIndividual, IdxIndividual, KeyIndividual, Pop, Ra
 from tests.test_evolver import CASES, META, coev_post, seed_rngs  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture(scope="module")
@@ -216,14 +220,20 @@ def test_gpu_generations_with_device_keystore(gpu, tmp_path):
         assert np.array_equal(a, b)
 
 
-@pytest.mark.parametrize("L,pop,pre", [(1, 4, 0), (10, 4, 3), (100, 5, 624), (311, 4, 1), (312, 7, 0),
-                                       (313, 6, 622), (1000, 33, 100), (1, 400, 0), (313, 384, 622),
-                                       (70000, 384, 5)])
+SMALL_SHAPES = [(1, 4, 0), (10, 4, 3), (100, 5, 624), (311, 4, 1), (312, 7, 0), (313, 6, 622), (1000, 33, 100),
+                (1, 400, 0), (313, 384, 622), (70000, 384, 5)]
+
+
+@pytest.mark.parametrize("L,pop,pre", SMALL_SHAPES)
 def test_gpu_de_small_shapes_vs_oracle(gpu, L, pop, pre):
     """Tiny generations (< 625 stream words: the end state is rebuilt from the base window
     without a jump), block-boundary lengths and every numpy position class; pop >= 384: the
     three-launch form (more individuals than the 256 CUs), L = 70000 across two of its
     65536-element mask segments."""
+    _small_shape_vs_oracle(L, pop, pre)
+
+
+def _small_shape_vs_oracle(L, pop, pre):
     rng = np.random.default_rng(L * 7 + pop)
     keys = rng.uniform(size=(pop, L))
     fit = list(rng.uniform(size=pop))
@@ -245,7 +255,6 @@ def test_gpu_de_small_shapes_vs_oracle(gpu, L, pop, pre):
         assert np.array_equal(st[1], np_after[1]) and st[2] == np_after[2], (strat, L, pop, pre)
         for k, w in zip(kids, want):
             assert np.array_equal(k.get_internal_genome(), w), (strat, L, pop, pre)
-
 
 
 @pytest.mark.parametrize("kind", ["helpers", "reference"])
@@ -341,8 +350,33 @@ def test_gpu_sade_matches_reference(gpu, name, tmp_path):
     crossover rate, tblup_de_step_device_async_mix) reproduces whole reference runs
     (tests/golden/sade.npz): every generation's children, the adaptive state, the parameter CSV,
     numpy's and python's RNG states."""
+    _sade_golden(name, tmp_path)
+
+
+def _sade_golden(name, tmp_path):
     from tblup_amd import evolver as EV
     from tests.test_evolver import ADAPT, SADE_META, _adaptive_run, _sade_state
     z = np.load(os.path.join(ADAPT, "sade.npz"))
     _adaptive_run(z, name, SADE_META[name], lambda d, g, clip: EV.SaDE(d, clip), (500, 600, 400), tmp_path,
                   _sade_state)
+
+
+def _child():
+    import tempfile
+    from pathlib import Path
+    for name in ("sade_rk_clip", "sade_index"):
+        with tempfile.TemporaryDirectory() as d:
+            _sade_golden(name, Path(d))
+    for L, pop, pre in SMALL_SHAPES[:7]:
+        _small_shape_vs_oracle(L, pop, pre)
+    print("de child ok")
+
+
+def test_gpu_de_small_populations_forced_three_launch_form(gpu):
+    """The per-individual strategy / F / cr arrays (SaDE's goldens, populations of 6) and the small
+    classic shapes (pop 4 to 33) through the three-launch form, which they never reach by
+    themselves.  TBLUP_DE_SPLIT is read when the library first runs a step: a fresh process."""
+    env = dict(os.environ, TBLUP_DE_SPLIT="4")
+    r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_evolver import _child; _child()"], cwd=ROOT, env=env,
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "de child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

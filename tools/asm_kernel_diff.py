@@ -6,10 +6,36 @@
 
 Every kernel's instruction stream -- comments dropped, block labels .LBB<function>_<block> renumbered
 to .LBB_<block>, since the function index changes when kernels move between files -- is compared with
-the same kernel's of the other build: "identical" or the first differing line.
+the same kernel's of the other build: "identical" or the first differing line.  A kernel found in
+one build only is paired by its demangled name without the parameter list (c++filt), for a build in
+which a parameter type moved to another namespace.
 """
 import re
+import subprocess
 import sys
+
+
+def qualified(name):
+    """tblup::(anonymous namespace)::k<1> of a mangled kernel symbol; the symbol without c++filt."""
+    try:
+        d = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip() or name
+    except OSError:
+        return name
+    depth = 0
+    for i in range(len(d) - 1, -1, -1):   # the parameter list: the last top-level (...)
+        depth += (d[i] == ")") - (d[i] == "(")
+        if depth == 0 and d[i] == "(":
+            return d[:i].split(" ", 1)[-1] if d.startswith("void ") else d[:i]
+    return d
+
+
+def pair_renamed(base, new):
+    """Kernels in one build only, re-keyed by qualified name where that pairs them one to one."""
+    for side, other in ((base, new), (new, base)):
+        for name in [n for n in side if n not in other]:
+            q = qualified(name)
+            if q != name and q not in side:
+                side[q] = side.pop(name)
 
 
 def kernels(paths):
@@ -37,6 +63,7 @@ def main():
     if "--" not in args:
         sys.exit(__doc__)
     base, new = kernels(args[:args.index("--")]), kernels(args[args.index("--") + 1:])
+    pair_renamed(base, new)
     differ = 0
     for name in sorted(set(base) | set(new)):
         a, b = base.get(name), new.get(name)

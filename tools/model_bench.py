@@ -72,23 +72,22 @@ def fit_vs_eval(eng, genomes, T, V, reps):
 
 def fit_raw(eng, genomes, T, V, reps):
     """The C entries alone (no PanelModel objects): tblup_eval_batch against tblup_fit_batch."""
-    import ctypes
-    from tblup_amd.engine import concat_genomes, _ptr
+    from tblup_amd.engine import concat_genomes
     from tblup_amd import _native
+    _ptr = _native.ptr
     sid = eng.split_id(T, V)
     idx, off = concat_genomes(genomes)
     B, total = len(genomes), int(off[-1])
     fit = np.empty(B)
     icp, cen, eff = np.empty((B, eng.n_traits)), np.empty(total), np.empty((eng.n_traits, total))
-    dp, ip = ctypes.c_double, ctypes.c_int64
     te, tf = [], []
     for r in range(reps + 2):
         t0 = time.perf_counter()
-        _native.check("tblup_eval_batch", eng._lib.tblup_eval_batch(eng._ctx, sid, _ptr(idx, ip), _ptr(off, ip), B, 0.4, 0,
-                                                                    _ptr(fit, dp), None))
+        _native.check("tblup_eval_batch", eng._lib.tblup_eval_batch(eng._ctx, sid, _ptr(idx), _ptr(off), B, 0.4, 0,
+                                                                    _ptr(fit), None))
         t1 = time.perf_counter()
-        _native.check("tblup_fit_batch", eng._lib.tblup_fit_batch(eng._ctx, sid, _ptr(idx, ip), _ptr(off, ip), B, 0.4, 0,
-                                                                  _ptr(fit, dp), _ptr(icp, dp), _ptr(cen, dp), _ptr(eff, dp)))
+        _native.check("tblup_fit_batch", eng._lib.tblup_fit_batch(eng._ctx, sid, _ptr(idx), _ptr(off), B, 0.4, 0,
+                                                                  _ptr(fit), _ptr(icp), _ptr(cen), _ptr(eff)))
         t2 = time.perf_counter()
         if r >= 2:
             te.append(t1 - t0)
