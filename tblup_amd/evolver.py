@@ -40,8 +40,8 @@ import numpy as np
 
 from . import _native
 from .distributed import shard_range, world
-from .keystore import DeviceKeyStore, TrackedGenome, freeze_heap, track, track_rows, work_stream
-from .shmrows import RING as _SHM
+from .hostrows import _BLOCKS, HostRows
+from .keystore import DeviceKeyStore, freeze_heap, work_stream
 
 
 def get_evolver(args):
@@ -67,8 +67,39 @@ def exclusive_randrange(begin, end, exclude):
     return r
 
 
+def _rand_one_draws(n, L, i):
+    """Individual i's python-`random` draws of DE/rand/1 in the reference's order: the donors (a, b, c)
+    of de_rand_one (evolver.py:118-121), then the crossover's forced position (evolver.py:76)."""
+    a = exclusive_randrange(0, n, [i])
+    b = exclusive_randrange(0, n, [i, a])
+    c = exclusive_randrange(0, n, [i, a, b])
+    return (a, b, c), random.randrange(0, L)
+
+
+def _current_to_best_draws(n, L, i, best):
+    """The same of DE/current-to-best/1: (best, a, b) (evolver.py:199-203), then the forced position.
+    i: the index excluded along with best's -- the individual's own, or MDE_pBX's parent_idx."""
+    a = exclusive_randrange(0, n, [i, best])
+    b = exclusive_randrange(0, n, [i, best, a])
+    return (best, a, b), random.randrange(0, L)
+
+
+def _draw_donors(n, draws):
+    """(donors, fixed) of a generation from draws(i), individual by individual."""
+    donors = np.empty((n, 3), dtype=np.int32)
+    fixed = np.empty(n, dtype=np.int64)
+    for i in range(n):
+        donors[i], fixed[i] = draws(i)
+    return donors, fixed
+
+
+def _best_index(population):
+    best = max(population, key=lambda individual: individual.fitness)   # evolver.py:235
+    return population.population.index(best)                            # evolver.py:194
+
+
 def _native_donors(strategy, n, L, best=-1):
-    """One generation's donor / fixed-position draws (the python loops of _donors below) on
+    """One generation's donor / fixed-position draws (the python loop of _draw_donors) on
     CPython's MT19937 state in native code (tblup_de_donors): the same draws and the same
     `random` state afterwards, without 4n interpreted randrange calls.  None when the loop must
     stay in python (n < 4 raises the reference's assertion there; n > 65535 or L >= 2^32)."""
@@ -108,10 +139,16 @@ class GpuDEStep:
         self.device = int(device)
 
     def _rng_state(self):
+        """numpy's global MT19937 state as (key, pos) buffers for the library to advance, and
+        hand_back(): makes them numpy's state again (the cached gaussian is kept)."""
         st = np.random.get_state()
         if st[0] != "MT19937":
             raise RuntimeError("numpy's global RandomState is not MT19937")
-        return st, np.array(st[1], dtype=np.uint32), ctypes.c_int32(int(st[2]))
+        key, pos = np.array(st[1], dtype=np.uint32), ctypes.c_int32(int(st[2]))
+
+        def hand_back():
+            np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
+        return key, pos, hand_back
 
     def step(self, strategy, parents, donors, fixed, F, cr, clip, clip_hi):
         """children (pop x L) for the current numpy global state, which is advanced
@@ -120,13 +157,13 @@ class GpuDEStep:
         pop, L = parents.shape
         donors = np.ascontiguousarray(donors, dtype=np.int32)
         fixed = np.ascontiguousarray(fixed, dtype=np.int64)
-        st, key, pos = self._rng_state()
+        key, pos, hand_back = self._rng_state()
         children = np.empty_like(parents)
         ptr = _native.ptr
         _native.check("tblup_de_step", self._lib.tblup_de_step(
             self._ctx, int(strategy), ptr(parents), pop, L, ptr(donors), ptr(fixed), float(F), float(cr),
             1 if clip else 0, float(clip_hi), ptr(key), ctypes.byref(pos), ptr(children)))
-        np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
+        hand_back()
         return children
 
     def mde_draws(self, pop, L, q_idx, p_idx, slack=-1):
@@ -148,7 +185,7 @@ class GpuDEStep:
         if n_words.value > 1 << 26:
             return False
         words = np.empty(max(n_words.value, 1), dtype=np.uint32)
-        st, key, pos = self._rng_state()
+        key, pos, _ = self._rng_state()
         ws = work_stream(self.device)
         ws.wait_stream(torch.cuda.current_stream(ws.device))
         _native.check("tblup_mde_draws", self._lib.tblup_mde_draws(
@@ -184,7 +221,7 @@ class GpuDEStep:
         ws.wait_stream(cur)   # parents may come from work queued on the caller's stream
         with torch.cuda.stream(ws):
             children = torch.empty_like(parents)
-        st, key, pos = self._rng_state()
+        key, pos, hand_back = self._rng_state()
         ptr = _native.ptr
 
         def each(x, dtype):   # one value per individual
@@ -210,7 +247,7 @@ class GpuDEStep:
 
         def finish():
             _native.check("tblup_de_state_wait", self._lib.tblup_de_state_wait(self._ctx, ptr(key), ctypes.byref(pos)))
-            np.random.set_state(("MT19937", key, pos.value, st[3], st[4]))
+            hand_back()
 
         if defer:
             return children, finish
@@ -256,45 +293,6 @@ def _child_dtypes(genomes, donors, strategy, mi, clip, parent_of=None):
     return out
 
 
-_POOL = None
-
-
-def _pool(workers=8):
-    global _POOL
-    if _POOL is None:
-        from concurrent.futures import ThreadPoolExecutor
-        _POOL = ThreadPoolExecutor(workers, thread_name_prefix="tblup-copy")
-    return _POOL
-
-
-def _copy_rows(host, dtypes, workers=8, ready=None, dest=None):
-    """An own array per child: float64 rows as TrackedGenome views (the key store mirrors
-    them on the device and must notice in-place writes), other dtypes as plain arrays.
-    ready: per-chunk callables that block until that chunk of `host` has arrived (the
-    device-to-host copy is chunked so the row copies of chunk c overlap the transfer of
-    chunk c + 1).  dest: preallocated float64 rows to copy into (dtypes None).  (Splitting
-    each chunk over all workers measured slower: 4.3 vs 3.0 ms at config 2.)"""
-    n = host.shape[0]
-    nchunk = workers if ready is None else len(ready)
-    step = (n + nchunk - 1) // nchunk
-
-    def chunk(c):
-        lo, hi = c * step, min(n, (c + 1) * step)
-        if ready is not None:
-            ready[c]()
-        if dtypes is None and dest is not None:
-            for i in range(lo, hi):
-                np.copyto(dest[i], host[i])
-            return [track(dest[i]) for i in range(lo, hi)]
-        if dtypes is None:
-            return [track(np.array(host[i])) for i in range(lo, hi)]
-        return [np.array(host[i], dtype=dtypes[i]) for i in range(lo, hi)]
-    if ready is None and n * host.shape[1] < (1 << 20):
-        return [a for c in range(nchunk) for a in chunk(c)]
-    parts = _pool(workers).map(chunk, range(nchunk))
-    return [a for part in parts for a in part]
-
-
 _NO_GENOME = np.empty(0)
 
 # diagnostics (tools/generation_bench.py): when a dict, evolve() adds its segment times (s)
@@ -309,149 +307,12 @@ def _mark(t0, name):
     return t
 
 
-class _RowBlocks:
-    """Page-locked blocks (one per generation) whose rows are children's genomes.
-
-    A row is a view, so a block stays allocated while any genome in it lives (the reference
-    gives every child its own array, individual.py:110-118; a view is one as far as any
-    reader can tell: disjoint rows, float64, written through the TrackedGenome paths).  DE selection leaves survivors spread
-    over older blocks: when more than `keep` older blocks are still referenced by the
-    population, the least-referenced ones are compacted -- those individuals' genomes are
-    replaced by equal own copies (set_internal_genome, individual.py:100-101) -- so at most
-    keep + 2 generations (about 2 GiB) stay page-locked.  The copies run on worker threads
-    while the next generation's GPU work and transfers are in flight, and the genomes are
-    swapped to them at the next compaction (an own array each: they are never DMA'd again,
-    their device rows stay in the key store).  Freed blocks go back to torch's caching host
-    allocator and are reused without new page-locking."""
-
-    def __init__(self, keep=12):
-        self.keep = keep
-        self._reg = {}   # id(block) -> weakref(block)
-        self._reserved = set()
-        self._pending = []   # (individual, its genome when the copy started, future of the copy)
-
-    def keep_for(self, nbytes):
-        """Older blocks kept page-locked for blocks of nbytes (about 2 GiB in all)."""
-        return max(1, min(self.keep, (2 << 30) // max(nbytes, 1)))
-
-    def reserve(self, shape):
-        """Pre-size torch's caching host allocator for blocks of `shape`: the steady state holds
-        keep_for + 2 blocks at once (the kept older ones, the current population's, the one being
-        filled), so page-lock that many once, on the first generation -- otherwise every
-        generation until the pool is full pins a fresh block (~10 ms per 100 MB).  Synchronously:
-        page-locking from a background thread (round 4) contended with the generation's own HIP
-        calls and made generations 2-12 slower (18 ms vs 12 ms at config 2) than pinning them
-        one by one."""
-        key = tuple(int(x) for x in shape)
-        if key in self._reserved:
-            return
-        self._reserved.add(key)
-        import torch
-        n = self.keep_for(8 * int(np.prod(key))) + 2
-        bufs = [torch.empty(key, dtype=torch.float64, pin_memory=True) for _ in range(n)]
-        del bufs   # back to the caching allocator, page-locked
-
-    def rows(self, block):
-        import weakref
-        self._reg[id(block)] = weakref.ref(block)
-        rows = track_rows(block)
-        block.flags.writeable = False   # the rows' private aliases are the only writable ones
-        return rows
-
-    def _block_of(self, g):
-        b = g._blk if type(g) is TrackedGenome else None   # set by track_rows: no base walk
-        if b is not None:
-            r = self._reg.get(id(b))
-            if r is not None and r() is b:
-                return b
-        b = g
-        while isinstance(b, np.ndarray):
-            r = self._reg.get(id(b))
-            if r is not None and r() is b:
-                return b
-            b = b.base
-        return None
-
-    def finish(self, store=None):
-        """Swap the members whose copies the last compaction started to those copies: skipped
-        for a genome replaced or written (TrackedGenome marks it stale) since the copy began --
-        it stays where it is and a later compaction takes it."""
-        pending, self._pending = self._pending, []
-        for indv, old, fut in pending:
-            new = fut.result()
-            if getattr(indv, "_genome", None) is not old or old._stale:
-                continue
-            t = track(new)
-            indv.set_internal_genome(t)
-            if store is not None:
-                store.rebind(indv, old, t)
-
-    def compact(self, individuals, store=None):
-        """Blocks that only a few members of the population still use (<= n / 64 rows), and
-        the least-used ones beyond `keep`: those members' genomes are copied into own arrays on
-        worker threads (np.copyto releases the GIL; the copies overlap the next generation's
-        transfers) and swapped by the next call (finish); the key store keeps their device rows.
-        (Round 4 copied them here, on the caller's thread, into page-locked buffers: 2-12 ms per
-        generation at pop 1024.)"""
-        self.finish(store)
-        self._reg = {k: r for k, r in self._reg.items() if r() is not None}
-        if not self._reg:
-            return
-        users = {}
-        for indv in individuals:
-            g = getattr(indv, "_genome", None)
-            blk = self._block_of(g) if isinstance(g, np.ndarray) else None
-            if blk is not None:
-                users.setdefault(id(blk), []).append(indv)
-        order = sorted(users, key=lambda k: len(users[k]))
-        few = max(1, len(individuals) // 64)
-        # at most `keep` older blocks, fewer when they are large (about 2 GiB page-locked)
-        big = max(r().nbytes for r in self._reg.values())
-        keep = self.keep_for(big) - 1   # the blocks dropped here are released at the next call (finish)
-        drop = [k for i, k in enumerate(order) if len(users[k]) <= few or i < len(order) - keep]
-        if not drop:
-            return
-        moved = [indv for k in drop for indv in users[k]
-                 if indv.get_internal_genome() is indv._genome]   # RandomKey / Index semantics only
-        pool = _pool()
-        # runs of rows per job: few pool round trips, each copy large enough to release the GIL
-        per = max(1, (len(moved) + 7) // 8)
-        for j0 in range(0, len(moved), per):
-            grp = moved[j0:j0 + per]
-            fut = pool.submit(_copy_genomes, [indv._genome for indv in grp])
-            for j, indv in enumerate(grp):
-                self._pending.append((indv, indv._genome, _Part(fut, j)))
-
-
-def _copy_genomes(genomes):
-    return [np.array(g.view(np.ndarray)) for g in genomes]
-
-
-class _Part:
-    """Item j of a future's list result."""
-
-    def __init__(self, fut, j):
-        self.fut, self.j = fut, j
-
-    def result(self):
-        return self.fut.result()[self.j]
-
-
 def _assigns_genome(indv):
     """Whether set_internal_genome only stores the array (IndexIndividual's, individual.py:100-101,
     inherited by RandomKey / Nullable): then a child may be bound to its row before the row's
     transfer has landed.  CoevolutionIndividual's reads the last element (individual.py:194-208)."""
     f = getattr(type(indv), "set_internal_genome", None)
     return getattr(f, "__qualname__", "") == "IndexIndividual.set_internal_genome"
-
-
-_BLOCKS = _RowBlocks()
-
-# a generation's float64 children up to this many bytes cross as one page-locked block
-_BLOCK_MAX = int(os.environ.get("TBLUP_BLOCK_ROWS_MB", "1024")) << 20
-
-# children of a generation up to this many bytes get page-locked genome buffers
-_PINNED_ROWS_MAX = int(os.environ.get("TBLUP_PINNED_ROWS_MB", "2048")) << 20
 
 
 _DC_INDEX = {}
@@ -495,10 +356,6 @@ def _members(population):
     if any(len(g) != L for g in genomes):
         raise ValueError("DE needs internal genomes of one length (numpy broadcasting in evolver.py:132)")
     return inds, genomes, L
-
-
-def _common_length(population):
-    return _members(population)[2]
 
 
 class Evolver(abc.ABC):
@@ -563,76 +420,31 @@ class _GpuDEEvolver(Evolver):
                 bases = inds if mde is None else [inds[j] for j in src]
                 speculated = bool(spec is not None and dtypes is None and spec(bases, children, population.generation))
                 t = _mark(t, "ev_speculate")
-                # float64 children: one DMA into a page-locked block whose rows become the children's
-                # genomes (views: no host copy); otherwise chunks, each followed by an event, so the
-                # per-row copies of one chunk overlap the transfer of the next
-                block_rows = dtypes is None and n * L * 8 <= _BLOCK_MAX
-                # several ranks of one node: a node-shared block, each rank copying its shard's rows
-                shared = _SHM.acquire(children.shape, _BLOCKS.keep_for(n * L * 8)) if block_rows else None
-                if shared is not None:
-                    rank, ws = world()
-                    lo, hi = shard_range(n, rank, ws)
-                    host = torch.from_numpy(shared)
-                    if lo < hi:
-                        host[lo:hi].copy_(children[lo:hi], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    events = [ev]
-                else:
-                    if block_rows:
-                        _BLOCKS.reserve(children.shape)
-                    host = torch.empty(children.shape, dtype=torch.float64, pin_memory=True)
-                    nchunk = 1 if block_rows else (8 if n >= 16 else 1)
-                    rows = (n + nchunk - 1) // nchunk
-                    events = []
-                    for c in range(nchunk):
-                        lo, hi = c * rows, min(n, (c + 1) * rows)
-                        if lo < hi:
-                            host[lo:hi].copy_(children[lo:hi], non_blocking=True)
-                        ev = torch.cuda.Event()
-                        ev.record()
-                        events.append(ev)
+                # the copies to the host, issued behind the step: one page-locked block whose rows become
+                # the genomes, a node-shared one, or chunks for an own array per child (HostRows)
+                rows = HostRows(children, dtypes, n, L, shard_range(n, *world()))
             finally:
                 rng_done()   # numpy's global state after the step's np.random.rand draws
         t = _mark(t, "ev_transfer_issue")
-
-        def rows_landed():   # the whole block (one event); every rank's shard of a shared one
-            events[-1].synchronize()
-            if shared is not None:
-                import torch.distributed as dist
-                dist.barrier()
         # the candidates (new uids, the parent's other attributes) while the transfer runs
         next_pop = [_copy_individual(population[j]) for j in src]
         t = _mark(t, "ev_candidates")
-        if (shared is not None or block_rows) and all(_assigns_genome(c) for c in next_pop):
-            # whole-block rows: every child is bound to its row (a view: nothing reads the values),
-            # recorded, and the older blocks compacted while the rows are still in flight; the
-            # children are returned once their rows have landed (every rank's, for a shared block)
-            arrays = _BLOCKS.rows(shared if shared is not None else host.numpy())
-            t = _mark(t, "ev_arrays")
-            self._bind(next_pop, arrays, inds, genomes, children, parents, store, speculated, evaluator)
-            t = _mark(t, "ev_bind_record")
-            _BLOCKS.compact(inds, store)
-            t = _mark(t, "ev_compact")
-            rows_landed()
-            _mark(t, "ev_rows_landed")
-            return next_pop
-        if shared is not None or block_rows:
-            rows_landed()
-            arrays = _BLOCKS.rows(shared if shared is not None else host.numpy())
-        else:
-            # an own array per child; float64 rows go into page-locked buffers from torch's caching
-            # host allocator, which hands back the buffers of dead genomes: no page faults on the copy
-            dest = None
-            if dtypes is None and n * L * 8 <= _PINNED_ROWS_MAX:
-                dest = [torch.empty(L, dtype=torch.float64, pin_memory=True).numpy() for _ in range(n)]
-            arrays = _copy_rows(host.numpy(), dtypes, ready=[ev.synchronize for ev in events], dest=dest)
+        # whole-block rows: every child is bound to its row (a view: nothing reads the values),
+        # recorded, and the older blocks compacted while the rows are still in flight; the
+        # children are returned once their rows have landed (every rank's, for a shared block)
+        early = rows.whole is not None and all(_assigns_genome(c) for c in next_pop)
+        if not early:
+            rows.landed()
+        arrays = rows.arrays()
         t = _mark(t, "ev_arrays")
         self._bind(next_pop, arrays, inds, genomes, children, parents, store, speculated, evaluator, dtypes)
         t = _mark(t, "ev_bind_record")
         # older blocks the parents leave sparsely used, while the GPU still evaluates the children
         _BLOCKS.compact(inds, store)
-        _mark(t, "ev_compact")
+        t = _mark(t, "ev_compact")
+        if early:
+            rows.landed()
+            _mark(t, "ev_rows_landed")
         return next_pop
 
     @staticmethod
@@ -642,7 +454,7 @@ class _GpuDEEvolver(Evolver):
         if speculated:
             evaluator._spec_bind(next_pop)
         if dtypes is None:   # float64 internal genomes: the device rows are the children's exact values
-            store.record_rows(children, next_pop, arrays)
+            store.record(children, next_pop, arrays)
             store.record(parents, inds, genomes, adopt=True)
         store.prune([x.uid for x in inds] + [x.uid for x in next_pop])
 
@@ -655,17 +467,7 @@ class DERandOneEvolver(_GpuDEEvolver):
     def _donors(self, population, L):
         n = len(population)
         drawn = _native_donors(self.strategy, n, L)
-        if drawn is not None:
-            return drawn
-        donors = np.empty((n, 3), dtype=np.int32)
-        fixed = np.empty(n, dtype=np.int64)
-        for i in range(n):   # de_rand_one (evolver.py:118-121) then crossover (evolver.py:76)
-            a = exclusive_randrange(0, n, [i])
-            b = exclusive_randrange(0, n, [i, a])
-            c = exclusive_randrange(0, n, [i, a, b])
-            donors[i] = (a, b, c)
-            fixed[i] = random.randrange(0, L)
-        return donors, fixed
+        return drawn if drawn is not None else _draw_donors(n, lambda i: _rand_one_draws(n, L, i))
 
 
 class DECurrentToBestOneEvolver(_GpuDEEvolver):
@@ -678,21 +480,9 @@ class DECurrentToBestOneEvolver(_GpuDEEvolver):
 
     def _donors(self, population, L):
         n = len(population)
-        best = max(population, key=lambda individual: individual.fitness)   # evolver.py:235
-        best_index = population.population.index(best)                      # evolver.py:194
-        drawn = _native_donors(self.strategy, n, L, best_index)
-        if drawn is not None:
-            return drawn
-        donors = np.empty((n, 3), dtype=np.int32)
-        fixed = np.empty(n, dtype=np.int64)
-        for i in range(n):   # evolver.py:199-203, then crossover (evolver.py:76)
-            exclusion_list = [i, best_index]
-            a = exclusive_randrange(0, n, exclusion_list)
-            exclusion_list.append(a)
-            b = exclusive_randrange(0, n, exclusion_list)
-            donors[i] = (best_index, a, b)
-            fixed[i] = random.randrange(0, L)
-        return donors, fixed
+        best = _best_index(population)
+        drawn = _native_donors(self.strategy, n, L, best)
+        return drawn if drawn is not None else _draw_donors(n, lambda i: _current_to_best_draws(n, L, i, best))
 
 
 # ---------------------------------------------------------------------------------------------
@@ -858,8 +648,7 @@ class SaDE(AdaptiveEvolver, _GpuDEEvolver):
         n = len(population)
         members = _members(population)
         L = members[2]
-        best = max(population, key=lambda indv: indv.fitness)
-        best_index = population.population.index(best)
+        best_index = _best_index(population)
         strategies = np.empty(n, dtype=np.int32)
         donors = np.empty((n, 3), dtype=np.int32)
         fixed = np.empty(n, dtype=np.int64)
@@ -868,14 +657,10 @@ class SaDE(AdaptiveEvolver, _GpuDEEvolver):
             if random.random() < self.p:   # DE/rand/1 (evolver.py:118-121)
                 self.strategy_one_indices.add(i)
                 strategies[i] = 0
-                a = exclusive_randrange(0, n, [i])
-                b = exclusive_randrange(0, n, [i, a])
-                donors[i] = (a, b, exclusive_randrange(0, n, [i, a, b]))
+                donors[i], fixed[i] = _rand_one_draws(n, L, i)
             else:                          # DE/current-to-best/1 (evolver.py:199-203)
                 strategies[i] = 1
-                a = exclusive_randrange(0, n, [i, best_index])
-                donors[i] = (best_index, a, exclusive_randrange(0, n, [i, best_index, a]))
-            fixed[i] = random.randrange(0, L)   # the crossover's forced position (evolver.py:76)
+                donors[i], fixed[i] = _current_to_best_draws(n, L, i, best_index)
         crs = np.array([float(c) for c in self.crs[:n]], dtype=np.float64)
         return self._gpu_generation(population, t, donors, fixed, strategies, f, crs, self.clip, members)
 
@@ -1038,20 +823,14 @@ class MDE_pBX(AdaptiveEvolver, _GpuDEEvolver):
 
 def _host_current_to_best(population, mi, cr, dimensionality, parent_idx, best, clip):
     """DECurrentToBestOneEvolver.de_currenttobest_one with binary crossover (evolver.py:63-82,
-    179-221) on the host: the reference's draws (exclusive_randrange x 2, random.randrange, one
-    np.random.rand(L)) and its float arithmetic order."""
-    n = len(population)
-    best_index = population.population.index(best)
-    excl = [parent_idx, best_index]
-    a = exclusive_randrange(0, n, excl)
-    excl.append(a)
-    b = exclusive_randrange(0, n, excl)
+    179-221) on the host: the reference's draws (_current_to_best_draws, one np.random.rand(L)) and
+    its float arithmetic order."""
+    L = len(population[parent_idx].get_internal_genome())
+    (_, a, b), fixed = _current_to_best_draws(len(population), L, parent_idx, population.population.index(best))
     ga, gb = population[a].get_internal_genome(), population[b].get_internal_genome()
     child = deepcopy(population[parent_idx])
     x = child.get_internal_genome()
     mutant = x + mi * (best.get_internal_genome() - x) + mi * (ga - gb)
-    L = len(x)
-    fixed = random.randrange(0, L)
     take = np.random.rand(L) < cr
     take[fixed] = True
     child.set_internal_genome(np.where(take, mutant, x))

@@ -28,6 +28,7 @@ device.
 """
 import os
 import weakref
+from operator import itemgetter
 
 import numpy as np
 
@@ -224,6 +225,17 @@ def work_stream(device):
     return s
 
 
+# An entry, one recorded device row: `tensor[row]` holds the genome array `ref()` (a weakref) of an
+# individual of that `length`; addr: the row's device address (0 unless the tensor is a plain row-major
+# float64 matrix), taken when the row is recorded, so the DE step's gather reads addresses instead of
+# tensor geometry; ncols: that matrix's row length (-1 with addr 0).  A plain tuple with its layout
+# named here and built in record() alone: 2 x 1024 entries are built per generation at pop 1024, where
+# a __slots__ class's python-level __init__ costs 0.21 ms per 1024 and a namedtuple 0.07 ms more than
+# the tuple (bound: `ev_bind_record` is 0.83 ms).
+_TENSOR, _ROW, _REF, _LENGTH, _ADDR, _NCOLS = range(6)
+_addr_of, _ncols_of = itemgetter(_ADDR), itemgetter(_NCOLS)
+
+
 class DeviceKeyStore:
     _instances = {}
 
@@ -236,10 +248,7 @@ class DeviceKeyStore:
 
     def __init__(self, device):
         self.device = int(device)
-        # uid -> (tensor, row, weakref(genome array), length, row address, row length): the row's
-        # device address (0 unless the tensor is a plain row-major float64 matrix) taken when the
-        # row is recorded, so the DE step's gather reads addresses instead of tensor geometry
-        self._entries = {}
+        self._entries = {}   # uid -> entry
 
     @staticmethod
     def _geo(tensor):
@@ -250,190 +259,106 @@ class DeviceKeyStore:
             return tensor.data_ptr(), 8 * tensor.stride(0), tensor.shape[1]
         return 0, 0, -1
 
-    @staticmethod
-    def _key_array(indv):
-        g = getattr(indv, "_genome", None)
-        return g if isinstance(g, np.ndarray) else None
-
-    def record_rows(self, tensor, individuals, arrays):
-        """record() for a generation's children that the evolver has just bound to fresh TrackedGenome
-        rows (every individual's genome IS arrays[i]): one dict update."""
-        p0, pitch, nc = self._geo(tensor)
-        self._entries.update({indv.uid: (tensor, i, weakref.ref(g), getattr(indv, "length", None),
-                                         p0 + pitch * i if p0 else 0, nc)
-                              for i, (indv, g) in enumerate(zip(individuals, arrays))
-                              if getattr(indv, "_genome", None) is g})
-
     def record(self, tensor, individuals, arrays, adopt=False):
         """Row i of `tensor` (pop x L, on the device) holds arrays[i]; recorded for individuals
         whose internal genome IS that array (RandomKey / Index semantics: get_internal_genome()
-        returns `_genome`) and a TrackedGenome (the evolver hands its children such views;
-        parents recorded from other arrays are not tracked and are read from the host).
+        returns `_genome`) and an unwritten TrackedGenome (the evolver hands its children such
+        views; parents recorded from other arrays are not tracked and are read from the host).
         Individuals that derive their internal genome (Coevolution appends its length) are not
-        recorded and are read from the host."""
-        ent = self._entries
+        recorded and are read from the host.  adopt: genomes the evolver did not create (the
+        initial population) become tracked views of their own buffers first.  One dict update."""
+        if adopt and set(map(type, arrays)) != {TrackedGenome}:
+            arrays = [self._adopted(indv, a) for indv, a in zip(individuals, arrays)]
         p0, pitch, nc = self._geo(tensor)
-        for i, (indv, a) in enumerate(zip(individuals, arrays)):
-            g = getattr(indv, "_genome", None)
-            if g is not a or g is None:
-                continue
-            if type(g) is TrackedGenome and not g._stale:   # the common case, inlined
-                ent[indv.uid] = (tensor, i, weakref.ref(g), getattr(indv, "length", None), p0 + pitch * i if p0 else 0, nc)
-                continue
-            if not isinstance(g, np.ndarray):
-                continue
-            if not isinstance(g, TrackedGenome):
-                # a genome the evolver did not create (the initial population): adopt it as a
-                # tracked view of the same buffer when nothing else views that buffer
-                if not adopt or g.base is not None or g.dtype != np.float64 or not g.flags.c_contiguous:
-                    continue
-                g = track(g)
-                indv._genome = g
-            if g._stale:
-                continue
-            ent[indv.uid] = (tensor, i, weakref.ref(g), getattr(indv, "length", None), p0 + pitch * i if p0 else 0, nc)
+        ref = weakref.ref
+        self._entries.update({indv.uid: (tensor, i, ref(g), getattr(indv, "length", None),
+                                         p0 + pitch * i if p0 else 0, nc)
+                              for i, (indv, g) in enumerate(zip(individuals, arrays))
+                              if getattr(indv, "_genome", None) is g and isinstance(g, TrackedGenome) and not g._stale})
 
-    def lookup(self, indv):
-        e = self._entries.get(indv.uid)
-        if e is None:
-            return None
-        g = e[2]()
-        if g is None or g is not self._key_array(indv) or g._stale or getattr(indv, "length", None) != e[3]:
-            del self._entries[indv.uid]
-            return None
-        return e[0], e[1]
+    @staticmethod
+    def _adopted(indv, g):
+        """g; where it is indv's own plain float64 genome and nothing else views its buffer, the
+        tracked view of that buffer, which the individual now holds instead."""
+        if (getattr(indv, "_genome", None) is g and isinstance(g, np.ndarray) and not isinstance(g, TrackedGenome)
+                and g.base is None and g.dtype == np.float64 and g.flags.c_contiguous):
+            g = indv._genome = track(g)
+        return g
 
     def rebind(self, indv, old, new):
         """indv's genome array `old` was replaced by the equal-valued TrackedGenome `new`
         (the evolver compacting page-locked blocks): keep its device row."""
         e = self._entries.get(indv.uid)
-        if e is not None and e[2]() is old and not old._stale:
-            self._entries[indv.uid] = (e[0], e[1], weakref.ref(new)) + e[3:]
+        if e is not None and e[_REF]() is old and not old._stale:
+            self._entries[indv.uid] = e[:_REF] + (weakref.ref(new),) + e[_REF + 1:]
 
-    def rows(self, individuals):
-        """(tensor, row) per individual (None where absent): lookup() inlined over the batch."""
+    def _hits(self, individuals):
+        """Each individual's entry, None where it has none or a dead one, which is dropped.  The one
+        statement of the validity rule (module docstring): the weakref is alive, the individual still
+        holds that very array, unwritten, and has the same length.  A batch loop with the rule inline
+        (a rule function called per individual measured 0.07 ms per 1024 slower); lookup(), rows() and
+        gather() derive from it."""
         ent = self._entries
+        REF, LENGTH = _REF, _LENGTH
         out = []
         for indv in individuals:
             e = ent.get(indv.uid)
             if e is not None:
-                g = e[2]()
-                k = getattr(indv, "_genome", None)
-                if (g is not None and g is k and isinstance(k, np.ndarray) and not g._stale
-                        and getattr(indv, "length", None) == e[3]):
-                    out.append((e[0], e[1]))
+                g = e[REF]()
+                if (g is not None and g is getattr(indv, "_genome", None) and not g._stale
+                        and getattr(indv, "length", None) == e[LENGTH]):
+                    out.append(e)
                     continue
                 del ent[indv.uid]
             out.append(None)
         return out
 
+    def lookup(self, indv):
+        return self.rows((indv,))[0]
+
+    def rows(self, individuals):
+        """(tensor, row) per individual (None where absent)."""
+        return [e and (e[_TENSOR], e[_ROW]) for e in self._hits(individuals)]
+
     def gather(self, individuals, L, host_rows=None, copy_rows=None):
         """A contiguous (len(individuals) x L) float64 device tensor of their internal genomes;
         rows not in the store come from host_rows(i) (None -> return None if any is missing).
         No copy when the individuals are exactly one recorded block in order.  copy_rows(out,
-        pointers): one native gather of the recorded rows (pointer 0 = row to skip)."""
+        pointers): one native gather of the recorded rows, taken when every one of them has a
+        recorded address and row length L; otherwise (and without copy_rows) one index_copy_ per
+        recorded tensor.  (After the scan of the individuals the entries are only read through
+        C-level iteration: the parent gather at pop 1024 is 0.3 ms of the generation.)"""
         import torch
         n = len(individuals)
-        if copy_rows is not None and n:
-            out = self._gather_ptrs(individuals, L, host_rows, copy_rows)
-            if out is not False:
-                return out
-        hits = self.rows(individuals)
-        if n and all(h is not None for h in hits):
-            t0 = hits[0][0]
-            if t0.shape == (n, L) and all(h[0] is t0 and h[1] == i for i, h in enumerate(hits)):
+        hits = self._hits(individuals)
+        missing = [i for i, e in enumerate(hits) if e is None] if None in hits else []
+        found = [e for e in hits if e is not None] if missing else hits
+        if n and not missing:   # exactly rows 0 .. n-1 of one recorded (n, L) tensor, in order?
+            t0 = hits[0][_TENSOR]
+            if t0.shape == (n, L) and all(e[_TENSOR] is t0 and e[_ROW] == i for i, e in enumerate(hits)):
                 return t0
-        if host_rows is None and any(h is None for h in hits):
-            return None
-        out = torch.empty((n, L), dtype=torch.float64, device="cuda:%d" % self.device)
-        # every row's device address in one pass: (base address, row pitch in bytes) per distinct
-        # device tensor (torch's accessors once per tensor, not per row), None if that tensor is not
-        # a plain row-major (., L) float64 matrix
-        if copy_rows is not None:
-            geo = {}
-            ptrs = [0] * n
-            missing = []
-            plain = True
-            for i, h in enumerate(hits):
-                if h is None:
-                    missing.append(i)
-                    continue
-                t, row = h
-                g = geo.get(id(t))
-                if g is None:
-                    g = geo[id(t)] = ((t.data_ptr(), 8 * t.stride(0))
-                                      if t.dim() == 2 and t.shape[1] == L and t.stride(1) == 1 else ())
-                if not g:
-                    plain = False
-                    break
-                ptrs[i] = g[0] + g[1] * row
-            if plain:
-                if len(missing) < n:
-                    if missing:   # missing slots: any recorded row, overwritten below
-                        any_row = next(q for q in ptrs if q)
-                        for i in missing:
-                            ptrs[i] = any_row
-                    copy_rows(out, ptrs)
-                if missing:
-                    self._fill_missing(out, missing, host_rows)
-                return out
-        by_tensor = {}
-        missing = []
-        for i, h in enumerate(hits):
-            if h is None:
-                missing.append(i)
-            elif h[0].shape[1] != L:
-                return None if host_rows is None else self._fill_missing(out, list(range(n)), host_rows)
-            else:
-                by_tensor.setdefault(id(h[0]), (h[0], [], []))
-                by_tensor[id(h[0])][1].append(i)
-                by_tensor[id(h[0])][2].append(h[1])
-        for t, dst, src in by_tensor.values():
-            di = torch.tensor(dst, device=out.device)
-            si = torch.tensor(src, device=out.device)
-            out.index_copy_(0, di, t.index_select(0, si))
-        if missing:
-            self._fill_missing(out, missing, host_rows)
-        return out
-
-    def _gather_ptrs(self, individuals, L, host_rows, copy_rows):
-        """gather() from the recorded row addresses in one pass (rows() inlined); False when some
-        recorded tensor is not a plain (., L) matrix (the caller's general path)."""
-        import torch
-        ent = self._entries
-        n = len(individuals)
-        ptrs = [0] * n
-        missing = []
-        t0 = None
-        block = True   # exactly rows 0 .. n-1 of one recorded (n, L) tensor, in order
-        for i, indv in enumerate(individuals):
-            e = ent.get(indv.uid)
-            if e is not None:
-                g = e[2]()
-                if (g is not None and g is getattr(indv, "_genome", None) and not g._stale
-                        and getattr(indv, "length", None) == e[3]):
-                    if not e[4] or e[5] != L:
-                        return False
-                    ptrs[i] = e[4]
-                    if block:
-                        if t0 is None:
-                            t0 = e[0]
-                        block = e[0] is t0 and e[1] == i
-                    continue
-                del ent[indv.uid]
-            missing.append(i)
-            block = False
-        if block and t0 is not None and t0.shape[0] == n:
-            return t0
         if missing and host_rows is None:
             return None
         out = torch.empty((n, L), dtype=torch.float64, device="cuda:%d" % self.device)
-        if len(missing) < n:
-            if missing:   # missing slots: any recorded row, overwritten below
-                any_row = next(q for q in ptrs if q)
-                for i in missing:
-                    ptrs[i] = any_row
-            copy_rows(out, ptrs)
+        addrs = list(map(_addr_of, found))
+        if copy_rows is not None and all(addrs) and set(map(_ncols_of, found)) <= {L}:
+            if missing and found:   # missing slots: any recorded row, overwritten below
+                addrs = [addrs[0] if e is None else e[_ADDR] for e in hits]
+            if found:
+                copy_rows(out, addrs)
+        elif any(e[_TENSOR].shape[1] != L for e in found):   # a row of another length: all from the host
+            return None if host_rows is None else self._fill_missing(out, list(range(n)), host_rows)
+        else:
+            by_tensor = {}
+            for i, e in enumerate(hits):
+                if e is not None:
+                    t, dst, src = by_tensor.setdefault(id(e[_TENSOR]), (e[_TENSOR], [], []))
+                    dst.append(i)
+                    src.append(e[_ROW])
+            for t, dst, src in by_tensor.values():
+                di = torch.tensor(dst, device=out.device)
+                si = torch.tensor(src, device=out.device)
+                out.index_copy_(0, di, t.index_select(0, si))
         if missing:
             self._fill_missing(out, missing, host_rows)
         return out

@@ -16,7 +16,7 @@ segment: 1/N of the transfer per rank and one host copy of the children per node
 A segment is free when no rank still holds a genome in it.  Liveness is per rank (weak
 references to the segment's block array, whose rows the genomes are); the ranks' masks are
 combined by one all-reduce (MAX) so every rank picks the same segment.  The page-locked-block
-compaction of tblup_amd.evolver (_RowBlocks.compact) moves the last survivors out of old blocks,
+compaction of tblup_amd.hostrows (_RowBlocks.compact) moves the last survivors out of old blocks,
 which frees their segments for reuse.  When no segment is free, or the ranks span several nodes,
 acquire() returns None and the caller copies the whole population as before.
 """

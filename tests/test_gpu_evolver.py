@@ -268,7 +268,7 @@ def test_gpu_block_rows_many_generations(gpu, tmp_path, kind):
     the rows are still in flight."""
     from tests import ga_driver as GD
     from oracle import blup_oracle as O
-    from tblup_amd import evolver as EVM
+    from tblup_amd import hostrows as HR
     from tblup_amd.evaluator import BlupParallelEvaluator
     from tblup_amd.keystore import DeviceKeyStore
     rng = np.random.default_rng(12)
@@ -297,7 +297,7 @@ def test_gpu_block_rows_many_generations(gpu, tmp_path, kind):
                 if use_gpu_de:
                     kids = evo.evolve(popn)
                     assert all(h is not None for h in DeviceKeyStore.get(0).rows(popn.population))
-                    alive.append(sum(r() is not None for r in EVM._BLOCKS._reg.values()))
+                    alive.append(sum(r() is not None for r in HR._BLOCKS._reg.values()))
                 else:
                     DeviceKeyStore.get(0).clear()
                     want = D.de_generation([x.get_internal_genome() for x in popn.population],
@@ -324,7 +324,7 @@ def test_gpu_block_rows_many_generations(gpu, tmp_path, kind):
     assert f_gpu == f_ref
     for x, y in zip(g_gpu, g_ref):
         assert np.array_equal(x, y)
-    assert max(alive) <= EVM._BLOCKS.keep + 2, alive
+    assert max(alive) <= HR._BLOCKS.keep + 2, alive
 
 
 @pytest.mark.parametrize("n,L,shift", [(1, 1, 0), (5, 7, 1), (130, 1000, 0), (300, 50_000, 0), (129, 33, 1)])
@@ -380,3 +380,49 @@ def test_gpu_de_small_populations_forced_three_launch_form(gpu):
     r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_evolver import _child; _child()"], cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "de child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
+
+
+# (L, pop, pre): one chunk (fewer than 16 children); 8 chunks of 2; 8 chunks of ceil(21 / 8) = 3 rows,
+# which hold 3,3,3,3,3,3,3,0 -- the last chunk is empty
+PER_ROW_SHAPES = [(7, 5, 0), (33, 16, 3), (100, 21, 624)]
+
+
+def _per_row_child():
+    from tblup_amd.keystore import DeviceKeyStore, TrackedGenome
+    for L, pop, pre in PER_ROW_SHAPES:
+        _small_shape_vs_oracle(L, pop, pre)
+    rng = np.random.default_rng(21)
+    pop, p = 21, 100
+    inds = [RandomKeyIndividual(rng.uniform(size=p), 10) for _ in range(pop)]
+    for x in inds:
+        x.fitness = float(rng.uniform())
+    random.seed(3)
+    np.random.seed(3)
+    popn = Pop(inds, 0)
+    evo = _evolver("de_rand_1", p, 0.8, 0.5, False)
+    for g in range(1, 4):
+        popn.generation = g
+        kids = evo.evolve(popn)
+        assert all(h is not None for h in DeviceKeyStore.get(0).rows(kids))
+        gs = [c.get_internal_genome() for c in kids]
+        assert all(type(a) is TrackedGenome for a in gs)
+        assert not any(np.shares_memory(gs[i], gs[j]) for i in range(pop) for j in range(i))
+        for c in kids:
+            c.fitness = float(rng.uniform())
+        popn.population = [c if c.fitness > q.fitness else q for q, c in zip(popn.population, kids)]
+    print("per-row child ok")
+
+
+@pytest.mark.parametrize("pinned", [True, False])
+def test_gpu_per_row_children_paths(gpu, pinned):
+    """Float64 children above TBLUP_BLOCK_ROWS_MB cross in chunks and get an own array each, in
+    page-locked buffers (pinned) or, above TBLUP_PINNED_ROWS_MB too, plain ones: one chunk, 8 even
+    chunks and 8 chunks with an empty last one against the oracle, then three generations whose
+    children all have a key-store row and a TrackedGenome of their own memory.  Both limits are
+    read at import: a fresh process."""
+    env = dict(os.environ, TBLUP_BLOCK_ROWS_MB="0")
+    if not pinned:
+        env["TBLUP_PINNED_ROWS_MB"] = "0"
+    r = subprocess.run([sys.executable, "-c", "from tests.test_gpu_evolver import _per_row_child; _per_row_child()"],
+                       cwd=ROOT, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "per-row child ok" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]

@@ -173,3 +173,83 @@ def test_track_rows_matches_track():
     c = rows[1].copy()
     assert not c._tracked() and np.array_equal(c, block[1])
     assert np.array_equal(copy.deepcopy(rows[0]), block[0])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("native", [True, False], ids=["copy_rows", "index_copy"])
+def test_gather_cases(gpu, native):
+    """DeviceKeyStore.gather, with and without the native pointer gather: the same-block shortcut,
+    rows of two tensors, written and unrecorded genomes read from the host (or None without
+    host_rows), and a hit in a tensor of another row length, which sends every row to the host.
+    The device tensors hold other values (+100) than the host arrays, so each row shows where it
+    came from."""
+    import torch
+    from tblup_amd.evolver import GpuDEStep
+    n, L = 5, 7
+    copy_rows = GpuDEStep.get(0).gather_rows if native else None
+    rng = np.random.default_rng(57)
+
+    def setup():
+        store = DeviceKeyStore(0)
+        groups = []
+        for t, cols in enumerate((L, L, 9)):             # A, B and C (5 x 9)
+            host = rng.uniform(size=(n, L))
+            dev = torch.from_numpy(rng.uniform(size=(n, cols)) + 100.0).cuda()
+            arrays = [track(host[i].copy()) for i in range(n)]
+            inds = [_Ind(1000 * t + i, arrays[i]) for i in range(n)]
+            store.record(dev, inds, arrays)
+            groups.append((dev, inds))
+        return store, groups
+
+    def gather(store, sel, host=True):
+        out = store.gather(sel, L, host_rows=(lambda i: sel[i]._genome) if host else None, copy_rows=copy_rows)
+        return out if out is None else out.cpu().numpy()
+
+    def dev_row(groups, ind):
+        t, i = divmod(ind.uid, 1000)
+        return groups[t][0][i, :L].cpu().numpy()
+
+    def mixed(groups):
+        (_, a), (_, b), _ = groups
+        return [b[2], a[4], a[0], b[3], a[1]]
+
+    # 1. the five individuals of A in order: A itself
+    store, groups = setup()
+    A, a = groups[0]
+    assert store.gather(a, L, host_rows=lambda i: a[i]._genome, copy_rows=copy_rows) is A
+    assert store.gather(a, L, copy_rows=copy_rows) is A
+    assert store.lookup(a[0]) is not None
+    # 2. rows of A and B mixed: equal values in a fresh tensor
+    sel = mixed(groups)
+    for host in (True, False):
+        out = store.gather(sel, L, host_rows=(lambda i: sel[i]._genome) if host else None, copy_rows=copy_rows)
+        assert out.shape == (n, L) and out.data_ptr() not in (A.data_ptr(), groups[1][0].data_ptr())
+        assert np.array_equal(out.cpu().numpy(), np.stack([dev_row(groups, x) for x in sel]))
+    assert all(store.lookup(x) is not None for x in sel)
+    # 3. two genomes written in place: those rows from the host, with the written values
+    sel[1]._genome[2] = -3.0
+    sel[3]._genome[0] = -4.0
+    want = np.stack([np.asarray(x._genome) if j in (1, 3) else dev_row(groups, x) for j, x in enumerate(sel)])
+    assert want[1, 2] == -3.0 and want[3, 0] == -4.0
+    assert np.array_equal(gather(store, sel), want)
+    assert store.lookup(sel[1]) is None and store.lookup(sel[3]) is None and store.lookup(sel[0]) is not None
+    # 4. the same without host_rows: None
+    store, groups = setup()
+    sel = mixed(groups)
+    sel[1]._genome[2] = -3.0
+    sel[3]._genome[0] = -4.0
+    assert gather(store, sel, host=False) is None
+    assert store.lookup(sel[1]) is None and store.lookup(sel[3]) is None and store.lookup(sel[2]) is not None
+    # 5. every row missing: all from the host
+    for x in sel:
+        x._genome[1] = -5.0
+    assert np.array_equal(gather(store, sel), np.stack([np.asarray(x._genome) for x in sel]))
+    assert gather(store, sel, host=False) is None
+    assert all(store.lookup(x) is None for x in sel) and store.lookup(groups[0][1][2]) is not None
+    # 6. one hit in a tensor of another row length (C, 5 x 9): every row from the host
+    store, groups = setup()
+    sel = mixed(groups)
+    sel[2] = groups[2][1][3]
+    assert np.array_equal(gather(store, sel), np.stack([np.asarray(x._genome) for x in sel]))
+    assert gather(store, sel, host=False) is None
+    assert all(store.lookup(x) is not None for x in sel)

@@ -72,15 +72,16 @@ def main(n=2000, p=50000, k=1000, pop=256, gens=4):
         for nm in ("genomes_to_evaluate", "_fitness", "_batch_genomes"):
             timed(ev, nm)
         import tblup_amd.evolver as EVM
-        for nm in ("_copy_rows", "_child_dtypes"):
-            fn = getattr(EVM, nm)
+        import tblup_amd.hostrows as HR
+        for mod, nm in ((HR, "_copy_rows"), (EVM, "_child_dtypes")):
+            fn = getattr(mod, nm)
 
             def wrap(*a, _fn=fn, _nm=nm, **kw):
                 t = time.perf_counter()
                 r = _fn(*a, **kw)
                 phase[_nm] = phase.get(_nm, 0.0) + time.perf_counter() - t
                 return r
-            setattr(EVM, nm, wrap)
+            setattr(mod, nm, wrap)
         timed(evo, "_donors")
         timed(EVM.GpuDEStep.get(0), "step_device")
         timed(ev.engine, "evaluate")
