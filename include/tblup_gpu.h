@@ -178,6 +178,45 @@ int tblup_reliability_batch(tblup_ctx* ctx, int split_id, const int64_t* animals
                             double* intercept, double* center, double* effects, double* reliability);
 
 /*
+ * Profile (restricted) log-likelihood of h2 for each of `batch` models, at `n_h2` values each: the
+ * evaluation's pipeline once per row of `h2`, plus one reduction over the factor it leaves behind.
+ * The model is the reference's own, the one tblup_reliability_batch documents: beta ~ N(0, sigma2_g / d I),
+ * e ~ N(0, sigma2_e I), sigma2_e / sigma2_g = lambda = (1-h2)/h2.  With N = n_T, A the gathered columns
+ * (duplicates kept), W_T = A_T - c (c the branch's centre), K = W W^T / d, V = K_TT + lambda I, and
+ * sigma2_g profiled out:
+ *   gblup branch (no mean is fitted, as the reference fits none; r = 0):
+ *     q = y_T^T V^{-1} y_T,   l = -1/2 [ N (log 2pi + 1 + log(q / N)) + log|V| ]
+ *   snp branch (intercept mean(y_T), centre over the train rows, so V 1 = lambda 1; r = 1):
+ *     q = yc^T V^{-1} yc, yc = y_T - mean(y_T); the restricted likelihood of the N - 1 error contrasts
+ *     A^T y_T (A orthonormal, A^T 1 = 0):
+ *     l_R = -1/2 [ (N-1)(log 2pi + 1 + log(q / (N-1))) + log|V| - log lambda ]
+ *     (log|A^T V A| = log|V| - log lambda: 1/sqrt(N) is an eigenvector of V with eigenvalue lambda)
+ *   sigma2_g = q / (N - r); the caller derives sigma2_e = lambda sigma2_g.
+ * From the factor M = L L^T of the form the batch's systems take: log|M| = -2 sum log(1 / L_ii) over the
+ * real rows; kernel form M = V and q = |z|^2 (z = L^{-1} rhs); SNP form M = W_T^T W_T / d + lambda I_k,
+ * rhs = W_T^T yc / d, and by Sylvester and Woodbury log|V| = (N - k) log lambda + log|M|,
+ * q = (yc^T yc - d |z|^2) / lambda.  Several traits share log|V|; q, l and sigma2_g are per trait.
+ *   h2       : n_h2 x batch, row g holds every model's h2 of pass g (a shared grid: constant rows);
+ *              each in (0, 1) -- lambda = 0 makes the snp branch's V singular, so h2 = 1 is
+ *              TBLUP_ERR_ARG here (and only here), as are h2 <= 0 and NaN
+ *   fitness  : optional out (may be NULL), n_h2 x batch; row g is bit-identical to tblup_eval_batch at
+ *              that h2 when row g of `h2` is constant
+ *   loglik   : out, n_h2 x batch x n_traits
+ *   sigma2_g : optional out (may be NULL), the same shape
+ * d = 0 (a monomorphic panel) or a quadratic form that is not positive and finite gives NaN, not an
+ * error.  n_h2 == 0 or batch == 0 returns 0 and writes nothing; a context without a panel gives
+ * TBLUP_ERR_STATE; idx / offsets / branch, the index rules (TBLUP_ERR_INDEX), the chunking and the
+ * chained solve's recovery are tblup_eval_batch's.  Per chunk the index lists are uploaded once and
+ * the n_h2 passes run back to back on the context's stream, the results copied out after the last.
+ * A model's values depend neither on the batch around it, nor on the other rows of `h2`, nor on the
+ * chunking (fixed-order sums, no atomics), and the same call gives the same bits twice.
+ * Host pointers, synchronous.
+ */
+int tblup_loglik_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                       const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
+                       double* sigma2_g);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

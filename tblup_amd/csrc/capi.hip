@@ -347,7 +347,7 @@ int64_t rel_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_re
 }
 
 size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv, bool with_model = false, int64_t n_rel = 0) {
+                   bool with_ebv, bool with_model = false, int64_t n_rel = 0, int64_t n_h2 = 0) {
   size_t s = 0;
   auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
   add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
@@ -380,6 +380,12 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
     add((size_t)B * n_rel * 8);                                 // the reliabilities
     add(reliab_in_lds(c, sd) ? 0                                // right-hand sides / V of one launch's slabs
                              : (size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W * 8);
+  }
+  if (n_h2 > 0) {                                               // tblup_loglik_batch, every pass of the chunk:
+    add((size_t)n_h2 * B * 8);                                  // the h2 rows
+    add((size_t)n_h2 * B * 8);                                  // the passes' fitnesses
+    add((size_t)n_h2 * B * d.nt * 8);                           // log-likelihoods
+    add((size_t)n_h2 * B * d.nt * 8);                           // sigma2_g
   }
   return s + 4096;
 }
@@ -479,6 +485,7 @@ struct ChunkReq {
   const FoldTab* ft = nullptr;   // the systems' splits when they are not all sp (fold-fused evaluation;
                                  // sp is then fold 0)
   ChunkMode mode = ChunkMode::Full;
+  const double* d_h2 = nullptr;  // [B] per-system h2 on the device (tblup_loglik_batch); null: h2
 };
 
 struct ChunkRes {
@@ -547,11 +554,11 @@ int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
   // the scalars formed after k_sys_tiles_st / k_sys_tiles_folds, in their K_JJ epilogue launch (one
   // launch less; neither reads a scalar), else by k_indiv_stats first
   const bool fuse_stats = !redo && use_st && sd.form == FORM_PRIMAL && (fold_share || sys_tiles_grid(cl) > 0);
-  const StatsFuse sf{csA, d.n, d.nT, rq.branch, rq.h2, (int32_t*)c->status.p + ST_INDEX, scal, u, rhs};
+  const StatsFuse sf{csA, d.n, d.nT, rq.branch, rq.h2, rq.d_h2, (int32_t*)c->status.p + ST_INDEX, scal, u, rhs};
   int rc = 0;
   if (!redo && !fuse_stats)
     rc = timed(c, s, KC_STATS, 2.0 * (double)h_off[B], stats_bytes, [&] {
-      return launch_indiv_stats(d_idx, d_off, B, ft, csA, d, sd, rq.branch, rq.h2, scal, u, rhs,
+      return launch_indiv_stats(d_idx, d_off, B, ft, csA, d, sd, rq.branch, rq.h2, rq.d_h2, scal, u, rhs,
                                 (int32_t*)c->status.p + ST_INDEX, s);
     });
   if (rc) return rc;
@@ -984,12 +991,12 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
 // pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
 int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
                                 double h2, int branch, double* fitness, double* ebv, const FitOut* fo,
-                                const RelOut* ro) {
+                                const RelOut* ro, const LogLikOut* lo) {
   g_err.clear();
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
   if (batch == 0) return 0;
-  if (!idx || !fitness) return fail(TBLUP_ERR_ARG, "null idx/fitness");
+  if (!idx || (!fitness && !lo)) return fail(TBLUP_ERR_ARG, "null idx/fitness");
   Split* sp = find_split(c, split_id);
   if (!sp) return fail(TBLUP_ERR_ARG, "unknown split id");
   if (int rc = check_indices(c, idx, offsets[batch])) return rc;
@@ -998,11 +1005,12 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
   const EvalDims d = dims_of(c, *sp);
   const bool want_ebv = ebv != nullptr;
   const int64_t n_rel = ro ? ro->n_pred : 0;
+  const int64_t n_h2 = lo ? lo->n_h2 : 0;
   const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
   const bool rel_lds = reliab_in_lds(c, sd);
   ChunkReq rq{sp, d, sd, c->stream, h2, branch};
   const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
-    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel);
+    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2);
   };
   const int rc = for_each_chunk(c, offsets, batch, 65535, bytes, [&](const Chunk& ck) -> int {
     const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
@@ -1021,6 +1029,45 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
     if (n_rel) HIPCHK(hipMemcpyAsync(d_an, ro->animals, (size_t)n_rel * 4, hipMemcpyHostToDevice, c->stream));
     rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
     rq.d_fit = d_fit; rq.d_ebv = d_ebv;
+    if (lo) {
+      // tblup_loglik_batch: the chunk's h2 columns up front, the n_h2 passes back to back (each the
+      // pipeline at its row of per-system h2, then k_loglik on the factor it leaves -- like the effects,
+      // without waiting for the solve), the results of every pass copied out behind the last
+      const size_t row = (size_t)B * 8, rowt = row * d.nt;
+      double* d_h2 = cv.take<double>((size_t)n_h2 * B);
+      double* d_fits = cv.take<double>((size_t)n_h2 * B);
+      double* d_ll = cv.take<double>((size_t)n_h2 * B * d.nt);
+      double* d_s2 = cv.take<double>((size_t)n_h2 * B * d.nt);
+      if (int rc = ws_check(c, cv)) return rc;
+      HIPCHK(hipMemcpy2DAsync(d_h2, row, lo->h2 + b0, (size_t)batch * 8, row, (size_t)n_h2, hipMemcpyHostToDevice,
+                              c->stream));
+      return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+        // redo: a chained solve of some pass gave up a wait -- the factors of all but the last pass are
+        // gone, so every pass runs again whole with the one-workgroup k_solve (the same bits), for the
+        // fitnesses only
+        for (int64_t g = 0; g < n_h2; ++g) {
+          Carve cvp = cv;
+          rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
+          rq.d_h2 = d_h2 + g * B;
+          rq.d_fit = d_fits + g * B;
+          ChunkRes res;
+          if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+          seqs.push_back(res.chain_seq);
+          if (!redo) HIPCHK(launch_loglik(res.cl, d_ll + g * B * d.nt, d_s2 + g * B * d.nt, c->stream));
+        }
+        if (fitness)
+          HIPCHK(hipMemcpy2DAsync(fitness + b0, (size_t)batch * 8, d_fits, row, row, (size_t)n_h2,
+                                  hipMemcpyDeviceToHost, c->stream));
+        if (!redo) {
+          HIPCHK(hipMemcpy2DAsync(lo->loglik + b0 * d.nt, (size_t)batch * d.nt * 8, d_ll, rowt, rowt, (size_t)n_h2,
+                                  hipMemcpyDeviceToHost, c->stream));
+          if (lo->sigma2)
+            HIPCHK(hipMemcpy2DAsync(lo->sigma2 + b0 * d.nt, (size_t)batch * d.nt * 8, d_s2, rowt, rowt, (size_t)n_h2,
+                                    hipMemcpyDeviceToHost, c->stream));
+        }
+        return 0;
+      });
+    }
     return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
       // redo: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
       Carve cvp = cv;

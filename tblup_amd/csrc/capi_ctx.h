@@ -196,8 +196,19 @@ struct RelOut {
   int64_t n_pred;
   double* reliability;
 };
+// tblup_loglik_batch: per-model h2 [n_h2][batch] (already checked), one pass of the pipeline per row,
+// and its host outputs loglik / sigma2 [n_h2][batch][nt] (sigma2 may be null); the entry's fitness is
+// then [n_h2][batch]
+struct LogLikOut {
+  const double* h2;
+  int64_t n_h2;
+  double* loglik;
+  double* sigma2;
+};
 // tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual;
-// ro != null: also the reliabilities of ro's animals under every individual's model
+// ro != null: also the reliabilities of ro's animals under every individual's model; lo != null: lo's
+// passes instead of the one at h2 (no ebv / fo / ro then)
 int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
-                    int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr);
+                    int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr,
+                    const LogLikOut* lo = nullptr);
 }  // namespace tblup_capi

@@ -1,5 +1,6 @@
 // C ABI of libtblup_gpu.so, taking the fitted model out (include/tblup_gpu.h): tblup_fit_batch
-// (the evaluation's chunks plus one k_effects launch each) and tblup_predict_batch (k_predict).
+// (the evaluation's chunks plus one k_effects launch each), tblup_predict_batch (k_predict) and
+// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -51,6 +52,22 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
   const FitOut fo{intercept, center, effects};
   const RelOut ro{a32.data(), n_pred, reliability};
   return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, any ? &fo : nullptr, &ro);
+}
+
+int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                       const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
+                       double* sigma2_g) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
+  if (batch == 0 || n_h2 == 0) return 0;
+  if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
+  // lambda = 0 makes the snp branch's V singular: (0, 1) here, not tblup_eval_batch's (0, 1]
+  for (int64_t i = 0; i < n_h2 * batch; ++i)
+    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  const LogLikOut lo{h2, n_h2, loglik, sigma2_g};
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2[0], branch, fitness, nullptr, nullptr, nullptr, &lo);
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,

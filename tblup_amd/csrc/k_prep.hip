@@ -158,19 +158,19 @@ hipError_t launch_fold_offsets(const int64_t* off, int64_t B, int64_t F, int64_t
 __global__ __launch_bounds__(STATS_THREADS) void k_indiv_stats(const int64_t* __restrict__ idx, const int64_t* __restrict__ off,
                                                                FoldTab ft, const int32_t* __restrict__ csA, int64_t n, int64_t nT, int64_t nTp, int64_t P, int form,
                                                                int64_t ns, int pad_first, int nt, int branch, double h2,
-                                                               double* __restrict__ scal, double* __restrict__ u,
+                                                               const double* __restrict__ h2v, double* __restrict__ scal, double* __restrict__ u,
                                                                double* __restrict__ rhs, int32_t* __restrict__ err) {
   __shared__ StatsShared sh;
-  stats_wg(idx, off, ft, csA, n, nT, nTp, P, form, ns, pad_first, nt, branch, h2, blockIdx.x, scal, err, sh);
+  stats_wg(idx, off, ft, csA, n, nT, nTp, P, form, ns, pad_first, nt, branch, h2, h2v, blockIdx.x, scal, err, sh);
   if (form == FORM_PRIMAL) stats_rows(idx, off, ft, P, ns, pad_first, nt, blockIdx.x, u, rhs, sh, 0, ns);
 }
 
 hipError_t launch_indiv_stats(const int64_t* idx, const int64_t* off, int64_t B, const FoldTab& ft,
                               const int32_t* colsum_all, const EvalDims& d, const SysDims& sd,
-                              int branch, double h2, double* scal, double* u, double* rhs, int32_t* err,
-                              hipStream_t s) {
+                              int branch, double h2, const double* h2v, double* scal, double* u, double* rhs,
+                              int32_t* err, hipStream_t s) {
   hipLaunchKernelGGL(k_indiv_stats, dim3((unsigned)B), dim3(STATS_THREADS), 0, s, idx, off, ft, colsum_all, d.n,
-                     d.nT, d.nTp, d.P, sd.form, sd.ns, sd.pad_first, d.nt, branch, h2, scal, u, rhs, err);
+                     d.nT, d.nTp, d.P, sd.form, sd.ns, sd.pad_first, d.nt, branch, h2, h2v, scal, u, rhs, err);
   return hipGetLastError();
 }
 

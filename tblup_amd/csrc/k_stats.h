@@ -19,12 +19,13 @@ struct StatsShared {
 };
 
 // Individual (system) b: branch, 1/N, q/N^2, 1/d, mu flag, lambda ... into sh.sc (every thread reads
-// them after the call) and, scal != null, into scal[b].  An index outside [-P, P) sets *err (vector
+// them after the call) and, scal != null, into scal[b].  h2v != null: system b's own h2, h2v[b].  An index outside [-P, P) sets *err (vector
 // store; every writer stores 1) and SC_BAD.
 __device__ __forceinline__ void stats_wg(const int64_t* __restrict__ idx, const int64_t* __restrict__ off,
                                          const FoldTab& ft, const int32_t* __restrict__ csA, int64_t n, int64_t nT,
                                          int64_t nTp, int64_t P, int form, int64_t ns, int pad_first, int nt,
-                                         int branch, double h2, int64_t b, double* __restrict__ scal,
+                                         int branch, double h2, const double* __restrict__ h2v, int64_t b,
+                                         double* __restrict__ scal,
                                          int32_t* __restrict__ err, StatsShared& sh) {
   const int t = threadIdx.x;
   const int64_t o0 = off[b], k = off[b + 1] - o0;
@@ -69,7 +70,8 @@ __device__ __forceinline__ void stats_wg(const int64_t* __restrict__ idx, const 
     sc[SC_CN] = primal ? 0.0 : Q / (N * N);
     sc[SC_INVD] = 1.0 / d;
     sc[SC_MUF] = (mode == 2) ? 1.0 : 0.0;
-    sc[SC_LAM] = (1.0 - h2) / h2;
+    const double h = h2v ? h2v[b] : h2;   // per-system h2 (tblup_loglik_batch), else the call's
+    sc[SC_LAM] = (1.0 - h) / h;
     sc[SC_D] = d;
     sc[SC_MODE] = (double)mode;
     sc[SC_K] = (double)k;

@@ -585,7 +585,7 @@ __global__ __launch_bounds__(64 * STW) void k_stats_diag_counts(CholArgs a, Stat
     u_sh[t] = (r < a.ns && sys_real(r, pad, k)) ? (double)csT[snp_col(a.idx[o0 + r - pad], a.P)] : 0.0;
   }
   // (stats_wg's barriers also publish u_sh)
-  stats_wg(a.idx, a.off, a.ft, x.csA, x.n, x.nT, a.ytp, a.P, a.form, a.ns, a.padfirst, a.nt, x.branch, x.h2, b,
+  stats_wg(a.idx, a.off, a.ft, x.csA, x.n, x.nT, a.ytp, a.P, a.form, a.ns, a.padfirst, a.nt, x.branch, x.h2, x.h2v, b,
            J == 0 ? x.scal : nullptr, x.err, sh);
   if (tile) sys_diag_epilogue_src(a, cnt, b, J, qr, qc, l, sh.sc, u_sh);
   // then the u / rhs rows, split between the individual's two workgroups (their stores overlap the

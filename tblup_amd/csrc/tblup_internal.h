@@ -170,11 +170,11 @@ hipError_t launch_build_split(const int8_t* geno_sm, int64_t n, int64_t P, const
 // fused offsets of F copies of a B-individual index list (sum_k indices each): out[F * B + 1]
 hipError_t launch_fold_offsets(const int64_t* off, int64_t B, int64_t F, int64_t sum_k, int64_t* out, hipStream_t s);
 // primal form (sd.form): also u[b][a] = s_a and rhs[b][t][a] = xty[t][p_a] / d over the ns rows
-// (colsum_T / xty of system b: ft's fold of b)
+// (colsum_T / xty of system b: ft's fold of b); h2v != null: [B] on the device, system b's own h2
 hipError_t launch_indiv_stats(const int64_t* idx, const int64_t* off, int64_t B, const FoldTab& ft,
                               const int32_t* colsum_all, const EvalDims& d, const SysDims& sd,
-                              int branch, double h2, double* scal, double* u, double* rhs, int32_t* err,
-                              hipStream_t s);
+                              int branch, double h2, const double* h2v, double* scal, double* u, double* rhs,
+                              int32_t* err, hipStream_t s);
 // kernel form: each system's 2-bit packed animal rows (dual_pk_row bytes each) from its split's rows
 // (ft: fold of system b)
 hipError_t launch_gather(const FoldTab& ft, const int64_t* idx, const int64_t* off, int64_t panel_stride, int64_t B,
@@ -194,6 +194,7 @@ struct StatsFuse {
   int64_t n, nT;
   int branch;
   double h2;
+  const double* h2v;     // [B] per-system h2 on the device, null: h2
   int32_t* err;          // the context's index-error status word
   double* scal;          // [B][SCAL]
   double* u;             // [B][ns]
@@ -370,6 +371,13 @@ bool reliab_lds(const SysDims& sd);
 int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int64_t aim);
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
                          int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s);
+
+// ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
+// loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,
+// z and the scalars that the chunk's pipeline left in c (SNP form: also the split's yT / ymu); one
+// workgroup per model, fixed-order sums, so a model's bits do not depend on the chunk around it.
+// NaN for d = 0, a flagged index or a quadratic form that is not positive and finite.
+hipError_t launch_loglik(const CholLaunch& c, double* loglik, double* sigma2, hipStream_t s);
 
 // ---- launcher (k_model.hip): EBVs of any animals of the panel from fitted models ----
 // ebv[(m * nt + t) * n_pred + v] = intercept[m * nt + t] + sum_j (x[animals[v], idx_j] - center_j)

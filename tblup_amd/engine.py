@@ -216,6 +216,99 @@ class GpuBlupEngine:
                 None, None, None, _ptr(rel)))
         return rel
 
+    # ------------------------------------------------- variance ratio by (RE)ML
+    def log_likelihood(self, genomes, train, valid, h2, branch="auto", return_sigma2=False):
+        """Profile (restricted) log-likelihood of h2 for the model each selected-index set fits on
+        (train, valid) (tblup_loglik_batch; include/tblup_gpu.h has the definition: the gblup branch's
+        likelihood with no mean fitted, the snp branch's restricted likelihood with its intercept).
+        h2: a scalar, a (G,) grid shared by all models, or a (G, B) matrix of per-model values, each in
+        (0, 1).  Returns (G, B) -- (B,) for a scalar -- with the trait axis appended for several traits,
+        as evaluate(return_ebv=True) shapes its output; return_sigma2=True: (loglik, sigma2_g), the
+        profiled genetic variance in the same shape (sigma2_e = (1 - h2) / h2 * sigma2_g).  A degenerate
+        panel gives NaN, not an error; a model's value does not depend on the batch it comes in."""
+        ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False)
+        return (ll, s2) if return_sigma2 else ll
+
+    def _loglik(self, genomes, train, valid, h2, branch, want_fitness):
+        self._settle()
+        idx, offsets = concat_genomes(genomes)
+        B, nt = len(genomes), self.n_traits
+        h = np.asarray(h2, dtype=np.float64)
+        scalar = h.ndim == 0
+        if h.ndim == 0:
+            h = h.reshape(1, 1)
+        if h.ndim == 1:
+            h = h[:, None]
+        if h.ndim != 2 or h.shape[1] not in (1, B):
+            raise ValueError("h2 must be a scalar, a (G,) grid or a (G, %d) matrix" % B)
+        G = h.shape[0]
+        hm = np.ascontiguousarray(np.broadcast_to(h, (G, B)))
+        ll = np.empty((G, B, nt), dtype=np.float64)
+        s2 = np.empty((G, B, nt), dtype=np.float64)
+        fit = np.empty((G, B), dtype=np.float64) if want_fitness else None
+        if B and G:
+            sid = self.split_id(train, valid)
+            _native.check("tblup_loglik_batch", self._lib.tblup_loglik_batch(
+                self._ctx, sid, _ptr(idx), _ptr(offsets), B, _ptr(hm), G, _native.BRANCH[branch],
+                _ptr(fit) if want_fitness else None, _ptr(ll), _ptr(s2)))
+        if nt == 1:
+            ll, s2 = ll[:, :, 0], s2[:, :, 0]
+        if scalar:
+            ll, s2, fit = ll[0], s2[0], (fit[0] if want_fitness else None)
+        return ll, s2, fit
+
+    def estimate_h2(self, genomes, train, valid, branch="auto", grid=np.linspace(0.02, 0.98, 25), refine=3,
+                    points=9):
+        """h2 of each model by maximising log_likelihood(): one pass over `grid` (ascending, shared by
+        all models), then `refine` rounds in which every model gets its own `points` evenly spaced
+        values between the neighbours of its current argmax, endpoints included (at an end of the
+        current values the bracket is that end and its one neighbour; ties take the first argmax);
+        each round is one call with a (points, B) matrix.  With several traits the grid pass is shared
+        and the refinement runs once per trait.
+        Returns a dict of arrays shaped (B,) -- (B, n_traits) for several traits: `h2`, `loglik` and
+        `sigma2_g` at the best point, `sigma2_e` = (1 - h2) / h2 * sigma2_g, `at_bound` (the best point
+        is an end of `grid`: the maximum lies outside it or at its edge) and `step`, the spacing of the
+        last round's values.  A model whose likelihood is NaN everywhere stays NaN.
+        The profile is not guaranteed to be unimodal: the answer is the best point seen, a local
+        maximum when the grid is too coarse to separate two."""
+        grid = np.asarray(grid, dtype=np.float64)
+        if grid.ndim != 1 or len(grid) < 2 or not np.all(np.diff(grid) > 0):
+            raise ValueError("grid must be 1-D, ascending, with at least two values")
+        if points < 3:
+            raise ValueError("points must be at least 3")
+        B, nt = len(genomes), self.n_traits
+        ll0, s20, _ = self._loglik(genomes, train, valid, grid, branch, False)
+        ll0, s20 = ll0.reshape(len(grid), B, nt), s20.reshape(len(grid), B, nt)
+        out = {k: np.full((B, nt), np.nan) for k in ("h2", "loglik", "sigma2_g", "sigma2_e", "step")}
+        out["at_bound"] = np.zeros((B, nt), dtype=bool)
+        cols = np.arange(B)
+        for t in range(nt):
+            h = np.repeat(grid[:, None], B, axis=1)
+            ll, s2 = ll0[:, :, t], s20[:, :, t]
+            best = None
+            for rnd in range(refine + 1):
+                i = np.argmax(np.where(np.isnan(ll), -np.inf, ll), axis=0)   # first maximum
+                cur = (h[i, cols], ll[i, cols], s2[i, cols])
+                if best is None:
+                    best = cur
+                else:
+                    up = cur[1] > best[1]
+                    best = tuple(np.where(up, c, b) for c, b in zip(cur, best))
+                step = h[1] - h[0]
+                if rnd == refine or B == 0:
+                    break
+                lo, hi = h[np.maximum(i - 1, 0), cols], h[np.minimum(i + 1, len(h) - 1), cols]
+                h = np.linspace(lo, hi, points)      # (points, B), both ends exact
+                ll, s2, _ = self._loglik(genomes, train, valid, h, branch, False)
+                ll, s2 = ll.reshape(points, B, nt)[:, :, t], s2.reshape(points, B, nt)[:, :, t]
+            dead = np.isnan(best[1])
+            hb = np.where(dead, np.nan, best[0])
+            out["h2"][:, t], out["loglik"][:, t], out["sigma2_g"][:, t] = hb, best[1], np.where(dead, np.nan, best[2])
+            out["sigma2_e"][:, t] = (1.0 - hb) / hb * out["sigma2_g"][:, t]
+            out["step"][:, t] = np.where(dead, np.nan, step)
+            out["at_bound"][:, t] = ~dead & ((hb == grid[0]) | (hb == grid[-1]))
+        return {k: v[:, 0] for k, v in out.items()} if nt == 1 else out
+
     def predict(self, models, animals):
         """EBVs of `animals` (row ids of this engine's panel: any order, repeats allowed, no split
         needed) under each PanelModel (tblup_predict_batch): (len(models), n_traits, len(animals)),

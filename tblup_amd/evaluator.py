@@ -419,6 +419,20 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
+    def log_likelihood(self, population, h2, final=True, train=None, valid=None, **kw):
+        """Profile (restricted) log-likelihood of every individual's model at `h2` (a scalar, a (G,)
+        grid or a (G, B) matrix): GpuBlupEngine.log_likelihood with fit_models' split and genome
+        conventions.  No RNG, no collective: under torch.distributed every rank computes what it is given."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.log_likelihood(genomes, train, valid, h2, **kw)
+
+    def estimate_h2(self, population, final=True, train=None, valid=None, **kw):
+        """The h2 that maximises each individual's profile (restricted) likelihood on the panel it
+        selected: GpuBlupEngine.estimate_h2 (its keywords pass through) with fit_models' split and genome
+        conventions.  The evaluator's own h2 is not consulted.  No RNG, no collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.estimate_h2(genomes, train, valid, **kw)
+
     def predict(self, models, animals):
         """EBVs of `animals` (row ids of the evaluator's data, any order, in or out of any split)
         under each model: GpuBlupEngine.predict.  No RNG, no collective."""

@@ -12,10 +12,13 @@ numbers go to PERFLOG.md.  One JSON line per part:
            (tblup_reliability_batch) against fit and evaluate from the same process, alternated; the
            derived fp64 MFMA floor of k_reliab (batch x n_pred x ns^2 flop over the measured 72.7 TF/s
            peak); and one kernel-form shape (the `dual` stand-in, all 1200 animals)
-  --stats CSV   the k_effects / k_predict / k_reliab share of a `rocprofv3 --kernel-trace --stats` run of
+  loglik   config 2 again: tblup_loglik_batch at 1 and at 8 grid points (per grid point: the 8-point call
+           over 8) beside tblup_eval_batch from the same process, alternated; one estimate_h2 with the
+           defaults (25 + 3 x 9 passes); k_loglik per launch comes from a --stats run of this part
+  --stats CSV   the k_effects / k_predict / k_reliab / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -145,13 +148,64 @@ def reliability_all(eng, genomes, T, V, n, ns, reps):
                     "the kernel alone: --stats; the floor is derived (flop / measured fp64 MFMA peak)"}
 
 
+def loglik_vs_eval(eng, genomes, T, V, reps, grid_n=8):
+    """tblup_eval_batch against tblup_loglik_batch at 1 and grid_n grid points (the C entries, alternated),
+    then one estimate_h2 with the defaults."""
+    from tblup_amd.engine import concat_genomes
+    from tblup_amd import _native
+    _ptr = _native.ptr
+    sid = eng.split_id(T, V)
+    idx, off = concat_genomes(genomes)
+    B, nt = len(genomes), eng.n_traits
+    fit = np.empty(B)
+    h1 = np.full((1, B), 0.4)
+    hg = np.ascontiguousarray(np.repeat(np.linspace(0.1, 0.8, grid_n)[:, None], B, axis=1))
+    fl, ll, s2 = np.empty((grid_n, B)), np.empty((grid_n, B, nt)), np.empty((grid_n, B, nt))
+
+    def loglik(h):
+        _native.check("tblup_loglik_batch", eng._lib.tblup_loglik_batch(
+            eng._ctx, sid, _ptr(idx), _ptr(off), B, _ptr(h), len(h), 0, _ptr(fl), _ptr(ll), _ptr(s2)))
+
+    te, t1s, tgs = [], [], []
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        _native.check("tblup_eval_batch", eng._lib.tblup_eval_batch(eng._ctx, sid, _ptr(idx), _ptr(off), B, 0.4, 0,
+                                                                    _ptr(fit), None))
+        t1 = time.perf_counter()
+        loglik(h1)
+        t2 = time.perf_counter()
+        same = bool(np.array_equal(fl[0], fit, equal_nan=True))
+        t2b = time.perf_counter()
+        loglik(hg)
+        t3 = time.perf_counter()
+        if r >= 2:
+            te.append(t1 - t0)
+            t1s.append(t2 - t1)
+            tgs.append(t3 - t2b)
+    t0 = time.perf_counter()
+    est = eng.estimate_h2(genomes, T, V)
+    t_est = time.perf_counter() - t0
+    return {"eval_batch_ms": med_ms(te), "loglik_1_ms": med_ms(t1s), "loglik_%d_ms" % grid_n: med_ms(tgs),
+            "per_grid_point_ms": round(med_ms(tgs) / grid_n, 4),
+            "extra_per_point_ms": round(med_ms(tgs) / grid_n - med_ms(te), 4),
+            "extra_single_ms": round(med_ms(t1s) - med_ms(te), 4),
+            "eval_batch_ms_all": [round(x * 1e3, 3) for x in te], "loglik_1_ms_all": [round(x * 1e3, 3) for x in t1s],
+            "loglik_%d_ms_all" % grid_n: [round(x * 1e3, 3) for x in tgs], "fitness_bit_equal": same,
+            "finite": bool(np.all(np.isfinite(ll))),
+            "estimate_h2_ms": round(t_est * 1e3, 2), "estimate_h2_passes": 25 + 3 * 9,
+            "estimate_h2_ms_per_pass": round(t_est * 1e3 / (25 + 3 * 9), 3),
+            "h2_median": float(np.nanmedian(est["h2"])), "at_bound": int(np.sum(est["at_bound"])),
+            "note": "every call ends in the stream's synchronisation; the grid call uploads the index lists once "
+                    "and copies the results out after the last pass; k_loglik alone: --stats"}
+
+
 def stats_share(path):
     rows = list(csv.DictReader(open(path)))
     tot = sum(float(r["TotalDurationNs"]) for r in rows)
     out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
     for r in rows:
         name = r["Name"]
-        for key in ("k_effects", "k_predict", "k_reliab", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_effects", "k_predict", "k_reliab", "k_loglik", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -198,6 +252,13 @@ def main():
             st = reliability_all(eng, genomes, T, V, n, 768, args.reps)
             print(json.dumps({"part": "reliability", "config": "config4-shaped stand-in: %d x %d, k=%d (gblup), n_T=%d"
                               % (n, P, k, nT), "models": pop, "k": k, "animals": n, "form": "kernel", "ns": 768, **st}))
+    if "loglik" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            st = loglik_vs_eval(eng, genomes, T, V, args.reps)
+            print(json.dumps({"part": "loglik", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **st}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
