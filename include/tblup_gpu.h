@@ -217,6 +217,48 @@ int tblup_loglik_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const i
                        double* sigma2_g);
 
 /*
+ * Mixed-model score statistics of `n_cand` SNPs of the context's panel against each of `batch` fitted
+ * panels (the score test of EMMAX / GRAMMAR-gamma): the evaluation's pipeline plus one forward
+ * substitution per listed SNP against the factor it leaves behind.  The model is the reference's own, as
+ * tblup_reliability_batch and tblup_loglik_batch document it.  For model b: A the gathered columns
+ * idx[0..k) (duplicates kept), c the branch's centre (all n animals for gblup, the train rows for snp),
+ * d = 2 sum p(1-p), lambda = (1-h2)/h2, W_T = A_T - c, K = W W^T / d, V = K_TT + lambda I,
+ * r_t = y_T,t - mu_t (mu = 0 for gblup, mean(y_T) for snp), N = n_T.  For a listed column j of the panel,
+ * whether or not it is in the model: w_j = x_T,j - c_j with the same centring rule (c_j the exact allele
+ * count of column j over the branch's reference rows, divided once by their number), and
+ *   score[b][t][j] = u = w_j^T V^{-1} r_t
+ *   info[b][j]     = v = w_j^T V^{-1} w_j      (trait-independent: one factor, shared h2)
+ *   q[b][t]        = r_t^T V^{-1} r_t          (what tblup_loglik_batch profiles sigma2_g from)
+ * Under snp w_j is orthogonal to 1 and V 1 = lambda 1, so these are also the REML (P-matrix) forms with
+ * the intercept fitted; under gblup no mean is fitted, as in the reference.  u / d is the SNP's
+ * back-solved BLUP effect to first order: for a SNP of the model it is tblup_fit_batch's effect.
+ * From the factor M = L L^T of the form the batch's systems take, z = L^{-1} rhs:
+ *   kernel form (M = V):  s_j = L^{-1} w_j;  u = s_j.z_t,  v = s_j.s_j,  q = |z_t|^2
+ *   SNP form (M = W_T^T W_T / d + lambda I_k, rhs = W_T^T r / d):  g_j = W_T^T w_j (exact integer counts
+ *     (A_T^T x_j)_i minus sT_i sT_j / n_T), s_j = L^{-1} g_j;  u = (w_j.r_t - s_j.z_t) / lambda,
+ *     v = (w_j.w_j - s_j.s_j / d) / lambda,  q = (r^T r - d |z|^2) / lambda
+ *   snps    : n_cand column indices with idx's rules -- negatives wrap, anything outside
+ *             [-n_snps, n_snps) is TBLUP_ERR_INDEX; any order, repeats allowed
+ *   h2      : in (0, 1): lambda = 0 makes the snp branch's V singular (TBLUP_ERR_ARG, as tblup_loglik_batch)
+ *   fitness : optional out (may be NULL), bit-identical to tblup_eval_batch's
+ *   score   : out, batch x n_traits x n_cand
+ *   info    : out, batch x n_cand
+ *   q       : optional out (may be NULL), batch x n_traits
+ * n_cand == 0 or batch == 0 returns 0 and writes nothing; a context without a panel gives
+ * TBLUP_ERR_STATE; idx / offsets / branch, the index rules, the chunking and the chained solve's recovery
+ * are tblup_eval_batch's.  d = 0 (a monomorphic model panel) gives NaN for every output of that model,
+ * not an error; a listed column that is constant over the reference rows has w_j = 0 and gives
+ * u = v = 0 exactly.
+ * A (model, SNP) value depends neither on n_cand, nor on the SNP's position in `snps`, nor on the other
+ * models of the batch (beyond the form they choose together), nor on the chunking (TBLUP_WORKSPACE_MB):
+ * independent workgroups, fixed-order sums, no atomics; the same call gives the same bits twice.
+ * Host pointers, synchronous.
+ */
+int tblup_snp_score_batch(tblup_ctx* ctx, int split_id, const int64_t* snps, int64_t n_cand, const int64_t* idx,
+                          const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                          double* score, double* info, double* q);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

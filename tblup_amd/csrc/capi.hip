@@ -346,8 +346,15 @@ int64_t rel_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_re
   return reliab_slabs(sd, B, n_rel, reliab_in_lds(c, sd), std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(c->budget / 4)));
 }
 
+// the same for k_snpscore (TBLUP_SCORE_LDS) and the SNP list of tblup_snp_score_batch
+bool score_in_lds(const tblup_ctx* c, const SysDims& sd) { return c->score_lds && reliab_lds(sd); }
+int64_t score_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_cand) {
+  return reliab_slabs(sd, B, n_cand, score_in_lds(c, sd), std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(c->budget / 4)));
+}
+
 size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv, bool with_model = false, int64_t n_rel = 0, int64_t n_h2 = 0) {
+                   bool with_ebv, bool with_model = false, int64_t n_rel = 0, int64_t n_h2 = 0,
+                   int64_t n_cand = 0) {
   size_t s = 0;
   auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
   add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
@@ -380,6 +387,14 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
     add((size_t)B * n_rel * 8);                                 // the reliabilities
     add(reliab_in_lds(c, sd) ? 0                                // right-hand sides / V of one launch's slabs
                              : (size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W * 8);
+  }
+  if (n_cand > 0) {                                             // tblup_snp_score_batch:
+    add((size_t)n_cand * 4);                                    // the SNP list
+    add((size_t)B * d.nt * n_cand * 8);                         // scores
+    add((size_t)B * n_cand * 8);                                // information
+    add((size_t)B * d.nt * 8);                                  // q
+    add(score_in_lds(c, sd) ? 0                                 // right-hand sides / V of one launch's slabs
+                            : (size_t)B * score_slabs(c, sd, B, n_cand) * sd.ns * SCORE_W * 8);
   }
   if (n_h2 > 0) {                                               // tblup_loglik_batch, every pass of the chunk:
     add((size_t)n_h2 * B * 8);                                  // the h2 rows
@@ -826,6 +841,7 @@ int tblup_ctx_create(const int8_t* geno, int64_t n, int64_t P, int layout, const
   if (const char* e = getenv("TBLUP_DIAG_E")) c->diag_e = std::max(-1, std::min(2, atoi(e)));
   if (const char* e = getenv("TBLUP_PAD_FIRST")) c->pad_first = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_RELIAB_LDS")) c->reliab_lds = atoi(e) != 0;
+  if (const char* e = getenv("TBLUP_SCORE_LDS")) c->score_lds = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_NRS")) c->nrs = (atoi(e) == 1 || atoi(e) == 2 || atoi(e) == 4) ? atoi(e) : 0;
   if (const char* e = getenv("TBLUP_CHAIN_DEBUG")) {
     int sp = 0, dl = 0, sh = 0;
@@ -991,7 +1007,7 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
 // pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
 int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
                                 double h2, int branch, double* fitness, double* ebv, const FitOut* fo,
-                                const RelOut* ro, const LogLikOut* lo) {
+                                const RelOut* ro, const LogLikOut* lo, const ScoreOut* so) {
   g_err.clear();
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
@@ -1008,9 +1024,11 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
   const int64_t n_h2 = lo ? lo->n_h2 : 0;
   const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
   const bool rel_lds = reliab_in_lds(c, sd);
+  const int64_t n_cand = so ? so->n_cand : 0;
+  const bool sco_lds = score_in_lds(c, sd);
   ChunkReq rq{sp, d, sd, c->stream, h2, branch};
   const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
-    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2);
+    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2, n_cand);
   };
   const int rc = for_each_chunk(c, offsets, batch, 65535, bytes, [&](const Chunk& ck) -> int {
     const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
@@ -1027,6 +1045,14 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
                          ? cv.take<double>((size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W)
                          : nullptr;
     if (n_rel) HIPCHK(hipMemcpyAsync(d_an, ro->animals, (size_t)n_rel * 4, hipMemcpyHostToDevice, c->stream));
+    int32_t* d_cand = n_cand ? cv.take<int32_t>((size_t)n_cand) : nullptr;
+    double* d_sco = n_cand ? cv.take<double>((size_t)B * d.nt * n_cand) : nullptr;
+    double* d_inf = n_cand ? cv.take<double>((size_t)B * n_cand) : nullptr;
+    double* d_q = n_cand ? cv.take<double>((size_t)B * d.nt) : nullptr;
+    double* d_sscr = (n_cand && !sco_lds)
+                         ? cv.take<double>((size_t)B * score_slabs(c, sd, B, n_cand) * sd.ns * SCORE_W)
+                         : nullptr;
+    if (n_cand) HIPCHK(hipMemcpyAsync(d_cand, so->snps, (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
     rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
     rq.d_fit = d_fit; rq.d_ebv = d_ebv;
     if (lo) {
@@ -1090,6 +1116,16 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
                              rel_lds, rel_slabs(c, sd, B, n_rel), d_vscr, d_rel, c->stream));
         HIPCHK(hipMemcpyAsync(ro->reliability + b0 * n_rel, d_rel, (size_t)B * n_rel * 8, hipMemcpyDeviceToHost,
                               c->stream));
+      }
+      if (n_cand && !redo) {
+        // like the reliabilities: L, the diagonal inverses, z, u and the scalars only, beside the first pass
+        HIPCHK(launch_snpscore(res.cl, (const int32_t*)c->colsum_all.p, d_cand, n_cand, sco_lds,
+                               score_slabs(c, sd, B, n_cand), d_sscr, d_sco, d_inf, d_q, c->stream));
+        HIPCHK(hipMemcpyAsync(so->score + b0 * d.nt * n_cand, d_sco, (size_t)B * d.nt * n_cand * 8,
+                              hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(so->info + b0 * n_cand, d_inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, c->stream));
+        if (so->q)
+          HIPCHK(hipMemcpyAsync(so->q + b0 * d.nt, d_q, (size_t)B * d.nt * 8, hipMemcpyDeviceToHost, c->stream));
       }
       HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
       if (want_ebv)

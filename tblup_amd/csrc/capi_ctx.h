@@ -127,6 +127,8 @@ struct tblup_ctx {
   // TBLUP_RELIAB_LDS=0: k_reliab keeps its right-hand sides in the workspace at every system size (what
   // it does above 1024 rows anyway; the same bits -- a test knob)
   int reliab_lds = 1;
+  // TBLUP_SCORE_LDS=0: the same for k_snpscore's right-hand sides (tblup_snp_score_batch)
+  int score_lds = 1;
   std::vector<int64_t> fold_hoff;   // host offsets of the last fold-fused chunk (host-side shapes only)
   DevBuf chain;          // its flags [B][chain_flags(NT)], the expiry ring [CHAIN_ERR_RING] and one
                          // scratch word (zeroed when allocated)
@@ -205,10 +207,20 @@ struct LogLikOut {
   double* loglik;
   double* sigma2;
 };
+// Host outputs of tblup_snp_score_batch: score [batch][nt][n_cand], info [batch][n_cand] and (may be null)
+// q [batch][nt] of the listed panel columns (already checked and wrapped to [0, P))
+struct ScoreOut {
+  const int32_t* snps;
+  int64_t n_cand;
+  double* score;
+  double* info;
+  double* q;
+};
 // tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual;
-// ro != null: also the reliabilities of ro's animals under every individual's model; lo != null: lo's
-// passes instead of the one at h2 (no ebv / fo / ro then)
+// ro != null: also the reliabilities of ro's animals under every individual's model; so != null: also the score statistics of so's
+// SNPs under every individual's model; lo != null: lo's passes instead of the one at h2 (no ebv / fo / ro /
+// so then)
 int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
                     int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr,
-                    const LogLikOut* lo = nullptr);
+                    const LogLikOut* lo = nullptr, const ScoreOut* so = nullptr);
 }  // namespace tblup_capi

@@ -1,6 +1,7 @@
 // C ABI of libtblup_gpu.so, taking the fitted model out (include/tblup_gpu.h): tblup_fit_batch
-// (the evaluation's chunks plus one k_effects launch each), tblup_predict_batch (k_predict) and
-// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each).
+// (the evaluation's chunks plus one k_effects launch each), tblup_predict_batch (k_predict),
+// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each) and
+// tblup_snp_score_batch (the chunks plus k_snpscore's launches each).
 #include <algorithm>
 #include <string>
 #include <vector>
@@ -68,6 +69,30 @@ int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int
     if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
   const LogLikOut lo{h2, n_h2, loglik, sigma2_g};
   return eval_batch_host(c, split_id, idx, offsets, batch, h2[0], branch, fitness, nullptr, nullptr, nullptr, &lo);
+}
+
+int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64_t n_cand, const int64_t* idx,
+                          const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness, double* score,
+                          double* info, double* q) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
+  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
+  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  if (batch == 0 || n_cand == 0) return 0;
+  // lambda = 0 makes the snp branch's V singular: (0, 1), as tblup_loglik_batch
+  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
+  std::vector<int32_t> s32((size_t)n_cand);
+  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
+  std::vector<double> fit_local;
+  if (!fitness) {
+    fit_local.resize((size_t)batch);
+    fitness = fit_local.data();
+  }
+  const ScoreOut so{s32.data(), n_cand, score, info, q};
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, nullptr, nullptr, nullptr, &so);
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,

@@ -14,7 +14,7 @@
 //     rows from the chunk's 2-bit packed panel (unpack16), the animals' genotypes gathered into LDS in
 //     the same byte order -- then (G_ta - (u_t + u_a)/N + q/N^2)/d in fp64; u_a and G_aa are exact
 //     integer sums.
-//   phase 2: blocked forward substitution with 16 right-hand sides on fp64 MFMA
+//   phase 2 (fwd_subst.h): blocked forward substitution with 16 right-hand sides on fp64 MFMA
 //     (v_mfma_f64_16x16x4_f64), block row by block row: V_J = X_J (R_J - sum_{L<J} L_JL V_L); wave q
 //     owns rows 16q .. 16q+15 of the block row, one accumulator chain over L = J0 .. J-1 and the rows
 //     of each tile in order (L read once per slab, from L2: a model's slabs run on one XCD), then
@@ -27,17 +27,18 @@
 // workspace slice of the workgroup's own -- the same arithmetic in the same order.
 #include <algorithm>
 
+#include "fwd_subst.h"
 #include "i8_tile.h"
 
 namespace tblup {
 
 namespace {
 
-constexpr int RTH = 512;          // 8 waves
+constexpr int RTH = FWD_TH;       // 8 waves
 constexpr int RKC = 1024;         // kernel form: SNPs per LDS stage of the animals' genotypes
 constexpr int RKS = RKC + 16;     // its row stride (bytes): 16 animals' 16-B reads on distinct banks
 constexpr int RPARTS = RTH / RELIAB_W;
-constexpr int RSTEP = 64;         // rows of L per step of the substitution's chain (16 MFMAs)
+static_assert(RELIAB_W == FWD_W, "k_reliab's slab is the substitution's 16 right-hand sides");
 
 template <int FORM, bool VLDS>
 __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __restrict__ geno,
@@ -165,89 +166,7 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
   const double* Lb = c.L + b * l_stride(NT);
   const double* Db = c.Dinv + b * (int64_t)NT * NPACK * BLKD;
   double nacc = 0.0;
-  // The tiles (J, Lc), Lc = 0 .. J-1, lie back to back and each holds L_JL^T (element [cc][r] =
-  // L_JL[r][cc]), so row kx = 128 Lc + cc of that run holds column kx of block row J: one chain over
-  // kx in order, RSTEP rows per step, through a ring of three register sets -- two steps' L values are
-  // in flight while a step's MFMAs run, and the first two steps of block row J + 1 (which need no V)
-  // are issued before block row J's barriers.  The zero rows of V that lead the system are skipped in
-  // whole steps.
-  constexpr int NA = RSTEP / 4;
-  const double* lrow = Lb + 16 * q + lc;
-  const double* vcol = V + lc;
-  const int ks = (int)(pad / RSTEP) * RSTEP;
-  double a0[NA], a1[NA], a2[NA];
-  auto lda = [&](double (&a)[NA], int k) {
-#pragma unroll
-    for (int e = 0; e < NA; ++e) a[e] = lrow[(int64_t)(k + 4 * e + lg) * TILE];
-  };
-  auto prime = [&](int Jn) {
-    lrow = Lb + (int64_t)Jn * NT * TILE * TILE + 16 * q + lc;
-    if (ks < Jn * TILE) lda(a0, ks);
-    if (ks + RSTEP < Jn * TILE) lda(a1, ks + RSTEP);
-  };
-  prime(J0);
-  for (int J = J0; J < J1; ++J) {
-    v4d acc = {0.0, 0.0, 0.0, 0.0};
-    // X_J's blocks (q, s), s = 0 .. q, of this wave through a ring of four register sets, the first
-    // four in flight under the chain below: stored block (q, s) element [r][cc] = X[16q + cc][16s + r]
-    const double* xq = Db + (int64_t)J * NPACK * BLKD + pk(q, 0);
-    double xr[4][4];
-    auto ldx = [&](double (&x)[4], int s) {
-#pragma unroll
-      for (int k4 = 0; k4 < 4; ++k4) x[k4] = xq[s * BLKD + bo(4 * k4 + lg, lc)];
-    };
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-      if (i <= q) ldx(xr[i], i);
-    {
-      const int ke = J * TILE;
-      auto mm = [&](const double (&a)[NA], int k) {
-#pragma unroll
-        for (int e = 0; e < NA; ++e)
-          acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[e], vcol[(int64_t)(k + 4 * e + lg) * W], acc, 0, 0, 0);
-      };
-      for (int k = ks; k < ke; k += 3 * RSTEP) {
-        if (k + 2 * RSTEP < ke) lda(a2, k + 2 * RSTEP);
-        mm(a0, k);
-        if (k + RSTEP < ke) {
-          if (k + 3 * RSTEP < ke) lda(a0, k + 3 * RSTEP);
-          mm(a1, k + RSTEP);
-        }
-        if (k + 2 * RSTEP < ke) {
-          if (k + 4 * RSTEP < ke) lda(a1, k + 4 * RSTEP);
-          mm(a2, k + 2 * RSTEP);
-        }
-      }
-    }
-    if (J + 1 < J1) prime(J + 1);
-    double* vj = V + ((int64_t)J * TILE) * W;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int i = (16 * q + lg + 4 * r) * W + lc;
-      vj[i] = vj[i] - acc[r];
-    }
-    __syncthreads();
-    v4d acc2 = {0.0, 0.0, 0.0, 0.0};
-    for (int s0 = 0; s0 <= q; s0 += 4) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int s = s0 + i;
-        if (s <= q) {
-#pragma unroll
-          for (int k4 = 0; k4 < 4; ++k4)
-            acc2 = __builtin_amdgcn_mfma_f64_16x16x4f64(xr[i][k4], vj[(16 * s + 4 * k4 + lg) * W + lc], acc2, 0, 0, 0);
-          if (s + 4 <= q) ldx(xr[i], s + 4);
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      vj[(16 * q + lg + 4 * r) * W + lc] = acc2[r];
-      nacc = __builtin_fma(acc2[r], acc2[r], nacc);
-    }
-    __syncthreads();
-  }
+  fwd_subst16(Lb, Db, V, NT, J0, J1, pad, q, lc, lg, [&](int, double v) { nacc = __builtin_fma(v, v, nacc); });
   nrm[t] = nacc;
   __syncthreads();
   if (t < W && sl * W + t < n_pred) {

@@ -372,6 +372,18 @@ int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
                          int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s);
 
+// ---- launcher (k_score.hip): mixed-model score statistics of listed SNPs from a chunk's factor ----
+// score[(b * nt + t) * n_cand + v] = w_j^T V^-1 r_t, info[b * n_cand + v] = w_j^T V^-1 w_j for column
+// j = cand[v] (already wrapped to [0, P)) under model b of the chunk whose pipeline left L, Dinv, z, u and
+// scal in c, and q[b * nt + t] = r_t^T V^-1 r_t (q may be null): one workgroup per (model, slab of SCORE_W
+// listed SNPs), right-hand sides from the split's 2-bit packed rows, then k_reliab's forward substitution
+// (fwd_subst.h).  lds / S / vscr: as launch_reliab (reliab_lds, reliab_slabs; ns x SCORE_W doubles for each
+// of the B x S workgroups of one launch).  The same bits either way, and for a SNP wherever it stands in
+// the list.  NaN for a model with d = 0 or a flagged index.
+constexpr int SCORE_W = 16;
+hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand, bool lds,
+                           int64_t S, double* vscr, double* score, double* info, double* q, hipStream_t s);
+
 // ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
 // loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,
 // z and the scalars that the chunk's pipeline left in c (SNP form: also the split's yT / ymu); one

@@ -216,6 +216,34 @@ class GpuBlupEngine:
                 None, None, None, _ptr(rel)))
         return rel
 
+    def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto"):
+        """Mixed-model score statistics of the panel's SNPs `snps` (column ids: any order, repeats
+        allowed, negatives wrap, in or out of the models; None: every column) against the model each
+        selected-index set fits on (train, valid): a tblup_amd.model.SnpScores from
+        tblup_snp_score_batch (include/tblup_gpu.h has the definitions) -- score u = w_j' V^-1 r_t
+        (B, nt, n_cand), info v = w_j' V^-1 w_j (B, n_cand), q = r_t' V^-1 r_t (B, nt) and dof = N - r.
+        u / d is the SNP's back-solved BLUP effect to first order (fit()'s effect for a SNP of the
+        model).  h2 in (0, 1).  A degenerate model panel gives NaN; a (model, SNP) value does not
+        depend on the list it comes in.  An empty list runs nothing: q is then NaN."""
+        from .model import SnpScores
+        self._settle()
+        cand = _as_int64(np.arange(self.n_snps) if snps is None else snps)
+        if cand.ndim != 1:
+            raise ValueError("snps must be a 1-D list of column ids")
+        sid = self.split_id(train, valid)
+        idx, offsets = concat_genomes(genomes)
+        B, nt, m = len(genomes), self.n_traits, len(cand)
+        score = np.empty((B, nt, m), dtype=np.float64)
+        info = np.empty((B, m), dtype=np.float64)
+        q = np.full((B, nt), np.nan)
+        _native.check("tblup_snp_score_batch", self._lib.tblup_snp_score_batch(
+            self._ctx, sid, _ptr(cand) if m else None, m, _ptr(idx), _ptr(offsets), B, float(h2),
+            _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q)))
+        k = np.diff(offsets)
+        snp = np.array([(branch == "snp") or (branch == "auto" and kk <= self.n_animals) for kk in k], dtype=bool)
+        dof = len(_as_int64(train)) - snp.astype(np.float64)
+        return SnpScores(score, info, q, dof.reshape(B), np.where(cand < 0, cand + self.n_snps, cand))
+
     # ------------------------------------------------- variance ratio by (RE)ML
     def log_likelihood(self, genomes, train, valid, h2, branch="auto", return_sigma2=False):
         """Profile (restricted) log-likelihood of h2 for the model each selected-index set fits on

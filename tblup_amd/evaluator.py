@@ -419,6 +419,14 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
+    def snp_scores(self, population, snps=None, final=True, train=None, valid=None):
+        """Mixed-model score statistics (tblup_amd.model.SnpScores) of the SNPs `snps` (column ids of the
+        evaluator's data; None: every column) against every individual's model: GpuBlupEngine.snp_scores
+        with fit_models' split and genome conventions.  No RNG, no collective: under torch.distributed
+        every rank computes what it is given."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.snp_scores(genomes, train, valid, self.h2, snps)
+
     def log_likelihood(self, population, h2, final=True, train=None, valid=None, **kw):
         """Profile (restricted) log-likelihood of every individual's model at `h2` (a scalar, a (G,)
         grid or a (G, B) matrix): GpuBlupEngine.log_likelihood with fit_models' split and genome

@@ -72,3 +72,57 @@ class PanelModel:
         with np.load(path, allow_pickle=False) as z:
             return cls(z["indices"], z["center"], z["effects"], z["intercept"], float(z["h2"]), str(z["branch"]),
                        float(z["fitness"]))
+
+
+class SnpScores:
+    """Mixed-model score statistics of listed SNPs against fitted panels (GpuBlupEngine.snp_scores,
+    tblup_snp_score_batch; include/tblup_gpu.h has the definitions).  For B models, nt traits and
+    n_cand listed SNPs:
+
+        score (B, nt, n_cand)  u = w_j' V^-1 r_t
+        info  (B, n_cand)      v = w_j' V^-1 w_j
+        q     (B, nt)          r_t' V^-1 r_t
+        dof   (B,)             N - r: the train animals, minus one under snp (the fitted intercept)
+        snps  (n_cand,)        the listed columns, wrapped to [0, P)
+
+    The derived statistics are plain numpy and need neither the GPU nor the library; all three give NaN
+    where v == 0 (a column that is constant over the reference rows)."""
+
+    __slots__ = ("score", "info", "q", "dof", "snps")
+
+    def __init__(self, score, info, q, dof, snps):
+        self.score = np.asarray(score, dtype=np.float64)
+        self.info = np.asarray(info, dtype=np.float64)
+        self.q = np.asarray(q, dtype=np.float64)
+        self.dof = np.asarray(dof, dtype=np.float64)
+        self.snps = np.asarray(snps, dtype=np.int64)
+        if self.score.ndim != 3:
+            raise ValueError("score must have shape (models, n_traits, n_cand)")
+        B, nt, m = self.score.shape
+        if self.info.shape != (B, m) or self.q.shape != (B, nt) or self.dof.shape != (B,) or self.snps.shape != (m,):
+            raise ValueError("info (B, n_cand), q (B, n_traits), dof (B,) and snps (n_cand,) must match score %s"
+                             % (self.score.shape,))
+
+    def _uv(self):
+        v = np.where(self.info == 0, np.nan, self.info)[:, None, :]
+        return self.score, v
+
+    def effect(self):
+        """u / v: the GLS effect of the SNP fitted as a covariate beside the panel, (B, nt, n_cand)."""
+        u, v = self._uv()
+        with np.errstate(all="ignore"):
+            return u / v
+
+    def chi2(self):
+        """u^2 / (v q / dof): the score test's statistic (1 degree of freedom), (B, nt, n_cand)."""
+        u, v = self._uv()
+        with np.errstate(all="ignore"):
+            return u * u / (v * (self.q / self.dof[:, None])[:, :, None])
+
+    def loglik_gain(self):
+        """dof / 2 * log(q / (q - u^2 / v)): the rise of the profile log-likelihood when the SNP is
+        fitted as a covariate at the same h2, (B, nt, n_cand)."""
+        u, v = self._uv()
+        q = self.q[:, :, None]
+        with np.errstate(all="ignore"):
+            return self.dof[:, None, None] / 2 * np.log(q / (q - u * u / v))

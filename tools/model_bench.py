@@ -15,10 +15,15 @@ numbers go to PERFLOG.md.  One JSON line per part:
   loglik   config 2 again: tblup_loglik_batch at 1 and at 8 grid points (per grid point: the 8-point call
            over 8) beside tblup_eval_batch from the same process, alternated; one estimate_h2 with the
            defaults (25 + 3 x 9 passes); k_loglik per launch comes from a --stats run of this part
-  --stats CSV   the k_effects / k_predict / k_reliab / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
+  score    config 2 again: snp_scores() of (i) 2,000 listed SNPs under the 256 models and (ii) all 50k SNPs
+           under one model, beside reliability() of 2,000 animals under the 256 models (the same number of
+           right-hand sides through the same substitution) and evaluate(), alternated in one process; the
+           derived fp64 MFMA floor (batch x n_cand x ns^2 flop over the measured 72.7 TF/s peak); k_snpscore
+           and k_reliab per launch come from a --stats run of this part
+  --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -148,6 +153,43 @@ def reliability_all(eng, genomes, T, V, n, ns, reps):
                     "the kernel alone: --stats; the floor is derived (flop / measured fp64 MFMA peak)"}
 
 
+def score_vs_reliability(eng, genomes, T, V, n, P, ns, reps, n_cand=2000):
+    """snp_scores() of n_cand SNPs under every model and of all P SNPs under one model, against
+    reliability() of n_cand animals (as many right-hand sides) and evaluate(), alternated on one engine."""
+    rng = np.random.default_rng(99)
+    cand = rng.choice(P, n_cand, replace=False)
+    an = rng.choice(n, n_cand, replace=n_cand > n)
+    te, tr, ts, t1 = [], [], [], []
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        eng.reliability(genomes, T, V, 0.4, an)
+        t.append(time.perf_counter())
+        sc = eng.snp_scores(genomes, T, V, 0.4, cand)
+        t.append(time.perf_counter())
+        one = eng.snp_scores(genomes[:1], T, V, 0.4)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for lst, i in ((te, 0), (tr, 1), (ts, 2), (t1, 3)):
+                lst.append(t[i + 1] - t[i])
+    B = len(genomes)
+    flop, flop1 = float(B) * n_cand * ns * ns, float(P) * ns * ns
+    floor = lambda f: round(f / (F64_MFMA_TFS * 1e12) * 1e3, 3)
+    return {"evaluate_ms": med_ms(te), "reliability_ms": med_ms(tr), "score_ms": med_ms(ts),
+            "score_extra_ms_over_evaluate": round(med_ms(ts) - med_ms(te), 4),
+            "reliability_extra_ms_over_evaluate": round(med_ms(tr) - med_ms(te), 4),
+            "score_over_reliability_extra": round((med_ms(ts) - med_ms(te)) / (med_ms(tr) - med_ms(te)), 4),
+            "score_floor_ms": floor(flop), "n_cand": n_cand,
+            "score_1xP_ms": med_ms(t1), "score_1xP_floor_ms": floor(flop1),
+            "score_ms_all": [round(x * 1e3, 3) for x in ts], "reliability_ms_all": [round(x * 1e3, 3) for x in tr],
+            "score_1xP_ms_all": [round(x * 1e3, 3) for x in t1],
+            "finite": bool(np.all(np.isfinite(sc.score)) and np.all(np.isfinite(one.score))),
+            "max_chi2_1xP": float(np.nanmax(one.chi2())),
+            "note": "each call is the whole evaluation plus the kernel and the D2H copy of its outputs; the "
+                    "kernels alone: --stats; the floors are derived (flop / measured fp64 MFMA peak)"}
+
+
 def loglik_vs_eval(eng, genomes, T, V, reps, grid_n=8):
     """tblup_eval_batch against tblup_loglik_batch at 1 and grid_n grid points (the C entries, alternated),
     then one estimate_h2 with the defaults."""
@@ -205,7 +247,7 @@ def stats_share(path):
     out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
     for r in rows:
         name = r["Name"]
-        for key in ("k_effects", "k_predict", "k_reliab", "k_loglik", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -258,6 +300,13 @@ def main():
         with GpuBlupEngine(geno, pheno) as eng:
             st = loglik_vs_eval(eng, genomes, T, V, args.reps)
             print(json.dumps({"part": "loglik", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **st}))
+    if "score" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            st = score_vs_reliability(eng, genomes, T, V, n, P, 1024, args.reps)
+            print(json.dumps({"part": "score", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **st}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
