@@ -560,6 +560,7 @@ int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
   cl.skip = dbg_skip(c) | (rq.mode == ChunkMode::DebugL ? FLAG_WRITE_LJJ : 0);
   cl.padskip = (sd.form == FORM_PRIMAL && sd.pad_first) ? 1 : 0;
   cl.sys_st = c->sys_st;
+  cl.diag_waves = c->diag_waves;
   std::vector<OffPlan> plan(sd.NT);
   for (int J = 0; J < sd.NT; ++J) {
     plan[J] = plan_of(c, B, sd.NT, J, use_st);
@@ -839,6 +840,7 @@ int tblup_ctx_create(const int8_t* geno, int64_t n, int64_t P, int layout, const
   if (const char* e = getenv("TBLUP_DUAL_ST")) c->dual_st = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_DIAG_D")) c->diag_d = std::max(-1, std::min(1, atoi(e)));
   if (const char* e = getenv("TBLUP_DIAG_E")) c->diag_e = std::max(-1, std::min(2, atoi(e)));
+  if (const char* e = getenv("TBLUP_DIAG_WAVES")) c->diag_waves = (atoi(e) == 8 || atoi(e) == 12 || atoi(e) == 16) ? atoi(e) : 0;
   if (const char* e = getenv("TBLUP_PAD_FIRST")) c->pad_first = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_RELIAB_LDS")) c->reliab_lds = atoi(e) != 0;
   if (const char* e = getenv("TBLUP_SCORE_LDS")) c->score_lds = atoi(e) != 0;

@@ -106,6 +106,8 @@ struct tblup_ctx {
   int nrs = 0;        // TBLUP_NRS: partial-sum row slices, 0 auto, else 1 / 2 / 4
   int diag_d = -1;    // TBLUP_DIAG_D: D-units in the diagonal launch (-1 auto, 0 never, 1 always)
   int diag_e = -1;    // TBLUP_DIAG_E: E-units in the diagonal launch (-1 auto, 0 never, 1 every tile)
+  int diag_waves = 0; // TBLUP_DIAG_WAVES: waves of the diagonal workgroups in launches without D- / E-units
+                      // (0 auto, 8, 12, 16: diag_waves(), tblup_internal.h)
   int chain_sync = 0;    // TBLUP_CHAIN_SYNC (k_solve.hip)
   int last_term = -1;    // TBLUP_LAST_TERM: -1 auto (last_term_mask), 0 never, 1 always (see use_last_term)
   int lt_mask = -1;      // TBLUP_LT_MASK: the diagonal launches in last-term mode by bit (A/B timing; -1 auto)

@@ -292,8 +292,9 @@ __device__ __forceinline__ int skip_rows(const CholArgs& a, int64_t b) {
 }
 
 // st: profiling only (phase stamps of one factorisation in diagonal workgroup 0), else null
+template <bool LJJ = true>   // LJJ false: a kernel that never runs the debug path (its launcher sees to it)
 __device__ __forceinline__ void factor16_any(const CholArgs& a, double* D, double* X, int l, uint64_t* st = nullptr) {
-  if (a.skip & FLAG_WRITE_LJJ)
+  if (LJJ && (a.skip & FLAG_WRITE_LJJ))
     factor16<true>(D, X, l, st);
   else
     factor16<false>(D, X, l, st);
@@ -325,9 +326,18 @@ __device__ __forceinline__ int32_t gsh_count(const CholArgs& a, int64_t s, int64
 // Each piece is written in the packed block layout the diagonal kernel factorises in,
 // so the diagonal kernel sums them with a linear sweep.
 // ---------------------------------------------------------------------------
-constexpr int DW = 8;            // waves per diagonal workgroup
+constexpr int DW = 8;            // waves per diagonal workgroup: phase A (S load, SYRK map), and the whole
+                                 // workgroup in the launches that carry D- / E-units
 constexpr int DTHR = 64 * DW;
-static_assert(DTHR == 4 * TILE, "diag z: four lanes per row");
+// waves of the diagonal workgroups in launches without D- / E-units (k_chol_diag_w): the extra
+// waves join at the factorisation windows as workers (diag_tile)
+constexpr int DWX = DIAG_WAVES_WIDE;
+static_assert(DWX > DW && DWX % 4 == 0 && DWX <= 16, "wide diagonal workgroup: 12 or 16 waves");
+// diag z: four lanes per row, so one wave forms the z of one 16-row block row (diag_z), whatever
+// the workgroup's wave count
+static_assert(64 == 4 * NB && DW >= NBLK, "diag z: four lanes per row, one wave per block row");
+
+
 
 // ===========================================================================
 // Off-diagonal launch, 8 waves (512 threads) per workgroup, two workgroups per CU:
@@ -778,17 +788,32 @@ __device__ __forceinline__ void xinv_block(const double* Tp, double* Xp, int q, 
 }
 
 // z_J[i] = sum_{c <= i} X[i][c] r[c] for the NTR right-hand sides: four lanes per row
-// (c = q mod 4), shuffle-reduced.
+// (c = q mod 4), shuffle-reduced.  One wave covers the 16 rows of block row qr (lane l: row
+// 16 qr + (l >> 2), q = l & 3), so a block row's z can be formed as soon as its X blocks are final.
 template <int NTR>
 __device__ __forceinline__ void diag_z(const CholArgs& a, const double* Xp, const double (*rsh)[TILE], int64_t b,
-                                       int64_t j0) {
-  const int t = threadIdx.x, i = t >> 2, q = t & 3;
-  const int qi = i >> 4, ii = i & 15;
+                                       int64_t j0, int qr) {
+  const int l = threadIdx.x & 63, ii = l >> 2, i = 16 * qr + ii, q = l & 3;
   double acc[NTR];
 #pragma unroll
   for (int tr = 0; tr < NTR; ++tr) acc[tr] = 0.0;
-  for (int c = q; c <= i; c += 4) {
-    const double xc = Xp[pk(qi, c >> 4) + bo(ii, c & 15)];
+  // c = q, q + 4, ... <= i in this order, one block (four c) per pass: the block's X and r loads
+  // are in flight together instead of one LDS round trip per term (the lane's fma chain is
+  // unchanged).  Blocks left of the diagonal hold only c <= i; the diagonal block's c > i are skipped.
+#pragma unroll 1
+  for (int cb = 0; cb < qr; ++cb) {
+    const double* xb = Xp + pk(qr, cb);
+    double xc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) xc[j] = xb[bo(ii, q + 4 * j)];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+#pragma unroll
+      for (int tr = 0; tr < NTR; ++tr) acc[tr] += xc[j] * rsh[tr][16 * cb + q + 4 * j];
+    }
+  }
+  for (int c = 16 * qr + q; c <= i; c += 4) {
+    const double xc = Xp[pk(qr, qr) + bo(ii, c & 15)];
 #pragma unroll
     for (int tr = 0; tr < NTR; ++tr) acc[tr] += xc * rsh[tr][c];
   }
@@ -800,6 +825,54 @@ __device__ __forceinline__ void diag_z(const CholArgs& a, const double* Xp, cons
     if (q == 0) a.z[(b * NTR + tr) * a.ns + j0 + i] = v;
   }
 }
+__device__ __forceinline__ void diag_z_row(const CholArgs& a, const double* Xp, const double (*rsh)[TILE], int64_t b,
+                                           int64_t j0, int qr) {
+  if (a.skip & (1 << 15)) return;
+  switch (a.nt) {
+    case 1: diag_z<1>(a, Xp, rsh, b, j0, qr); break;
+    case 2: diag_z<2>(a, Xp, rsh, b, j0, qr); break;
+    case 3: diag_z<3>(a, Xp, rsh, b, j0, qr); break;
+    default: diag_z<4>(a, Xp, rsh, b, j0, qr); break;
+  }
+}
+
+// Block row qr of X into Dinv, each block transposed (block (q, jb) holds X_{q,jb}^T in the bo()
+// layout): thread tid of nthr writes the 16-B pairs k = first pair of the row + tid, + nthr, ...,
+// i.e. elements (r, c0), (r, c0 + 1) of block blk's transpose, read from X at bo(c0, r), bo(c0 + 1, r)
+// (coalesced; the packed blocks of one row are contiguous).
+__device__ __forceinline__ void dinv_store_row(const CholArgs& a, const double* Xp, double* Xg, int qr, int tid,
+                                               int nthr) {
+  if (a.skip & (1 << 14)) return;
+  const int k0 = pk(qr, 0) / 2, k1 = pk(qr, qr + 1) / 2;
+  for (int k = k0 + tid; k < k1; k += nthr) {
+    const int g = 2 * k, blk = g >> 8, o = g & 255, r = o >> 4;
+    const int c0 = 2 * (((o & 15) >> 1) ^ ((r >> 1) & 7));
+    const double* xb = Xp + blk * BLKD;
+    *reinterpret_cast<v2d*>(Xg + g) = v2d{xb[bo(c0, r)], xb[bo(c0 + 1, r)]};
+  }
+}
+
+// Waves of a diagonal workgroup beyond the SYRK's eight: the barriers of syrk_lower8_32 (same
+// arguments), nothing else.
+__device__ __forceinline__ void syrk_lower8_32_bystander(int nst16, int r0 = 0) {
+  const int nst = nst16 >> 1, s0 = r0 >> 5, kf = (r0 & 31) >> 2;
+  if (nst <= s0) return;
+  int s = s0;
+  if (kf > 0) {
+    __builtin_amdgcn_s_barrier();
+    ++s;
+  }
+  for (; s < nst; ++s) __builtin_amdgcn_s_barrier();
+  __syncthreads();
+}
+
+// Rank of worker wave w (1 .. NW-1) of a diagonal workgroup: 8 waves in wave order; more waves:
+// the waves off wave 0's SIMD first (w & 3 != 0), then its SIMD mates 4, 8, ...
+template <int NW>
+__device__ __forceinline__ int diag_rank(int w) {
+  if constexpr (NW == DW) return w - 1;
+  return (w & 3) ? 3 * (w >> 2) + (w & 3) - 1 : 3 * (NW / 4) + (w >> 2) - 1;
+}
 
 // Diagonal tile J of individual b.  T = S - sum_{L0 <= L < J} L_JL L_JL^T where S is
 // K_JJ - sum_{L < L0} (the buffer slot J&1 left by an earlier off-diagonal launch) when
@@ -807,10 +880,28 @@ __device__ __forceinline__ void diag_z(const CholArgs& a, const double* Xp, cons
 // LDS (lds >= 2 * NPACK * BLKD doubles = 144 KiB): Tp = T -> L (packed lower 16x16 blocks),
 // Xp = X = L^{-1} in the same packed layout; before the factorisation Xp's space is the
 // 64 KiB SYRK stage ring.  X never round-trips through global memory: Dinv receives X^T
-// once, at the end.
+// block row by block row, as the rows become final.
+//
+// NW waves (DW, or DWX in the launches without D- / E-units).  Phase A runs on waves < DW whatever
+// NW; the factorisation windows spread their off-chain work over the workers, waves 1 .. NW-1 in
+// rank order (diag_rank: wave 0's SIMD mates last).  Window p (block (p, p) factored, X_pp in LDS):
+//   wave 0  : L_{p+1,p} = T_{p+1,p} X_pp^T                                        | barrier a_p |
+//             T_{p+1,p+1} -= L_{p+1,p} L_{p+1,p}^T, factor16 of block (p+1, p+1)  | barrier w_p
+//   workers : L_qp, q > p+1                                                       | barrier a_p |
+//             trailing blocks T_qs -= L_qp L_sp^T; X block row p (xinv_block);
+//             block row p-1 of X^T into Dinv and its 16 rows of z                 | barrier w_p
+// so the pivot chain is one L block, one update and factor16 per window, and after the last window
+// only the last block row of X, its store and its z remain (row NBLK-2's store and z beside them).
+// Every block keeps its MFMA chain and every z row its fma order whichever wave takes it, so the
+// results do not depend on NW.
+template <int NW>
 __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, int L0, double* lds,
                                           double (*rsh)[TILE]) {
+  constexpr int NTHR = 64 * NW;
   const int t = threadIdx.x, l = t & 63, w = t >> 6;
+  // the wave's role from a scalar: those branches are then scalar too, so every wave meets each
+  // barrier in exactly one of them
+  const int wu = __builtin_amdgcn_readfirstlane(w);
   const int64_t ns = a.ns;
   const int NT = a.NT;
   const int64_t j0 = (int64_t)J * TILE;
@@ -843,40 +934,49 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
   // launch's loads are HBM-bound and the SYRK at 2 waves per SIMD then runs after them.)
   const double* src = (L0 == 0) ? a.Kd + (b * NT + J) * (int64_t)NPACK * BLKD
                                 : a.S + (b * NSLOT + (J & 1)) * (int64_t)NPACK * BLKD;
+  const bool aw = NW == DW || wu < DW;   // phase A's loads and SYRK: the first DW waves
   {
+    if (aw) {
 #pragma unroll
-    for (int e = 0; e < NPACK * BLKD / 2 / DTHR; ++e) {   // 9 x 16 B per thread
-      const int chunk = (e * DW + w) * 64;
-      __builtin_amdgcn_global_load_lds(src + 2 * (chunk + l), (lds_ptr_t)(Tp + 2 * chunk), 16, 0, 2);   // aux 2: non-temporal
+      for (int e = 0; e < NPACK * BLKD / 2 / DTHR; ++e) {   // 9 x 16 B per thread
+        const int chunk = (e * DW + w) * 64;
+        __builtin_amdgcn_global_load_lds(src + 2 * (chunk + l), (lds_ptr_t)(Tp + 2 * chunk), 16, 0, 2);   // aux 2: non-temporal
+      }
     }
     if (J > L0 && a.q != nullptr) {
       // last-term mode: Q = L_{J,J-1} L_{J,J-1}^T came with launch J-1's tile (J, J-1)
       const double* qg = a.q + b * (int64_t)NPACK * BLKD;
+      if (aw) {
 #pragma unroll
-      for (int e = 0; e < NPACK * BLKD / 2 / DTHR; ++e) {
-        const int chunk = (e * DW + w) * 64;
-        __builtin_amdgcn_global_load_lds(qg + 2 * (chunk + l), (lds_ptr_t)(Xp + 2 * chunk), 16, 0, 0);
+        for (int e = 0; e < NPACK * BLKD / 2 / DTHR; ++e) {
+          const int chunk = (e * DW + w) * 64;
+          __builtin_amdgcn_global_load_lds(qg + 2 * (chunk + l), (lds_ptr_t)(Xp + 2 * chunk), 16, 0, 0);
+        }
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
-      for (int e = t; e < NPACK * BLKD; e += DTHR) Tp[e] -= Xp[e];
+      for (int e = t; e < NPACK * BLKD; e += NTHR) Tp[e] -= Xp[e];
       __syncthreads();
     } else if (J > L0 && !(a.skip & 2)) {
-      v4d acc[5];
+      if (aw) {
+        v4d acc[5];
 #pragma unroll
-      for (int i = 0; i < 5; ++i) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
-      // waits for all its stages (and the older S loads) and ends in a barrier
-      // (no padding skip here: at J = 1 only, and it keeps the peeled stage out of this kernel)
-      syrk_lower8_32(a.L + b * l_stride(NT) + ((int64_t)J * NT + L0) * TT, 8 * (J - L0), Xp, acc);
+        for (int i = 0; i < 5; ++i) acc[i] = v4d{0.0, 0.0, 0.0, 0.0};
+        // waits for all its stages (and the older S loads) and ends in a barrier
+        // (no padding skip here: at J = 1 only, and it keeps the peeled stage out of this kernel)
+        syrk_lower8_32(a.L + b * l_stride(NT) + ((int64_t)J * NT + L0) * TT, 8 * (J - L0), Xp, acc);
 #pragma unroll
-      for (int i = 0; i < 5; ++i) {
-        const int e = syrk_e(w, i);
-        if (i < syrk_nb(w)) {
-          const int q = tri_q_rt(e);
-          double* blk = Tp + pk(q, e - q * (q + 1) / 2);
+        for (int i = 0; i < 5; ++i) {
+          const int e = syrk_e(w, i);
+          if (i < syrk_nb(w)) {
+            const int q = tri_q_rt(e);
+            double* blk = Tp + pk(q, e - q * (q + 1) / 2);
 #pragma unroll
-          for (int r = 0; r < 4; ++r) blk[bo((l >> 4) + 4 * r, l & 15)] -= acc[i][r];
+            for (int r = 0; r < 4; ++r) blk[bo((l >> 4) + 4 * r, l & 15)] -= acc[i][r];
+          }
         }
+      } else {
+        syrk_lower8_32_bystander(8 * (J - L0));
       }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -884,7 +984,7 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
   // X's diagonal blocks start as the reversed identity (factor16's inverse rows load it); the
   // SYRK ring that shared their space is drained
 #pragma unroll
-  for (int e = t; e < NBLK * BLKD; e += DTHR) {
+  for (int e = t; e < NBLK * BLKD; e += NTHR) {
     const int p = e >> 8, o = e & 255, r = o >> 4;
     const int c = 2 * (((o & 15) >> 1) ^ ((r >> 1) & 7)) + (o & 1);   // bo(r, c) == o
     Xp[pk(p, p) + o] = (c == NB - 1 - r) ? 1.0 : 0.0;
@@ -897,44 +997,58 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
   __syncthreads();
   dstamp(a, 2);
 
-  // C. blocked right-looking factorisation over 16-column panels, with a one-block
-  //    look-ahead: wave 0 updates diagonal block p+1 first and factors it while waves 1-3
-  //    finish the rest of step p's trailing update.
+  // C. blocked right-looking factorisation over 16-column panels.  Wave 0 is the pivot chain: it
+  //    forms the one L block the next pivot block needs, updates that block and factors it; the
+  //    workers take the rest of panel p's L column, the trailing update and the X rows.
+  const int rk = diag_rank<NW>(wu);
+  constexpr int NWK = NW - 1;                                   // workers
+  constexpr int ZR = NW == DW ? NWK - 1 : 3 * (NW / 4) - 1;     // wave NW-1's rank: rows of X^T and z
+  double* Xg = a.Dinv + (b * NT + J) * (int64_t)NPACK * BLKD;
+  constexpr int LR = NBLK - 1;
+  auto upd_next = [&](int p) {   // T_{p+1,p+1} -= L_{p+1,p} L_{p+1,p}^T
+    v4d x = {0.0, 0.0, 0.0, 0.0};
+    x = mma_abt(Tp + pk(p + 1, p), Tp + pk(p + 1, p), x, l);
+    double* dst = Tp + pk(p + 1, p + 1);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) dst[bo((l >> 4) + 4 * r, l & 15)] -= x[r];
+  };
   if (!(a.skip & 4)) {
-    if (w == 0 && !(a.skip & 256)) factor16_any(a, Tp + pk(0, 0), Xp + pk(0, 0), l);
+    if (wu == 0 && !(a.skip & 256)) factor16_any<NW == DW>(a, Tp + pk(0, 0), Xp + pk(0, 0), l);
     __syncthreads();
   }
-  for (int p = 0; p < ((a.skip & 4) ? 0 : NBLK); ++p) {
-    for (int q = p + 1 + w; q < ((a.skip & 512) ? 0 : NBLK); q += DW) {
+  for (int p = 0; p + 1 < ((a.skip & 4) ? 0 : NBLK); ++p) {
+    // L column of panel p: block (p+1, p) on wave 0, block (p+2+r, p) on the worker of rank r
+    const int qc = (wu == 0) ? p + 1 : p + 2 + rk;
+    if (qc < ((a.skip & 512) ? 0 : NBLK)) {
       v4d x = {0.0, 0.0, 0.0, 0.0};
-      x = mma_abt(Tp + pk(q, p), Xp + pk(p, p), x, l);
+      x = mma_abt(Tp + pk(qc, p), Xp + pk(p, p), x, l);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) Tp[pk(q, p) + bo((l >> 4) + 4 * r, l & 15)] = x[r];
+      for (int r = 0; r < 4; ++r) Tp[pk(qc, p) + bo((l >> 4) + 4 * r, l & 15)] = x[r];
     }
     dstamp(a, 3 + 3 * p);
-    __syncthreads();
-    if (p + 1 == NBLK) break;
+    __syncthreads();   // a_p: L column p complete (the workers read L_{p+1,p} too)
     const int nb = NBLK - 1 - p;
-    if (w == 0) {
+    if (wu == 0) {
       uint64_t* st = (a.dtr && blockIdx.x == 0 && p == 3) ? a.dtr : nullptr;
       fstamp(st, 54);
-      if (!(a.skip & 512)) {
-        v4d x = {0.0, 0.0, 0.0, 0.0};
-        x = mma_abt(Tp + pk(p + 1, p), Tp + pk(p + 1, p), x, l);
-        double* dst = Tp + pk(p + 1, p + 1);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) dst[bo((l >> 4) + 4 * r, l & 15)] -= x[r];
-      }
-      if (!(a.skip & 256)) factor16_any(a, Tp + pk(p + 1, p + 1), Xp + pk(p + 1, p + 1), l, st);
+      // (after the barrier: its own L block is back in LDS, and the workers start their trailing
+      // blocks an update earlier; before the barrier measured even)
+      if (!(a.skip & 512)) upd_next(p);
+      if (!(a.skip & 256)) factor16_any<NW == DW>(a, Tp + pk(p + 1, p + 1), Xp + pk(p + 1, p + 1), l, st);
     } else {
-      // trailing blocks e = 1 .. nb(nb+1)/2 - 1 (e = 0 is block (p+1, p+1)) over waves 1 .. DW-1
-      // (wave DW/2 shares wave 0's SIMD; factor16 leaves it enough issue slots)
-      const int wi = w - 1;   // 0 .. DW-2
-      constexpr int NTW = DW - 1;
+      // trailing blocks e = 1 .. nb(nb+1)/2 - 1 (e = 0 is block (p+1, p+1)).  8 waves: over all
+      // seven workers, which then take the X blocks and the finished row.  More waves: ranks < p
+      // build X row p, the ranks from p up to ZR take the trailing blocks; wave 0's SIMD mates (the
+      // ranks past ZR) run no MFMA beside factor16 (with trailing blocks on them: +0.7% per step).
+      int ti = rk, ntw = NWK;
+      if constexpr (NW != DW) {
+        ntw = ZR - p;
+        ti = (rk < ZR) ? rk - p : -1;
+      }
       // two blocks per pass: independent MFMA chains and LDS traffic overlap
       const int ne = (a.skip & 512) ? 0 : nb * (nb + 1) / 2;
-      for (int e = wi + 1; e < ne; e += 2 * NTW) {
-        const int e2 = e + NTW;
+      for (int e = ti + 1; ti >= 0 && e < ne; e += 2 * ntw) {
+        const int e2 = e + ntw;
         int qq = 0;
         while ((qq + 1) * (qq + 2) / 2 <= e) ++qq;
         const int q = p + 1 + qq, sb = p + 1 + (e - qq * (qq + 1) / 2);
@@ -964,7 +1078,15 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
       }
       // D (overlapped). block row p of X = L^{-1}: L row p and X rows < p are final and
       // X_pp came out of the previous window's factor16
-      if (!(a.skip & 8) && wi < p) xinv_block(Tp, Xp, p, wi, l);
+      if (!(a.skip & 8) && rk < p) xinv_block(Tp, Xp, p, rk, l);
+      // E (overlapped). block row p-1 of X is final since barrier w_{p-1}: into Dinv, and its z.
+      // z (fp64 VALU) on rank ZR, off wave 0's SIMD; the store there too, or (wide workgroup)
+      // over wave 0's mates, which it costs LDS reads and stores only
+      if (p >= 1 && !(a.skip & 8)) {
+        if (NW == DW && rk == ZR) dinv_store_row(a, Xp, Xg, p - 1, l, 64);
+        if (NW != DW && rk > ZR) dinv_store_row(a, Xp, Xg, p - 1, 64 * (rk - ZR - 1) + l, 64 * (NWK - 1 - ZR));
+        if (rk == ZR) diag_z_row(a, Xp, rsh, b, j0, p - 1);
+      }
     }
     dstamp(a, 4 + 3 * p);
     __syncthreads();
@@ -972,9 +1094,15 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
   }
   if (a.skip & 16) return;
 
-  // D. last block row of X (rows < NBLK-1 were built inside the factorisation windows)
+  // D. last block row of X (rows < NBLK-1 were built inside the factorisation windows), beside it
+  //    block row NBLK-2 into Dinv
   if (!(a.skip & 4) && !(a.skip & 8)) {
-    if (w < NBLK - 1) xinv_block(Tp, Xp, NBLK - 1, w, l);
+    const int jb = (NW == DW) ? wu : (wu == 0 ? LR : rk);
+    if (jb < LR) xinv_block(Tp, Xp, LR, jb, l);
+    // (8 waves: the one wave without an X block; wide: wave 0 and the ranks past the X blocks')
+    if (NW == DW && wu == NW - 1) dinv_store_row(a, Xp, Xg, LR - 1, l, 64);
+    if (NW != DW && (wu == 0 || rk >= LR))
+      dinv_store_row(a, Xp, Xg, LR - 1, 64 * (wu == 0 ? 0 : rk - LR + 1) + l, 64 * (NW - LR));
     dstamp(a, 26);
     __syncthreads();
     dstamp(a, 27);
@@ -982,35 +1110,22 @@ __device__ __forceinline__ void diag_tile(const CholArgs& a, int64_t b, int J, i
 
   // E. X into Dinv as packed lower blocks, each block transposed (block (q, jb) holds
   //    X_{q,jb}^T in the bo() layout), z_J = X r, and L_JJ^T only for the debug readback.
-  {
-    // coalesced: thread writes the 16-B pair at g = 2k of Dinv, i.e. elements (r, c0), (r, c0+1)
-    // of block blk's transpose, read from X at bo(c0, r), bo(c0 + 1, r)
-    double* Xg = a.Dinv + (b * NT + J) * (int64_t)NPACK * BLKD;
-    for (int k = t; k < ((a.skip & (1 << 14)) ? 0 : NPACK * BLKD / 2); k += DTHR) {
-      const int g = 2 * k, blk = g >> 8, o = g & 255, r = o >> 4;
-      const int c0 = 2 * (((o & 15) >> 1) ^ ((r >> 1) & 7));
-      const double* xb = Xp + blk * BLKD;
-      *reinterpret_cast<v2d*>(Xg + g) = v2d{xb[bo(c0, r)], xb[bo(c0 + 1, r)]};
-    }
-  }
-  if (a.skip & FLAG_WRITE_LJJ) {
+  if (NW == DW && (a.skip & FLAG_WRITE_LJJ)) {   // (the debug path runs the 8-wave kernel: launch_chol_diag)
     double* Ld = a.L + b * l_stride(NT) + ((int64_t)J * NT + J) * TT;
-    for (int e = t; e < TT; e += DTHR) {
+    for (int e = t; e < TT; e += NTHR) {
       const int rr = e >> 7, cc = e & 127;
       Ld[e] = (cc >= rr) ? Tp[pk(cc >> 4, rr >> 4) + bo(cc & 15, rr & 15)] : 0.0;
     }
   }
+  // what is left: z of block rows NBLK-2 and NBLK-1 on the last two waves (two SIMDs, neither
+  // wave 0's), the last row's eight blocks of X^T over the others
+  if (wu == NW - 1)
+    diag_z_row(a, Xp, rsh, b, j0, LR - 1);
+  else if (wu == NW - 2)
+    diag_z_row(a, Xp, rsh, b, j0, LR);
+  else
+    dinv_store_row(a, Xp, Xg, LR, t, 64 * (NW - 2));
   dstamp(a, 28);
-  // z_J[i] = sum_{c <= i} X[i][c] r[c]: four lanes per row (c = q mod 4), shuffle-reduced
-  if (!(a.skip & (1 << 15))) {
-    switch (nt) {
-      case 1: diag_z<1>(a, Xp, rsh, b, j0); break;
-      case 2: diag_z<2>(a, Xp, rsh, b, j0); break;
-      case 3: diag_z<3>(a, Xp, rsh, b, j0); break;
-      default: diag_z<4>(a, Xp, rsh, b, j0); break;
-    }
-  }
-  dstamp(a, 29);
 }
 
 // ---------------------------------------------------------------------------
@@ -1324,7 +1439,20 @@ __global__ __launch_bounds__(DTHR) void k_chol_diag(CholArgs a, int64_t ne, int 
   }
   // individual b on the XCD that runs its off-diagonal tiles (same L2 for L, S, X, w)
   const int64_t b = xcd_remap(blockIdx.x, a.B);
-  diag_tile(a, b, a.J, a.J >= 2 ? a.J - 1 : 0, lds, rsh);
+  diag_tile<DW>(a, b, a.J, a.J >= 2 ? a.J - 1 : 0, lds, rsh);
+  tr.done(WGT_DIAG, a.J, a.J, b);
+}
+
+// The same diagonal tile on NW waves, for the launches with no D- or E-units beside the B diagonal
+// workgroups (every launch at B >= the CU count): the workgroup has its CU to itself (LDS), and the
+// extra waves give the windows' off-chain work slack (diag_tile).
+template <int NW>
+__global__ __launch_bounds__(64 * NW) void k_chol_diag_w(CholArgs a) {
+  __shared__ __attribute__((aligned(16))) double lds[2 * NPACK * BLKD];   // 144 KiB: T/L and X
+  __shared__ double rsh[MAXT][TILE];
+  WgTrace tr(a.wgt);
+  const int64_t b = xcd_remap(blockIdx.x, a.B);
+  diag_tile<NW>(a, b, a.J, a.J >= 2 ? a.J - 1 : 0, lds, rsh);
   tr.done(WGT_DIAG, a.J, a.J, b);
 }
 
@@ -1547,7 +1675,10 @@ hipError_t launch_chol_diag(const CholLaunch& c, int J, const OffPlan& p, hipStr
   if (p.ne > 0 && (c.part == nullptr || J < 1 || p.ne > c.B * p.nI || c.ft.gsh)) return hipErrorInvalidValue;
   // profiling: the phase stamps of this launch follow its workgroup records
   if (c.wgt) a.dtr = c.wgt + nwg * WGT_REC;
-  hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nwg), dim3(DTHR), 0, s, a, p.ne, p.ahead_cur ? J - 1 : 0);
+  if (diag_waves(p, c.diag_waves) == DWX && !(a.skip & FLAG_WRITE_LJJ))
+    hipLaunchKernelGGL(k_chol_diag_w<DWX>, dim3((unsigned)nwg), dim3(64 * DWX), 0, s, a);
+  else
+    hipLaunchKernelGGL(k_chol_diag, dim3((unsigned)nwg), dim3(DTHR), 0, s, a, p.ne, p.ahead_cur ? J - 1 : 0);
   return hipGetLastError();
 }
 

@@ -237,6 +237,7 @@ struct CholLaunch {
                          // [B][NT][36 packed lower blocks][64 lanes][4] (KD_TILE int16 per tile); the
                          // consumers form K_JJ + lambda I from them (kd_block, k_chol.hip)
   int sys_st = -1;       // k_sys_tiles_st: -1 auto, 0 never, 1 whenever it applies (TBLUP_SYS_ST)
+  int diag_waves = 0;    // diagonal workgroup waves where the launch has no D- / E-units: 0 auto (TBLUP_DIAG_WAVES)
   const StatsFuse* stats = nullptr;   // launch_sys_tiles: form the scalars after k_sys_tiles_st
 };
 // k_sys_tiles output: per individual NT(NT-1)/2 off-diagonal tiles (I > J, t = I(I-1)/2 + J) of
@@ -250,8 +251,8 @@ constexpr int64_t KC_MAX_NT = 8191;
 // s_memrealtime ticks (100 MHz); kinds below
 constexpr int WGT_REC = 4;
 // a diagonal launch's records are followed by DTR_RECS records holding the phase stamps of
-// its workgroup 0 (8 waves x 64 uint64), written as kind-0 records
-constexpr int DTR_RECS = 8 * 64 / WGT_REC;
+// its workgroup 0 (up to 16 waves x 64 uint64), written as kind-0 records
+constexpr int DTR_RECS = 16 * 64 / WGT_REC;
 enum { WGT_DIAG = 1, WGT_TILE = 2, WGT_PREP = 3, WGT_KJJ = 4, WGT_SYS = 5, WGT_PART = 6, WGT_DPREP = 9, WGT_EPART = 10 };   // 7 / 8: the chained solve (k_solve.hip)
 // Work units of the off-diagonal launch of column J, per individual (k_chol.hip):
 //   nI  T-units: tiles (I, J), I > J
@@ -292,6 +293,15 @@ constexpr int DD_MAX_J = 3;
 // the column (tests), 2 only columns covered whole
 OffPlan off_plan(int64_t B, int NT, int J, bool sys_tiles, int ahead, int nrs, int64_t slots = AHEAD_SLOTS,
                  int diag_d = 0, int dd_maxj = DD_MAX_J, int diag_e = 0, int64_t ncu = 0);
+// Waves of launch J's diagonal workgroups.  A launch with D- or E-units keeps the 8-wave kernel (its
+// units are 8-wave code); the others run the wide workgroup, DIAG_WAVES_WIDE waves, whose extra
+// waves shorten the factorisation windows (k_chol.hip diag_tile).  knob: 0 auto, else 8 or the wide
+// count forces the choice for the launches without units (a count that is not built: auto).
+constexpr int DIAG_WAVES_WIDE = 16;
+inline int diag_waves(const OffPlan& p, int knob) {
+  if (p.ndd > 0 || p.ne > 0) return 8;
+  return knob == 8 ? 8 : DIAG_WAVES_WIDE;
+}
 // multiprocessor count of the current device (256 when the query fails)
 int cu_count();
 inline int64_t offdiag_grid(const OffPlan& p, int64_t B) { return p.nI > 0 ? B * p.units() + p.n_kd : 0; }

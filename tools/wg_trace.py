@@ -4,7 +4,8 @@ For every Cholesky launch: makespan, workgroups by kind with their mean / max du
 slot utilisation (sum of workgroup time / (resident slots x makespan); the off-diagonal
 kernel fits 2 workgroups per CU, the diagonal 1), the time the first / last workgroup
 starts, and the gap to the previous launch.  Writes the raw records to an .npy for later
-analysis.   usage: python tools/wg_trace.py [out.npy] [--pop N] [--config configN]
+analysis.   usage: python tools/wg_trace.py [out.npy] [--pop N] [--config configN] [--stamp-waves 8]
+(--stamp-waves 8: a library from before the 16-wave diagonal workgroup, whose stamp block holds 8 waves)
 """
 import os
 import sys
@@ -97,12 +98,17 @@ def main():
             k0, g1, xs, en = p[m, 0], p[m, 1], p[m, 2], tot_us[m]
             print(f"  J={J}: n={int(m.sum()):5d}  K {k0.mean():6.1f}  GEMM1 {(g1 - k0).mean():6.1f}  "
                   f"X {(xs - g1).mean():5.1f}  GEMM2+ {(en - xs).mean():5.1f}  total {en.mean():6.1f}")
-    # phase stamps of diagonal workgroup 0 (tblup_internal.h DTR_RECS): per wave, 30 slots.  They
+    # phase stamps of diagonal workgroup 0 (tblup_internal.h DTR_RECS: 16 waves x 64 slots): per wave, 30 slots.  They
     # follow the diagonal launch's own records (B x (1 + D-units beside it) + E-units), so locate them from
     # the last diagonal record of launch J (the units per launch depend on the schedule policy)
     NT = 8
-    names = ["start", "pre-barrier", "post-barrier"] + [f"{x}{p}" for p in range(8) for x in ("a", "b", "w")] + [
-        "xinv7", "post-xinv7", "dinv", "z", "syrk-issued", "-"] + [f"{x}{t}" for t in range(8) for x in
+    nsw = int(sys.argv[sys.argv.index("--stamp-waves") + 1]) if "--stamp-waves" in sys.argv else 16
+    # window p: a_p before the barrier that completes L column p, b_p the wave's window work done, w_p
+    # after the window's closing barrier; then the last X row (xinv7 / post-xinv7: before / after its
+    # barrier) and the end of the tail (tail-done: the wave's share of the last X^T row stored or its z row
+    # formed; a library from before the rows left inside the windows: X^T stored, then z-done)
+    names = ["start", "pre-barrier", "post-barrier"] + [f"{x}{p}" for p in range(7) for x in ("a", "b", "w")] + [
+        "-", "-", "xinv7", "post-xinv7", "tail-done", "z-done", "syrk-issued", "-", "-"] + [f"{x}{t}" for t in range(8) for x in
                                                                    ("stg-ready", "stg-go")] + ["syrk-done"] + [
         "f4-upd-done", "f4-x-init", "f4-steps", "f4-stored", "f4-branch"]
     rkind = (raw[:, 2] >> np.uint64(56)).astype(np.int64)
@@ -112,14 +118,17 @@ def main():
         if not len(diag_rows):
             continue
         pos = int(diag_rows.max()) + 1
-        st = raw[pos:pos + 128].reshape(-1).reshape(8, 64).astype(np.int64)
+        st = np.zeros((16, 64), dtype=np.int64)
+        st[:nsw] = raw[pos:pos + 16 * nsw].reshape(-1).reshape(nsw, 64).astype(np.int64)
         if J in (0, 3):
             base = st[0, 0]
-            print(f"diag J={J} wg0 phase stamps (us from start), waves 0 / 1 / 4:")
+            # the wide workgroup's last wave stores the finished X rows and forms their z
+            waves = (0, 1, 4, 7, 15) if st[15, 1] else (0, 1, 4, 7)
+            print(f"diag J={J} wg0 phase stamps (us from start), waves {' / '.join(map(str, waves))}:")
             for k in [0, 30] + list(range(32, 49)) + list(range(1, 30)) + [54, 50, 51, 52, 53]:
                 if st[0, k] == 0 and st[1, k] == 0:
                     continue
-                vals = " ".join(f"{(st[w, k] - base) / 100.0:7.2f}" if st[w, k] else "      -" for w in (0, 1, 4))
+                vals = " ".join(f"{(st[w, k] - base) / 100.0:7.2f}" if st[w, k] else "      -" for w in waves)
                 print(f"  {names[k]:>12s} {vals}")
 
 
