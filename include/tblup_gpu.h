@@ -259,6 +259,47 @@ int tblup_snp_score_batch(tblup_ctx* ctx, int split_id, const int64_t* snps, int
                           double* score, double* info, double* q);
 
 /*
+ * Fixed-effect covariates in the fitted model: tblup_fit_batch with `n_cov` covariates (sex, herd, batch,
+ * ancestry PCs ..) fitted beside the genomic effects by generalised least squares on the same factor.
+ * cov is n x n_cov, row-major, one row per animal of the panel, 1 <= n_cov <= 16.  Per model b and trait t,
+ * with V, W_T, d, lambda and the branch's mu as tblup_snp_score_batch documents them,
+ *   y_T = mu 1 + Q~_T b + g + e,   Q~ = Q - 1 m^T
+ * with m_j the mean of column j over the train rows in split order under snp (then Q~_T^T 1 = 0 and
+ * V 1 = lambda 1: the intercept stays mean(y_T) and decouples) and m = 0 under gblup: no mean is fitted
+ * there unless the caller passes a column of ones, which is the way to fit one.  r_t = y_T,t - mu_t,
+ *   b_t = (Q~_T^T V^{-1} Q~_T)^{-1} Q~_T^T V^{-1} r_t      (the GLS estimate)
+ * and the genomic model is the branch's own model of the adjusted phenotype y*_t = y_t - Q~ b_t (every
+ * animal, train and validation alike):
+ *   fitness     : optional out (may be NULL), batch: the mean over traits of |pearson(ebv_V, y*_V)|, the
+ *                 predictive ability on phenotypes corrected for the fitted fixed effects
+ *   ebv         : optional out (may be NULL), batch x n_traits x n_valid: tblup_eval_batch's for phenotype y*
+ *   cov_effects : out, batch x n_traits x n_cov: b
+ *   cov_center  : out, batch x n_cov: m (all zero for a gblup model)
+ *   intercept / center / effects : optional as a triple (all NULL or none): tblup_fit_batch's for phenotype y*
+ * so that the value of an animal with genotype x and covariates q is
+ *   intercept[t] + sum_j (x[idx_j] - center[j]) effects[t][j] + sum_i (q_i - cov_center[i]) cov_effects[t][i].
+ * From the factor M = L L^T, S = L^{-1} R (one forward substitution with the covariates as one slab of 16
+ * right-hand sides), G = Q~^T V^{-1} Q~, h_t = Q~^T V^{-1} r_t:
+ *   kernel form (M = V):  R = Q~_T;  G = S^T S,  h_t = S^T z_t,  corrected z_t - S b_t
+ *   SNP form (M = W_T^T W_T / d + lambda I_k):  R = W_T^T Q~_T;  G = (Q~_T^T Q~_T - S^T S / d) / lambda,
+ *     h_t = (Q~_T^T r_t - S^T z_t) / lambda,  corrected z_t - S b_t / d
+ * b_t = G^{-1} h_t by an n_cov x n_cov Cholesky; then the back substitution, the prediction and the effects
+ * run a second time on the corrected z.  A pivot of G that is not positive (above 1e-12 of its own diagonal
+ * entry of G: a repeated column leaves rounding noise of either sign) and finite (collinear covariates;
+ * a column that is constant over the train rows under snp; h2 = 1 in the SNP form) gives NaN for every output
+ * of that model, as d = 0 does: not an error.  A NaN or Inf in cov, or n_cov outside [1, 16], is TBLUP_ERR_ARG.
+ * idx / offsets / h2 / branch, the index rules and errors and the chunking are tblup_fit_batch's; batch == 0
+ * returns 0 and writes nothing; a context without a panel gives TBLUP_ERR_STATE.  The call keeps no state in
+ * the context.  A model's bits depend neither on the other models of the batch (beyond the form they
+ * choose together), nor on the chunking, nor on where the right-hand sides live (TBLUP_SCORE_LDS): fixed-order
+ * sums, no atomics.  Host pointers, synchronous.
+ */
+#define TBLUP_MAX_COV 16
+int tblup_fit_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
+                        const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness, double* ebv,
+                        double* cov_effects, double* cov_center, double* intercept, double* center, double* effects);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

@@ -354,7 +354,7 @@ int64_t score_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_
 
 size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
                    bool with_ebv, bool with_model = false, int64_t n_rel = 0, int64_t n_h2 = 0,
-                   int64_t n_cand = 0) {
+                   int64_t n_cand = 0, int64_t n_cov = 0) {
   size_t s = 0;
   auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
   add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
@@ -395,6 +395,15 @@ size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int
     add((size_t)B * d.nt * 8);                                  // q
     add(score_in_lds(c, sd) ? 0                                 // right-hand sides / V of one launch's slabs
                             : (size_t)B * score_slabs(c, sd, B, n_cand) * sd.ns * SCORE_W * 8);
+  }
+  if (n_cov > 0) {                                              // tblup_fit_cov_batch:
+    add((size_t)2 * COVAR_W * d.nTp * 8);                       // the covariates of the train rows, both planes
+    add((size_t)2 * COVAR_W * d.nV * 8);                        // and of the validation rows
+    add((size_t)B * d.nt * n_cov * 8);                          // their fitted effects
+    add((size_t)B * d.nt * sd.ns * 8);                          // z of the adjusted phenotype
+    add((size_t)B * 8);                                         // the first pass's fitness (not returned)
+    add((size_t)B * d.nt * d.nV * 8);                           // the second solve's EBVs
+    add(score_in_lds(c, sd) ? 0 : (size_t)B * sd.ns * COVAR_W * 8);   // right-hand sides / V, one slab per model
   }
   if (n_h2 > 0) {                                               // tblup_loglik_batch, every pass of the chunk:
     add((size_t)n_h2 * B * 8);                                  // the h2 rows
@@ -1009,7 +1018,7 @@ int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64
 // pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
 int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
                                 double h2, int branch, double* fitness, double* ebv, const FitOut* fo,
-                                const RelOut* ro, const LogLikOut* lo, const ScoreOut* so) {
+                                const RelOut* ro, const LogLikOut* lo, const ScoreOut* so, const CovOut* co) {
   g_err.clear();
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
@@ -1021,16 +1030,40 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
   HIPCHK(hipSetDevice(c->device));
   HostEntry he(c);
   const EvalDims d = dims_of(c, *sp);
-  const bool want_ebv = ebv != nullptr;
+  const bool want_ebv = ebv != nullptr && !co;   // (the covariate model's EBVs come from its second solve)
   const int64_t n_rel = ro ? ro->n_pred : 0;
   const int64_t n_h2 = lo ? lo->n_h2 : 0;
   const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
   const bool rel_lds = reliab_in_lds(c, sd);
   const int64_t n_cand = so ? so->n_cand : 0;
   const bool sco_lds = score_in_lds(c, sd);
+  // tblup_fit_cov_batch: the covariates of the split's rows gathered once per call, covariate-major and
+  // zero-padded, as given (plane 0: gblup models) and centred by the column means over the train rows in
+  // split order (plane 1: snp models)
+  const int64_t n_cov = co ? co->n_cov : 0;
+  std::vector<double> cov_m((size_t)n_cov), h_qT, h_qV;
+  if (co) {
+    h_qT.assign((size_t)2 * COVAR_W * d.nTp, 0.0);
+    h_qV.assign((size_t)2 * COVAR_W * d.nV, 0.0);
+    for (int64_t j = 0; j < n_cov; ++j) {
+      long double acc = 0.0L;
+      for (int64_t i = 0; i < d.nT; ++i) acc += co->cov[sp->train[i] * n_cov + j];
+      const double m = cov_m[j] = (double)(acc / (long double)d.nT);
+      for (int64_t i = 0; i < d.nT; ++i) {
+        const double v = co->cov[sp->train[i] * n_cov + j];
+        h_qT[j * d.nTp + i] = v;
+        h_qT[(COVAR_W + j) * d.nTp + i] = v - m;
+      }
+      for (int64_t i = 0; i < d.nV; ++i) {
+        const double v = co->cov[sp->valid[i] * n_cov + j];
+        h_qV[j * d.nV + i] = v;
+        h_qV[(COVAR_W + j) * d.nV + i] = v - m;
+      }
+    }
+  }
   ChunkReq rq{sp, d, sd, c->stream, h2, branch};
   const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
-    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2, n_cand);
+    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2, n_cand, n_cov);
   };
   const int rc = for_each_chunk(c, offsets, batch, 65535, bytes, [&](const Chunk& ck) -> int {
     const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
@@ -1057,6 +1090,47 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
     if (n_cand) HIPCHK(hipMemcpyAsync(d_cand, so->snps, (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
     rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
     rq.d_fit = d_fit; rq.d_ebv = d_ebv;
+    if (co) {
+      // tblup_fit_cov_batch: the pipeline with the one-workgroup solve (nothing to recover), k_covar on
+      // the factor and z it leaves, then the solve, the fitness and the effects of the adjusted phenotype
+      // from the corrected z in a buffer of its own
+      const int nc = (int)n_cov;
+      double* d_qT = cv.take<double>(h_qT.size());
+      double* d_qV = cv.take<double>(h_qV.size());
+      double* d_b = cv.take<double>((size_t)B * d.nt * nc);
+      double* d_z2 = cv.take<double>((size_t)B * d.nt * sd.ns);
+      double* d_fit0 = cv.take<double>((size_t)B);
+      double* d_ebv2 = cv.take<double>((size_t)B * d.nt * d.nV);
+      double* d_cscr = sco_lds ? nullptr : cv.take<double>((size_t)B * sd.ns * COVAR_W);
+      if (int rc = ws_check(c, cv)) return rc;
+      const hipStream_t s = c->stream;
+      HIPCHK(hipMemcpyAsync(d_qT, h_qT.data(), h_qT.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(d_qV, h_qV.data(), h_qV.size() * 8, hipMemcpyHostToDevice, s));
+      Carve cvp = cv;
+      rq.mode = ChunkMode::NoChain;
+      rq.d_fit = d_fit0;
+      rq.d_ebv = nullptr;
+      ChunkRes res;
+      if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+      HIPCHK(launch_covar(res.cl, d_qT, nc, sco_lds, d_cscr, d_b, d_z2, s));
+      CholLaunch cl2 = res.cl;
+      cl2.z = d_z2;
+      HIPCHK(launch_solve(cl2, nullptr, d_fit0, d_ebv2, s));
+      HIPCHK(launch_cov_fitness(cl2, d_ebv2, d_qV, d_b, nc, d_fit, s));
+      if (fo) {
+        HIPCHK(launch_effects(cl2, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, s));
+        HIPCHK(hipMemcpyAsync(fo->center + offsets[b0], d_cen, (size_t)sum_k * 8, hipMemcpyDeviceToHost, s));
+        for (int t = 0; t < d.nt; ++t)
+          HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
+                                (size_t)sum_k * 8, hipMemcpyDeviceToHost, s));
+      }
+      HIPCHK(hipMemcpyAsync(co->cov_effects + b0 * d.nt * nc, d_b, (size_t)B * d.nt * nc * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+      if (ebv)
+        HIPCHK(hipMemcpyAsync(ebv + b0 * d.nt * d.nV, d_ebv2, (size_t)B * d.nt * d.nV * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+      return 0;
+    }
     if (lo) {
       // tblup_loglik_batch: the chunk's h2 columns up front, the n_h2 passes back to back (each the
       // pipeline at its row of per-system h2, then k_loglik on the factor it leaves -- like the effects,
@@ -1142,6 +1216,21 @@ int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, 
     for (int64_t b = 0; b < batch; ++b) {
       const int mode = branch ? branch : (offsets[b + 1] - offsets[b] > c->n ? 1 : 2);
       for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = mode == 2 ? sp->meanyT[t] : 0.0;
+    }
+  }
+  if (co) {
+    // cov_center: the train rows' column means under snp, 0 under gblup; a model whose covariate effects are
+    // NaN (d = 0, collinear covariates) is NaN in every output
+    const double nan = std::nan("");
+    for (int64_t b = 0; b < batch; ++b) {
+      const int mode = branch ? branch : (offsets[b + 1] - offsets[b] > c->n ? 1 : 2);
+      bool dead = false;
+      for (int64_t i = 0; i < d.nt * n_cov; ++i) dead = dead || std::isnan(co->cov_effects[b * d.nt * n_cov + i]);
+      for (int64_t j = 0; j < n_cov; ++j) co->cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cov_m[j] : 0.0);
+      if (dead && fo) {
+        for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = nan;
+        for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) fo->center[i] = nan;
+      }
     }
   }
   return c->profiling ? drain_events(c) : 0;

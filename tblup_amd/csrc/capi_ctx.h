@@ -218,11 +218,20 @@ struct ScoreOut {
   double* info;
   double* q;
 };
+// tblup_fit_cov_batch: the covariates cov [n][n_cov] row-major (already checked: finite, 1 <= n_cov <= COVAR_W)
+// and its host outputs cov_effects [batch][nt][n_cov] and cov_center [batch][n_cov]; fitness, ebv and fo are
+// then those of the phenotype adjusted for the fitted covariates
+struct CovOut {
+  const double* cov;
+  int64_t n_cov;
+  double* cov_effects;
+  double* cov_center;
+};
 // tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual;
 // ro != null: also the reliabilities of ro's animals under every individual's model; so != null: also the score statistics of so's
 // SNPs under every individual's model; lo != null: lo's passes instead of the one at h2 (no ebv / fo / ro /
-// so then)
+// so then); co != null: the covariate model (capi.hip; no ro / lo / so then)
 int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
                     int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr,
-                    const LogLikOut* lo = nullptr, const ScoreOut* so = nullptr);
+                    const LogLikOut* lo = nullptr, const ScoreOut* so = nullptr, const CovOut* co = nullptr);
 }  // namespace tblup_capi

@@ -1,8 +1,10 @@
 // C ABI of libtblup_gpu.so, taking the fitted model out (include/tblup_gpu.h): tblup_fit_batch
 // (the evaluation's chunks plus one k_effects launch each), tblup_predict_batch (k_predict),
-// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each) and
-// tblup_snp_score_batch (the chunks plus k_snpscore's launches each).
+// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each),
+// tblup_snp_score_batch (the chunks plus k_snpscore's launches each) and tblup_fit_cov_batch (the chunks plus
+// k_covar, a second solve, k_cov_fitness and k_effects each).
 #include <algorithm>
+#include <cmath>
 #include <string>
 #include <vector>
 
@@ -25,6 +27,31 @@ int tblup_fit_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_
   }
   const FitOut fo{intercept, center, effects};
   return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, &fo);
+}
+
+int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
+                        const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness, double* ebv,
+                        double* cov_effects, double* cov_center, double* intercept, double* center, double* effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
+  if (!cov) return fail(TBLUP_ERR_ARG, "null cov");
+  for (int64_t i = 0; i < c->n * n_cov; ++i)
+    if (!std::isfinite(cov[i])) return fail(TBLUP_ERR_ARG, "covariates must be finite");
+  const bool any = intercept || center || effects;
+  if (any && !(intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  if (batch > 0 && (!cov_effects || !cov_center)) return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
+  std::vector<double> fit_local;
+  if (!fitness && batch > 0) {
+    fit_local.resize((size_t)batch);
+    fitness = fit_local.data();
+  }
+  const FitOut fo{intercept, center, effects};
+  const CovOut co{cov, n_cov, cov_effects, cov_center};
+  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, ebv, any ? &fo : nullptr, nullptr,
+                         nullptr, nullptr, &co);
 }
 
 int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, int64_t n_pred, const int64_t* idx,

@@ -394,6 +394,26 @@ constexpr int SCORE_W = 16;
 hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand, bool lds,
                            int64_t S, double* vscr, double* score, double* info, double* q, hipStream_t s);
 
+// ---- launchers (k_covar.hip): fixed-effect covariates fitted by GLS from a chunk's factor ----
+// qT [2][COVAR_W][nTp] / qV [2][COVAR_W][nV]: the call's covariates of the split's train / validation rows,
+// covariate-major, plane 0 as given (gblup models), plane 1 centred by the column means over the train rows
+// (snp models); zero at padding rows and at columns past n_cov.  launch_covar: bhat[(b * nt + t) * n_cov + j]
+// the GLS effects under model b of the chunk whose pipeline left L, Dinv, z, u and scal in c, and
+// z2 [B][nt][ns] = L^-1 rhs of the adjusted phenotype (c.z is not written) -- one workgroup per model,
+// k_reliab's forward substitution (fwd_subst.h) on the covariates as one slab.  lds / vscr: as launch_snpscore
+// with one slab per model (ns x COVAR_W doubles per model in vscr).  NaN for a model with d = 0, a flagged
+// index or covariates that are collinear over the train rows.  launch_cov_fitness: fit[b] = the mean over
+// traits of |pearson(ebv_V, y_V - Q~_V b)| from ebv [B][nt][nV] (the solve on z2).
+constexpr int COVAR_W = 16;
+// a pivot of the covariates' Cholesky counts as positive above this fraction of its diagonal entry of
+// Q~^T V^-1 Q~ (1 - R^2 of the column on the earlier ones): below it the effects have no digit left at the
+// tests' 1e-9, and an exactly repeated column leaves rounding noise of either sign, ~1e-16 of the entry
+constexpr double COVAR_PIV_RTOL = 1e-12;
+hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, bool lds, double* vscr, double* bhat,
+                        double* z2, hipStream_t s);
+hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const double* qV, const double* bhat, int n_cov,
+                              double* fit, hipStream_t s);
+
 // ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
 // loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,
 // z and the scalars that the chunk's pipeline left in c (SNP form: also the split's yT / ymu); one

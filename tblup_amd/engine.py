@@ -154,15 +154,30 @@ class GpuBlupEngine:
         return (fit, ebv) if return_ebv else fit
 
     # ------------------------------------------------------- taking the model out
-    def fit(self, genomes, train, valid, h2, branch="auto", reliability_of=None):
+    def fit(self, genomes, train, valid, h2, branch="auto", reliability_of=None, covariates=None, return_ebv=False):
         """evaluate() plus what it fitted: one PanelModel per selected-index set (tblup_fit_batch),
         whose `fitness` is evaluate()'s value bit for bit.  Out-of-range indices raise
         TblupIndexError; a degenerate panel gives NaN effects, not an error.
         reliability_of: a list of animals (row ids of the panel) -- the return value is then
         (models, reliabilities) from one pass (tblup_reliability_batch), the models bit-identical to
-        fit()'s and the (len(genomes), len(animals)) array to reliability()'s."""
+        fit()'s and the (len(genomes), len(animals)) array to reliability()'s.
+        covariates: an (n_animals, c) float matrix Q of fixed-effect covariates, 1 <= c <= 16, one row per
+        animal of the panel (a 1-D array is one column) -- they are fitted beside the genomic effects by
+        GLS (tblup_fit_cov_batch; include/tblup_gpu.h has the model) and every model carries `cov_effects`
+        (nt, c) and `cov_center` (c,): the column means over the train rows under snp, zero under gblup,
+        where a mean is fitted only by a column of ones.  The models' effects, intercept and `fitness` are
+        then those of the adjusted phenotype y* = y - (Q - cov_center) cov_effects (PanelModel.adjust);
+        return_ebv=True also returns the validation EBVs of y*, (B, n_valid) or (B, nt, n_valid), as
+        (models, ebv).  Collinear covariates give a NaN model, not an error; NaN / Inf in Q is a ValueError.
+        Not combined with reliability_of."""
         from .model import PanelModel
         self._settle()
+        if covariates is not None:
+            if reliability_of is not None:
+                raise ValueError("reliability_of is not supported together with covariates")
+            return self._fit_cov(genomes, train, valid, h2, branch, covariates, return_ebv)
+        if return_ebv:
+            raise ValueError("return_ebv needs covariates (evaluate(return_ebv=True) gives the plain model's EBVs)")
         an = None
         if reliability_of is not None:
             an = _as_int64(reliability_of)
@@ -192,6 +207,47 @@ class GpuBlupEngine:
             models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
                                      fit[b]))
         return models if an is None else (models, rel)
+
+    def _covariates(self, covariates):
+        """The (n_animals, c) float64 matrix of a `covariates` argument, validated."""
+        q = np.asarray(covariates, dtype=np.float64)
+        if q.ndim == 1:
+            q = q[:, None]
+        if q.ndim != 2 or q.shape[0] != self.n_animals:
+            raise ValueError(f"covariates must have one row per animal ({self.n_animals}), got shape {q.shape}")
+        if not 1 <= q.shape[1] <= _native.MAX_COV:
+            raise ValueError(f"need 1 <= covariates <= {_native.MAX_COV}, got {q.shape[1]}")
+        if not np.all(np.isfinite(q)):
+            raise ValueError("covariates must be finite")
+        return np.ascontiguousarray(q)
+
+    def _fit_cov(self, genomes, train, valid, h2, branch, covariates, return_ebv):
+        from .model import PanelModel
+        q = self._covariates(covariates)
+        nc = q.shape[1]
+        sid = self.split_id(train, valid)
+        idx, offsets = concat_genomes(genomes)
+        B, nt, total, n_valid = len(genomes), self.n_traits, int(offsets[-1]), len(valid)
+        fit = np.empty(B, dtype=np.float64)
+        intercept = np.empty((B, nt), dtype=np.float64)
+        center = np.empty(total, dtype=np.float64)
+        effects = np.empty((nt, total), dtype=np.float64)
+        cov_eff = np.empty((B, nt, nc), dtype=np.float64)
+        cov_cen = np.empty((B, nc), dtype=np.float64)
+        ebv = np.empty((B, n_valid) if nt == 1 else (B, nt, n_valid), dtype=np.float64) if return_ebv else None
+        if B:
+            _native.check("tblup_fit_cov_batch", self._lib.tblup_fit_cov_batch(
+                self._ctx, sid, _ptr(q), nc, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit),
+                _ptr(ebv) if return_ebv else None, _ptr(cov_eff), _ptr(cov_cen), _ptr(intercept), _ptr(center),
+                _ptr(effects)))
+        wrapped = np.where(idx < 0, idx + self.n_snps, idx)
+        models = []
+        for b in range(B):
+            lo, hi = int(offsets[b]), int(offsets[b + 1])
+            fitted = branch if branch != "auto" else ("gblup" if hi - lo > self.n_animals else "snp")
+            models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
+                                     fit[b], cov_effects=cov_eff[b], cov_center=cov_cen[b]))
+        return (models, ebv) if return_ebv else models
 
     def reliability(self, genomes, train, valid, h2, animals, branch="auto"):
         """Reliability (squared accuracy, 1 - PEV / (sigma_g^2 K_aa)) of the genomic value of each of

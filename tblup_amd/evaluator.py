@@ -395,7 +395,7 @@ class BlupParallelEvaluator(ParallelEvaluator):
             valid = self.testing_indices if final else self.validation_indices
         return genomes, train, valid
 
-    def fit_models(self, population, final=True, train=None, valid=None, reliability_of=None):
+    def fit_models(self, population, final=True, train=None, valid=None, reliability_of=None, covariates=None):
         """The fitted model (tblup_amd.model.PanelModel) of every individual, in population order.
 
         final=True is evaluate_testing's set-up -- train = T u V, valid = the testing animals, the
@@ -404,9 +404,13 @@ class BlupParallelEvaluator(ParallelEvaluator):
         plain genome.  Explicit `train` / `valid` override either side of the split.
         reliability_of: a list of animals -- returns (models, reliabilities) from the same pass
         (GpuBlupEngine.fit).
+        covariates: an (animals, c) matrix of fixed-effect covariates, one row per animal of the evaluator's
+        data -- fitted beside the genomic effects (GpuBlupEngine.fit); not with reliability_of.
         Draws no RNG and uses no collective: under torch.distributed every rank fits the population
         it is given (call it on one rank, or with that rank's share)."""
         genomes, train, valid = self._model_setup(population, final, train, valid)
+        if covariates is not None:
+            return self.engine.fit(genomes, train, valid, self.h2, reliability_of=reliability_of, covariates=covariates)
         if reliability_of is None:
             return self.engine.fit(genomes, train, valid, self.h2)
         return self.engine.fit(genomes, train, valid, self.h2, reliability_of=reliability_of)

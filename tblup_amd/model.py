@@ -9,6 +9,10 @@ data[:, indices]),
 
 `predict` below is that formula in plain numpy, so a saved model needs neither the GPU nor the
 library to be applied to a genotype matrix.
+
+A model fitted with fixed-effect covariates (`GpuBlupEngine.fit(..., covariates=Q)`,
+tblup_fit_cov_batch) also carries their GLS effects and centre; the value of an animal with
+covariates q is then the genomic value above plus sum_i (q_i - cov_center[i]) * cov_effects[t][i].
 """
 import numpy as np
 
@@ -16,11 +20,13 @@ import numpy as np
 class PanelModel:
     """indices (k,) wrapped to [0, P); center (k,) = 2p of each column over the branch's reference
     rows; effects (nt, k); intercept (nt,); h2, branch ("gblup" / "snp": the branch that was fitted)
-    and the fit's validation fitness."""
+    and the fit's validation fitness.  cov_effects (nt, c) and cov_center (c,): the fitted fixed-effect
+    covariates, or None for a model without any."""
 
-    __slots__ = ("indices", "center", "effects", "intercept", "h2", "branch", "fitness")
+    __slots__ = ("indices", "center", "effects", "intercept", "h2", "branch", "fitness", "cov_effects", "cov_center")
 
-    def __init__(self, indices, center, effects, intercept, h2=float("nan"), branch="snp", fitness=float("nan")):
+    def __init__(self, indices, center, effects, intercept, h2=float("nan"), branch="snp", fitness=float("nan"),
+                 cov_effects=None, cov_center=None):
         idx = np.asarray(indices)
         if idx.ndim != 1 or idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
             raise ValueError("indices must be a non-empty 1-D integer array")
@@ -45,14 +51,56 @@ class PanelModel:
         self.h2 = float(h2)
         self.branch = branch
         self.fitness = float(fitness)
+        if (cov_effects is None) != (cov_center is None):
+            raise ValueError("cov_effects and cov_center are given together or not at all")
+        self.cov_effects = self.cov_center = None
+        if cov_effects is not None:
+            ce = np.asarray(cov_effects, dtype=np.float64)
+            if ce.ndim == 1:
+                ce = ce[None, :]
+            cc = np.ascontiguousarray(np.atleast_1d(np.asarray(cov_center, dtype=np.float64)))
+            if ce.ndim != 2 or ce.shape[0] != eff.shape[0] or ce.shape[1] < 1 or cc.shape != (ce.shape[1],):
+                raise ValueError(f"cov_effects must have shape ({eff.shape[0]}, c) and cov_center (c,), got "
+                                 f"{ce.shape} and {cc.shape}")
+            self.cov_effects, self.cov_center = np.ascontiguousarray(ce), cc
+
+    @property
+    def n_covariates(self):
+        return 0 if self.cov_effects is None else self.cov_effects.shape[1]
 
     @property
     def n_traits(self):
         return self.effects.shape[0]
 
-    def predict(self, genotypes):
+    def _cov_part(self, covariates, rows):
+        """(Q - cov_center) cov_effects^T as (n_traits, animals)."""
+        if self.cov_effects is None:
+            raise ValueError("the model was fitted without covariates")
+        q = np.asarray(covariates, dtype=np.float64)
+        if q.ndim == 1:
+            q = q[:, None]
+        if q.shape != (rows, self.n_covariates):
+            raise ValueError(f"covariates must have shape ({rows}, {self.n_covariates}), got {q.shape}")
+        return self.cov_effects @ (q - self.cov_center).T
+
+    def adjust(self, y, covariates):
+        """The phenotype adjusted for the fitted fixed effects, y* = y - (Q - cov_center) cov_effects: y is
+        (animals,) for one trait, else (animals, n_traits); covariates (animals, c).  Host numpy."""
+        y = np.asarray(y, dtype=np.float64)
+        part = self._cov_part(covariates, y.shape[0])
+        if y.ndim == 1:
+            if self.n_traits != 1:
+                raise ValueError("y must be (animals, n_traits)")
+            return y - part[0]
+        if y.ndim != 2 or y.shape[1] != self.n_traits:
+            raise ValueError("y must be (animals, n_traits)")
+        return y - part.T
+
+    def predict(self, genotypes, covariates=None):
         """EBVs of the rows of an (animals x P) {0,1,2} genotype matrix: (animals,) for one trait,
-        else (n_traits, animals) -- the shapes GpuBlupEngine.predict gives per model.  Host numpy."""
+        else (n_traits, animals) -- the shapes GpuBlupEngine.predict gives per model.  Host numpy.
+        covariates (animals, c): the fitted fixed effects (Q - cov_center) cov_effects are added (a model
+        fitted with covariates; without the argument it returns the genomic value and intercept alone)."""
         g = np.asarray(genotypes)
         if g.ndim != 2:
             raise ValueError("genotypes must be 2-D (animals x SNPs)")
@@ -60,18 +108,22 @@ class PanelModel:
             raise IndexError(f"index {int(self.indices.max())} is out of bounds for axis 1 with size {g.shape[1]}")
         xc = g[:, self.indices].astype(np.float64) - self.center
         out = self.effects @ xc.T + self.intercept[:, None]
+        if covariates is not None:
+            out = out + self._cov_part(covariates, g.shape[0])
         return out[0] if self.n_traits == 1 else out
 
     def save(self, path):
         """Write the model as an .npz (numpy appends the suffix when it is missing)."""
+        extra = {} if self.cov_effects is None else {"cov_effects": self.cov_effects, "cov_center": self.cov_center}
         np.savez(path, indices=self.indices, center=self.center, effects=self.effects, intercept=self.intercept,
-                 h2=np.float64(self.h2), branch=np.array(self.branch), fitness=np.float64(self.fitness))
+                 h2=np.float64(self.h2), branch=np.array(self.branch), fitness=np.float64(self.fitness), **extra)
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
+            cov = {k: z[k] for k in ("cov_effects", "cov_center") if k in z.files}   # (files without them: no covariates)
             return cls(z["indices"], z["center"], z["effects"], z["intercept"], float(z["h2"]), str(z["branch"]),
-                       float(z["fitness"]))
+                       float(z["fitness"]), **cov)
 
 
 class SnpScores:

@@ -20,10 +20,14 @@ numbers go to PERFLOG.md.  One JSON line per part:
            right-hand sides through the same substitution) and evaluate(), alternated in one process; the
            derived fp64 MFMA floor (batch x n_cand x ns^2 flop over the measured 72.7 TF/s peak); k_snpscore
            and k_reliab per launch come from a --stats run of this part
+  covar    config 2 again: fit(covariates=Q) with 16 covariates (tblup_fit_cov_batch) beside fit() (tblup_fit_batch)
+           and snp_scores() of 16 listed SNPs -- the same substitution, one slab per model -- alternated in one
+           process; k_covar beside k_snpscore, the second k_solve and k_cov_fitness per launch come from a
+           --stats run of this part
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -190,6 +194,37 @@ def score_vs_reliability(eng, genomes, T, V, n, P, ns, reps, n_cand=2000):
                     "kernels alone: --stats; the floors are derived (flop / measured fp64 MFMA peak)"}
 
 
+def covar_vs_fit(eng, genomes, T, V, n, P, reps, n_cov=16):
+    """fit(covariates=) with n_cov covariates against fit() and snp_scores() of n_cov listed SNPs (one slab per
+    model through the same substitution), alternated on one engine."""
+    rng = np.random.default_rng(77)
+    q = rng.standard_normal((n, n_cov))
+    q[:, 0] = rng.random(n) < 0.5
+    cand = rng.choice(P, n_cov, replace=False)
+    tf, tc, ts = [], [], []
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        plain = eng.fit(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        models = eng.fit(genomes, T, V, 0.4, covariates=q)
+        t.append(time.perf_counter())
+        eng.snp_scores(genomes, T, V, 0.4, cand)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for lst, i in ((tf, 0), (tc, 1), (ts, 2)):
+                lst.append(t[i + 1] - t[i])
+    return {"fit_ms": med_ms(tf), "fit_cov_ms": med_ms(tc), "score_16_ms": med_ms(ts), "n_cov": n_cov,
+            "extra_ms_over_fit": round(med_ms(tc) - med_ms(tf), 4),
+            "fit_ms_all": [round(x * 1e3, 3) for x in tf], "fit_cov_ms_all": [round(x * 1e3, 3) for x in tc],
+            "score_16_ms_all": [round(x * 1e3, 3) for x in ts],
+            "finite": bool(all(np.all(np.isfinite(m.cov_effects)) for m in models)),
+            "fitness_plain_median": float(np.median([m.fitness for m in plain])),
+            "fitness_cov_median": float(np.median([m.fitness for m in models])),
+            "note": "each call is the whole evaluation plus its kernels, the D2H copies and the PanelModel objects; "
+                    "the covariate call runs the one-workgroup k_solve twice (no chained solve); the kernels alone: "
+                    "--stats"}
+
+
 def loglik_vs_eval(eng, genomes, T, V, reps, grid_n=8):
     """tblup_eval_batch against tblup_loglik_batch at 1 and grid_n grid points (the C entries, alternated),
     then one estimate_h2 with the defaults."""
@@ -247,7 +282,7 @@ def stats_share(path):
     out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
     for r in rows:
         name = r["Name"]
-        for key in ("k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -307,6 +342,13 @@ def main():
         with GpuBlupEngine(geno, pheno) as eng:
             st = score_vs_reliability(eng, genomes, T, V, n, P, 1024, args.reps)
             print(json.dumps({"part": "score", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **st}))
+    if "covar" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            st = covar_vs_fit(eng, genomes, T, V, n, P, args.reps)
+            print(json.dumps({"part": "covar", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **st}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
