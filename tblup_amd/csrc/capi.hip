@@ -1,9 +1,10 @@
 // C ABI of libtblup_gpu.so (see include/tblup_gpu.h): context, splits, workspace,
 // batched evaluation pipeline and per-kernel-class event timing.
 //
-// Pipeline per chunk of B individuals (one HIP stream, no host syncs inside):
+// Pipeline per chunk of B individuals (run_chunk: one HIP stream, no host syncs inside):
 //   k_indiv_stats -> k_gather -> k_grm -> for J: (k_chol_diag, k_chol_offdiag) -> k_solve
-//   (tblup_fit_batch: -> k_effects, on the factor and z the pipeline leaves in the workspace)
+// The host entries' driver (capi_ctx.h) and tblup_eval_batch are here; the entries that read the factor the
+// pipeline leaves are in capi_model.hip.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -338,82 +339,6 @@ bool use_last_term(const tblup_ctx* c, const SysDims& sd, int64_t B) { return la
 // there the all-launches mask (~1u, J >= 1) keeps its meaning while a sparse mask names none
 inline bool lt_bit(uint32_t m, int J) { return J < 32 ? ((m >> J) & 1u) != 0 : m == ~1u; }
 
-// k_reliab keeps a slab's right-hand sides in LDS (else in workspace slices, reliab_slabs at a time)
-bool reliab_in_lds(const tblup_ctx* c, const SysDims& sd) { return c->reliab_lds && reliab_lds(sd); }
-// slabs of the animal list per k_reliab launch: all of them, or what a quarter of the workspace budget
-// (at most RELIAB_SCRATCH) holds of their workspace slices -- never less than one slab per model
-int64_t rel_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_rel) {
-  return reliab_slabs(sd, B, n_rel, reliab_in_lds(c, sd), std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(c->budget / 4)));
-}
-
-// the same for k_snpscore (TBLUP_SCORE_LDS) and the SNP list of tblup_snp_score_batch
-bool score_in_lds(const tblup_ctx* c, const SysDims& sd) { return c->score_lds && reliab_lds(sd); }
-int64_t score_slabs(const tblup_ctx* c, const SysDims& sd, int64_t B, int64_t n_cand) {
-  return reliab_slabs(sd, B, n_cand, score_in_lds(c, sd), std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(c->budget / 4)));
-}
-
-size_t chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv, bool with_model = false, int64_t n_rel = 0, int64_t n_h2 = 0,
-                   int64_t n_cand = 0, int64_t n_cov = 0) {
-  size_t s = 0;
-  auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
-  add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
-  add((size_t)B * sd.prow * 8);                                 // u
-  add((size_t)B * SCAL * 8);                                    // scal
-  add((size_t)B * l_stride(sd.NT) * 8);                         // L (Lt tiles)
-  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // Dinv (packed X)
-  add((size_t)B * d.nt * sd.ns * 8);                            // z
-  add((size_t)B * d.nt * sd.ns * 8);                            // w
-  add((size_t)B * d.nt * sd.ns * 8);                            // rhs
-  add((size_t)B * TBLUP_NSLOT * 36 * 256 * 8);                  // next diagonal tile (minus its last SYRK term)
-  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // diagonal GRM tiles
-  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * KD_TILE * 2 : 0);  // their int16 counts (k_sys_tiles)
-  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * (sd.NT - 1) / 2 * KC_TILE * 2 : 0);   // off-diagonal counts
-  add(uses_part(c, B, sd.NT, sys_tiles(c, d, sd)) ? (size_t)2 * B * sd.NT * TILE * TILE * 8 : 0);   // partial sums
-  if (use_chain(c, sd, B, d.nt)) {                                    // chained solve: beta, c_{J->I}, EBV shares
-    add((size_t)B * d.nt * sd.ns * 8);
-    add((size_t)B * sd.NT * sd.NT * d.nt * TILE * 8);
-    add((size_t)B * sd.NT * d.nt * d.nV * 8);
-    add((size_t)B * sd.NT * d.nt * 8);
-  }
-  add(use_last_term(c, sd, B) ? (size_t)B * NPACK * BLKD * 8 : 0);   // diagonal tiles' last SYRK terms
-  add((size_t)B * 8);                                           // fitness
-  add(with_ebv ? (size_t)B * d.nt * d.nV * 8 : 0);              // ebv
-  add((size_t)sum_k * 8 + (size_t)(B + 1) * 8);                 // idx, off
-  add(with_model ? (size_t)sum_k * 8 : 0);                      // the fitted models' centres
-  add(with_model ? (size_t)d.nt * sum_k * 8 : 0);               // and effects (tblup_fit_batch)
-  if (n_rel > 0) {                                              // tblup_reliability_batch:
-    add((size_t)n_rel * 4);                                     // the animal list
-    add((size_t)B * n_rel * 8);                                 // the reliabilities
-    add(reliab_in_lds(c, sd) ? 0                                // right-hand sides / V of one launch's slabs
-                             : (size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W * 8);
-  }
-  if (n_cand > 0) {                                             // tblup_snp_score_batch:
-    add((size_t)n_cand * 4);                                    // the SNP list
-    add((size_t)B * d.nt * n_cand * 8);                         // scores
-    add((size_t)B * n_cand * 8);                                // information
-    add((size_t)B * d.nt * 8);                                  // q
-    add(score_in_lds(c, sd) ? 0                                 // right-hand sides / V of one launch's slabs
-                            : (size_t)B * score_slabs(c, sd, B, n_cand) * sd.ns * SCORE_W * 8);
-  }
-  if (n_cov > 0) {                                              // tblup_fit_cov_batch:
-    add((size_t)2 * COVAR_W * d.nTp * 8);                       // the covariates of the train rows, both planes
-    add((size_t)2 * COVAR_W * d.nV * 8);                        // and of the validation rows
-    add((size_t)B * d.nt * n_cov * 8);                          // their fitted effects
-    add((size_t)B * d.nt * sd.ns * 8);                          // z of the adjusted phenotype
-    add((size_t)B * 8);                                         // the first pass's fitness (not returned)
-    add((size_t)B * d.nt * d.nV * 8);                           // the second solve's EBVs
-    add(score_in_lds(c, sd) ? 0 : (size_t)B * sd.ns * COVAR_W * 8);   // right-hand sides / V, one slab per model
-  }
-  if (n_h2 > 0) {                                               // tblup_loglik_batch, every pass of the chunk:
-    add((size_t)n_h2 * B * 8);                                  // the h2 rows
-    add((size_t)n_h2 * B * 8);                                  // the passes' fitnesses
-    add((size_t)n_h2 * B * d.nt * 8);                           // log-likelihoods
-    add((size_t)n_h2 * B * d.nt * 8);                           // sigma2_g
-  }
-  return s + 4096;
-}
-
 EvalDims dims_of(const tblup_ctx* c, const Split& sp) {
   EvalDims d;
   d.n = c->n;
@@ -439,8 +364,7 @@ SysDims choose_sys(const tblup_ctx* c, const EvalDims& d, const int64_t* h_off, 
   for (int64_t b = 0; b < B; ++b) {
     const int64_t k = h_off[b + 1] - h_off[b];
     max_k = std::max(max_k, k);
-    const int mode = branch ? branch : (k > c->n ? 1 : 2);   // evaluator.py:257
-    if (mode != 2) all_snp = false;
+    if (branch_of(c, k, branch) != 2) all_snp = false;
   }
   const int64_t kp = round_up(max_k, TILE);
   // equal tile counts (kp == nTp, e.g. k = 1000 against a 1024-animal CV fold) also take the SNP
@@ -480,47 +404,55 @@ FoldTab single_fold(const Split& sp, int64_t B) {
   return ft;
 }
 
-enum class ChunkMode {
-  Full,        // the whole pipeline
-  DebugK,      // debug readback: the pipeline up to the full K block (k_grm)
-  DebugL,      // debug readback: the pipeline up to the factor L and z
-  SolveOnly,   // the solve only, through the one-workgroup k_solve, on the factor an earlier run_chunk
-               // of the same chunk left in the same carve (host entries, after that run's chained
-               // solve gave up a wait: bit-identical results)
-  NoChain,     // the whole pipeline with the one-workgroup k_solve instead of the chained solve (a
-               // per-call choice: the context's policy is not touched)
-};
+// Host entries, after the chunk's stream synchronisation: whether one of the chained solves `seqs`
+// (0: none) gave up a wait.  Its ring slot holds seq exactly then (slots of other calls hold their own seqs).
+int chain_expired(tblup_ctx* c, const std::vector<int32_t>& seqs, bool* out) {
+  *out = false;
+  for (int32_t seq : seqs) {
+    if (seq <= 0 || !c->chain.p) continue;
+    const int32_t* ring = (const int32_t*)c->chain.p + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
+    int32_t v = 0;
+    HIPCHK(hipMemcpyAsync(&v, ring + seq % CHAIN_ERR_RING, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out = *out || v == seq;
+  }
+  return 0;
+}
 
-// One chunk whose idx/off already sit in device memory, as run_chunk enqueues it.  An entry fixes the
-// first six members once (ChunkReq rq{sp, d, sd, s, h2, branch}: six distinct types); the chunk's
-// pointers, B and the mode are set by name.
-struct ChunkReq {
-  const Split* sp;
-  EvalDims d;
-  SysDims sd;
-  hipStream_t s;
-  double h2;
-  int branch;
-  const int64_t *d_idx = nullptr, *d_off = nullptr;
-  const int64_t* h_off = nullptr;   // host copy of the offsets (work accounting and shapes)
-  int64_t B = 0;
-  double* d_fit = nullptr;       // [B] fitness
-  double* d_ebv = nullptr;       // [B][nt][nV], if wanted
-  const FoldTab* ft = nullptr;   // the systems' splits when they are not all sp (fold-fused evaluation;
-                                 // sp is then fold 0)
-  ChunkMode mode = ChunkMode::Full;
-  const double* d_h2 = nullptr;  // [B] per-system h2 on the device (tblup_loglik_batch); null: h2
-};
+}  // namespace
 
-struct ChunkRes {
-  int32_t chain_seq = 0;    // seq of the chained solve this run enqueued, 0 if none
-  double* K = nullptr;      // debug readbacks: the K block (DebugK), else the factor L
-  double* z = nullptr;
-  CholLaunch cl{};          // the chunk's buffers, for a launch after the pipeline (launch_effects)
-};
+size_t tblup_capi::chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
+                               bool with_ebv) {
+  size_t s = 0;
+  auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
+  add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
+  add((size_t)B * sd.prow * 8);                                 // u
+  add((size_t)B * SCAL * 8);                                    // scal
+  add((size_t)B * l_stride(sd.NT) * 8);                         // L (Lt tiles)
+  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // Dinv (packed X)
+  add((size_t)B * d.nt * sd.ns * 8);                            // z
+  add((size_t)B * d.nt * sd.ns * 8);                            // w
+  add((size_t)B * d.nt * sd.ns * 8);                            // rhs
+  add((size_t)B * TBLUP_NSLOT * 36 * 256 * 8);                  // next diagonal tile (minus its last SYRK term)
+  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // diagonal GRM tiles
+  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * KD_TILE * 2 : 0);  // their int16 counts (k_sys_tiles)
+  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * (sd.NT - 1) / 2 * KC_TILE * 2 : 0);   // off-diagonal counts
+  add(uses_part(c, B, sd.NT, sys_tiles(c, d, sd)) ? (size_t)2 * B * sd.NT * TILE * TILE * 8 : 0);   // partial sums
+  if (use_chain(c, sd, B, d.nt)) {                                    // chained solve: beta, c_{J->I}, EBV shares
+    add((size_t)B * d.nt * sd.ns * 8);
+    add((size_t)B * sd.NT * sd.NT * d.nt * TILE * 8);
+    add((size_t)B * sd.NT * d.nt * d.nV * 8);
+    add((size_t)B * sd.NT * d.nt * 8);
+  }
+  add(use_last_term(c, sd, B) ? (size_t)B * NPACK * BLKD * 8 : 0);   // diagonal tiles' last SYRK terms
+  add((size_t)B * 8);                                           // fitness
+  add(with_ebv ? (size_t)B * d.nt * d.nV * 8 : 0);              // ebv
+  add((size_t)sum_k * 8 + (size_t)(B + 1) * 8);                 // idx, off
+  return s + 4096;
+}
 
 // Enqueue the pipeline for one chunk (no host synchronisation unless the chain flags must grow).
-int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
+int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
   const EvalDims& d = rq.d;
   const SysDims& sd = rq.sd;
   const hipStream_t s = rq.s;
@@ -733,27 +665,7 @@ int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
   return timed(c, s, KC_SOLVE, fs, bs, [&] { return launch_solve(cl, chp, rq.d_fit, rq.d_ebv, s); });
 }
 
-// Host entries, after the chunk's stream synchronisation: whether one of the chained solves `seqs`
-// (0: none) gave up a wait.  Its ring slot holds seq exactly then (slots of other calls hold their own seqs).
-int chain_expired(tblup_ctx* c, const std::vector<int32_t>& seqs, bool* out) {
-  *out = false;
-  for (int32_t seq : seqs) {
-    if (seq <= 0 || !c->chain.p) continue;
-    const int32_t* ring = (const int32_t*)c->chain.p + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
-    int32_t v = 0;
-    HIPCHK(hipMemcpyAsync(&v, ring + seq % CHAIN_ERR_RING, 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    *out = *out || v == seq;
-  }
-  return 0;
-}
-
-// A host entry's chunk with recovery.  enqueue(redo, seqs) enqueues one pass on the context's stream --
-// its launches and the copies of the results to the host -- and lists the chained solves it enqueued.
-// Pass 0 (redo false) is the chunk as usual; when one of its chained solves gave up a wait, the pass
-// is enqueued once more with redo set (the entry solves through k_solve then) and the chunk counted.
-template <typename Enqueue>
-int run_recovering(tblup_ctx* c, Enqueue&& enqueue) {
+int tblup_capi::run_recovering(tblup_ctx* c, const std::function<int(bool, std::vector<int32_t>&)>& enqueue) {
   std::vector<int32_t> seqs;
   for (int pass = 0;; ++pass) {
     seqs.clear();
@@ -765,6 +677,8 @@ int run_recovering(tblup_ctx* c, Enqueue&& enqueue) {
     ++c->chain_recoveries;
   }
 }
+
+namespace {
 
 // Device entries: the workspace grown to `need` bytes.  Large enough already: no synchronisation (the
 // entries are asynchronous); else it may still be in use by earlier work on either stream.
@@ -1007,236 +921,80 @@ static int validate_batch(tblup_ctx* c, int branch, double h2, const int64_t* of
   return 0;
 }
 
-int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
-                     double h2, int branch, double* fitness, double* ebv) {
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, ebv, nullptr);
-}
-
 }  // extern "C"
 
-// tblup_eval_batch, and with `fo` tblup_fit_batch (capi_model.hip): the same chunks through the same
-// pipeline, plus one k_effects launch per chunk on the factor the pipeline leaves behind.
-int tblup_capi::eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
-                                double h2, int branch, double* fitness, double* ebv, const FitOut* fo,
-                                const RelOut* ro, const LogLikOut* lo, const ScoreOut* so, const CovOut* co) {
-  g_err.clear();
+int tblup_capi::open_host_batch(HostBatch& hb, tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets,
+                                int64_t batch, double h2, int branch, bool have_fitness) {
+  hb = HostBatch{};
   if (int rc = check_ctx(c)) return rc;
   if (int rc = validate_batch(c, branch, h2, offsets, batch)) return rc;
   if (batch == 0) return 0;
-  if (!idx || (!fitness && !lo)) return fail(TBLUP_ERR_ARG, "null idx/fitness");
+  if (!idx || !have_fitness) return fail(TBLUP_ERR_ARG, "null idx/fitness");
   Split* sp = find_split(c, split_id);
   if (!sp) return fail(TBLUP_ERR_ARG, "unknown split id");
   if (int rc = check_indices(c, idx, offsets[batch])) return rc;
   HIPCHK(hipSetDevice(c->device));
-  HostEntry he(c);
   const EvalDims d = dims_of(c, *sp);
-  const bool want_ebv = ebv != nullptr && !co;   // (the covariate model's EBVs come from its second solve)
-  const int64_t n_rel = ro ? ro->n_pred : 0;
-  const int64_t n_h2 = lo ? lo->n_h2 : 0;
-  const SysDims sd = choose_sys(c, d, offsets, batch, branch, c->form_pref);
-  const bool rel_lds = reliab_in_lds(c, sd);
-  const int64_t n_cand = so ? so->n_cand : 0;
-  const bool sco_lds = score_in_lds(c, sd);
-  // tblup_fit_cov_batch: the covariates of the split's rows gathered once per call, covariate-major and
-  // zero-padded, as given (plane 0: gblup models) and centred by the column means over the train rows in
-  // split order (plane 1: snp models)
-  const int64_t n_cov = co ? co->n_cov : 0;
-  std::vector<double> cov_m((size_t)n_cov), h_qT, h_qV;
-  if (co) {
-    h_qT.assign((size_t)2 * COVAR_W * d.nTp, 0.0);
-    h_qV.assign((size_t)2 * COVAR_W * d.nV, 0.0);
-    for (int64_t j = 0; j < n_cov; ++j) {
-      long double acc = 0.0L;
-      for (int64_t i = 0; i < d.nT; ++i) acc += co->cov[sp->train[i] * n_cov + j];
-      const double m = cov_m[j] = (double)(acc / (long double)d.nT);
-      for (int64_t i = 0; i < d.nT; ++i) {
-        const double v = co->cov[sp->train[i] * n_cov + j];
-        h_qT[j * d.nTp + i] = v;
-        h_qT[(COVAR_W + j) * d.nTp + i] = v - m;
-      }
-      for (int64_t i = 0; i < d.nV; ++i) {
-        const double v = co->cov[sp->valid[i] * n_cov + j];
-        h_qV[j * d.nV + i] = v;
-        h_qV[(COVAR_W + j) * d.nV + i] = v - m;
-      }
-    }
-  }
-  ChunkReq rq{sp, d, sd, c->stream, h2, branch};
+  hb = HostBatch{c, sp, d, choose_sys(c, d, offsets, batch, branch, c->form_pref), idx, offsets, batch, h2, branch};
+  return 0;
+}
+
+int tblup_capi::run_host_batch(const HostBatch& hb, bool with_ebv, const ChunkCarve& carve, const ChunkBody& body) {
+  tblup_ctx* c = hb.c;
+  HostEntry he(c);
+  ChunkReq rq{hb.sp, hb.d, hb.sd, c->stream, hb.h2, hb.branch};
   const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
-    return chunk_bytes(c, d, sd, B, sum_k, want_ebv, fo != nullptr, n_rel, n_h2, n_cand, n_cov);
+    Carve own{nullptr};
+    if (carve) carve(own, B, sum_k);
+    return chunk_bytes(c, hb.d, hb.sd, B, sum_k, with_ebv) + (size_t)round_up((int64_t)own.used, 256);
   };
-  const int rc = for_each_chunk(c, offsets, batch, 65535, bytes, [&](const Chunk& ck) -> int {
-    const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
+  const int rc = for_each_chunk(c, hb.offsets, hb.batch, 65535, bytes, [&](const Chunk& ck) -> int {
     Carve cv{(char*)c->ws.p};
     int64_t *d_idx, *d_off;
-    if (int rc = upload_chunk(c, cv, idx, offsets, ck, &d_idx, &d_off)) return rc;
-    double* d_fit = cv.take<double>((size_t)B);
-    double* d_ebv = want_ebv ? cv.take<double>((size_t)B * d.nt * d.nV) : nullptr;
-    double* d_cen = fo ? cv.take<double>((size_t)sum_k) : nullptr;
-    double* d_eff = fo ? cv.take<double>((size_t)d.nt * sum_k) : nullptr;
-    int32_t* d_an = n_rel ? cv.take<int32_t>((size_t)n_rel) : nullptr;
-    double* d_rel = n_rel ? cv.take<double>((size_t)B * n_rel) : nullptr;
-    double* d_vscr = (n_rel && !rel_lds)
-                         ? cv.take<double>((size_t)B * rel_slabs(c, sd, B, n_rel) * sd.ns * RELIAB_W)
-                         : nullptr;
-    if (n_rel) HIPCHK(hipMemcpyAsync(d_an, ro->animals, (size_t)n_rel * 4, hipMemcpyHostToDevice, c->stream));
-    int32_t* d_cand = n_cand ? cv.take<int32_t>((size_t)n_cand) : nullptr;
-    double* d_sco = n_cand ? cv.take<double>((size_t)B * d.nt * n_cand) : nullptr;
-    double* d_inf = n_cand ? cv.take<double>((size_t)B * n_cand) : nullptr;
-    double* d_q = n_cand ? cv.take<double>((size_t)B * d.nt) : nullptr;
-    double* d_sscr = (n_cand && !sco_lds)
-                         ? cv.take<double>((size_t)B * score_slabs(c, sd, B, n_cand) * sd.ns * SCORE_W)
-                         : nullptr;
-    if (n_cand) HIPCHK(hipMemcpyAsync(d_cand, so->snps, (size_t)n_cand * 4, hipMemcpyHostToDevice, c->stream));
-    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
-    rq.d_fit = d_fit; rq.d_ebv = d_ebv;
-    if (co) {
-      // tblup_fit_cov_batch: the pipeline with the one-workgroup solve (nothing to recover), k_covar on
-      // the factor and z it leaves, then the solve, the fitness and the effects of the adjusted phenotype
-      // from the corrected z in a buffer of its own
-      const int nc = (int)n_cov;
-      double* d_qT = cv.take<double>(h_qT.size());
-      double* d_qV = cv.take<double>(h_qV.size());
-      double* d_b = cv.take<double>((size_t)B * d.nt * nc);
-      double* d_z2 = cv.take<double>((size_t)B * d.nt * sd.ns);
-      double* d_fit0 = cv.take<double>((size_t)B);
-      double* d_ebv2 = cv.take<double>((size_t)B * d.nt * d.nV);
-      double* d_cscr = sco_lds ? nullptr : cv.take<double>((size_t)B * sd.ns * COVAR_W);
-      if (int rc = ws_check(c, cv)) return rc;
-      const hipStream_t s = c->stream;
-      HIPCHK(hipMemcpyAsync(d_qT, h_qT.data(), h_qT.size() * 8, hipMemcpyHostToDevice, s));
-      HIPCHK(hipMemcpyAsync(d_qV, h_qV.data(), h_qV.size() * 8, hipMemcpyHostToDevice, s));
-      Carve cvp = cv;
-      rq.mode = ChunkMode::NoChain;
-      rq.d_fit = d_fit0;
-      rq.d_ebv = nullptr;
-      ChunkRes res;
-      if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-      HIPCHK(launch_covar(res.cl, d_qT, nc, sco_lds, d_cscr, d_b, d_z2, s));
-      CholLaunch cl2 = res.cl;
-      cl2.z = d_z2;
-      HIPCHK(launch_solve(cl2, nullptr, d_fit0, d_ebv2, s));
-      HIPCHK(launch_cov_fitness(cl2, d_ebv2, d_qV, d_b, nc, d_fit, s));
-      if (fo) {
-        HIPCHK(launch_effects(cl2, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, s));
-        HIPCHK(hipMemcpyAsync(fo->center + offsets[b0], d_cen, (size_t)sum_k * 8, hipMemcpyDeviceToHost, s));
-        for (int t = 0; t < d.nt; ++t)
-          HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
-                                (size_t)sum_k * 8, hipMemcpyDeviceToHost, s));
-      }
-      HIPCHK(hipMemcpyAsync(co->cov_effects + b0 * d.nt * nc, d_b, (size_t)B * d.nt * nc * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-      if (ebv)
-        HIPCHK(hipMemcpyAsync(ebv + b0 * d.nt * d.nV, d_ebv2, (size_t)B * d.nt * d.nV * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
-      return 0;
-    }
-    if (lo) {
-      // tblup_loglik_batch: the chunk's h2 columns up front, the n_h2 passes back to back (each the
-      // pipeline at its row of per-system h2, then k_loglik on the factor it leaves -- like the effects,
-      // without waiting for the solve), the results of every pass copied out behind the last
-      const size_t row = (size_t)B * 8, rowt = row * d.nt;
-      double* d_h2 = cv.take<double>((size_t)n_h2 * B);
-      double* d_fits = cv.take<double>((size_t)n_h2 * B);
-      double* d_ll = cv.take<double>((size_t)n_h2 * B * d.nt);
-      double* d_s2 = cv.take<double>((size_t)n_h2 * B * d.nt);
-      if (int rc = ws_check(c, cv)) return rc;
-      HIPCHK(hipMemcpy2DAsync(d_h2, row, lo->h2 + b0, (size_t)batch * 8, row, (size_t)n_h2, hipMemcpyHostToDevice,
-                              c->stream));
-      return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
-        // redo: a chained solve of some pass gave up a wait -- the factors of all but the last pass are
-        // gone, so every pass runs again whole with the one-workgroup k_solve (the same bits), for the
-        // fitnesses only
-        for (int64_t g = 0; g < n_h2; ++g) {
-          Carve cvp = cv;
-          rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
-          rq.d_h2 = d_h2 + g * B;
-          rq.d_fit = d_fits + g * B;
-          ChunkRes res;
-          if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-          seqs.push_back(res.chain_seq);
-          if (!redo) HIPCHK(launch_loglik(res.cl, d_ll + g * B * d.nt, d_s2 + g * B * d.nt, c->stream));
-        }
-        if (fitness)
-          HIPCHK(hipMemcpy2DAsync(fitness + b0, (size_t)batch * 8, d_fits, row, row, (size_t)n_h2,
-                                  hipMemcpyDeviceToHost, c->stream));
-        if (!redo) {
-          HIPCHK(hipMemcpy2DAsync(lo->loglik + b0 * d.nt, (size_t)batch * d.nt * 8, d_ll, rowt, rowt, (size_t)n_h2,
-                                  hipMemcpyDeviceToHost, c->stream));
-          if (lo->sigma2)
-            HIPCHK(hipMemcpy2DAsync(lo->sigma2 + b0 * d.nt, (size_t)batch * d.nt * 8, d_s2, rowt, rowt, (size_t)n_h2,
-                                    hipMemcpyDeviceToHost, c->stream));
-        }
-        return 0;
-      });
-    }
-    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
-      // redo: the chained solve of pass 0 gave up a wait -- the same factor, solved by k_solve
-      Carve cvp = cv;
-      rq.mode = redo ? ChunkMode::SolveOnly : ChunkMode::Full;
-      ChunkRes res;
-      if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-      seqs.push_back(res.chain_seq);
-      if (fo && !redo) {
-        // neither solve kernel writes L, the diagonal inverses or z: the effects do not wait for the
-        // chained solve's verdict (a recovery pass re-solves for the fitness only)
-        HIPCHK(launch_effects(res.cl, (const int32_t*)c->colsum_all.p, d_cen, d_eff, sum_k, c->stream));
-        HIPCHK(hipMemcpyAsync(fo->center + offsets[b0], d_cen, (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
-        for (int t = 0; t < d.nt; ++t)
-          HIPCHK(hipMemcpyAsync(fo->effects + (int64_t)t * offsets[batch] + offsets[b0], d_eff + (int64_t)t * sum_k,
-                                (size_t)sum_k * 8, hipMemcpyDeviceToHost, c->stream));
-      }
-      if (n_rel && !redo) {
-        // like the effects: L, the diagonal inverses, u and the scalars only, so no wait for the solve
-        HIPCHK(launch_reliab(res.cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, d_an, n_rel,
-                             rel_lds, rel_slabs(c, sd, B, n_rel), d_vscr, d_rel, c->stream));
-        HIPCHK(hipMemcpyAsync(ro->reliability + b0 * n_rel, d_rel, (size_t)B * n_rel * 8, hipMemcpyDeviceToHost,
-                              c->stream));
-      }
-      if (n_cand && !redo) {
-        // like the reliabilities: L, the diagonal inverses, z, u and the scalars only, beside the first pass
-        HIPCHK(launch_snpscore(res.cl, (const int32_t*)c->colsum_all.p, d_cand, n_cand, sco_lds,
-                               score_slabs(c, sd, B, n_cand), d_sscr, d_sco, d_inf, d_q, c->stream));
-        HIPCHK(hipMemcpyAsync(so->score + b0 * d.nt * n_cand, d_sco, (size_t)B * d.nt * n_cand * 8,
-                              hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(so->info + b0 * n_cand, d_inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, c->stream));
-        if (so->q)
-          HIPCHK(hipMemcpyAsync(so->q + b0 * d.nt, d_q, (size_t)B * d.nt * 8, hipMemcpyDeviceToHost, c->stream));
-      }
-      HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
-      if (want_ebv)
-        HIPCHK(hipMemcpyAsync(ebv + b0 * d.nt * d.nV, d_ebv, (size_t)B * d.nt * d.nV * 8, hipMemcpyDeviceToHost,
-                              c->stream));
-      return 0;
-    });
+    if (int rc = upload_chunk(c, cv, hb.idx, hb.offsets, ck, &d_idx, &d_off)) return rc;
+    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = ck.B;
+    rq.d_fit = cv.take<double>((size_t)ck.B);
+    rq.d_ebv = with_ebv ? cv.take<double>((size_t)ck.B * hb.d.nt * hb.d.nV) : nullptr;
+    rq.mode = ChunkMode::Full;
+    return body(ck, cv, rq);
   });
   if (rc) return rc;
-  if (fo) {
-    // intercept: the split's mean(y_T) the evaluation uses under snp, 0 under gblup (evaluator.py:257 dispatch)
-    for (int64_t b = 0; b < batch; ++b) {
-      const int mode = branch ? branch : (offsets[b + 1] - offsets[b] > c->n ? 1 : 2);
-      for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = mode == 2 ? sp->meanyT[t] : 0.0;
-    }
-  }
-  if (co) {
-    // cov_center: the train rows' column means under snp, 0 under gblup; a model whose covariate effects are
-    // NaN (d = 0, collinear covariates) is NaN in every output
-    const double nan = std::nan("");
-    for (int64_t b = 0; b < batch; ++b) {
-      const int mode = branch ? branch : (offsets[b + 1] - offsets[b] > c->n ? 1 : 2);
-      bool dead = false;
-      for (int64_t i = 0; i < d.nt * n_cov; ++i) dead = dead || std::isnan(co->cov_effects[b * d.nt * n_cov + i]);
-      for (int64_t j = 0; j < n_cov; ++j) co->cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cov_m[j] : 0.0);
-      if (dead && fo) {
-        for (int t = 0; t < d.nt; ++t) fo->intercept[b * d.nt + t] = nan;
-        for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) fo->center[i] = nan;
-      }
-    }
-  }
   return c->profiling ? drain_events(c) : 0;
 }
 
+int tblup_capi::factor_pass(const HostBatch& hb, const Chunk& ck, const Carve& cv, ChunkReq& rq, double* fitness,
+                            double* ebv, const std::function<int(const CholLaunch&)>& after) {
+  tblup_ctx* c = hb.c;
+  const size_t ebv_row = (size_t)hb.d.nt * hb.d.nV;
+  return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+    Carve cvp = cv;
+    rq.mode = redo ? ChunkMode::SolveOnly : ChunkMode::Full;
+    ChunkRes res;
+    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+    seqs.push_back(res.chain_seq);
+    if (after && !redo)
+      if (int rc = after(res.cl)) return rc;
+    HIPCHK(hipMemcpyAsync(fitness + ck.b0, rq.d_fit, (size_t)ck.B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (ebv)
+      HIPCHK(hipMemcpyAsync(ebv + ck.b0 * ebv_row, rq.d_ebv, (size_t)ck.B * ebv_row * 8, hipMemcpyDeviceToHost,
+                            c->stream));
+    return 0;
+  });
+}
+
 extern "C" {
+
+// Fitness and, if wanted, the validation EBVs: the chunks through the pipeline, nothing behind it
+int tblup_eval_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                     double h2, int branch, double* fitness, double* ebv) {
+  g_err.clear();
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, fitness != nullptr)) return rc;
+  if (!hb.sp) return 0;
+  return run_host_batch(hb, ebv != nullptr, nullptr, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) {
+    return factor_pass(hb, ck, cv, rq, fitness, ebv, nullptr);
+  });
+}
 
 int tblup_eval_batch_device(tblup_ctx* c, int split_id, const int64_t* d_idx, const int64_t* d_offsets,
                             const int64_t* h_offsets, int64_t batch, double h2, int branch, double* d_fitness,

@@ -1,5 +1,6 @@
-// Internal to libtblup_gpu.so's C-ABI translation units (capi.hip, capi_aux.hip): the context
-// (struct tblup_ctx of include/tblup_gpu.h), its device buffers and the error / allocation helpers.
+// Internal to libtblup_gpu.so's C-ABI translation units (capi.hip, capi_aux.hip, capi_model.hip): the context
+// (struct tblup_ctx of include/tblup_gpu.h), its device buffers, the error / allocation helpers, the
+// evaluation pipeline of one chunk and the host entries' chunk driver.
 #pragma once
 #include <functional>
 #include <map>
@@ -148,14 +149,15 @@ void dev_free(tblup_ctx* c, DevBuf& b);
 int check_ctx(tblup_ctx* c);
 void clear_error();
 
-// Buffers of a chunk, taken in order from the workspace (each starts on a 256-byte boundary)
+// Buffers of a chunk, taken in order from the workspace (each starts on a 256-byte boundary).  A Carve
+// without a base only measures: it hands out null pointers and `used` is what the same takes need.
 struct Carve {
   char* base;
   size_t used = 0;
   template <typename T>
   T* take(size_t count) {
     used = round_up((int64_t)used, 256);
-    T* p = reinterpret_cast<T*>(base + used);
+    T* p = base ? reinterpret_cast<T*>(base + used) : nullptr;
     used += count * sizeof(T);
     return p;
   }
@@ -168,6 +170,8 @@ int ws_check(const tblup_ctx* c, const Carve& cv);
 int check_indices(const tblup_ctx* c, const int64_t* idx, int64_t count);
 // every one of the batch's index lists is non-empty ("every <who> needs k >= 1 indices")
 int check_counts(const int64_t* offsets, int64_t batch, const char* who);
+// the branch an individual of k SNPs takes (evaluator.py:257): 1 gblup, 2 snp; branch 0 = auto
+inline int branch_of(const tblup_ctx* c, int64_t k, int branch) { return branch ? branch : (k > c->n ? 1 : 2); }
 
 // The host entries' chunk loop.  Individuals [b0, b0 + B) of the batch: sum_k indices, hoff their
 // B + 1 offsets rebased to 0 (valid until the body returns).
@@ -186,52 +190,95 @@ int for_each_chunk(tblup_ctx* c, const int64_t* offsets, int64_t batch, int64_t 
 int upload_chunk(tblup_ctx* c, Carve& cv, const int64_t* idx, const int64_t* offsets, const Chunk& ck,
                  int64_t** d_idx, int64_t** d_off);
 
-// Host outputs of tblup_fit_batch (capi_model.hip): intercept [batch][nt], center [offsets[batch]],
-// effects [nt][offsets[batch]].
-struct FitOut {
-  double* intercept;
-  double* center;
-  double* effects;
+// ---- the evaluation pipeline of one chunk (capi.hip) ----
+enum class ChunkMode {
+  Full,        // the whole pipeline
+  DebugK,      // debug readback: the pipeline up to the full K block (k_grm)
+  DebugL,      // debug readback: the pipeline up to the factor L and z
+  SolveOnly,   // the solve only, through the one-workgroup k_solve, on the factor an earlier run_chunk
+               // of the same chunk left in the same carve (host entries, after that run's chained
+               // solve gave up a wait: bit-identical results)
+  NoChain,     // the whole pipeline with the one-workgroup k_solve instead of the chained solve (a
+               // per-call choice: the context's policy is not touched)
 };
-// Host output of tblup_reliability_batch: reliability [batch][n_pred] of the listed panel rows
-// (already checked against [0, n))
-struct RelOut {
-  const int32_t* animals;
-  int64_t n_pred;
-  double* reliability;
+
+// One chunk whose idx/off already sit in device memory, as run_chunk enqueues it.  An entry fixes the
+// first six members once (ChunkReq rq{sp, d, sd, s, h2, branch}: six distinct types); the chunk's
+// pointers, B and the mode are set by name.
+struct ChunkReq {
+  const Split* sp;
+  tblup::EvalDims d;
+  tblup::SysDims sd;
+  hipStream_t s;
+  double h2;
+  int branch;
+  const int64_t *d_idx = nullptr, *d_off = nullptr;
+  const int64_t* h_off = nullptr;   // host copy of the offsets (work accounting and shapes)
+  int64_t B = 0;
+  double* d_fit = nullptr;       // [B] fitness
+  double* d_ebv = nullptr;       // [B][nt][nV], if wanted
+  const tblup::FoldTab* ft = nullptr;   // the systems' splits when they are not all sp (fold-fused evaluation;
+                                        // sp is then fold 0)
+  ChunkMode mode = ChunkMode::Full;
+  const double* d_h2 = nullptr;  // [B] per-system h2 on the device (tblup_loglik_batch); null: h2
 };
-// tblup_loglik_batch: per-model h2 [n_h2][batch] (already checked), one pass of the pipeline per row,
-// and its host outputs loglik / sigma2 [n_h2][batch][nt] (sigma2 may be null); the entry's fitness is
-// then [n_h2][batch]
-struct LogLikOut {
-  const double* h2;
-  int64_t n_h2;
-  double* loglik;
-  double* sigma2;
+
+struct ChunkRes {
+  int32_t chain_seq = 0;    // seq of the chained solve this run enqueued, 0 if none
+  double* K = nullptr;      // debug readbacks: the K block (DebugK), else the factor L
+  double* z = nullptr;
+  tblup::CholLaunch cl{};   // the chunk's buffers, for a launch after the pipeline (launch_effects)
 };
-// Host outputs of tblup_snp_score_batch: score [batch][nt][n_cand], info [batch][n_cand] and (may be null)
-// q [batch][nt] of the listed panel columns (already checked and wrapped to [0, P))
-struct ScoreOut {
-  const int32_t* snps;
-  int64_t n_cand;
-  double* score;
-  double* info;
-  double* q;
+
+// Workspace bytes of run_chunk's carve for B individuals of the system shape sd, plus what every host
+// entry carves in front of it: idx / off, the fitness and, with_ebv, the EBVs (no entry's own buffers).
+size_t chunk_bytes(const tblup_ctx* c, const tblup::EvalDims& d, const tblup::SysDims& sd, int64_t B, int64_t sum_k,
+                   bool with_ebv);
+// Enqueue the pipeline for one chunk (no host synchronisation unless the chain flags must grow); its
+// buffers are carved next from cv.
+int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res);
+// A host entry's chunk with recovery.  enqueue(redo, seqs) enqueues one pass on the context's stream --
+// its launches and the copies of the results to the host -- and lists the chained solves it enqueued.
+// Pass 0 (redo false) is the chunk as usual; when one of its chained solves gave up a wait, the pass
+// is enqueued once more with redo set (the entry solves through k_solve then) and the chunk counted.
+int run_recovering(tblup_ctx* c, const std::function<int(bool redo, std::vector<int32_t>& seqs)>& enqueue);
+
+// ---- the host entries' driver (capi.hip) ----
+// tblup_eval_batch (capi.hip) and the entries that read the factor it leaves (capi_model.hip) are each one
+// function: its argument checks, open_host_batch, run_host_batch with its body as a lambda, its host-side
+// post-pass.  The driver owns the batch's validation, the split, the system shape, the chunking, idx / off /
+// fitness / EBVs and ChunkReq's per-chunk members.  An entry writes its own buffers down once, as a carve
+// function: the body calls it on the chunk's Carve, the chunker on a measuring one.
+struct HostBatch {
+  tblup_ctx* c;
+  Split* sp;                 // null: an empty batch, nothing to run
+  tblup::EvalDims d;
+  tblup::SysDims sd;         // one form for the whole call
+  const int64_t *idx, *offsets;
+  int64_t batch;
+  double h2;
+  int branch;
+  std::vector<double> own_fitness;   // fitness_or_own: room for the batch's where the caller wants none
+  double* fitness_or_own(double* fitness) {
+    if (!fitness) own_fitness.resize((size_t)batch);
+    return fitness ? fitness : own_fitness.data();
+  }
 };
-// tblup_fit_cov_batch: the covariates cov [n][n_cov] row-major (already checked: finite, 1 <= n_cov <= COVAR_W)
-// and its host outputs cov_effects [batch][nt][n_cov] and cov_center [batch][n_cov]; fitness, ebv and fo are
-// then those of the phenotype adjusted for the fitted covariates
-struct CovOut {
-  const double* cov;
-  int64_t n_cov;
-  double* cov_effects;
-  double* cov_center;
-};
-// tblup_eval_batch's implementation (capi.hip); fo != null: also the fitted model of every individual;
-// ro != null: also the reliabilities of ro's animals under every individual's model; so != null: also the score statistics of so's
-// SNPs under every individual's model; lo != null: lo's passes instead of the one at h2 (no ebv / fo / ro /
-// so then); co != null: the covariate model (capi.hip; no ro / lo / so then)
-int eval_batch_host(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
-                    int branch, double* fitness, double* ebv, const FitOut* fo, const RelOut* ro = nullptr,
-                    const LogLikOut* lo = nullptr, const ScoreOut* so = nullptr, const CovOut* co = nullptr);
+// Validates in order: context, branch / h2 / offsets, the empty batch (0, hb.sp null), idx and `have_fitness`,
+// the split, the indices; then selects the device and fills hb.
+int open_host_batch(HostBatch& hb, tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets,
+                    int64_t batch, double h2, int branch, bool have_fitness);
+// The entry's own buffers of a chunk of B individuals and sum_k indices, taken from cv (a result is ignored)
+using ChunkCarve = std::function<void(Carve& cv, int64_t B, int64_t sum_k)>;
+// A chunk, the Carve behind its idx / off / fitness / EBVs, the request with every per-chunk member set
+using ChunkBody = std::function<int(const Chunk& ck, Carve& cv, ChunkReq& rq)>;
+// Runs the batch chunk by chunk as a synchronous entry (its chained solves recover on expiry), a chunk's
+// bytes chunk_bytes plus what `carve` (null: nothing) takes; then collects the profiling events.
+int run_host_batch(const HostBatch& hb, bool with_ebv, const ChunkCarve& carve, const ChunkBody& body);
+// One pass of a chunk's pipeline with recovery (redo: the same factor solved by k_solve, for the fitness and
+// the EBVs only).  after(cl) (null: nothing) is enqueued behind pass 0 on the factor it leaves: neither solve
+// kernel writes L, the diagonal inverses, z, u or the scalars, so it does not wait for the chained solve's
+// verdict.  Behind either pass the chunk's fitness and, ebv non-null, EBVs [batch][nt][nV] are copied out.
+int factor_pass(const HostBatch& hb, const Chunk& ck, const Carve& cv, ChunkReq& rq, double* fitness, double* ebv,
+                const std::function<int(const tblup::CholLaunch& cl)>& after);
 }  // namespace tblup_capi

@@ -1,8 +1,12 @@
-// C ABI of libtblup_gpu.so, taking the fitted model out (include/tblup_gpu.h): tblup_fit_batch
-// (the evaluation's chunks plus one k_effects launch each), tblup_predict_batch (k_predict),
-// tblup_loglik_batch (the chunks once per h2 row plus one k_loglik launch each),
-// tblup_snp_score_batch (the chunks plus k_snpscore's launches each) and tblup_fit_cov_batch (the chunks plus
-// k_covar, a second solve, k_cov_fitness and k_effects each).
+// C ABI of libtblup_gpu.so (include/tblup_gpu.h), the host entries that read the factor the evaluation's
+// pipeline leaves in the workspace, each one function on the host-batch driver of capi_ctx.h.  Its body carves
+// the entry's buffers (a *Bufs struct below; the chunker measures the same carve), runs the pipeline and then:
+//   tblup_fit_batch          k_effects
+//   tblup_reliability_batch  k_reliab's launches, k_effects when the model is wanted too
+//   tblup_snp_score_batch    k_snpscore's launches
+//   tblup_loglik_batch       the pipeline once per h2 row, k_loglik behind each
+//   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
+// tblup_predict_batch (k_predict) runs no pipeline: its own chunks and byte function.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -13,6 +17,93 @@
 using namespace tblup;
 using namespace tblup_capi;
 
+namespace {
+
+// The fitted model of a chunk (the reliabilities and the covariates carve it first if their caller wants it)
+struct ModelBufs {
+  double *cen, *eff;   // centres [sum_k], effects [nt][sum_k]
+  static ModelBufs carve(Carve& cv, const HostBatch& hb, int64_t sum_k, bool wanted = true) {
+    if (!wanted) return {};
+    return {cv.take<double>((size_t)sum_k), cv.take<double>((size_t)hb.d.nt * sum_k)};
+  }
+  // k_effects on cl's factor and z, then the chunk's stretch of center and of every trait plane of effects
+  int enqueue(const HostBatch& hb, const Chunk& ck, const CholLaunch& cl, double* center, double* effects) const {
+    const hipStream_t s = hb.c->stream;
+    const int64_t at = hb.offsets[ck.b0], total = hb.offsets[hb.batch];
+    HIPCHK(launch_effects(cl, (const int32_t*)hb.c->colsum_all.p, cen, eff, ck.sum_k, s));
+    HIPCHK(hipMemcpyAsync(center + at, cen, (size_t)ck.sum_k * 8, hipMemcpyDeviceToHost, s));
+    for (int t = 0; t < hb.d.nt; ++t)
+      HIPCHK(hipMemcpyAsync(effects + (int64_t)t * total + at, eff + (int64_t)t * ck.sum_k, (size_t)ck.sum_k * 8,
+                            hipMemcpyDeviceToHost, s));
+    return 0;
+  }
+};
+
+// intercept [batch][nt]: the split's mean(y_T) the evaluation uses under snp, 0 under gblup
+void fill_intercepts(const HostBatch& hb, double* intercept) {
+  const int nt = hb.d.nt;
+  for (int64_t b = 0; b < hb.batch; ++b) {
+    const int mode = branch_of(hb.c, hb.offsets[b + 1] - hb.offsets[b], hb.branch);
+    for (int t = 0; t < nt; ++t) intercept[b * nt + t] = mode == 2 ? hb.sp->meanyT[t] : 0.0;
+  }
+}
+
+// A list's slab plan: the slices of a launch aim at a quarter of the workspace budget, RELIAB_SCRATCH at most
+SlabPlan plan_slabs(const HostBatch& hb, int64_t B, int64_t n_items, int lds_knob) {
+  return slab_plan(hb.sd, B, n_items, lds_knob != 0, std::min<int64_t>(RELIAB_SCRATCH, (int64_t)(hb.c->budget / 4)));
+}
+double* carve_slices(Carve& cv, const SlabPlan& p) { return p.lds ? nullptr : cv.take<double>(p.scratch()); }
+
+struct ReliabBufs {   // tblup_reliability_batch
+  ModelBufs m;
+  SlabPlan plan;
+  int32_t* an;          // the animal list [n_rel]
+  double *rel, *vscr;   // reliabilities [B][n_rel]; the slices of one launch's slabs
+  static ReliabBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, bool model) {
+    const SlabPlan p = plan_slabs(hb, B, n_rel, hb.c->reliab_lds);
+    return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<int32_t>((size_t)n_rel),
+            cv.take<double>((size_t)B * n_rel), carve_slices(cv, p)};
+  }
+};
+
+struct ScoreBufs {   // tblup_snp_score_batch
+  SlabPlan plan;
+  int32_t* cand;                    // the SNP list [n_cand]
+  double *sco, *inf, *q, *vscr;     // score [B][nt][n_cand], info [B][n_cand], q [B][nt]; the slices
+  static ScoreBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cand) {
+    const SlabPlan p = plan_slabs(hb, B, n_cand, hb.c->score_lds);
+    const size_t nt = (size_t)hb.d.nt;
+    return {p, cv.take<int32_t>((size_t)n_cand), cv.take<double>(B * nt * n_cand), cv.take<double>((size_t)B * n_cand),
+            cv.take<double>(B * nt), carve_slices(cv, p)};
+  }
+};
+
+struct LogLikBufs {   // tblup_loglik_batch, every pass of the chunk
+  double *h2, *fits, *ll, *s2;   // h2 rows and fitnesses [n_h2][B]; log-likelihoods and sigma2_g [n_h2][B][nt]
+  static LogLikBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_h2) {
+    const size_t n = (size_t)n_h2 * B;
+    return {cv.take<double>(n), cv.take<double>(n), cv.take<double>(n * hb.d.nt), cv.take<double>(n * hb.d.nt)};
+  }
+};
+
+struct CovBufs {   // tblup_fit_cov_batch
+  ModelBufs m;
+  SlabPlan plan;       // one slab per model: a COVAR_W-item list; the knob is k_snpscore's, TBLUP_SCORE_LDS
+  double *qT, *qV;     // the covariates of the train and of the validation rows, both planes
+  double *b, *z2;      // their fitted effects [B][nt][n_cov]; z of the adjusted phenotype [B][nt][ns]
+  double *fit0, *ebv2, *vscr;   // the first pass's fitness (not returned); the second solve's EBVs; the slices
+  static CovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_cov, bool model) {
+    const EvalDims& d = hb.d;
+    const SlabPlan p = plan_slabs(hb, B, COVAR_W, hb.c->score_lds);
+    const size_t Bt = (size_t)B * d.nt;
+    return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<double>((size_t)2 * COVAR_W * d.nTp),
+            cv.take<double>((size_t)2 * COVAR_W * d.nV), cv.take<double>(Bt * n_cov), cv.take<double>(Bt * hb.sd.ns),
+            cv.take<double>((size_t)B), cv.take<double>(Bt * d.nV), carve_slices(cv, p)};
+  }
+};
+
+}  // namespace
+
 extern "C" {
 
 int tblup_fit_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
@@ -20,38 +111,18 @@ int tblup_fit_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_
   clear_error();
   if (int rc = check_ctx(c)) return rc;
   if (batch > 0 && (!intercept || !center || !effects)) return fail(TBLUP_ERR_ARG, "null intercept/center/effects");
-  std::vector<double> fit_local;
-  if (!fitness && batch > 0) {
-    fit_local.resize((size_t)batch);
-    fitness = fit_local.data();
-  }
-  const FitOut fo{intercept, center, effects};
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, &fo);
-}
-
-int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
-                        const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness, double* ebv,
-                        double* cov_effects, double* cov_center, double* intercept, double* center, double* effects) {
-  clear_error();
-  if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
-  if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
-  if (!cov) return fail(TBLUP_ERR_ARG, "null cov");
-  for (int64_t i = 0; i < c->n * n_cov; ++i)
-    if (!std::isfinite(cov[i])) return fail(TBLUP_ERR_ARG, "covariates must be finite");
-  const bool any = intercept || center || effects;
-  if (any && !(intercept && center && effects))
-    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
-  if (batch > 0 && (!cov_effects || !cov_center)) return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
-  std::vector<double> fit_local;
-  if (!fitness && batch > 0) {
-    fit_local.resize((size_t)batch);
-    fitness = fit_local.data();
-  }
-  const FitOut fo{intercept, center, effects};
-  const CovOut co{cov, n_cov, cov_effects, cov_center};
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, ebv, any ? &fo : nullptr, nullptr,
-                         nullptr, nullptr, &co);
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  if (!hb.sp) return 0;
+  fitness = hb.fitness_or_own(fitness);
+  const auto carve = [&](Carve& cv, int64_t, int64_t sum_k) { return ModelBufs::carve(cv, hb, sum_k); };
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const ModelBufs mb = carve(cv, ck.B, ck.sum_k);
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr,
+                       [&](const CholLaunch& cl) { return mb.enqueue(hb, ck, cl, center, effects); });
+  });
+  if (!rc) fill_intercepts(hb, intercept);
+  return rc;
 }
 
 int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, int64_t n_pred, const int64_t* idx,
@@ -61,8 +132,8 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
   if (int rc = check_ctx(c)) return rc;
   if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
   if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
-  const bool any = intercept || center || effects;
-  if (any && !(intercept && center && effects))
+  const bool model = intercept || center || effects;
+  if (model && !(intercept && center && effects))
     return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
   if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
   std::vector<int32_t> a32((size_t)n_pred);
@@ -72,30 +143,25 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
   }
   if (batch == 0 || n_pred == 0) return 0;
   if (!reliability) return fail(TBLUP_ERR_ARG, "null reliability");
-  std::vector<double> fit_local;
-  if (!fitness) {
-    fit_local.resize((size_t)batch);
-    fitness = fit_local.data();
-  }
-  const FitOut fo{intercept, center, effects};
-  const RelOut ro{a32.data(), n_pred, reliability};
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, any ? &fo : nullptr, &ro);
-}
-
-int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
-                       const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
-                       double* sigma2_g) {
-  clear_error();
-  if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
-  if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
-  if (batch == 0 || n_h2 == 0) return 0;
-  if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
-  // lambda = 0 makes the snp branch's V singular: (0, 1) here, not tblup_eval_batch's (0, 1]
-  for (int64_t i = 0; i < n_h2 * batch; ++i)
-    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
-  const LogLikOut lo{h2, n_h2, loglik, sigma2_g};
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2[0], branch, fitness, nullptr, nullptr, nullptr, &lo);
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  fitness = hb.fitness_or_own(fitness);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return ReliabBufs::carve(cv, hb, B, sk, n_pred, model); };
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const ReliabBufs rb = carve(cv, ck.B, ck.sum_k);
+    HIPCHK(hipMemcpyAsync(rb.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      if (model)
+        if (int rc = rb.m.enqueue(hb, ck, cl, center, effects)) return rc;
+      HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.an, n_pred, rb.plan,
+                           rb.vscr, rb.rel, s));
+      HIPCHK(hipMemcpyAsync(reliability + ck.b0 * n_pred, rb.rel, (size_t)ck.B * n_pred * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+  if (!rc && model) fill_intercepts(hb, intercept);
+  return rc;
 }
 
 int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64_t n_cand, const int64_t* idx,
@@ -113,13 +179,164 @@ int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64
   if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
   std::vector<int32_t> s32((size_t)n_cand);
   for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
-  std::vector<double> fit_local;
-  if (!fitness) {
-    fit_local.resize((size_t)batch);
-    fitness = fit_local.data();
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  fitness = hb.fitness_or_own(fitness);
+  const int nt = hb.d.nt;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreBufs::carve(cv, hb, B, n_cand); };
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const ScoreBufs sb = carve(cv, B, ck.sum_k);
+    HIPCHK(hipMemcpyAsync(sb.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, sb.sco, sb.inf,
+                             sb.q, s));
+      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
+      if (q) HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+}
+
+int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                       const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
+                       double* sigma2_g) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
+  if (batch == 0 || n_h2 == 0) return 0;
+  if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
+  // lambda = 0 makes the snp branch's V singular: (0, 1) here, not tblup_eval_batch's (0, 1]
+  for (int64_t i = 0; i < n_h2 * batch; ++i)
+    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
+  const int nt = hb.d.nt;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikBufs::carve(cv, hb, B, n_h2); };
+  // per chunk: its h2 columns up front, the n_h2 passes back to back (each the pipeline at its row of
+  // per-system h2, then k_loglik on the factor it leaves, without waiting for the solve), the results of
+  // every pass copied out behind the last
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
+    const LogLikBufs lb = carve(cv, B, ck.sum_k);
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
+    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+      // redo: a chained solve of some pass gave up a wait -- the factors of all but the last pass are
+      // gone, so every pass runs again whole with the one-workgroup k_solve (the same bits), for the
+      // fitnesses only
+      for (int64_t g = 0; g < n_h2; ++g) {
+        Carve cvp = cv;
+        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
+        rq.d_h2 = lb.h2 + g * B;
+        rq.d_fit = lb.fits + g * B;
+        ChunkRes res;
+        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+        seqs.push_back(res.chain_seq);
+        if (!redo) HIPCHK(launch_loglik(res.cl, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
+      }
+      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
+        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
+      };
+      if (fitness) HIPCHK(out(fitness + b0, pitch, lb.fits, row));
+      if (redo) return 0;
+      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
+      if (sigma2_g) HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
+      return 0;
+    });
+  });
+}
+
+int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
+                        const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness, double* ebv,
+                        double* cov_effects, double* cov_center, double* intercept, double* center, double* effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
+  if (!cov) return fail(TBLUP_ERR_ARG, "null cov");
+  for (int64_t i = 0; i < c->n * n_cov; ++i)
+    if (!std::isfinite(cov[i])) return fail(TBLUP_ERR_ARG, "covariates must be finite");
+  const bool model = intercept || center || effects;
+  if (model && !(intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  if (batch > 0 && (!cov_effects || !cov_center)) return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  if (!hb.sp) return 0;
+  fitness = hb.fitness_or_own(fitness);
+  const EvalDims& d = hb.d;
+  const int nt = d.nt, nc = (int)n_cov;
+  // the covariates of the split's rows gathered once per call, covariate-major and zero-padded, as given
+  // (plane 0: gblup models) and centred by the column means over the train rows in split order (plane 1:
+  // snp models)
+  std::vector<double> cov_m((size_t)n_cov), h_qT((size_t)2 * COVAR_W * d.nTp, 0.0);
+  std::vector<double> h_qV((size_t)2 * COVAR_W * d.nV, 0.0);
+  for (int64_t j = 0; j < n_cov; ++j) {
+    long double acc = 0.0L;
+    for (int64_t i = 0; i < d.nT; ++i) acc += cov[hb.sp->train[i] * n_cov + j];
+    const double m = cov_m[j] = (double)(acc / (long double)d.nT);
+    const auto planes = [&](const std::vector<int64_t>& rows, int64_t n_rows, int64_t ld, std::vector<double>& q) {
+      for (int64_t i = 0; i < n_rows; ++i) {
+        const double v = cov[rows[i] * n_cov + j];
+        q[j * ld + i] = v;
+        q[(COVAR_W + j) * ld + i] = v - m;
+      }
+    };
+    planes(hb.sp->train, d.nT, d.nTp, h_qT);
+    planes(hb.sp->valid, d.nV, d.nV, h_qV);
   }
-  const ScoreOut so{s32.data(), n_cand, score, info, q};
-  return eval_batch_host(c, split_id, idx, offsets, batch, h2, branch, fitness, nullptr, nullptr, nullptr, nullptr, &so);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return CovBufs::carve(cv, hb, B, sk, n_cov, model); };
+  // per chunk: the pipeline with the one-workgroup solve (nothing to recover; its EBVs are not wanted),
+  // k_covar on the factor and z it leaves, then the solve, the fitness and the effects of the adjusted
+  // phenotype from the corrected z in a buffer of its own
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const CovBufs cb = carve(cv, B, ck.sum_k);
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpyAsync(cb.qT, h_qT.data(), h_qT.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(cb.qV, h_qV.data(), h_qV.size() * 8, hipMemcpyHostToDevice, s));
+    double* d_fit = rq.d_fit;
+    Carve cvp = cv;
+    rq.mode = ChunkMode::NoChain;
+    rq.d_fit = cb.fit0;
+    ChunkRes res;
+    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+    HIPCHK(launch_covar(res.cl, cb.qT, nc, cb.plan, cb.vscr, cb.b, cb.z2, s));
+    CholLaunch cl2 = res.cl;
+    cl2.z = cb.z2;
+    HIPCHK(launch_solve(cl2, nullptr, cb.fit0, cb.ebv2, s));
+    HIPCHK(launch_cov_fitness(cl2, cb.ebv2, cb.qV, cb.b, nc, d_fit, s));
+    if (model)
+      if (int rc = cb.m.enqueue(hb, ck, cl2, center, effects)) return rc;
+    HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, cb.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    if (ebv) HIPCHK(hipMemcpyAsync(ebv + b0 * nt * d.nV, cb.ebv2, (size_t)B * nt * d.nV * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    return 0;
+  });
+  if (rc) return rc;
+  if (model) fill_intercepts(hb, intercept);
+  // cov_center: the train rows' column means under snp, 0 under gblup; a model whose covariate effects are
+  // NaN (d = 0, collinear covariates) is NaN in every output
+  const double nan = std::nan("");
+  for (int64_t b = 0; b < batch; ++b) {
+    const int mode = branch_of(c, offsets[b + 1] - offsets[b], branch);
+    bool dead = false;
+    for (int64_t i = 0; i < nt * n_cov; ++i) dead = dead || std::isnan(cov_effects[b * nt * n_cov + i]);
+    for (int64_t j = 0; j < n_cov; ++j) cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cov_m[j] : 0.0);
+    if (dead && model) {
+      for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
+      for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+    }
+  }
+  return 0;
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,

@@ -1,5 +1,6 @@
 // Blocked forward substitution with 16 right-hand sides on fp64 MFMA (v_mfma_f64_16x16x4_f64), shared
-// by k_reliab (k_reliab.hip) and k_snpscore (k_score.hip): one 512-thread workgroup solves
+// by k_reliab (k_reliab.hip), k_snpscore (k_score.hip) and k_covar (k_covar.hip), and the host side of their
+// slab launches (launch_slabs): one 512-thread workgroup solves
 //   V_J = X_J (R_J - sum_{L<J} L_JL V_L),  J = J0 .. J1-1,
 // in place in V [ns][16] (LDS or a workspace slice of the workgroup's own), from a model's Lt tiles and
 // the inverted diagonal tiles X_J = L_JJ^{-1} that the chunk's pipeline left in the workspace.
@@ -7,6 +8,8 @@
 // of each tile in order, then over the blocks s = 0 .. q of X_J.  Both kernels run this one chain, so a
 // right-hand side's solution is the same bits in either.
 #pragma once
+#include <algorithm>
+
 #include "tblup_internal.h"
 
 namespace tblup {
@@ -106,6 +109,30 @@ __device__ __forceinline__ void fwd_subst16(const double* __restrict__ Lb, const
     }
     __syncthreads();
   }
+}
+
+// Host side of the slab kernels.  kern: a kernel's four <FORM, VLDS> instances at [2 * (SNP form) + lds];
+// the one that the chunk and the plan select runs over the list's nslab slabs, p.S of them per launch
+// (B x sn workgroups of FWD_TH threads): launch(kernel, grid, shm, s0, sn) enqueues slabs [s0, s0 + sn).
+// With p.lds the right-hand sides are dynamic LDS; the attribute that allows them is set whenever shm > 0.
+template <class Kern, class Launch>
+hipError_t launch_slabs(const Kern (&kern)[4], const CholLaunch& c, const SlabPlan& p, const double* vscr,
+                        int64_t nslab, Launch&& launch) {
+  const size_t shm = p.lds ? (size_t)c.sd.ns * FWD_W * 8 : 0;
+  if (shm > (size_t)RELIAB_LDS_V || (!p.lds && !vscr)) return hipErrorInvalidValue;
+  if (p.S < 1 || c.B * p.S > 0x7fffffff || p.slices != c.B * p.S || p.ns != c.sd.ns) return hipErrorInvalidValue;
+  const Kern k = kern[(c.sd.form == FORM_PRIMAL ? 2 : 0) + (p.lds ? 1 : 0)];
+  if (shm > 0) {
+    hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+    if (e != hipSuccess) return e;
+  }
+  for (int64_t s0 = 0; s0 < nslab; s0 += p.S) {
+    const int64_t sn = std::min(p.S, nslab - s0);
+    launch(k, dim3((unsigned)(c.B * sn)), shm, s0, sn);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
 }
 
 }  // namespace tblup

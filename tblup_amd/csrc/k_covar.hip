@@ -31,7 +31,7 @@
 //     rounding noise of either sign, some 1e-16 of that entry.
 //   phase 5: z* for every trait by all threads; the pipeline's z is left as it is.
 // So a model's bits are a function of the model, the covariates and the system alone: not of the batch, the
-// chunking or where V lives (LDS when ns x 16 doubles fit, reliab_lds; else a workspace slice of its own).
+// chunking or where V lives (LDS when ns x 16 doubles fit, SlabPlan::lds; else a workspace slice of its own).
 //
 // k_cov_fitness: one 512-thread workgroup per model; y*_V = y_V - Q~_V b_t (one chain over the covariates in
 // order) and the mean over traits of |pearson(ebv_V, y*_V)| through the solve kernels' own restatement
@@ -277,28 +277,16 @@ __global__ __launch_bounds__(CTHR) void k_cov_fitness(CholLaunch c, const double
 
 }  // namespace
 
-hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, bool lds, double* vscr, double* bhat,
-                        double* z2, hipStream_t s) {
+hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, const SlabPlan& p, double* vscr,
+                        double* bhat, double* z2, hipStream_t s) {
   if (c.B < 1) return hipSuccess;
-  if (c.d.nt < 1 || c.d.nt > MAXT || n_cov < 1 || n_cov > COVAR_W) return hipErrorInvalidValue;
-  if (lds && !reliab_lds(c.sd)) return hipErrorInvalidValue;
-  if (!lds && !vscr) return hipErrorInvalidValue;
-  const size_t shm = lds ? (size_t)c.sd.ns * COVAR_W * 8 : 0;
-  auto launch = [&](const void* fn, auto kernel) -> hipError_t {
-    if (shm > 0) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)c.B), dim3(CTHR), shm, s, c, qT, n_cov, vscr, bhat, z2);
-    return hipGetLastError();
-  };
-  const int sel = (c.sd.form == FORM_PRIMAL ? 2 : 0) + (lds ? 1 : 0);
-  switch (sel) {
-    case 0: return launch((const void*)k_covar<FORM_DUAL, false>, k_covar<FORM_DUAL, false>);
-    case 1: return launch((const void*)k_covar<FORM_DUAL, true>, k_covar<FORM_DUAL, true>);
-    case 2: return launch((const void*)k_covar<FORM_PRIMAL, false>, k_covar<FORM_PRIMAL, false>);
-    default: return launch((const void*)k_covar<FORM_PRIMAL, true>, k_covar<FORM_PRIMAL, true>);
-  }
+  if (c.d.nt < 1 || c.d.nt > MAXT || n_cov < 1 || n_cov > COVAR_W || p.S != 1) return hipErrorInvalidValue;
+  using Kern = decltype(&k_covar<FORM_DUAL, false>);
+  const Kern kern[4] = {k_covar<FORM_DUAL, false>, k_covar<FORM_DUAL, true>, k_covar<FORM_PRIMAL, false>,
+                        k_covar<FORM_PRIMAL, true>};
+  return launch_slabs(kern, c, p, vscr, 1, [&](Kern k, dim3 grid, size_t shm, int64_t, int64_t) {
+    hipLaunchKernelGGL(k, grid, dim3(CTHR), shm, s, c, qT, n_cov, vscr, bhat, z2);
+  });
 }
 
 hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const double* qV, const double* bhat, int n_cov,

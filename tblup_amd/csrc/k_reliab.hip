@@ -183,43 +183,24 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
 
 }  // namespace
 
-bool reliab_lds(const SysDims& sd) { return sd.ns * RELIAB_W * 8 <= RELIAB_LDS_V; }
-
-int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int64_t aim) {
-  const int64_t nslab = (n_pred + RELIAB_W - 1) / RELIAB_W;
-  int64_t S = nslab;
-  if (!lds) S = std::min(S, std::max<int64_t>(1, aim / (B * sd.ns * RELIAB_W * 8)));
-  return std::max<int64_t>(1, std::min(S, (int64_t)0x7fffffff / std::max<int64_t>(B, 1)));
+SlabPlan slab_plan(const SysDims& sd, int64_t B, int64_t n_items, bool lds_knob, int64_t aim) {
+  const bool lds = lds_knob && sd.ns * FWD_W * 8 <= RELIAB_LDS_V;
+  int64_t S = (n_items + FWD_W - 1) / FWD_W;
+  if (!lds) S = std::min(S, std::max<int64_t>(1, aim / (B * sd.ns * FWD_W * 8)));
+  S = std::max<int64_t>(1, std::min(S, (int64_t)0x7fffffff / std::max<int64_t>(B, 1)));
+  return {lds, S, B * S, sd.ns};
 }
 
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
-                         int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s) {
+                         int64_t n_pred, const SlabPlan& p, double* vscr, double* rel, hipStream_t s) {
   if (c.B < 1 || n_pred < 1) return hipSuccess;
-  if (lds && !reliab_lds(c.sd)) return hipErrorInvalidValue;
-  if ((!lds && !vscr) || S < 1 || c.B * S > 0x7fffffff) return hipErrorInvalidValue;
-  const int64_t nslab = (n_pred + RELIAB_W - 1) / RELIAB_W;
-  const size_t shm = lds ? (size_t)c.sd.ns * RELIAB_W * 8 : 0;
-  auto launch = [&](const void* fn, auto kernel) -> hipError_t {
-    if (shm > 32 * 1024) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-    }
-    for (int64_t s0 = 0; s0 < nslab; s0 += S) {
-      const int64_t sn = std::min(S, nslab - s0);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)(c.B * sn)), dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn,
-                         vscr, rel);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+  using Kern = decltype(&k_reliab<FORM_DUAL, false>);
+  const Kern kern[4] = {k_reliab<FORM_DUAL, false>, k_reliab<FORM_DUAL, true>, k_reliab<FORM_PRIMAL, false>,
+                        k_reliab<FORM_PRIMAL, true>};
+  const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
+    hipLaunchKernelGGL(k, grid, dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn, vscr, rel);
   };
-  const int sel = (c.sd.form == FORM_PRIMAL ? 2 : 0) + (lds ? 1 : 0);
-  switch (sel) {
-    case 0: return launch((const void*)k_reliab<FORM_DUAL, false>, k_reliab<FORM_DUAL, false>);
-    case 1: return launch((const void*)k_reliab<FORM_DUAL, true>, k_reliab<FORM_DUAL, true>);
-    case 2: return launch((const void*)k_reliab<FORM_PRIMAL, false>, k_reliab<FORM_PRIMAL, false>);
-    default: return launch((const void*)k_reliab<FORM_PRIMAL, true>, k_reliab<FORM_PRIMAL, true>);
-  }
+  return launch_slabs(kern, c, p, vscr, (n_pred + RELIAB_W - 1) / RELIAB_W, launch);
 }
 
 }  // namespace tblup

@@ -27,7 +27,7 @@
 //     partial sums of a SNP are added in a fixed order at the end.
 // So a (model, SNP) value is a function of the column and the system alone: not of n_cand, of its place
 // in the list, of its slab, of the batch or of the chunking.  q is written by the model's first slab.
-// V lives in LDS when ns x 16 doubles fit (reliab_lds: ns <= 1024), else in a workspace slice of the
+// V lives in LDS when ns x 16 doubles fit (SlabPlan::lds: ns <= 1024), else in a workspace slice of the
 // workgroup's own -- the same arithmetic in the same order.
 // NaN for every output of a model with d = 0 or a flagged index; a column that is constant over the
 // reference rows has w_j = 0 and gives u = v = 0 exactly.
@@ -301,35 +301,17 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
 
 }  // namespace
 
-hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand, bool lds,
-                           int64_t S, double* vscr, double* score, double* info, double* q, hipStream_t s) {
+hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
+                           const SlabPlan& p, double* vscr, double* score, double* info, double* q, hipStream_t s) {
   if (c.B < 1 || n_cand < 1) return hipSuccess;
   if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
-  if (lds && !reliab_lds(c.sd)) return hipErrorInvalidValue;
-  if ((!lds && !vscr) || S < 1 || c.B * S > 0x7fffffff) return hipErrorInvalidValue;
-  const int64_t nslab = (n_cand + SCORE_W - 1) / SCORE_W;
-  const size_t shm = lds ? (size_t)c.sd.ns * SCORE_W * 8 : 0;
-  auto launch = [&](const void* fn, auto kernel) -> hipError_t {
-    if (shm > 0) {
-      hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
-      if (e != hipSuccess) return e;
-    }
-    for (int64_t s0 = 0; s0 < nslab; s0 += S) {
-      const int64_t sn = std::min(S, nslab - s0);
-      hipLaunchKernelGGL(kernel, dim3((unsigned)(c.B * sn)), dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr,
-                         score, info, q);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+  using Kern = decltype(&k_snpscore<FORM_DUAL, false>);
+  const Kern kern[4] = {k_snpscore<FORM_DUAL, false>, k_snpscore<FORM_DUAL, true>, k_snpscore<FORM_PRIMAL, false>,
+                        k_snpscore<FORM_PRIMAL, true>};
+  const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
+    hipLaunchKernelGGL(k, grid, dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr, score, info, q);
   };
-  const int sel = (c.sd.form == FORM_PRIMAL ? 2 : 0) + (lds ? 1 : 0);
-  switch (sel) {
-    case 0: return launch((const void*)k_snpscore<FORM_DUAL, false>, k_snpscore<FORM_DUAL, false>);
-    case 1: return launch((const void*)k_snpscore<FORM_DUAL, true>, k_snpscore<FORM_DUAL, true>);
-    case 2: return launch((const void*)k_snpscore<FORM_PRIMAL, false>, k_snpscore<FORM_PRIMAL, false>);
-    default: return launch((const void*)k_snpscore<FORM_PRIMAL, true>, k_snpscore<FORM_PRIMAL, true>);
-  }
+  return launch_slabs(kern, c, p, vscr, (n_cand + SCORE_W - 1) / SCORE_W, launch);
 }
 
 }  // namespace tblup

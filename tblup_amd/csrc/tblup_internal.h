@@ -366,33 +366,47 @@ hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitne
 hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
                           hipStream_t s);
 
+// ---- the slab kernels behind a chunk's factor: k_reliab, k_snpscore, k_covar (fwd_subst.h) ----
+// Each walks a list (animals, SNPs, covariates) in slabs of 16 right-hand sides, one workgroup per (model,
+// slab).  How one call does so, decided in one place: lds -- a slab's ns x 16 right-hand sides live in LDS
+// (the entry's knob allows it and they fit RELIAB_LDS_V), else in a workspace slice of the workgroup's own;
+// S -- slabs of the list per launch: all of them, or without LDS what `aim` bytes hold of the B x S slices
+// of one launch, never less than one slab per model and never a grid beyond 2^31 - 1; scratch() -- the
+// doubles of those slices (vscr; 0 with LDS).  The same bits either way.
+// tblup_reliability_batch plans with TBLUP_RELIAB_LDS, tblup_snp_score_batch with TBLUP_SCORE_LDS;
+// tblup_fit_cov_batch's covariates are one slab per model (n_items = COVAR_W) and its plan keeps reading
+// TBLUP_SCORE_LDS.
+constexpr int64_t RELIAB_LDS_V = 128 * 1024;          // bytes of LDS for V beside the staging buffers
+constexpr int64_t RELIAB_SCRATCH = 64ll << 20;        // aim of the workspace slices' size (>= one slab per model)
+struct SlabPlan {
+  bool lds = false;
+  int64_t S = 1;
+  int64_t slices = 0;   // B x S
+  int64_t ns = 0;
+  size_t scratch() const { return lds ? 0 : (size_t)(slices * ns * 16); }
+};
+SlabPlan slab_plan(const SysDims& sd, int64_t B, int64_t n_items, bool lds_knob, int64_t aim);
+
 // ---- launcher (k_reliab.hip): reliabilities of any animals of the panel from a chunk's factor ----
 // rel[b * n_pred + v] for animal animals[v] (a row of geno_sm, int8 [P][n]) under model b of the chunk
 // whose pipeline left L, Dinv, u, scal (and, kernel form, the packed panel) in c: one workgroup per
-// (model, slab of RELIAB_W listed animals), a blocked forward substitution on fp64 MFMA.  lds: the
-// slab's ns x RELIAB_W right-hand sides live in LDS (reliab_lds); else in vscr, ns x RELIAB_W doubles
-// for each of the B x S workgroups of one launch (the list is walked S slabs at a time, in several
-// launches when S = reliab_slabs(aim bytes of slices) is below the list's slabs).
+// (model, slab of RELIAB_W listed animals), a blocked forward substitution on fp64 MFMA.  p / vscr: the
+// list's slab_plan and its scratch() doubles (null with LDS).
 // The same bits either way, and for an animal wherever it stands in the list.
 constexpr int RELIAB_W = 16;
-constexpr int64_t RELIAB_LDS_V = 128 * 1024;          // bytes of LDS for V beside the staging buffers
-constexpr int64_t RELIAB_SCRATCH = 64ll << 20;        // aim of the workspace slices' size (>= one slab per model)
-bool reliab_lds(const SysDims& sd);
-int64_t reliab_slabs(const SysDims& sd, int64_t B, int64_t n_pred, bool lds, int64_t aim);
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
-                         int64_t n_pred, bool lds, int64_t S, double* vscr, double* rel, hipStream_t s);
+                         int64_t n_pred, const SlabPlan& p, double* vscr, double* rel, hipStream_t s);
 
 // ---- launcher (k_score.hip): mixed-model score statistics of listed SNPs from a chunk's factor ----
 // score[(b * nt + t) * n_cand + v] = w_j^T V^-1 r_t, info[b * n_cand + v] = w_j^T V^-1 w_j for column
 // j = cand[v] (already wrapped to [0, P)) under model b of the chunk whose pipeline left L, Dinv, z, u and
 // scal in c, and q[b * nt + t] = r_t^T V^-1 r_t (q may be null): one workgroup per (model, slab of SCORE_W
 // listed SNPs), right-hand sides from the split's 2-bit packed rows, then k_reliab's forward substitution
-// (fwd_subst.h).  lds / S / vscr: as launch_reliab (reliab_lds, reliab_slabs; ns x SCORE_W doubles for each
-// of the B x S workgroups of one launch).  The same bits either way, and for a SNP wherever it stands in
+// (fwd_subst.h).  p / vscr: as launch_reliab.  The same bits either way, and for a SNP wherever it stands in
 // the list.  NaN for a model with d = 0 or a flagged index.
 constexpr int SCORE_W = 16;
-hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand, bool lds,
-                           int64_t S, double* vscr, double* score, double* info, double* q, hipStream_t s);
+hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
+                           const SlabPlan& p, double* vscr, double* score, double* info, double* q, hipStream_t s);
 
 // ---- launchers (k_covar.hip): fixed-effect covariates fitted by GLS from a chunk's factor ----
 // qT [2][COVAR_W][nTp] / qV [2][COVAR_W][nV]: the call's covariates of the split's train / validation rows,
@@ -400,8 +414,8 @@ hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_
 // (snp models); zero at padding rows and at columns past n_cov.  launch_covar: bhat[(b * nt + t) * n_cov + j]
 // the GLS effects under model b of the chunk whose pipeline left L, Dinv, z, u and scal in c, and
 // z2 [B][nt][ns] = L^-1 rhs of the adjusted phenotype (c.z is not written) -- one workgroup per model,
-// k_reliab's forward substitution (fwd_subst.h) on the covariates as one slab.  lds / vscr: as launch_snpscore
-// with one slab per model (ns x COVAR_W doubles per model in vscr).  NaN for a model with d = 0, a flagged
+// k_reliab's forward substitution (fwd_subst.h) on the covariates as one slab.  p / vscr: as launch_reliab,
+// the plan of a COVAR_W-item list.  NaN for a model with d = 0, a flagged
 // index or covariates that are collinear over the train rows.  launch_cov_fitness: fit[b] = the mean over
 // traits of |pearson(ebv_V, y_V - Q~_V b)| from ebv [B][nt][nV] (the solve on z2).
 constexpr int COVAR_W = 16;
@@ -409,8 +423,8 @@ constexpr int COVAR_W = 16;
 // Q~^T V^-1 Q~ (1 - R^2 of the column on the earlier ones): below it the effects have no digit left at the
 // tests' 1e-9, and an exactly repeated column leaves rounding noise of either sign, ~1e-16 of the entry
 constexpr double COVAR_PIV_RTOL = 1e-12;
-hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, bool lds, double* vscr, double* bhat,
-                        double* z2, hipStream_t s);
+hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, const SlabPlan& p, double* vscr,
+                        double* bhat, double* z2, hipStream_t s);
 hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const double* qV, const double* bhat, int n_cov,
                               double* fit, hipStream_t s);
 

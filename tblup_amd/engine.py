@@ -170,7 +170,6 @@ class GpuBlupEngine:
         return_ebv=True also returns the validation EBVs of y*, (B, n_valid) or (B, nt, n_valid), as
         (models, ebv).  Collinear covariates give a NaN model, not an error; NaN / Inf in Q is a ValueError.
         Not combined with reliability_of."""
-        from .model import PanelModel
         self._settle()
         if covariates is not None:
             if reliability_of is not None:
@@ -183,30 +182,43 @@ class GpuBlupEngine:
             an = _as_int64(reliability_of)
             if an.ndim != 1:
                 raise ValueError("reliability_of must be a 1-D list of row ids")
+        B = len(genomes)
+        rel = None if an is None else np.empty((B, len(an)), dtype=np.float64)
+        if an is not None and len(an):
+            def call(sid, idx, offsets, *outs):
+                _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
+                    self._ctx, sid, _ptr(an), len(an), idx, offsets, B, float(h2), _native.BRANCH[branch], *outs,
+                    _ptr(rel)))
+        else:
+            def call(sid, idx, offsets, *outs):
+                _native.check("tblup_fit_batch", self._lib.tblup_fit_batch(
+                    self._ctx, sid, idx, offsets, B, float(h2), _native.BRANCH[branch], *outs))
+        models = self._fit_models(genomes, train, valid, h2, branch, call)
+        return models if an is None else (models, rel)
+
+    def _fitted_branch(self, k, branch):
+        """The branch a model of k SNPs is fitted under (evaluator.py:257)."""
+        return branch if branch != "auto" else ("gblup" if k > self.n_animals else "snp")
+
+    def _fit_models(self, genomes, train, valid, h2, branch, call, **cov):
+        """The fitted-model entries' frame: the outputs allocated, call(sid, idx, offsets, fitness, intercept,
+        center, effects) made for a non-empty batch (all but sid as pointers), one PanelModel per index set.
+        cov: the cov_effects / cov_center arrays that the call fills, a row per model."""
+        from .model import PanelModel
         sid = self.split_id(train, valid)
         idx, offsets = concat_genomes(genomes)
         B, nt, total = len(genomes), self.n_traits, int(offsets[-1])
-        fit = np.empty(B, dtype=np.float64)
-        intercept = np.empty((B, nt), dtype=np.float64)
-        center = np.empty(total, dtype=np.float64)
-        effects = np.empty((nt, total), dtype=np.float64)
-        rel = None if an is None else np.empty((B, len(an)), dtype=np.float64)
-        if B and an is not None and len(an):
-            _native.check("tblup_reliability_batch", self._lib.tblup_reliability_batch(
-                self._ctx, sid, _ptr(an), len(an), _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch],
-                _ptr(fit), _ptr(intercept), _ptr(center), _ptr(effects), _ptr(rel)))
-        elif B:
-            _native.check("tblup_fit_batch", self._lib.tblup_fit_batch(
-                self._ctx, sid, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit),
-                _ptr(intercept), _ptr(center), _ptr(effects)))
+        fit, intercept = np.empty(B, dtype=np.float64), np.empty((B, nt), dtype=np.float64)
+        center, effects = np.empty(total, dtype=np.float64), np.empty((nt, total), dtype=np.float64)
+        if B:
+            call(sid, *map(_ptr, (idx, offsets, fit, intercept, center, effects)))
         wrapped = np.where(idx < 0, idx + self.n_snps, idx)
         models = []
         for b in range(B):
             lo, hi = int(offsets[b]), int(offsets[b + 1])
-            fitted = branch if branch != "auto" else ("gblup" if hi - lo > self.n_animals else "snp")
-            models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
-                                     fit[b]))
-        return models if an is None else (models, rel)
+            models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2,
+                                     self._fitted_branch(hi - lo, branch), fit[b], **{k: v[b] for k, v in cov.items()}))
+        return models
 
     def _covariates(self, covariates):
         """The (n_animals, c) float64 matrix of a `covariates` argument, validated."""
@@ -222,31 +234,17 @@ class GpuBlupEngine:
         return np.ascontiguousarray(q)
 
     def _fit_cov(self, genomes, train, valid, h2, branch, covariates, return_ebv):
-        from .model import PanelModel
         q = self._covariates(covariates)
-        nc = q.shape[1]
-        sid = self.split_id(train, valid)
-        idx, offsets = concat_genomes(genomes)
-        B, nt, total, n_valid = len(genomes), self.n_traits, int(offsets[-1]), len(valid)
-        fit = np.empty(B, dtype=np.float64)
-        intercept = np.empty((B, nt), dtype=np.float64)
-        center = np.empty(total, dtype=np.float64)
-        effects = np.empty((nt, total), dtype=np.float64)
+        B, nt, nc, n_valid = len(genomes), self.n_traits, q.shape[1], len(valid)
         cov_eff = np.empty((B, nt, nc), dtype=np.float64)
         cov_cen = np.empty((B, nc), dtype=np.float64)
         ebv = np.empty((B, n_valid) if nt == 1 else (B, nt, n_valid), dtype=np.float64) if return_ebv else None
-        if B:
+
+        def call(sid, idx, offsets, fit, *model):
             _native.check("tblup_fit_cov_batch", self._lib.tblup_fit_cov_batch(
-                self._ctx, sid, _ptr(q), nc, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit),
-                _ptr(ebv) if return_ebv else None, _ptr(cov_eff), _ptr(cov_cen), _ptr(intercept), _ptr(center),
-                _ptr(effects)))
-        wrapped = np.where(idx < 0, idx + self.n_snps, idx)
-        models = []
-        for b in range(B):
-            lo, hi = int(offsets[b]), int(offsets[b + 1])
-            fitted = branch if branch != "auto" else ("gblup" if hi - lo > self.n_animals else "snp")
-            models.append(PanelModel(wrapped[lo:hi], center[lo:hi], effects[:, lo:hi], intercept[b], h2, fitted,
-                                     fit[b], cov_effects=cov_eff[b], cov_center=cov_cen[b]))
+                self._ctx, sid, _ptr(q), nc, idx, offsets, B, float(h2), _native.BRANCH[branch], fit,
+                _ptr(ebv) if return_ebv else None, _ptr(cov_eff), _ptr(cov_cen), *model))
+        models = self._fit_models(genomes, train, valid, h2, branch, call, cov_effects=cov_eff, cov_center=cov_cen)
         return (models, ebv) if return_ebv else models
 
     def reliability(self, genomes, train, valid, h2, animals, branch="auto"):
@@ -295,8 +293,7 @@ class GpuBlupEngine:
         _native.check("tblup_snp_score_batch", self._lib.tblup_snp_score_batch(
             self._ctx, sid, _ptr(cand) if m else None, m, _ptr(idx), _ptr(offsets), B, float(h2),
             _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q)))
-        k = np.diff(offsets)
-        snp = np.array([(branch == "snp") or (branch == "auto" and kk <= self.n_animals) for kk in k], dtype=bool)
+        snp = np.array([self._fitted_branch(k, branch) == "snp" for k in np.diff(offsets)], dtype=bool)
         dof = len(_as_int64(train)) - snp.astype(np.float64)
         return SnpScores(score, info, q, dof.reshape(B), np.where(cand < 0, cand + self.n_snps, cand))
 

@@ -15,6 +15,7 @@ Panel: 331 animals (odd: the SNP-major rows k_predict reads are unaligned) x 600
   E  TBLUP_WORKSPACE_MB=1, TBLUP_SOLVE_CHAIN=0/1, TBLUP_SOLVE_PULL=0/1: the same bits
   F  a monomorphic panel (NaN, no error), out-of-range indices, a context without a panel
   G  BlupParallelEvaluator.fit_models / predict, PanelModel save / load
+  H  the host entries back to back on one context, each bit-equal to the same call on a fresh context
 
 Tolerances: EBV_RTOL = 1e-9 relative max-norm (tests/test_gpu_parity.py); effects the same 1e-9
 relative to the individual's max |effect|, on cases where tests/test_model_host.py shows the
@@ -468,3 +469,66 @@ def test_g_fit_models_matches_evaluate_testing(gpu, tmp_path, removed):
         np.testing.assert_array_equal(ev.predict(loaded, herd), ev.predict(models, herd))
         for m, l in zip(models, loaded):
             np.testing.assert_array_equal(l.predict(pn["geno"]), m.predict(pn["geno"]))
+
+
+# ---------------------------------------------------------------------------------------------
+# H. the host entries share one workspace
+# ---------------------------------------------------------------------------------------------
+def _entry_calls():
+    """(name, call(engine) -> list of arrays) of the host entries on the (257, 70) split, three SNP-form
+    genomes (k in 257..331: three tile columns), in an order that alternates small and large workspace
+    layouts."""
+    from tests.covar_ref import make_cov
+    pn = R.panel()
+    T, V = pn["splits"][257, 70]
+    rng = np.random.default_rng(331)
+    genomes = [rng.choice(P, k, replace=False) for k in (257, 300, 331)]
+    animals, snps = rng.integers(0, N, 17), rng.integers(0, P, 17)
+    q = make_cov(N, 2)
+
+    def model(m):
+        extra = [m.cov_effects, m.cov_center] if m.cov_effects is not None else []
+        return [m.center, m.effects, m.intercept, np.asarray(m.fitness)] + extra
+
+    def evaluate(e):
+        return list(e.evaluate(genomes, T, V, H2, return_ebv=True))
+
+    def fit_cov(e):
+        models, ebv = e.fit(genomes, T, V, H2, covariates=q, return_ebv=True)
+        return [ebv] + [a for m in models for a in model(m)]
+
+    def loglik(e):
+        return list(e.log_likelihood(genomes, T, V, [0.2, 0.45, 0.7], return_sigma2=True))
+
+    def reliability_fit(e):
+        models, rel = e.fit(genomes, T, V, H2, reliability_of=animals)
+        return [rel] + [a for m in models for a in model(m)]
+
+    def score(e):
+        sc = e.snp_scores(genomes, T, V, H2, snps)
+        return [sc.score, sc.info, sc.q]
+
+    return [("eval", evaluate), ("fit_cov", fit_cov), ("eval", evaluate), ("loglik", loglik),
+            ("reliability+fit", reliability_fit), ("score", score), ("eval", evaluate)]
+
+
+def test_h_entries_back_to_back_leave_nothing_behind(gpu):
+    """One context, the host entries back to back (eval, fit with covariates, eval, log-likelihood,
+    reliabilities with the model, SNP scores, eval): every result is bit-equal to the same call on a fresh
+    context, so nothing that an entry leaves in the shared workspace reaches an entry of another layout."""
+    pn = R.panel()
+    calls = _entry_calls()
+    with _engine(pn["geno"], pn["pheno"]) as e:
+        shared = [call(e) for _, call in calls]
+    fresh = {}
+    for name, call in calls:
+        if name not in fresh:
+            with _engine(pn["geno"], pn["pheno"]) as e:
+                fresh[name] = call(e)
+    for (name, _), got in zip(calls, shared):
+        assert len(got) == len(fresh[name]), name
+        for i, (a, b) in enumerate(zip(got, fresh[name])):
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+            assert a.shape == b.shape and a.dtype == b.dtype, (name, i)
+            assert np.all(np.isfinite(a)), (name, i)
+            assert a.tobytes() == b.tobytes(), (name, i)
