@@ -108,12 +108,10 @@ int for_each_chunk(tblup_ctx* c, const int64_t* offsets, int64_t batch, int64_t 
   return 0;
 }
 
-int upload_chunk(tblup_ctx* c, Carve& cv, const int64_t* idx, const int64_t* offsets, const Chunk& ck, int64_t** d_idx,
-                 int64_t** d_off) {
-  *d_idx = cv.take<int64_t>((size_t)ck.sum_k);
-  *d_off = cv.take<int64_t>((size_t)ck.B + 1);
-  HIPCHK(hipMemcpyAsync(*d_idx, idx + offsets[ck.b0], (size_t)ck.sum_k * 8, hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipMemcpyAsync(*d_off, ck.hoff, (size_t)(ck.B + 1) * 8, hipMemcpyHostToDevice, c->stream));
+int upload_chunk(tblup_ctx* c, const int64_t* idx, const int64_t* offsets, const Chunk& ck, int64_t* d_idx,
+                 int64_t* d_off) {
+  HIPCHK(hipMemcpyAsync(d_idx, idx + offsets[ck.b0], (size_t)ck.sum_k * 8, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(d_off, ck.hoff, (size_t)(ck.B + 1) * 8, hipMemcpyHostToDevice, c->stream));
   return 0;
 }
 
@@ -419,37 +417,84 @@ int chain_expired(tblup_ctx* c, const std::vector<int32_t>& seqs, bool* out) {
   return 0;
 }
 
-}  // namespace
-
-size_t tblup_capi::chunk_bytes(const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, int64_t sum_k,
-                               bool with_ebv) {
-  size_t s = 0;
-  auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
-  add(sd.form == FORM_DUAL ? (size_t)B * sd.prow * dual_pk_row(sd) : 0);   // packed panel (dual only)
-  add((size_t)B * sd.prow * 8);                                 // u
-  add((size_t)B * SCAL * 8);                                    // scal
-  add((size_t)B * l_stride(sd.NT) * 8);                         // L (Lt tiles)
-  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // Dinv (packed X)
-  add((size_t)B * d.nt * sd.ns * 8);                            // z
-  add((size_t)B * d.nt * sd.ns * 8);                            // w
-  add((size_t)B * d.nt * sd.ns * 8);                            // rhs
-  add((size_t)B * TBLUP_NSLOT * 36 * 256 * 8);                  // next diagonal tile (minus its last SYRK term)
-  add((size_t)B * sd.NT * NPACK * BLKD * 8);                    // diagonal GRM tiles
-  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * KD_TILE * 2 : 0);  // their int16 counts (k_sys_tiles)
-  add(sys_tiles(c, d, sd) ? (size_t)B * sd.NT * (sd.NT - 1) / 2 * KC_TILE * 2 : 0);   // off-diagonal counts
-  add(uses_part(c, B, sd.NT, sys_tiles(c, d, sd)) ? (size_t)2 * B * sd.NT * TILE * TILE * 8 : 0);   // partial sums
-  if (use_chain(c, sd, B, d.nt)) {                                    // chained solve: beta, c_{J->I}, EBV shares
-    add((size_t)B * d.nt * sd.ns * 8);
-    add((size_t)B * sd.NT * sd.NT * d.nt * TILE * 8);
-    add((size_t)B * sd.NT * d.nt * d.nV * 8);
-    add((size_t)B * sd.NT * d.nt * 8);
+// What a host entry carves first: the chunk's index list and offsets, n_fit fitnesses, n_ebv EBVs (0: none)
+struct HeadBufs {
+  int64_t *idx, *off;
+  double *fit, *ebv;
+  static HeadBufs carve(Carve& cv, int64_t B, int64_t sum_k, int64_t n_fit, int64_t n_ebv) {
+    return {cv.take<int64_t>((size_t)sum_k), cv.take<int64_t>((size_t)B + 1), cv.take<double>((size_t)n_fit),
+            n_ebv ? cv.take<double>((size_t)n_ebv) : nullptr};
   }
-  add(use_last_term(c, sd, B) ? (size_t)B * NPACK * BLKD * 8 : 0);   // diagonal tiles' last SYRK terms
-  add((size_t)B * 8);                                           // fitness
-  add(with_ebv ? (size_t)B * d.nt * d.nV * 8 : 0);              // ebv
-  add((size_t)sum_k * 8 + (size_t)(B + 1) * 8);                 // idx, off
-  return s + 4096;
+};
+
+// The pipeline's buffers of a chunk of B systems.  A new one is one line of this carve: run_chunk lays the
+// chunk out with it and every entry measures its workspace with it.
+struct PipeBufs {
+  bool use_st, chain;   // system tiles from k_sys_tiles; the mode runs the chained solve
+  uint8_t* panel;
+  double *u, *scal, *L, *Dinv, *z, *w, *rhs, *Sp, *Kdg;
+  int16_t *kdb, *kcb;
+  double *Pp, *Qb, *K, *beta, *cpart, *epart, *mbpart;
+  // gsh: a kernel-form fold chunk that reads its counts from the shared A_R A_R^T instead of system tiles
+  static PipeBufs carve(Carve& cv, const tblup_ctx* c, const EvalDims& d, const SysDims& sd, int64_t B, ChunkMode mode,
+                        bool gsh) {
+    PipeBufs p{};
+    const size_t nB = (size_t)B, vec = nB * d.nt * sd.ns, dg = nB * sd.NT * NPACK * BLKD;
+    p.use_st = sys_tiles(c, d, sd) && mode != ChunkMode::DebugK && !gsh;
+    p.chain = mode == ChunkMode::Full && use_chain(c, sd, B, d.nt);
+    p.panel = cv.take<uint8_t>(sd.form == FORM_DUAL ? nB * sd.prow * dual_pk_row(sd) : 0);   // packed (kernel form)
+    p.u = cv.take<double>(nB * sd.prow); p.scal = cv.take<double>(nB * SCAL);
+    p.L = cv.take<double>(nB * l_stride(sd.NT));   // Lt tiles
+    p.Dinv = cv.take<double>(dg);                  // packed X
+    p.z = cv.take<double>(vec); p.w = cv.take<double>(vec); p.rhs = cv.take<double>(vec);
+    p.Sp = cv.take<double>(nB * TBLUP_NSLOT * 36 * 256);   // next diagonal tile (minus its last SYRK term)
+    // diagonal system tiles: fp64 K_JJ + lambda I (with k_sys_tiles: J < 2 only, the diagonal kernel's direct
+    // reads) and, with k_sys_tiles, the exact int16 counts of J >= 2 (the D-units') and of the off-diagonal tiles
+    p.Kdg = cv.take<double>(dg);
+    if (p.use_st) p.kdb = cv.take<int16_t>(nB * sd.NT * KD_TILE);
+    if (p.use_st) p.kcb = cv.take<int16_t>(nB * sd.NT * (sd.NT - 1) / 2 * KC_TILE);
+    // the off-diagonal tiles' partial sums; the diagonal tiles' last SYRK terms
+    if (uses_part(c, B, sd.NT, sys_tiles(c, d, sd))) p.Pp = cv.take<double>(2 * nB * sd.NT * TILE * TILE);
+    if (use_last_term(c, sd, B)) p.Qb = cv.take<double>(nB * NPACK * BLKD);
+    if (mode == ChunkMode::DebugK) p.K = cv.take<double>(nB * d.nRp * d.nTp);   // the full K_{R,T} block
+    if (p.chain) {   // beta, c_{J->I}, EBV shares
+      p.beta = cv.take<double>(vec); p.cpart = cv.take<double>(nB * sd.NT * sd.NT * d.nt * TILE);
+      p.epart = cv.take<double>(nB * sd.NT * d.nt * d.nV); p.mbpart = cv.take<double>(nB * sd.NT * d.nt);
+    }
+    return p;
+  }
+};
+
+// The chained solve's launch arguments: the context's flags (grown and zeroed when too small: a host
+// synchronisation), the next seq and its ring slot, the chunk's buffers, the debug knob's shots
+int chain_args(tblup_ctx* c, const ChunkReq& rq, const PipeBufs& pb, SolveChain& ch) {
+  const size_t fbytes = ((size_t)rq.B * chain_flags(rq.sd.NT) + CHAIN_ERR_RING + 1) * 4;
+  if (c->chain.bytes < fbytes || c->chain_seq >= INT32_MAX - 1) {
+    HIPCHK(hipStreamSynchronize(rq.s));   // the flags may still be read by an earlier chained solve
+    if (int rc = dev_alloc(c, c->chain, fbytes)) return rc;
+    HIPCHK(hipMemsetAsync(c->chain.p, 0, c->chain.bytes, rq.s));
+    c->chain_seq = 0;
+  }
+  ch.flags = (int32_t*)c->chain.p;
+  int32_t* ring = ch.flags + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
+  ch.beta = pb.beta; ch.cpart = pb.cpart; ch.epart = pb.epart; ch.mbpart = pb.mbpart;
+  ch.seq = ++c->chain_seq;
+  ch.err = ring + ch.seq % CHAIN_ERR_RING;
+  // host entries recover from their ring slot (chain_expired); device entries raise the status word
+  ch.expired = c->host_entry ? ring + CHAIN_ERR_RING : (int32_t*)c->status.p + ST_SOLVE;
+  ch.mode = c->chain_sync;
+  // pull units for one trait (several traits: their registers spill at two units per CU)
+  ch.pull = c->solve_pull == 1 || (c->solve_pull < 0 && rq.d.nt == 1);
+  ch.spin_max = CHAIN_SPIN_MAX;
+  if (c->chain_dbg_shots > 0) {
+    --c->chain_dbg_shots;
+    ch.spin_max = c->chain_dbg_spin;
+    ch.delay = c->chain_dbg_delay;
+  }
+  return 0;
 }
+
+}  // namespace
 
 // Enqueue the pipeline for one chunk (no host synchronisation unless the chain flags must grow).
 int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res) {
@@ -462,7 +507,9 @@ int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes&
   cl.ft = rq.ft ? *rq.ft : single_fold(*rq.sp, B);
   const FoldTab& ft = cl.ft;
   const bool redo = rq.mode == ChunkMode::SolveOnly;
-  const bool chain = rq.mode != ChunkMode::NoChain && use_chain(c, sd, B, d.nt);
+  const PipeBufs pb = PipeBufs::carve(cv, c, d, sd, B, rq.mode, ft.gsh != nullptr);
+  if (int rc = ws_check(c, cv)) return rc;
+  const bool use_st = pb.use_st;
   double grm_flops = 0.0, gather_bytes = 0.0, stats_bytes = 0.0;
   const double tri = (double)d.nT * (d.nT + 1) / 2.0 + (double)d.nV * d.nT;
   for (int64_t b = 0; b < B; ++b) {
@@ -473,31 +520,13 @@ int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes&
   }
   const int64_t pk_row = (sd.form == FORM_DUAL) ? dual_pk_row(sd) : 0;
   const int64_t pstride = sd.prow * pk_row;
-  uint8_t* panel = cv.take<uint8_t>((size_t)B * pstride);
-  double* u = cv.take<double>((size_t)B * sd.prow);
-  double* scal = cv.take<double>((size_t)B * SCAL);
-  double* L = cv.take<double>((size_t)B * l_stride(sd.NT));
-  double* Dinv = cv.take<double>((size_t)B * sd.NT * NPACK * BLKD);
-  double* z = cv.take<double>((size_t)B * d.nt * sd.ns);
-  double* wv = cv.take<double>((size_t)B * d.nt * sd.ns);
-  double* rhs = cv.take<double>((size_t)B * d.nt * sd.ns);
-  double* Sp = cv.take<double>((size_t)B * TBLUP_NSLOT * 36 * 256);
-  // (kernel-form fold chunks read their counts from the shared A_R A_R^T instead)
-  const bool use_st = sys_tiles(c, d, sd) && rq.mode != ChunkMode::DebugK && !ft.gsh;
-  // diagonal system tiles: fp64 K_JJ + lambda I (with k_sys_tiles: J < 2 only, the diagonal
-  // kernel's direct reads) and, with k_sys_tiles, the exact int16 counts of J >= 2 (the D-units')
-  double* Kdg = cv.take<double>((size_t)B * sd.NT * NPACK * BLKD);
-  int16_t* kdb = use_st ? cv.take<int16_t>((size_t)B * sd.NT * KD_TILE) : nullptr;
-  int16_t* kcb = use_st ? cv.take<int16_t>((size_t)B * sd.NT * (sd.NT - 1) / 2 * KC_TILE) : nullptr;
-  double* Pp = uses_part(c, B, sd.NT, sys_tiles(c, d, sd)) ? cv.take<double>((size_t)2 * B * sd.NT * TILE * TILE) : nullptr;
-  double* Qb = use_last_term(c, sd, B) ? cv.take<double>((size_t)B * NPACK * BLKD) : nullptr;
+  double *const u = pb.u, *const scal = pb.scal, *const rhs = pb.rhs, *const Qb = pb.Qb;
   const bool fold_share = use_st && sd.form == FORM_PRIMAL && ft.nf > 1 && ft.share;   // k_sys_tiles_folds
-  if (int rc = ws_check(c, cv)) return rc;
   // the launches' arguments, by name (cl.ft above; wgt, q and stats change from launch to launch)
   cl.d = d; cl.sd = sd; cl.B = B; cl.off = rq.d_off; cl.idx = rq.d_idx;
-  cl.L = L; cl.Dinv = Dinv; cl.z = z; cl.w = wv; cl.rhs = rhs; cl.S = Sp; cl.u = u; cl.scal = scal;
-  cl.Kd = Kdg; cl.kd = kdb; cl.kc = kcb; cl.part = Pp; cl.q = Qb;
-  cl.yT = (const double*)rq.sp->yT.p; cl.panel = panel; cl.pstride = pstride; cl.gs_row = d.nRp; cl.gpk_row = d.nRp / 4;
+  cl.L = pb.L; cl.Dinv = pb.Dinv; cl.z = pb.z; cl.w = pb.w; cl.rhs = rhs; cl.S = pb.Sp; cl.u = u; cl.scal = scal;
+  cl.Kd = pb.Kdg; cl.kd = pb.kdb; cl.kc = pb.kcb; cl.part = pb.Pp; cl.q = Qb;
+  cl.yT = (const double*)rq.sp->yT.p; cl.panel = pb.panel; cl.pstride = pstride; cl.gs_row = d.nRp; cl.gpk_row = d.nRp / 4;
   cl.skip = dbg_skip(c) | (rq.mode == ChunkMode::DebugL ? FLAG_WRITE_LJJ : 0);
   cl.padskip = (sd.form == FORM_PRIMAL && sd.pad_first) ? 1 : 0;
   cl.sys_st = c->sys_st;
@@ -522,22 +551,20 @@ int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes&
   if (sd.form == FORM_DUAL && !redo) {
     // primal rows are read in place from the split matrix: no gather
     rc = timed(c, s, KC_GATHER, 0.0, gather_bytes, [&] {
-      return launch_gather(ft, d_idx, d_off, pstride, B, csA, scal, d, pk_row, panel, u, s);
+      return launch_gather(ft, d_idx, d_off, pstride, B, csA, scal, d, pk_row, pb.panel, u, s);
     });
     if (rc) return rc;
   }
-  res.z = z;
+  res.z = pb.z;
   if (rq.mode == ChunkMode::DebugK) {
     // parity readback only: the full K_{R,T} block of the unified form (k_grm); the
     // production path never materialises K (the Cholesky kernels rebuild each tile)
-    double* K = cv.take<double>((size_t)B * d.nRp * d.nTp);
-    if (int rc2 = ws_check(c, cv)) return rc2;
-    res.K = K;
+    res.K = pb.K;
     const double kbytes = (double)B * ((double)d.nT * d.nT / 2.0 + (double)d.nV * d.nT) * 8.0;
     return timed(c, s, KC_GRM, grm_flops, kbytes + gather_bytes / 2.0,
-                 [&] { return launch_grm(panel, pstride, pk_row, d_off, u, scal, d, B, K, s); });
+                 [&] { return launch_grm(pb.panel, pstride, pk_row, d_off, u, scal, d, B, pb.K, s); });
   }
-  res.K = L;
+  res.K = pb.L;
   const double T3 = (double)TILE * TILE * TILE;
   // profiling only: room for one record per Cholesky workgroup of this chunk
   uint64_t* wgt = nullptr;
@@ -545,7 +572,7 @@ int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes&
     int64_t nwg = 0;
     for (int J = 0; J < sd.NT; ++J) nwg += B * (1 + plan[J].ndd) + plan[J].ne + DTR_RECS + offdiag_grid(plan[J], B);
     if (use_st) nwg += B * sd.NT * (sd.NT + 1) / 2;
-    if (chain) nwg += B * sd.NT;   // chained solve units
+    if (pb.chain) nwg += B * sd.NT;   // chained solve units
     if (int rc = dev_alloc(c, c->wgt, (size_t)nwg * WGT_REC * 8)) return rc;
     HIPCHK(hipMemsetAsync(c->wgt.p, 0, (size_t)nwg * WGT_REC * 8, s));
     wgt = (uint64_t*)c->wgt.p;
@@ -629,36 +656,9 @@ int tblup_capi::run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes&
                                  kbar * (double)(d.nT + d.nV));
   SolveChain ch{};
   const SolveChain* chp = nullptr;
-  if (!redo && chain) {
-    const size_t fbytes = ((size_t)B * chain_flags(sd.NT) + CHAIN_ERR_RING + 1) * 4;
-    if (c->chain.bytes < fbytes || c->chain_seq >= INT32_MAX - 1) {
-      HIPCHK(hipStreamSynchronize(s));   // the flags may still be read by an earlier chained solve
-      if (int rc2 = dev_alloc(c, c->chain, fbytes)) return rc2;
-      HIPCHK(hipMemsetAsync(c->chain.p, 0, c->chain.bytes, s));
-      c->chain_seq = 0;
-    }
-    ch.flags = (int32_t*)c->chain.p;
-    int32_t* ring = ch.flags + (c->chain.bytes / 4 - CHAIN_ERR_RING - 1);
-    ch.beta = cv.take<double>((size_t)B * d.nt * sd.ns);
-    ch.cpart = cv.take<double>((size_t)B * sd.NT * sd.NT * d.nt * TILE);
-    ch.epart = cv.take<double>((size_t)B * sd.NT * d.nt * d.nV);
-    ch.mbpart = cv.take<double>((size_t)B * sd.NT * d.nt);
-    if (int rc2 = ws_check(c, cv)) return rc2;
-    ch.seq = ++c->chain_seq;
-    ch.err = ring + ch.seq % CHAIN_ERR_RING;
-    // host entries recover from their ring slot (chain_expired); device entries raise the status word
-    ch.expired = c->host_entry ? ring + CHAIN_ERR_RING : (int32_t*)c->status.p + ST_SOLVE;
+  if (pb.chain) {
+    if (int rc2 = chain_args(c, rq, pb, ch)) return rc2;
     res.chain_seq = ch.seq;
-    ch.mode = c->chain_sync;
-    // pull units for one trait (several traits: their registers spill at two units per CU)
-    ch.pull = c->solve_pull == 1 || (c->solve_pull < 0 && d.nt == 1);
-    ch.spin_max = CHAIN_SPIN_MAX;
-    ch.delay = 0;
-    if (c->chain_dbg_shots > 0) {
-      --c->chain_dbg_shots;
-      ch.spin_max = c->chain_dbg_spin;
-      ch.delay = c->chain_dbg_delay;
-    }
     chp = &ch;
     if (wgt) trace(B * sd.NT);
   }
@@ -943,18 +943,21 @@ int tblup_capi::run_host_batch(const HostBatch& hb, bool with_ebv, const ChunkCa
   tblup_ctx* c = hb.c;
   HostEntry he(c);
   ChunkReq rq{hb.sp, hb.d, hb.sd, c->stream, hb.h2, hb.branch};
+  const int64_t ebv_row = with_ebv ? hb.d.nt * hb.d.nV : 0;
+  const auto head = [&](Carve& cv, int64_t B, int64_t sum_k) { return HeadBufs::carve(cv, B, sum_k, B, B * ebv_row); };
   const ChunkBytes bytes = [&](const int64_t*, int64_t B, int64_t sum_k) {   // one form for the whole call
-    Carve own{nullptr};
-    if (carve) carve(own, B, sum_k);
-    return chunk_bytes(c, hb.d, hb.sd, B, sum_k, with_ebv) + (size_t)round_up((int64_t)own.used, 256);
+    return measure([&](Carve& cv) {
+      head(cv, B, sum_k);
+      if (carve) carve(cv, B, sum_k);
+      PipeBufs::carve(cv, c, hb.d, hb.sd, B, ChunkMode::Full, false);
+    });
   };
   const int rc = for_each_chunk(c, hb.offsets, hb.batch, 65535, bytes, [&](const Chunk& ck) -> int {
     Carve cv{(char*)c->ws.p};
-    int64_t *d_idx, *d_off;
-    if (int rc = upload_chunk(c, cv, hb.idx, hb.offsets, ck, &d_idx, &d_off)) return rc;
-    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = ck.B;
-    rq.d_fit = cv.take<double>((size_t)ck.B);
-    rq.d_ebv = with_ebv ? cv.take<double>((size_t)ck.B * hb.d.nt * hb.d.nV) : nullptr;
+    const HeadBufs h = head(cv, ck.B, ck.sum_k);
+    if (int rc = upload_chunk(c, hb.idx, hb.offsets, ck, h.idx, h.off)) return rc;
+    rq.d_idx = h.idx; rq.d_off = h.off; rq.h_off = ck.hoff; rq.B = ck.B;
+    rq.d_fit = h.fit; rq.d_ebv = h.ebv;
     rq.mode = ChunkMode::Full;
     return body(ck, cv, rq);
   });
@@ -1011,7 +1014,8 @@ int tblup_eval_batch_device(tblup_ctx* c, int split_id, const int64_t* d_idx, co
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
   const EvalDims d = dims_of(c, *sp);
   const SysDims sd = choose_sys(c, d, h_offsets, batch, branch, c->form_pref);
-  if (int rc = ensure_ws(c, s, chunk_bytes(c, d, sd, batch, 0, false))) return rc;
+  const auto pipe = [&](Carve& cv) { PipeBufs::carve(cv, c, d, sd, batch, ChunkMode::Full, false); };
+  if (int rc = ensure_ws(c, s, measure(pipe))) return rc;
   Carve cv{(char*)c->ws.p};
   ChunkReq rq{sp, d, sd, s, h2, branch};
   rq.d_idx = d_idx; rq.d_off = d_offsets; rq.h_off = h_offsets; rq.B = batch;
@@ -1029,8 +1033,7 @@ int tblup_eval_batch_device(tblup_ctx* c, int split_id, const int64_t* d_idx, co
 // back on one stream, reusing one workspace in stream order.  Results are bit-identical either
 // way (every system's arithmetic is independent of the batch it runs in).
 
-// Fused layout of a chunk: the F splits of equal dimensions in the SNP form with system tiles
-// (otherwise 0).  sd: the common system shape.
+// Whether a chunk can run fused: 2..MAXF splits of equal dimensions, one launch's grid (sd: their common shape)
 static bool fold_fusable(const tblup_ctx* c, const std::vector<Split*>& sps, const int64_t* h_off, int64_t B,
                          int branch, SysDims& sd) {
   const int64_t F = (int64_t)sps.size();
@@ -1056,10 +1059,17 @@ static bool fold_gshare(const tblup_ctx* c, const std::vector<Split*>& sps, cons
       return false;
   return true;
 }
-static size_t gshare_bytes(const std::vector<Split*>& sps, int64_t B) {
-  const int64_t nRp = sps[0]->nRp, nTp = sps[0]->nTp, F = (int64_t)sps.size();
-  return (size_t)round_up(B * nRp * nRp * 4, 256) + (size_t)round_up(F * nTp * 4, 256) + 512;
-}
+struct FoldBufs {   // run_folds_fused's own buffers, ahead of the pipeline's
+  int64_t *idx_f, *off_f;   // the index lists replicated per fold [F][sum_k]; the fused offsets [F B + 1]
+  int32_t *gsh, *dmap;      // under fold_gshare: the shared counts [B][nRp][nRp], the fold row maps [F][nTp]
+  static FoldBufs carve(Carve& cv, const tblup_ctx* c, const std::vector<Split*>& sps, const SysDims& sd, int64_t B,
+                        int64_t sum_k) {
+    const size_t F = sps.size(), nRp = (size_t)sps[0]->nRp;
+    const bool g = fold_gshare(c, sps, sd);
+    return {cv.take<int64_t>(F * sum_k), cv.take<int64_t>(F * B + 1), g ? cv.take<int32_t>(B * nRp * nRp) : nullptr,
+            g ? cv.take<int32_t>(F * sps[0]->nTp) : nullptr};
+  }
+};
 
 // The fused chunk: the index lists replicated per fold (F x sum_k, device to device), the fused
 // offsets built on the device, then run_chunk over F x B systems.  rq: the chunk of B individuals as
@@ -1067,67 +1077,69 @@ static size_t gshare_bytes(const std::vector<Split*>& sps, int64_t B) {
 static int run_folds_fused(tblup_ctx* c, const std::vector<Split*>& sps, ChunkReq rq, Carve& cv, ChunkRes& res) {
   const int64_t B = rq.B, F = (int64_t)sps.size(), FB = F * B, sum_k = rq.h_off[B];
   const int64_t *d_idx = rq.d_idx, *d_off = rq.d_off, *h_off = rq.h_off;
-  const SysDims& sd = rq.sd;
   const hipStream_t s = rq.s;
-  int64_t* idx_f = cv.take<int64_t>((size_t)(F * sum_k));
-  int64_t* off_f = cv.take<int64_t>((size_t)FB + 1);
+  const FoldBufs fb = FoldBufs::carve(cv, c, sps, rq.sd, B, sum_k);
+  if (int rc = ws_check(c, cv)) return rc;
   std::vector<int64_t>& ho = c->fold_hoff;   // host copy (run_chunk's work accounting and shapes)
   ho.assign((size_t)FB + 1, 0);
   for (int64_t f = 0; f < F; ++f)
     for (int64_t b = 0; b < B; ++b) ho[f * B + b] = f * sum_k + h_off[b];
   ho[FB] = F * sum_k;
   for (int64_t f = 0; f < F; ++f)
-    HIPCHK(hipMemcpyAsync(idx_f + f * sum_k, d_idx, (size_t)sum_k * 8, hipMemcpyDeviceToDevice, s));
-  HIPCHK(launch_fold_offsets(d_off, B, F, sum_k, off_f, s));
+    HIPCHK(hipMemcpyAsync(fb.idx_f + f * sum_k, d_idx, (size_t)sum_k * 8, hipMemcpyDeviceToDevice, s));
+  HIPCHK(launch_fold_offsets(d_off, B, F, sum_k, fb.off_f, s));
   FoldTab ft{};
   ft.bpf = B;
   ft.nf = (int)F;
   ft.share = c->fold_share;
   for (int64_t f = 1; f < F; ++f) ft.share = ft.share && sps[f]->rows == sps[0]->rows;
-  if (fold_gshare(c, sps, sd)) {
+  if (fb.gsh && rq.mode != ChunkMode::SolveOnly) {   // (the solve-only re-run does not read the counts again)
     const int64_t nRp = sps[0]->nRp, nTp = sps[0]->nTp, nT = sps[0]->nT;
-    int32_t* gsh = cv.take<int32_t>((size_t)(B * nRp * nRp));
-    int32_t* dmap = cv.take<int32_t>((size_t)(F * nTp));
-    if (int rc = ws_check(c, cv)) return rc;
-    // (the solve-only re-run does not read the counts again, but its carve must match the first pass)
-    if (rq.mode != ChunkMode::SolveOnly) {
-      // the fold row maps: system row r of fold f -> fold 0's split row of the same animal
-      std::unordered_map<int64_t, int32_t> pos0;
-      pos0.reserve((size_t)(sps[0]->nT + sps[0]->nV) * 2);
-      for (int64_t i = 0; i < sps[0]->nT; ++i) pos0[sps[0]->train[i]] = (int32_t)i;
-      for (int64_t j = 0; j < sps[0]->nV; ++j) pos0[sps[0]->valid[j]] = (int32_t)(nTp + j);
-      std::vector<int32_t>& hm = c->gmap_host;
-      HIPCHK(hipStreamSynchronize(s));   // the previous chunk's map copy may still read hm
-      hm.assign((size_t)(F * nTp), -1);
-      for (int64_t f = 0; f < F; ++f)
-        for (int64_t r = 0; r < nT; ++r) {
-          const auto it = pos0.find(sps[f]->train[r]);
-          if (it == pos0.end()) return fail(TBLUP_ERR_STATE, "internal error: fold rows are not one animal set");
-          hm[(size_t)(f * nTp + r)] = it->second;
-        }
-      HIPCHK(hipMemcpyAsync(dmap, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, s));
-      ft.gsh = gsh;
-      ft.gmap = dmap;
-      ft.gsh_ld = nRp;
-      ft.gmap_ld = nTp;
-    }
+    // the fold row maps: system row r of fold f -> fold 0's split row of the same animal
+    std::unordered_map<int64_t, int32_t> pos0;
+    pos0.reserve((size_t)(sps[0]->nT + sps[0]->nV) * 2);
+    for (int64_t i = 0; i < sps[0]->nT; ++i) pos0[sps[0]->train[i]] = (int32_t)i;
+    for (int64_t j = 0; j < sps[0]->nV; ++j) pos0[sps[0]->valid[j]] = (int32_t)(nTp + j);
+    std::vector<int32_t>& hm = c->gmap_host;
+    HIPCHK(hipStreamSynchronize(s));   // the previous chunk's map copy may still read hm
+    hm.assign((size_t)(F * nTp), -1);
+    for (int64_t f = 0; f < F; ++f)
+      for (int64_t r = 0; r < nT; ++r) {
+        const auto it = pos0.find(sps[f]->train[r]);
+        if (it == pos0.end()) return fail(TBLUP_ERR_STATE, "internal error: fold rows are not one animal set");
+        hm[(size_t)(f * nTp + r)] = it->second;
+      }
+    HIPCHK(hipMemcpyAsync(fb.dmap, hm.data(), hm.size() * 4, hipMemcpyHostToDevice, s));
+    ft.gsh = fb.gsh; ft.gmap = fb.dmap; ft.gsh_ld = nRp; ft.gmap_ld = nTp;
   }
   for (int64_t f = 0; f < F; ++f) set_fold(ft, f, *sps[f]);
-  rq.d_idx = idx_f;
-  rq.d_off = off_f;
-  rq.h_off = ho.data();
-  rq.B = FB;
+  rq.d_idx = fb.idx_f; rq.d_off = fb.off_f; rq.h_off = ho.data(); rq.B = FB;
   rq.ft = &ft;
   return run_chunk(c, rq, cv, res);
 }
 
-// workspace of a fused chunk: its replicated index lists and the diagonal tiles' counts included,
-// plus room for the host entry's own copy of the chunk's index list and offsets ahead of it
-static size_t fused_bytes(const tblup_ctx* c, const std::vector<Split*>& sps, const SysDims& sd, int64_t B,
-                          int64_t sum_k) {
-  const int64_t F = (int64_t)sps.size();
-  return chunk_bytes(c, dims_of(c, *sps[0]), sd, F * B, F * sum_k, false) + (size_t)(sum_k + B + 1) * 8 + 1024 +
-         (fold_gshare(c, sps, sd) ? gshare_bytes(sps, B) : 0);
+// Workspace of a fold chunk (off: its offsets), behind the host entry's head where there is one: the fused
+// layout (0: not fusable) and the largest split-by-split pipeline.  The host entry's chunks fit the larger;
+// the device entry runs fused where that fits the budget, else split by split.
+struct FoldBytes {
+  size_t fused, split;
+  SysDims fsd;   // fusable: the folds' common shape
+};
+static FoldBytes fold_chunk_bytes(const tblup_ctx* c, const std::vector<Split*>& sps, const int64_t* off, int64_t B,
+                                  int branch, bool host) {
+  const int64_t F = (int64_t)sps.size(), sum_k = off[B];
+  const auto bytes = [&](const Split& sp, const SysDims& sd, bool fused) {
+    return measure([&](Carve& cv) {
+      if (host) HeadBufs::carve(cv, B, sum_k, F * B, 0);
+      if (fused) FoldBufs::carve(cv, c, sps, sd, B, sum_k);
+      PipeBufs::carve(cv, c, dims_of(c, sp), sd, fused ? F * B : B, ChunkMode::Full, fused && fold_gshare(c, sps, sd));
+    });
+  };
+  FoldBytes fb{};
+  for (const Split* sp : sps)
+    fb.split = std::max(fb.split, bytes(*sp, choose_sys(c, dims_of(c, *sp), off, B, branch, c->form_pref), false));
+  if (fold_fusable(c, sps, off, B, branch, fb.fsd)) fb.fused = bytes(*sps[0], fb.fsd, true);
+  return fb;
 }
 
 static int validate_splits(tblup_ctx* c, const int* split_ids, int n_splits, std::vector<Split*>& sps) {
@@ -1172,20 +1184,14 @@ int tblup_eval_folds_device(tblup_ctx* c, const int* split_ids, int n_splits, co
   if (batch > 65535) return fail(TBLUP_ERR_ARG, "device batch limited to 65535 individuals per call");
   HIPCHK(hipSetDevice(c->device));
   hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-  SysDims fsd{};
-  size_t need = fold_fusable(c, sps, h_offsets, batch, branch, fsd) ? fused_bytes(c, sps, fsd, batch, h_offsets[batch]) : 0;
-  const bool fused = need > 0 && need <= c->budget;
-  if (!fused) need = 0;   // split by split: the largest split's chunk
-  for (int f = 0; !fused && f < n_splits; ++f) {
-    const EvalDims d = dims_of(c, *sps[f]);
-    need = std::max(need, chunk_bytes(c, d, choose_sys(c, d, h_offsets, batch, branch, c->form_pref), batch, 0, false));
-  }
-  if (int rc = ensure_ws(c, s, need)) return rc;
+  const FoldBytes need = fold_chunk_bytes(c, sps, h_offsets, batch, branch, false);
+  const bool fused = need.fused > 0 && need.fused <= c->budget;   // else split by split: the largest split's chunk
+  if (int rc = ensure_ws(c, s, fused ? need.fused : need.split)) return rc;
   ChunkReq rq{nullptr, {}, {}, s, h2, branch};   // run_folds sets the split, its dims and the system shape
   rq.d_idx = d_idx; rq.d_off = d_offsets; rq.h_off = h_offsets; rq.B = batch;
   rq.d_fit = d_fitness;
   std::vector<int32_t> seqs;   // device entry: an expiry raises the status word instead
-  return run_folds(c, sps, rq, fused, fsd, Carve{(char*)c->ws.p}, seqs);
+  return run_folds(c, sps, rq, fused, need.fsd, Carve{(char*)c->ws.p}, seqs);
 }
 
 int tblup_eval_folds(tblup_ctx* c, const int* split_ids, int n_splits, const int64_t* idx, const int64_t* offsets,
@@ -1201,25 +1207,18 @@ int tblup_eval_folds(tblup_ctx* c, const int* split_ids, int n_splits, const int
   HIPCHK(hipSetDevice(c->device));
   HostEntry he(c);
   // the form is chosen per chunk, from the candidate's own offsets
-  const ChunkBytes fold_bytes = [&](const int64_t* off, int64_t B, int64_t sum_k) {
-    size_t m = 0;
-    for (const Split* sp : sps) {
-      const EvalDims d = dims_of(c, *sp);
-      m = std::max(m, chunk_bytes(c, d, choose_sys(c, d, off, B, branch, c->form_pref), B, sum_k, false));
-    }
-    SysDims fsd{};
-    if (fold_fusable(c, sps, off, B, branch, fsd)) m = std::max(m, fused_bytes(c, sps, fsd, B, sum_k));
-    return m + (size_t)n_splits * B * 8 + 256;
+  const ChunkBytes fold_bytes = [&](const int64_t* off, int64_t B, int64_t) {
+    const FoldBytes fb = fold_chunk_bytes(c, sps, off, B, branch, true);
+    return std::max(fb.fused, fb.split);
   };
   ChunkReq rq{nullptr, {}, {}, c->stream, h2, branch};   // run_folds sets the split, its dims and the system shape
   const int rc = for_each_chunk(c, offsets, batch, 65535, fold_bytes, [&](const Chunk& ck) -> int {
     const int64_t B = ck.B;
     Carve head{(char*)c->ws.p};
-    int64_t *d_idx, *d_off;
-    if (int rc = upload_chunk(c, head, idx, offsets, ck, &d_idx, &d_off)) return rc;
-    double* d_fit = head.take<double>((size_t)n_splits * B);
-    rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = ck.hoff; rq.B = B;
-    rq.d_fit = d_fit;
+    const HeadBufs h = HeadBufs::carve(head, B, ck.sum_k, n_splits * B, 0);
+    if (int rc = upload_chunk(c, idx, offsets, ck, h.idx, h.off)) return rc;
+    double* const d_fit = rq.d_fit = h.fit;
+    rq.d_idx = h.idx; rq.d_off = h.off; rq.h_off = ck.hoff; rq.B = B;
     SysDims fsd{};
     const bool fused = fold_fusable(c, sps, ck.hoff, B, branch, fsd);
     return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
@@ -1284,15 +1283,16 @@ int tblup_debug_grm(tblup_ctx* c, int split_id, const int64_t* idx, int64_t k, d
   const EvalDims d = dims_of(c, *sp);
   const SysDims sd = choose_sys(c, d, offs, 1, branch, 1);   // readback is of the kernel (dual) form
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (int rc = dev_alloc(c, c->ws, chunk_bytes(c, d, sd, 1, k, false) + (size_t)d.nRp * d.nTp * 8 + 4096)) return rc;
+  const ChunkMode mode = stage == 1 ? ChunkMode::DebugK : ChunkMode::DebugL;
+  const auto carve = [&](Carve& cv) { HeadBufs::carve(cv, 1, k, 1, 0); PipeBufs::carve(cv, c, d, sd, 1, mode, false); };
+  if (int rc = dev_alloc(c, c->ws, measure(carve))) return rc;
   Carve cv{(char*)c->ws.p};
-  int64_t *d_idx, *d_off;
-  if (int rc = upload_chunk(c, cv, idx, offs, Chunk{0, 1, k, offs}, &d_idx, &d_off)) return rc;
-  double* d_fit = cv.take<double>(1);
+  const HeadBufs h = HeadBufs::carve(cv, 1, k, 1, 0);
+  if (int rc = upload_chunk(c, idx, offs, Chunk{0, 1, k, offs}, h.idx, h.off)) return rc;
   ChunkReq rq{sp, d, sd, c->stream, h2, branch};
-  rq.d_idx = d_idx; rq.d_off = d_off; rq.h_off = offs; rq.B = 1;
-  rq.d_fit = d_fit;
-  rq.mode = stage == 1 ? ChunkMode::DebugK : ChunkMode::DebugL;
+  rq.d_idx = h.idx; rq.d_off = h.off; rq.h_off = offs; rq.B = 1;
+  rq.d_fit = h.fit;
+  rq.mode = mode;
   ChunkRes res;
   if (int rc = run_chunk(c, rq, cv, res)) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));

@@ -162,6 +162,13 @@ struct Carve {
     return p;
   }
 };
+// The bytes a carve function takes: the one place a workspace size comes from (no slack on top)
+template <typename F>
+size_t measure(F&& carve) {
+  Carve cv{nullptr};
+  carve(cv);
+  return (size_t)round_up((int64_t)cv.used, 256);
+}
 // Every buffer carved so far lies inside the workspace (checked before the launches that use
 // them: a sizing mistake fails the call instead of faulting the GPU)
 int ws_check(const tblup_ctx* c, const Carve& cv);
@@ -186,9 +193,9 @@ using ChunkBytes = std::function<size_t(const int64_t* hoff, int64_t B, int64_t 
 // fits.  Before the body: the context's stream synchronised, the workspace grown to the chunk's bytes.
 int for_each_chunk(tblup_ctx* c, const int64_t* offsets, int64_t batch, int64_t max_B, const ChunkBytes& bytes,
                    const std::function<int(const Chunk&)>& body);
-// The chunk's index list and offsets carved next from cv and their upload enqueued on the context's stream
-int upload_chunk(tblup_ctx* c, Carve& cv, const int64_t* idx, const int64_t* offsets, const Chunk& ck,
-                 int64_t** d_idx, int64_t** d_off);
+// The chunk's index list and offsets on their way to d_idx [sum_k] / d_off [B + 1] on the context's stream
+int upload_chunk(tblup_ctx* c, const int64_t* idx, const int64_t* offsets, const Chunk& ck, int64_t* d_idx,
+                 int64_t* d_off);
 
 // ---- the evaluation pipeline of one chunk (capi.hip) ----
 enum class ChunkMode {
@@ -230,12 +237,8 @@ struct ChunkRes {
   tblup::CholLaunch cl{};   // the chunk's buffers, for a launch after the pipeline (launch_effects)
 };
 
-// Workspace bytes of run_chunk's carve for B individuals of the system shape sd, plus what every host
-// entry carves in front of it: idx / off, the fitness and, with_ebv, the EBVs (no entry's own buffers).
-size_t chunk_bytes(const tblup_ctx* c, const tblup::EvalDims& d, const tblup::SysDims& sd, int64_t B, int64_t sum_k,
-                   bool with_ebv);
 // Enqueue the pipeline for one chunk (no host synchronisation unless the chain flags must grow); its
-// buffers are carved next from cv.
+// buffers (PipeBufs, capi.hip) are carved next from cv and the lot checked against the workspace.
 int run_chunk(tblup_ctx* c, const ChunkReq& rq, Carve& cv, ChunkRes& res);
 // A host entry's chunk with recovery.  enqueue(redo, seqs) enqueues one pass on the context's stream --
 // its launches and the copies of the results to the host -- and lists the chained solves it enqueued.
@@ -273,7 +276,7 @@ using ChunkCarve = std::function<void(Carve& cv, int64_t B, int64_t sum_k)>;
 // A chunk, the Carve behind its idx / off / fitness / EBVs, the request with every per-chunk member set
 using ChunkBody = std::function<int(const Chunk& ck, Carve& cv, ChunkReq& rq)>;
 // Runs the batch chunk by chunk as a synchronous entry (its chained solves recover on expiry), a chunk's
-// bytes chunk_bytes plus what `carve` (null: nothing) takes; then collects the profiling events.
+// bytes measured on the head's, `carve`'s (null: nothing) and the pipeline's takes; then collects the events.
 int run_host_batch(const HostBatch& hb, bool with_ebv, const ChunkCarve& carve, const ChunkBody& body);
 // One pass of a chunk's pipeline with recovery (redo: the same factor solved by k_solve, for the fitness and
 // the EBVs only).  after(cl) (null: nothing) is enqueued behind pass 0 on the factor it leaves: neither solve

@@ -6,7 +6,7 @@
 //   tblup_snp_score_batch    k_snpscore's launches
 //   tblup_loglik_batch       the pipeline once per h2 row, k_loglik behind each
 //   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
-// tblup_predict_batch (k_predict) runs no pipeline: its own chunks and byte function.
+// tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
 #include <string>
@@ -99,6 +99,17 @@ struct CovBufs {   // tblup_fit_cov_batch
     return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<double>((size_t)2 * COVAR_W * d.nTp),
             cv.take<double>((size_t)2 * COVAR_W * d.nV), cv.take<double>(Bt * n_cov), cv.take<double>(Bt * hb.sd.ns),
             cv.take<double>((size_t)B), cv.take<double>(Bt * d.nV), carve_slices(cv, p)};
+  }
+};
+
+struct PredictBufs {   // tblup_predict_batch: no pipeline, these are the chunk
+  int32_t* an;                      // the animal list [n_pred]
+  int64_t *idx, *off;               // the models' index lists and offsets
+  double *icpt, *cen, *eff, *ebv;   // intercepts [B][nt], centres [sum_k], effects [nt][sum_k]; EBVs [B][nt][n_pred]
+  static PredictBufs carve(Carve& cv, int64_t B, int64_t sum_k, int64_t n_pred, int nt) {
+    const size_t sk = (size_t)sum_k, Bt = (size_t)B * nt;
+    return {cv.take<int32_t>((size_t)n_pred), cv.take<int64_t>(sk), cv.take<int64_t>((size_t)B + 1),
+            cv.take<double>(Bt), cv.take<double>(sk), cv.take<double>(nt * sk), cv.take<double>(Bt * n_pred)};
   }
 };
 
@@ -361,18 +372,8 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
   }
   HIPCHK(hipSetDevice(c->device));
   const int nt = (int)n_traits;
-  // device bytes of models [b0, b1) (every buffer rounded up to 256 B)
   const ChunkBytes bytes_of = [&](const int64_t*, int64_t B, int64_t sum_k) {
-    size_t s = 0;
-    auto add = [&](size_t x) { s = (size_t)round_up((int64_t)(s + x), 256); };
-    add((size_t)n_pred * 4);
-    add((size_t)sum_k * 8);
-    add((size_t)(B + 1) * 8);
-    add((size_t)B * nt * 8);
-    add((size_t)sum_k * 8);
-    add((size_t)nt * sum_k * 8);
-    add((size_t)B * nt * n_pred * 8);
-    return s + 256;
+    return measure([&](Carve& cv) { PredictBufs::carve(cv, B, sum_k, n_pred, nt); });
   };
   // models per chunk: within the workspace budget (TBLUP_WORKSPACE_MB) and one launch's grid,
   // B * nblk <= 0x7fffffff
@@ -380,24 +381,19 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
   return for_each_chunk(c, offsets, batch, 0x7fffffff / nblk, bytes_of, [&](const Chunk& ck) -> int {
     const int64_t b0 = ck.b0, B = ck.B, sum_k = ck.sum_k;
     Carve cv{(char*)c->ws.p};
-    int32_t* d_an = cv.take<int32_t>((size_t)n_pred);
-    int64_t *d_idx, *d_off;
-    if (int rc = upload_chunk(c, cv, idx, offsets, ck, &d_idx, &d_off)) return rc;
-    double* d_int = cv.take<double>((size_t)B * nt);
-    double* d_cen = cv.take<double>((size_t)sum_k);
-    double* d_eff = cv.take<double>((size_t)nt * sum_k);
-    double* d_ebv = cv.take<double>((size_t)B * nt * n_pred);
-    if (ws_check(c, cv)) return fail(TBLUP_ERR_STATE, "internal error: predict buffers overrun the workspace");
+    const PredictBufs pb = PredictBufs::carve(cv, B, sum_k, n_pred, nt);
+    if (int rc = ws_check(c, cv)) return rc;
+    if (int rc = upload_chunk(c, idx, offsets, ck, pb.idx, pb.off)) return rc;
     hipStream_t s = c->stream;
-    HIPCHK(hipMemcpyAsync(d_an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_int, intercept + b0 * nt, (size_t)B * nt * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(d_cen, center + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(pb.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(pb.icpt, intercept + b0 * nt, (size_t)B * nt * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(pb.cen, center + offsets[b0], (size_t)sum_k * 8, hipMemcpyHostToDevice, s));
     for (int t = 0; t < nt; ++t)
-      HIPCHK(hipMemcpyAsync(d_eff + (int64_t)t * sum_k, effects + (int64_t)t * total + offsets[b0], (size_t)sum_k * 8,
+      HIPCHK(hipMemcpyAsync(pb.eff + (int64_t)t * sum_k, effects + (int64_t)t * total + offsets[b0], (size_t)sum_k * 8,
                             hipMemcpyHostToDevice, s));
-    HIPCHK(launch_predict((const int8_t*)c->geno_sm.p, c->n, c->P, d_an, n_pred, d_idx, d_off, B, d_int, d_cen, d_eff,
-                          sum_k, nt, d_ebv, s));
-    HIPCHK(hipMemcpyAsync(ebv + b0 * nt * n_pred, d_ebv, (size_t)B * nt * n_pred * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(launch_predict((const int8_t*)c->geno_sm.p, c->n, c->P, pb.an, n_pred, pb.idx, pb.off, B, pb.icpt, pb.cen,
+                          pb.eff, sum_k, nt, pb.ebv, s));
+    HIPCHK(hipMemcpyAsync(ebv + b0 * nt * n_pred, pb.ebv, (size_t)B * nt * n_pred * 8, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
     return 0;
   });

@@ -16,6 +16,8 @@ Panel: 331 animals (odd: the SNP-major rows k_predict reads are unaligned) x 600
   F  a monomorphic panel (NaN, no error), out-of-range indices, a context without a panel
   G  BlupParallelEvaluator.fit_models / predict, PanelModel save / load
   H  the host entries back to back on one context, each bit-equal to the same call on a fresh context
+  I  every entry's one call on a fresh context (its workspace is exactly the measured carve), bit-equal to
+     the same call behind a larger one
 
 Tolerances: EBV_RTOL = 1e-9 relative max-norm (tests/test_gpu_parity.py); effects the same 1e-9
 relative to the individual's max |effect|, on cases where tests/test_model_host.py shows the
@@ -474,6 +476,11 @@ def test_g_fit_models_matches_evaluate_testing(gpu, tmp_path, removed):
 # ---------------------------------------------------------------------------------------------
 # H. the host entries share one workspace
 # ---------------------------------------------------------------------------------------------
+def _model_arrays(m):
+    extra = [m.cov_effects, m.cov_center] if m.cov_effects is not None else []
+    return [m.center, m.effects, m.intercept, np.asarray(m.fitness)] + extra
+
+
 def _entry_calls():
     """(name, call(engine) -> list of arrays) of the host entries on the (257, 70) split, three SNP-form
     genomes (k in 257..331: three tile columns), in an order that alternates small and large workspace
@@ -486,9 +493,7 @@ def _entry_calls():
     animals, snps = rng.integers(0, N, 17), rng.integers(0, P, 17)
     q = make_cov(N, 2)
 
-    def model(m):
-        extra = [m.cov_effects, m.cov_center] if m.cov_effects is not None else []
-        return [m.center, m.effects, m.intercept, np.asarray(m.fitness)] + extra
+    model = _model_arrays
 
     def evaluate(e):
         return list(e.evaluate(genomes, T, V, H2, return_ebv=True))
@@ -531,4 +536,94 @@ def test_h_entries_back_to_back_leave_nothing_behind(gpu):
             a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
             assert a.shape == b.shape and a.dtype == b.dtype, (name, i)
             assert np.all(np.isfinite(a)), (name, i)
+            assert a.tobytes() == b.tobytes(), (name, i)
+
+
+def _single_call_paths():
+    """(name, env, n_traits, call(engine) -> list of arrays): one call per workspace layout, on the 331 x 600
+    panel.  Together they carve every conditional buffer of the pipeline at least once: the int16 counts and
+    the partial sums (SNP form, three tile columns), the last-term tiles, the chained solve's buffers, the K
+    block (debug_grm stage 1), the folds' shared counts and row maps (TBLUP_DUAL_ST=0)."""
+    from tests.covar_ref import make_cov
+    pn = R.panel()
+    T, V = pn["splits"][257, 70]
+    rng = np.random.default_rng(331)
+    snp = [rng.choice(P, k, replace=False) for k in (257, 300, 331)]      # SNP form, three tile columns
+    kern = [pn["genomes"][400], snp[1]]                                   # k = 400 / 300: kernel form
+    animals, snps = rng.integers(0, N, 17), rng.integers(0, P, 17)
+    q, keys = make_cov(N, 2), rng.random((3, P))
+    parts = np.array_split(np.random.default_rng(17).permutation(330), 3)
+    folds = [(np.concatenate([parts[g] for g in range(3) if g != f]), parts[f]) for f in range(3)]
+    fold_snp = [pn["genomes"][k] for k in (63, 129, 200, "neg")]
+    fold_kern = [pn["genomes"][400], snp[1], pn["genomes"][332]]
+
+    def models(ms):
+        return [a for m in ms for a in _model_arrays(m)]
+
+    def scores(e):
+        sc = e.snp_scores(snp, T, V, H2, snps)
+        return [sc.score, sc.info, sc.q]
+
+    def grm_block(e):
+        K, _ = e.debug_grm(snp[1], T, V, H2, stage=1)     # (stage 1 stops before z is formed)
+        return [np.tril(K[:len(T)]), K[len(T):]]          # k_grm computes the lower-triangle tiles of K_TT only
+
+    def keys_async(e):
+        import torch
+        ev, host, status = e.eval_keys_async(torch.from_numpy(keys).to("cuda:0"), [257, 300, 331], T, V, H2)
+        ev.synchronize()
+        e.raise_status(status)
+        return [host.numpy().copy()]
+
+    paths = []
+    for nt in (1, 2):
+        paths.append(("evaluate nt=%d" % nt, {}, nt, lambda e: [e.evaluate(snp, T, V, H2)]))
+        paths.append(("evaluate+ebv nt=%d" % nt, {}, nt, lambda e: list(e.evaluate(snp, T, V, H2, return_ebv=True))))
+    paths += [
+        ("evaluate kernel form", {}, 1, lambda e: list(e.evaluate(kern, T, V, H2, return_ebv=True))),
+        ("fit", {}, 1, lambda e: models(e.fit(snp, T, V, H2))),
+        ("reliability", {}, 1, lambda e: [e.reliability(snp, T, V, H2, animals)]),
+        ("snp_scores", {}, 1, scores),
+        ("log_likelihood", {}, 1, lambda e: list(e.log_likelihood(snp, T, V, [0.2, 0.45, 0.7], return_sigma2=True))),
+        ("fit covariates", {}, 1, lambda e: models(e.fit(snp, T, V, H2, covariates=q))),
+        ("folds fused", {}, 1, lambda e: [e.evaluate_folds(fold_snp, folds, H2)]),
+        ("folds fused kernel form", {}, 1, lambda e: [e.evaluate_folds(fold_kern, folds, H2)]),
+        ("folds DUAL_ST=0", {"TBLUP_DUAL_ST": "0"}, 1, lambda e: [e.evaluate_folds(fold_kern, folds, H2)]),
+        ("debug_grm 1", {}, 1, grm_block),
+        ("debug_grm 2", {}, 1, lambda e: list(e.debug_grm(snp[1], T, V, H2, stage=2))),
+        ("eval_keys_async", {}, 1, keys_async),
+    ]
+    return paths, (snp, T, V, animals)
+
+
+def test_i_fresh_context_fits_every_layout(gpu):
+    """A context's workspace only grows, so in one context a large early call hides a later call whose measured
+    size misses a buffer.  Every workspace size is the measured carve with nothing added: each path makes its
+    one call on a fresh context, which allocates exactly that size, so a missed buffer fails the call
+    (TBLUP_ERR_STATE from ws_check).  It must succeed and equal, bit for bit, the same call on a context that
+    first made a larger one (8 genomes of k = 331 with EBVs)."""
+    pn = R.panel()
+    paths, (snp, T, V, animals) = _single_call_paths()
+    big = [snp[2]] * 8
+
+    def pheno(nt):
+        return pn["pheno"] if nt == 1 else np.ascontiguousarray(pn["Y"][:, :nt])
+
+    with _engine(pn["geno"], pn["pheno"]) as e:          # predict needs models: from a context of their own
+        fitted = e.fit(snp + [pn["genomes"][400]], T, V, H2)
+    paths.append(("predict", {}, 1, lambda e: [e.predict(fitted, animals)]))
+    want = {}
+    for env, nt in sorted({(tuple(p[1].items()), p[2]) for p in paths}):
+        with _engine(pn["geno"], pheno(nt), dict(env)) as e:
+            e.evaluate(big, T, V, H2, return_ebv=True)
+            for name, penv, pnt, call in paths:
+                if (tuple(penv.items()), pnt) == (env, nt):
+                    want[name] = call(e)
+    for name, env, nt, call in paths:
+        with _engine(pn["geno"], pheno(nt), env) as e:
+            got = call(e)
+        assert len(got) == len(want[name]), name
+        for i, (a, b) in enumerate(zip(got, want[name])):
+            a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+            assert a.shape == b.shape and a.dtype == b.dtype, (name, i)
             assert a.tobytes() == b.tobytes(), (name, i)
