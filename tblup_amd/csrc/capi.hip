@@ -848,6 +848,7 @@ int tblup_set_split(tblup_ctx* c, int split_id, const int64_t* train, int64_t nT
   const int nt = c->nt;
   std::vector<double> yT((size_t)nt * sp->nTp, 0.0), yV((size_t)nt * nV);
   sp->meanyT.assign(nt, 0.0);
+  YResidual yres{};
   for (int t = 0; t < nt; ++t) {
     // mean(y_T) as numpy computes it for Ridge's y_offset (pairwise summation differs only in rounding)
     long double acc = 0.0L;
@@ -857,6 +858,9 @@ int tblup_set_split(tblup_ctx* c, int split_id, const int64_t* train, int64_t nT
       acc += y;
     }
     sp->meanyT[t] = (double)(acc / (long double)nT);
+    long double res = 0.0L;   // what the rounded mean leaves: sum of the doubles y - mean
+    for (int64_t i = 0; i < nT; ++i) res += (long double)(yT[t * sp->nTp + i] - sp->meanyT[t]);
+    yres.v[t] = (double)res;
     for (int64_t i = 0; i < nV; ++i) yV[t * nV + i] = c->pheno[valid[i] * nt + t];
   }
   if (int rc = dev_alloc(c, sp->gpk, (size_t)(c->P + 1) * (sp->nRp / 4) + 64)) return rc;
@@ -872,7 +876,7 @@ int tblup_set_split(tblup_ctx* c, int split_id, const int64_t* train, int64_t nT
   HIPCHK(hipMemcpyAsync(sp->yV.p, yV.data(), yV.size() * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(sp->ymu.p, sp->meanyT.data(), (size_t)nt * 8, hipMemcpyHostToDevice, c->stream));
   HIPCHK(launch_build_split((const int8_t*)c->geno_sm.p, c->n, c->P, (const int32_t*)rm.p, sp->nRp, nT,
-                            (const double*)sp->yT.p, (const double*)sp->ymu.p, nt, (uint8_t*)sp->gpk.p, (int32_t*)sp->colsumT.p, (double*)sp->xty.p, c->stream));
+                            (const double*)sp->yT.p, (const double*)sp->ymu.p, yres, nt, (uint8_t*)sp->gpk.p, (int32_t*)sp->colsumT.p, (double*)sp->xty.p, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   dev_free(c, rm);
   if (Split* old = find_split(c, split_id)) old->release(c);

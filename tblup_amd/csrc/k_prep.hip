@@ -83,7 +83,7 @@ hipError_t launch_colsum_all(const int8_t* geno_sm, int32_t* colsum, int64_t n, 
 __global__ __launch_bounds__(256) void k_build_split(const int8_t* __restrict__ g, int64_t n, int64_t P,
                                                      const int32_t* __restrict__ rowmap, int64_t nRp, int64_t nT,
                                                      const double* __restrict__ yT, const double* __restrict__ ymu,
-                                                     int nt, uint8_t* __restrict__ opk,
+                                                     YResidual yres, int nt, uint8_t* __restrict__ opk,
                                                      int32_t* __restrict__ csT, double* __restrict__ xty) {
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int64_t p = (int64_t)blockIdx.x * 4 + w;
@@ -124,17 +124,20 @@ __global__ __launch_bounds__(256) void k_build_split(const int8_t* __restrict__ 
   }
   if (l == 0) {
     csT[p] = s;
+    // sum_r (x_r - c)(y_r - mu) with c = s / n_T: mu is mean(y_T) rounded to a double, so the residuals sum to
+    // yres = -n_T (mu - mean), not to zero -- 1e-8 for phenotypes around 1e6 -- and the raw x_r carry c of it
+    const double cen = (double)s / (double)nT;
 #pragma unroll
     for (int t = 0; t < MAXT; ++t)
-      if (t < nt) xty[t * P + p] = dot[t];
+      if (t < nt) xty[t * P + p] = dot[t] - cen * yres.v[t];
   }
 }
 
 hipError_t launch_build_split(const int8_t* geno_sm, int64_t n, int64_t P, const int32_t* rowmap, int64_t nRp,
-                              int64_t nT, const double* yT, const double* ymu, int nt,
+                              int64_t nT, const double* yT, const double* ymu, YResidual yres, int nt,
                               uint8_t* geno_packed, int32_t* colsum_T, double* xty, hipStream_t s) {
   hipLaunchKernelGGL(k_build_split, dim3((unsigned)((P + 1 + 3) / 4)), dim3(256), 0, s, geno_sm, n, P, rowmap, nRp,
-                     nT, yT, ymu, nt, geno_packed, colsum_T, xty);
+                     nT, yT, ymu, yres, nt, geno_packed, colsum_T, xty);
   return hipGetLastError();
 }
 

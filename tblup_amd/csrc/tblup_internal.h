@@ -8,7 +8,7 @@
 //                                 2-bit packed (animal 4j+i at bits 2i of byte j); row P is all zero
 //                                 (padding rows of the primal form)
 //     colsum_T  int32 [P]         allele counts over T (snp p)
-//     xty       f64  [nt][P]      sum_t x_tp (y_t - mean y_T): the primal right-hand side, per SNP and trait
+//     xty       f64  [nt][P]      sum_t (x_tp - c_p)(y_t - mean y_T): the primal right-hand side, per SNP and trait
 //     yT        f64 [nTp]         phenotypes of T (0 in padding), yV f64 [nV]
 //   per evaluation chunk of B individuals (workspace):
 //   Two equivalent forms of the per-individual system (chosen per chunk, see SysDims):
@@ -163,8 +163,11 @@ __host__ __device__ __forceinline__ int fold_of(const FoldTab& ft, int64_t s) { 
 // ---- launchers (k_prep.hip) ----
 hipError_t launch_transpose_geno(const int8_t* src, int8_t* dst, int64_t n, int64_t P, hipStream_t s);
 hipError_t launch_colsum_all(const int8_t* geno_sm, int32_t* colsum, int64_t n, int64_t P, hipStream_t s);
+// yres[t] = sum over T of the doubles y_t - ymu[t] (each rounded as the kernel rounds it; only their sum is taken
+// in long double)
+struct YResidual { double v[MAXT]; };
 hipError_t launch_build_split(const int8_t* geno_sm, int64_t n, int64_t P, const int32_t* rowmap,
-                              int64_t nRp, int64_t nT, const double* yT, const double* ymu, int nt,
+                              int64_t nRp, int64_t nT, const double* yT, const double* ymu, YResidual yres, int nt,
                               uint8_t* geno_packed, int32_t* colsum_T, double* xty,
                               hipStream_t s);
 // fused offsets of F copies of a B-individual index list (sum_k indices each): out[F * B + 1]

@@ -100,7 +100,8 @@ def _chol_solve(A, b):
 def fit_wide(idx, train, geno, pheno, h2, branch="auto"):
     """The same model from exact integer counts centred in np.longdouble and a longdouble
     Cholesky (tests/test_edge_cases_cpu.py's wider solve, returning the effects): effects (k,)
-    in longdouble, or None when the system is not positive definite (d = 0)."""
+    in longdouble -- (k, t) for an (n, t) phenotype matrix, one factor for every column -- or None
+    when the system is not positive definite (d = 0)."""
     geno = np.asarray(geno)
     idx = np.asarray(idx, dtype=np.int64)
     T = np.asarray(train)
@@ -114,7 +115,7 @@ def fit_wide(idx, train, geno, pheno, h2, branch="auto"):
     if not d > 0:
         return None
     y = np.asarray(pheno, dtype=np.float64).astype(LD)
-    yc = y[T] - (LD(0) if branch == "gblup" else y[T].mean())
+    yc = y[T] - (LD(0) if branch == "gblup" else y[T].mean(axis=0))
     alpha = (LD(1) - LD(h2)) / LD(h2) * d
     wt = a[T].astype(LD) - m.astype(LD) / LD(N)
     if branch == "snp" and len(idx) <= len(T):
