@@ -300,6 +300,52 @@ int tblup_fit_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t
                         double* cov_effects, double* cov_center, double* intercept, double* center, double* effects);
 
 /*
+ * The score statistics of tblup_snp_score_batch and the likelihood of tblup_loglik_batch for the model with
+ * fixed-effect covariates that tblup_fit_cov_batch fits: cov, n_cov, Q~, G = Q~_T^T V^{-1} Q~_T = C C^T,
+ * h_t = Q~_T^T V^{-1} r_t and b_t = G^{-1} h_t as documented there, and with
+ *   P = V^{-1} - V^{-1} Q~_T G^{-1} Q~_T^T V^{-1},   c = n_cov,   dof = N - r - c.
+ *
+ * tblup_snp_score_cov_batch: for listed column j, w_j as tblup_snp_score_batch defines it, a_j = Q~_T^T V^{-1} w_j:
+ *   score : out, batch x n_traits x n_cand: u_P = w_j^T P r_t = u - (C^{-1} a_j).(C^{-1} h_t)
+ *   info  : out, batch x n_cand:            v_P = w_j^T P w_j = v - |C^{-1} a_j|^2
+ *   q     : optional out, batch x n_traits:  q_P = r_t^T P r_t = q - h_t^T b_t
+ *   cov_effects : optional out, batch x n_traits x n_cov: tblup_fit_cov_batch's b at this h2, bit for bit
+ *   fitness : optional out, batch: tblup_eval_batch's value, bit for bit (the model without covariates)
+ * u_P / v_P is the GLS effect of the SNP fitted as one more covariate beside Q; u_P^2 / (v_P q_P / dof) the
+ * score test.  From the factor, with S = L^{-1} R the covariates' slab (tblup_fit_cov_batch) and s_j the SNP's
+ * solved column (tblup_snp_score_batch):
+ *   kernel form:  a_j = S^T s_j          SNP form:  a_j = (Q~_T^T x_T,j - S^T s_j / d) / lambda
+ * (Q~_T sums to zero over the train rows there, so the centre of w_j drops out).  A listed SNP with
+ * v_P <= 1e-12 v -- constant over the reference rows, or in the span of the covariates -- gives u_P = v_P = 0
+ * exactly.
+ *
+ * tblup_loglik_cov_batch: the restricted likelihood of the N - r - c error contrasts A^T y_T (A orthonormal,
+ * A^T [1 Q~_T] = 0 under snp, A^T Q_T = 0 under gblup, where a mean is fitted only by a column of ones in Q),
+ * sigma2_g profiled out:
+ *   log|A^T V A| = log|V| - r log lambda + log|G| - log|Q~_T^T Q~_T|
+ *   loglik   : out, n_h2 x batch x n_traits: -1/2 [ dof (log 2 pi + 1 + log(q_P / dof)) + log|A^T V A| ]
+ *   sigma2_g : optional out, same shape: q_P / dof
+ *   cov_effects : optional out, n_h2 x batch x n_traits x n_cov: b at each h2
+ *   fitness  : optional out, n_h2 x batch: tblup_eval_batch's value at each h2
+ * log|Q~_T^T Q~_T| does not depend on h2: once per call on the host, in long double; a plane (branch) whose
+ * Q~_T is not of full rank by the pivot rule gives NaN for the models of that branch.
+ *
+ * Both: a model whose G has a pivot that is not positive (tblup_fit_cov_batch's rule) and finite, d = 0, a
+ * flagged index or dof <= 0 gives NaN in score / info / q / loglik / sigma2_g (and cov_effects, except for
+ * dof <= 0): not an error.  cov / n_cov and their errors are tblup_fit_cov_batch's; every other argument, the
+ * index rules, h2 in (0, 1), the empty-call rules, the chunking and the chained-solve recovery are
+ * tblup_snp_score_batch's / tblup_loglik_batch's.  A (model, SNP) value depends neither on the list, the
+ * slab, the batch, the chunking nor TBLUP_SCORE_LDS: fixed-order sums, no atomics.  Host pointers, synchronous.
+ */
+int tblup_snp_score_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* snps,
+                              int64_t n_cand, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                              int branch, double* fitness, double* score, double* info, double* q,
+                              double* cov_effects);
+int tblup_loglik_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
+                           const int64_t* offsets, int64_t batch, const double* h2, int64_t n_h2, int branch,
+                           double* fitness, double* loglik, double* sigma2_g, double* cov_effects);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

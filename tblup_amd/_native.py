@@ -52,6 +52,10 @@ SIGNATURES = {
                                       _DP]),
     "tblup_snp_score_batch": (_c.c_int, [_P, _c.c_int, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _c.c_double,
                                          _c.c_int, _DP, _DP, _DP, _DP]),
+    "tblup_snp_score_cov_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64,
+                                             _c.c_double, _c.c_int, _DP, _DP, _DP, _DP, _DP]),
+    "tblup_loglik_cov_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _I64P, _c.c_int64, _DP, _c.c_int64,
+                                          _c.c_int, _DP, _DP, _DP, _DP]),
     "tblup_predict_batch": (_c.c_int, [_P, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _DP, _DP, _DP, _c.c_int64,
                                        _DP]),
     "tblup_eval_batch_device": (_c.c_int, [_P, _c.c_int, _P, _P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _P, _P,

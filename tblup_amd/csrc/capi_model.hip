@@ -6,6 +6,8 @@
 //   tblup_snp_score_batch    k_snpscore's launches
 //   tblup_loglik_batch       the pipeline once per h2 row, k_loglik behind each
 //   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
+//   tblup_snp_score_cov_batch  k_covar in keep mode, k_snpscore's covariate-adjusted launches
+//   tblup_loglik_cov_batch     the pipeline once per h2 row, k_covar in keep mode and k_loglik behind each
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -101,6 +103,110 @@ struct CovBufs {   // tblup_fit_cov_batch
             cv.take<double>((size_t)B), cv.take<double>(Bt * d.nV), carve_slices(cv, p)};
   }
 };
+
+// What k_covar keeps of a chunk's GLS step for the covariate-adjusted score statistics and likelihood
+// (CovKeep): one slab per model, planned as CovBufs plans it.  passes: the h2 rows whose effects are kept.
+struct CovKeepBufs {
+  SlabPlan plan;
+  double* qT;            // the covariates of the train rows, both planes
+  double* b;             // their fitted effects [passes][B][nt][n_cov]
+  CovKeep keep;          // keep.sq doubles as the slices of a plan without LDS
+  double* lqq;           // log|Q~_T^T Q~_T| of the two planes
+  static CovKeepBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cov, int64_t passes) {
+    const SlabPlan p = plan_slabs(hb, B, COVAR_W, hb.c->score_lds);
+    CovKeepBufs k{p, cv.take<double>((size_t)2 * COVAR_W * hb.d.nTp),
+                  cv.take<double>((size_t)passes * B * hb.d.nt * n_cov), {}, nullptr};
+    k.keep.sq = cv.take<double>((size_t)B * hb.sd.ns * COVAR_W);
+    k.keep.cf = cv.take<double>((size_t)B * COVAR_W * COVAR_W);
+    k.keep.ch = cv.take<double>((size_t)B * MAXT * COVAR_W);
+    k.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
+    k.lqq = cv.take<double>(2);
+    return k;
+  }
+  double* vscr() const { return plan.lds ? nullptr : keep.sq; }
+};
+
+struct ScoreCovBufs {   // tblup_snp_score_cov_batch
+  ScoreBufs s;
+  CovKeepBufs k;
+  static ScoreCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cand, int64_t n_cov) {
+    const ScoreBufs s = ScoreBufs::carve(cv, hb, B, n_cand);
+    return {s, CovKeepBufs::carve(cv, hb, B, n_cov, 1)};
+  }
+};
+
+struct LogLikCovBufs {   // tblup_loglik_cov_batch
+  LogLikBufs l;
+  CovKeepBufs k;
+  static LogLikCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_h2, int64_t n_cov) {
+    const LogLikBufs l = LogLikBufs::carve(cv, hb, B, n_h2);
+    return {l, CovKeepBufs::carve(cv, hb, B, n_cov, n_h2)};
+  }
+};
+
+// The argument checks every covariate entry shares (tblup_fit_cov_batch's)
+int check_cov(const tblup_ctx* c, const double* cov, int64_t n_cov) {
+  if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
+  if (!cov) return fail(TBLUP_ERR_ARG, "null cov");
+  for (int64_t i = 0; i < c->n * n_cov; ++i)
+    if (!std::isfinite(cov[i])) return fail(TBLUP_ERR_ARG, "covariates must be finite");
+  return 0;
+}
+
+// The covariates of the split's rows gathered once per call, covariate-major and zero-padded, as given
+// (plane 0: gblup models) and centred by the column means over the train rows in split order (plane 1:
+// snp models): m [n_cov], qT [2][COVAR_W][nTp], qV [2][COVAR_W][nV] (valid: wanted).
+struct CovPlanes {
+  std::vector<double> m, qT, qV;
+};
+CovPlanes gather_cov(const HostBatch& hb, const double* cov, int64_t n_cov, bool valid) {
+  const EvalDims& d = hb.d;
+  CovPlanes cp{std::vector<double>((size_t)n_cov), std::vector<double>((size_t)2 * COVAR_W * d.nTp, 0.0),
+               std::vector<double>(valid ? (size_t)2 * COVAR_W * d.nV : 0, 0.0)};
+  for (int64_t j = 0; j < n_cov; ++j) {
+    long double acc = 0.0L;
+    for (int64_t i = 0; i < d.nT; ++i) acc += cov[hb.sp->train[i] * n_cov + j];
+    const double m = cp.m[j] = (double)(acc / (long double)d.nT);
+    const auto planes = [&](const std::vector<int64_t>& rows, int64_t n_rows, int64_t ld, std::vector<double>& q) {
+      for (int64_t i = 0; i < n_rows; ++i) {
+        const double v = cov[rows[i] * n_cov + j];
+        q[j * ld + i] = v;
+        q[(COVAR_W + j) * ld + i] = v - m;
+      }
+    };
+    planes(hb.sp->train, d.nT, d.nTp, cp.qT);
+    if (valid) planes(hb.sp->valid, d.nV, d.nV, cp.qV);
+  }
+  return cp;
+}
+
+// log|Q~_T^T Q~_T| of a plane of qT in long double, by Cholesky under k_covar's pivot rule (COVAR_PIV_RTOL of
+// the pivot's own diagonal entry); NaN for a plane that is not of full rank
+double log_det_qq(const double* q, int64_t nT, int64_t nTp, int64_t n_cov) {
+  long double a[COVAR_W][COVAR_W];
+  for (int64_t i = 0; i < n_cov; ++i)
+    for (int64_t j = 0; j <= i; ++j) {
+      long double acc = 0.0L;
+      for (int64_t r = 0; r < nT; ++r) acc += (long double)q[i * nTp + r] * (long double)q[j * nTp + r];
+      a[i][j] = acc;
+    }
+  long double ld = 0.0L;
+  for (int64_t k = 0; k < n_cov; ++k) {
+    const long double gkk = a[k][k];
+    long double p = gkk;
+    for (int64_t m = 0; m < k; ++m) p -= a[k][m] * a[k][m];
+    if (!(p > (long double)COVAR_PIV_RTOL * gkk) || !std::isfinite((double)p)) return std::nan("");
+    const long double ckk = std::sqrt(p);
+    ld += 2.0L * std::log(ckk);
+    for (int64_t i = k + 1; i < n_cov; ++i) {
+      long double v = a[i][k];
+      for (int64_t m = 0; m < k; ++m) v -= a[i][m] * a[k][m];
+      a[i][k] = v / ckk;
+    }
+    a[k][k] = ckk;
+  }
+  return (double)ld;
+}
 
 struct PredictBufs {   // tblup_predict_batch: no pipeline, these are the chunk
   int32_t* an;                      // the animal list [n_pred]
@@ -201,8 +307,8 @@ int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64
     const ScoreBufs sb = carve(cv, B, ck.sum_k);
     HIPCHK(hipMemcpyAsync(sb.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
     return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
-      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, sb.sco, sb.inf,
-                             sb.q, s));
+      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, nullptr, sb.sco,
+                             sb.inf, sb.q, s));
       HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
       HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
       if (q) HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
@@ -249,7 +355,7 @@ int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int
         ChunkRes res;
         if (int rc = run_chunk(c, rq, cvp, res)) return rc;
         seqs.push_back(res.chain_seq);
-        if (!redo) HIPCHK(launch_loglik(res.cl, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
+        if (!redo) HIPCHK(launch_loglik(res.cl, nullptr, nullptr, 0, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
       }
       const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
         return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
@@ -269,10 +375,7 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
   clear_error();
   if (int rc = check_ctx(c)) return rc;
   if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
-  if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
-  if (!cov) return fail(TBLUP_ERR_ARG, "null cov");
-  for (int64_t i = 0; i < c->n * n_cov; ++i)
-    if (!std::isfinite(cov[i])) return fail(TBLUP_ERR_ARG, "covariates must be finite");
+  if (int rc = check_cov(c, cov, n_cov)) return rc;
   const bool model = intercept || center || effects;
   if (model && !(intercept && center && effects))
     return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
@@ -283,25 +386,8 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
   fitness = hb.fitness_or_own(fitness);
   const EvalDims& d = hb.d;
   const int nt = d.nt, nc = (int)n_cov;
-  // the covariates of the split's rows gathered once per call, covariate-major and zero-padded, as given
-  // (plane 0: gblup models) and centred by the column means over the train rows in split order (plane 1:
-  // snp models)
-  std::vector<double> cov_m((size_t)n_cov), h_qT((size_t)2 * COVAR_W * d.nTp, 0.0);
-  std::vector<double> h_qV((size_t)2 * COVAR_W * d.nV, 0.0);
-  for (int64_t j = 0; j < n_cov; ++j) {
-    long double acc = 0.0L;
-    for (int64_t i = 0; i < d.nT; ++i) acc += cov[hb.sp->train[i] * n_cov + j];
-    const double m = cov_m[j] = (double)(acc / (long double)d.nT);
-    const auto planes = [&](const std::vector<int64_t>& rows, int64_t n_rows, int64_t ld, std::vector<double>& q) {
-      for (int64_t i = 0; i < n_rows; ++i) {
-        const double v = cov[rows[i] * n_cov + j];
-        q[j * ld + i] = v;
-        q[(COVAR_W + j) * ld + i] = v - m;
-      }
-    };
-    planes(hb.sp->train, d.nT, d.nTp, h_qT);
-    planes(hb.sp->valid, d.nV, d.nV, h_qV);
-  }
+  const CovPlanes cp = gather_cov(hb, cov, n_cov, true);
+  const std::vector<double>&cov_m = cp.m, &h_qT = cp.qT, &h_qV = cp.qV;
   const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return CovBufs::carve(cv, hb, B, sk, n_cov, model); };
   // per chunk: the pipeline with the one-workgroup solve (nothing to recover; its EBVs are not wanted),
   // k_covar on the factor and z it leaves, then the solve, the fitness and the effects of the adjusted
@@ -319,7 +405,7 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
     rq.d_fit = cb.fit0;
     ChunkRes res;
     if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-    HIPCHK(launch_covar(res.cl, cb.qT, nc, cb.plan, cb.vscr, cb.b, cb.z2, s));
+    HIPCHK(launch_covar(res.cl, cb.qT, nc, cb.plan, cb.vscr, cb.b, cb.z2, CovKeep{}, s));
     CholLaunch cl2 = res.cl;
     cl2.z = cb.z2;
     HIPCHK(launch_solve(cl2, nullptr, cb.fit0, cb.ebv2, s));
@@ -348,6 +434,109 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
     }
   }
   return 0;
+}
+
+int tblup_snp_score_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* snps,
+                              int64_t n_cand, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                              int branch, double* fitness, double* score, double* info, double* q,
+                              double* cov_effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_cov(c, cov, n_cov)) return rc;
+  if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
+  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
+  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  if (batch == 0 || n_cand == 0) return 0;
+  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
+  std::vector<int32_t> s32((size_t)n_cand);
+  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  fitness = hb.fitness_or_own(fitness);
+  const int nt = hb.d.nt, nc = (int)n_cov;
+  const CovPlanes cp = gather_cov(hb, cov, n_cov, false);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreCovBufs::carve(cv, hb, B, n_cand, n_cov); };
+  // per chunk, behind the pipeline: k_covar keeps the model's GLS step, k_snpscore's launches read it
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const ScoreCovBufs sb = carve(cv, B, ck.sum_k);
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpyAsync(sb.s.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sb.k.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      HIPCHK(launch_covar(cl, sb.k.qT, nc, sb.k.plan, sb.k.vscr(), sb.k.b, nullptr, sb.k.keep, s));
+      const ScoreCov sc{sb.k.keep.sq, sb.k.keep.cf, sb.k.keep.ch, sb.k.keep.ks, sb.k.qT, nc};
+      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.s.cand, n_cand, sb.s.plan, sb.s.vscr, &sc,
+                             sb.s.sco, sb.s.inf, sb.s.q, s));
+      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.s.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.s.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
+      if (q) HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.s.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      if (cov_effects)
+        HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, sb.k.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+}
+
+int tblup_loglik_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* idx,
+                           const int64_t* offsets, int64_t batch, const double* h2, int64_t n_h2, int branch,
+                           double* fitness, double* loglik, double* sigma2_g, double* cov_effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_cov(c, cov, n_cov)) return rc;
+  if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
+  if (batch == 0 || n_h2 == 0) return 0;
+  if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
+  for (int64_t i = 0; i < n_h2 * batch; ++i)
+    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
+  const int nt = hb.d.nt, nc = (int)n_cov;
+  const CovPlanes cp = gather_cov(hb, cov, n_cov, false);
+  // log|Q~_T^T Q~_T| does not depend on h2: once per call, one value per plane
+  const double lqq[2] = {log_det_qq(cp.qT.data(), hb.d.nT, hb.d.nTp, n_cov),
+                         log_det_qq(cp.qT.data() + (size_t)COVAR_W * hb.d.nTp, hb.d.nT, hb.d.nTp, n_cov)};
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikCovBufs::carve(cv, hb, B, n_h2, n_cov); };
+  // tblup_loglik_batch's passes, each with k_covar (keep mode, no z*) between the pipeline and k_loglik
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
+    const LogLikCovBufs lc = carve(cv, B, ck.sum_k);
+    const LogLikBufs& lb = lc.l;
+    const CovKeepBufs& kb = lc.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(kb.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(kb.lqq, lqq, sizeof(lqq), hipMemcpyHostToDevice, s));
+    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+      for (int64_t g = 0; g < n_h2; ++g) {
+        Carve cvp = cv;
+        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
+        rq.d_h2 = lb.h2 + g * B;
+        rq.d_fit = lb.fits + g * B;
+        ChunkRes res;
+        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+        seqs.push_back(res.chain_seq);
+        if (redo) continue;
+        HIPCHK(launch_covar(res.cl, kb.qT, nc, kb.plan, kb.vscr(), kb.b + g * B * nt * nc, nullptr, kb.keep, s));
+        HIPCHK(launch_loglik(res.cl, kb.keep.ks, kb.lqq, nc, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
+      }
+      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
+        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
+      };
+      if (fitness) HIPCHK(out(fitness + b0, pitch, lb.fits, row));
+      if (redo) return 0;
+      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
+      if (sigma2_g) HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
+      if (cov_effects) HIPCHK(out(cov_effects + b0 * nt * nc, pitch * nt * nc, kb.b, rowt * nc));
+      return 0;
+    });
+  });
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,

@@ -29,7 +29,12 @@
 //     NaN for b and for z*, so for everything the model's second pass produces.  Positive means above
 //     COVAR_PIV_RTOL of the pivot's own diagonal entry of G: the pivot of a column that repeats another is
 //     rounding noise of either sign, some 1e-16 of that entry.
-//   phase 5: z* for every trait by all threads; the pipeline's z is left as it is.
+//   phase 5: z* for every trait by all threads; the pipeline's z is left as it is.  Skipped when z2 is null.
+// Keep mode (CovKeep non-null, the entries that adjust the score statistics and the likelihood for the
+// covariates): what phases 2 - 4 compute stays in the workspace -- S [ns][16] (copied out of LDS when V
+// lives there; else V is that buffer), C (row-major, identity past c), C^{-1} h_t per trait, and per model
+// {log|G| = 2 sum log C_ii, the bad flag, h_t^T b_t = |C^{-1} h_t|^2 per trait}.  b and z* are the same bits
+// with or without it.
 // So a model's bits are a function of the model, the covariates and the system alone: not of the batch, the
 // chunking or where V lives (LDS when ns x 16 doubles fit, SlabPlan::lds; else a workspace slice of its own).
 //
@@ -52,10 +57,10 @@ static_assert(COVAR_W == FWD_W, "the covariates are one slab of the substitution
 static_assert(COVAR_W * MAXT == 64, "phase 4: one wave, one lane per (trait, covariate)");
 static_assert(CTHR == 2 * CW * CW, "phase 3: two threads per entry of S^T S");
 
-template <int FORM, bool VLDS>
+template <int FORM, bool VLDS, bool KEEP>
 __global__ __launch_bounds__(CTHR) void k_covar(CholLaunch c, const double* __restrict__ qT, int nc,
                                                 double* __restrict__ vscr, double* __restrict__ bhat,
-                                                double* __restrict__ z2) {
+                                                double* __restrict__ z2, CovKeep keep) {
   extern __shared__ __attribute__((aligned(16))) double dyn[];
   __shared__ double pss[2][CW * CW];          // S^T S partial sums by row parity
   __shared__ double psz[CTHR / 64][64];       // S^T z_t partial sums by wave: [wave][16 t + j]
@@ -145,6 +150,13 @@ __global__ __launch_bounds__(CTHR) void k_covar(CholLaunch c, const double* __re
   const double* zb = c.z + b * nt * ns;
   fwd_subst16(Lb, Db, V, NT, J0, J1, pad, q, lc, lg, [](int, double) {});
 
+  if constexpr (VLDS && KEEP) {
+    {
+      double* sq = keep.sq + b * ns * W;
+      for (int64_t i = t; i < ns * W; i += CTHR) sq[i] = V[i];
+    }
+  }
+
   // phase 3: S^T S and S^T z_t over the real rows
   {
     const int i = (t >> 4) & 15, j = t & 15, hp = t >> 8;
@@ -210,6 +222,7 @@ __global__ __launch_bounds__(CTHR) void k_covar(CholLaunch c, const double* __re
       if (i == k) y = yk;
       rhs = __builtin_fma(-g[k], yk, rhs);
     }
+    const double ych = y;   // (C^{-1} h_t)_i
     double bsol = 0.0;
 #pragma unroll
     for (int k = W - 1; k >= 0; --k) {
@@ -222,6 +235,37 @@ __global__ __launch_bounds__(CTHR) void k_covar(CholLaunch c, const double* __re
     b_s[tr][i] = bv;
     if (tr < nt && i < nc) bhat[(b * nt + tr) * nc + i] = bv;
     if (t == 0) bad_s = bad ? 1 : 0;
+    if constexpr (KEEP) {
+      // h_t^T b_t = |C^{-1} h_t|^2: one chain over the covariates in order
+      double hb = 0.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const double yk = __shfl(ych, k, W);
+        hb = __builtin_fma(yk, yk, hb);
+      }
+      // sum log C_kk (C_kk = 1 past c): every lane the log of its own diagonal entry, added in order
+      double cii = 1.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) cii = (k == i) ? g[k] : cii;
+      const double lci = log(cii);
+      double slog = 0.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) slog += __shfl(lci, k, W);
+      if (tr == 0) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) keep.cf[(b * W + i) * W + k] = k <= i ? g[k] : 0.0;
+      }
+      keep.ch[(b * MAXT + tr) * W + i] = ych;
+      double* ks = keep.ks + b * COVAR_KS;
+      if (i == 0) ks[KS_HB + tr] = hb;
+      if (t == 0) {
+        ks[KS_LOGG] = 2.0 * slog;
+        ks[KS_BAD] = bad ? 1.0 : 0.0;
+      }
+    }
+  }
+  if constexpr (KEEP) {
+    if (!z2) return;
   }
   __syncthreads();
 
@@ -278,14 +322,20 @@ __global__ __launch_bounds__(CTHR) void k_cov_fitness(CholLaunch c, const double
 }  // namespace
 
 hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, const SlabPlan& p, double* vscr,
-                        double* bhat, double* z2, hipStream_t s) {
+                        double* bhat, double* z2, const CovKeep& keep, hipStream_t s) {
   if (c.B < 1) return hipSuccess;
   if (c.d.nt < 1 || c.d.nt > MAXT || n_cov < 1 || n_cov > COVAR_W || p.S != 1) return hipErrorInvalidValue;
-  using Kern = decltype(&k_covar<FORM_DUAL, false>);
-  const Kern kern[4] = {k_covar<FORM_DUAL, false>, k_covar<FORM_DUAL, true>, k_covar<FORM_PRIMAL, false>,
-                        k_covar<FORM_PRIMAL, true>};
-  return launch_slabs(kern, c, p, vscr, 1, [&](Kern k, dim3 grid, size_t shm, int64_t, int64_t) {
-    hipLaunchKernelGGL(k, grid, dim3(CTHR), shm, s, c, qT, n_cov, vscr, bhat, z2);
+  // keep mode: every buffer or none; without LDS the slices are S themselves
+  const bool kp = keep.sq || keep.cf || keep.ch || keep.ks;
+  if (kp && !(keep.sq && keep.cf && keep.ch && keep.ks && (p.lds || vscr == keep.sq))) return hipErrorInvalidValue;
+  if (!kp && !z2) return hipErrorInvalidValue;
+  using Kern = decltype(&k_covar<FORM_DUAL, false, false>);
+  const Kern plain[4] = {k_covar<FORM_DUAL, false, false>, k_covar<FORM_DUAL, true, false>,
+                         k_covar<FORM_PRIMAL, false, false>, k_covar<FORM_PRIMAL, true, false>};
+  const Kern kept[4] = {k_covar<FORM_DUAL, false, true>, k_covar<FORM_DUAL, true, true>,
+                        k_covar<FORM_PRIMAL, false, true>, k_covar<FORM_PRIMAL, true, true>};
+  return launch_slabs(kp ? kept : plain, c, p, vscr, 1, [&](Kern k, dim3 grid, size_t shm, int64_t, int64_t) {
+    hipLaunchKernelGGL(k, grid, dim3(CTHR), shm, s, c, qT, n_cov, vscr, bhat, z2, keep);
   });
 }
 

@@ -13,6 +13,12 @@
 // One workgroup per system; several traits share log|V|.  Every lane sums a fixed strided subset of the
 // rows, the wave sum is a fixed-order xor butterfly, the waves' partials meet in LDS and are added in
 // wave order: no atomics, so a system's bits do not depend on the batch around it.
+//
+// With fixed-effect covariates Q~ (ks non-null: what k_covar kept of the model's GLS step at the same h2), the
+// restricted likelihood of the N - r - c error contrasts A^T y (A^T [1 Q~_T] = 0):
+//   q_P = q - h_t^T b_t,  dof = N - r - c,  log|A^T V A| = log|V| - r log lambda + log|G| - log|Q~_T^T Q~_T|
+//   l_R = -1/2 [ dof (log 2 pi + 1 + log(q_P / dof)) + log|A^T V A| ],  sigma2_g = q_P / dof
+// log|Q~_T^T Q~_T| does not depend on h2: the host's, one value per branch (lqq; NaN: not of full rank).
 #include "tblup_internal.h"
 
 namespace tblup {
@@ -27,8 +33,9 @@ __device__ __forceinline__ double wave_sum(double v) {
   return v;
 }
 
-__global__ __launch_bounds__(LL_THREADS) void k_loglik(CholLaunch c, double* __restrict__ loglik,
-                                                       double* __restrict__ sigma2) {
+__global__ __launch_bounds__(LL_THREADS) void k_loglik(CholLaunch c, const double* __restrict__ ks,
+                                                       const double* __restrict__ lqq, int nc,
+                                                       double* __restrict__ loglik, double* __restrict__ sigma2) {
   __shared__ double part[LL_WAVES][LL_SUMS];
   const int t = threadIdx.x;
   const int64_t b = blockIdx.x;
@@ -83,22 +90,37 @@ __global__ __launch_bounds__(LL_THREADS) void k_loglik(CholLaunch c, double* __r
     yy += part[w][1 + MAXT + t];
   }
   const double lam = sc[SC_LAM], d = sc[SC_D], r = sc[SC_MUF];
-  const double N = (double)nT, df = N - r;
+  const double N = (double)nT;
+  double df = N - r;
   const double loglam = log(lam);
   const double logM = -2.0 * slog;
   const double logV = primal ? (N - (double)nrow) * loglam + logM : logM;
-  const double q = primal ? (yy - d * zz) / lam : zz;
-  const bool ok = d > 0.0 && sc[SC_BAD] == 0.0 && q > 0.0 && q < __builtin_inf() && df > 0.0;
+  double q = primal ? (yy - d * zz) / lam : zz;
+  double ldg = 0.0;   // log|G| - log|Q~_T^T Q~_T|
+  bool ok = d > 0.0 && sc[SC_BAD] == 0.0;
+  if (ks) {
+    const double* kb = ks + b * COVAR_KS;
+    const double lq = lqq[(int)sc[SC_MODE] == 1 ? 0 : 1];
+    df = df - (double)nc;
+    q = q - kb[KS_HB + t];
+    ldg = kb[KS_LOGG] - lq;
+    ok = ok && kb[KS_BAD] == 0.0 && lq == lq;
+  }
+  ok = ok && q > 0.0 && q < __builtin_inf() && df > 0.0;
   const double two_pi = 6.283185307179586476925286766559;
-  const double l = -0.5 * (df * (log(two_pi) + 1.0 + log(q / df)) + logV - r * loglam);
+  double m2l = df * (log(two_pi) + 1.0 + log(q / df)) + logV - r * loglam;
+  if (ks) m2l = m2l + ldg;
+  const double l = -0.5 * m2l;
   const double nan = __builtin_nan("");
   loglik[b * nt + t] = ok && l == l ? l : nan;
   sigma2[b * nt + t] = ok ? q / df : nan;
 }
 
-hipError_t launch_loglik(const CholLaunch& c, double* loglik, double* sigma2, hipStream_t s) {
+hipError_t launch_loglik(const CholLaunch& c, const double* ks, const double* lqq, int n_cov, double* loglik,
+                         double* sigma2, hipStream_t s) {
   if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_loglik, dim3((unsigned)c.B), dim3(LL_THREADS), 0, s, c, loglik, sigma2);
+  if (ks && (!lqq || n_cov < 1 || n_cov > COVAR_W)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_loglik, dim3((unsigned)c.B), dim3(LL_THREADS), 0, s, c, ks, lqq, n_cov, loglik, sigma2);
   return hipGetLastError();
 }
 

@@ -31,6 +31,19 @@
 // workgroup's own -- the same arithmetic in the same order.
 // NaN for every output of a model with d = 0 or a flagged index; a column that is constant over the
 // reference rows has w_j = 0 and gives u = v = 0 exactly.
+//
+// COV instances (tblup_snp_score_cov_batch): the statistics of the model with fixed-effect covariates Q~ that
+// k_covar fits, from what its keep mode left in the workspace -- S = L^{-1} R of the covariates, the factor C of
+// G = Q~_T^T V^{-1} Q~_T, C^{-1} h_t and {log|G|, bad flag, h_t^T b_t}:
+//   a_j = Q~_T^T V^{-1} w_j:  kernel form S^T s_j;  SNP form (Q~_T^T x_T,j - S^T s_j / d) / lambda
+//   u_P = u - (C^{-1} a_j).(C^{-1} h_t),  v_P = v - |C^{-1} a_j|^2,  q_P = q - h_t^T b_t
+// behind phase 2, with the same sums for u, v, q as the plain instances:
+//   T = S^T s for the slab's 16 SNPs on fp64 MFMA, wave q over the 4-row groups pad / 4 + q, + 8, .. of the real
+//     rows in order (S from global / L2: a model's slabs share an XCD), the 8 tiles added in wave order in LDS;
+//   SNP form: Q~_T^T x_T,j one fma chain over the train rows in order per (covariate, SNP), 256 threads;
+//   one lane per SNP: a_j, C y = a_j column by column, u_P and v_P; v_P <= COVAR_PIV_RTOL v gives exact zeros.
+// The staging reuses part (tiles, Q~^T x) and ired (C, C^{-1} h_t): no static LDS beyond the plain instances'.
+// NaN also for a model whose G has no positive pivot and for N - r - c <= 0.
 #include <algorithm>
 
 #include "fwd_subst.h"
@@ -46,10 +59,10 @@ constexpr int SKC = 8;                  // SNP form: 16-B loads per operand in f
 static_assert(SCORE_W == FWD_W, "a slab is the substitution's 16 right-hand sides");
 static_assert(SCORE_W * MAXT == 64, "w.r chains: one wave, one lane per (SNP, trait)");
 
-template <int FORM, bool VLDS>
+template <int FORM, bool VLDS, bool COV>
 __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* __restrict__ csA,
                                                   const int32_t* __restrict__ cand, int64_t n_cand, int64_t slab0,
-                                                  int64_t nslab, double* __restrict__ vscr,
+                                                  int64_t nslab, double* __restrict__ vscr, ScoreCov cv,
                                                   double* __restrict__ score, double* __restrict__ info,
                                                   double* __restrict__ qout) {
   extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -228,25 +241,149 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
 #pragma unroll
   for (int tr = 0; tr < MAXT; ++tr) part[1 + tr][t] = zacc[tr];
   __syncthreads();
-  const bool dead = !(dd > 0.0) || sc[SC_BAD] != 0.0;
+  bool dead = !(dd > 0.0) || sc[SC_BAD] != 0.0;
   const double nan = __builtin_nan("");
-  if (t < W && sl * W + t < n_cand) {
-    double s2 = 0.0, sz[MAXT] = {0.0, 0.0, 0.0, 0.0};
-    for (int w = 0; w < STH / 64; ++w)
-      for (int g = 0; g < 4; ++g) {
-        s2 += part[0][64 * w + 16 * g + t];
+  const bool fin = t < W && sl * W + t < n_cand;   // this lane finishes a listed SNP
+  if constexpr (!COV) {
+    if (fin) {
+      double s2 = 0.0, sz[MAXT] = {0.0, 0.0, 0.0, 0.0};
+      for (int w = 0; w < STH / 64; ++w)
+        for (int g = 0; g < 4; ++g) {
+          s2 += part[0][64 * w + 16 * g + t];
 #pragma unroll
-        for (int tr = 0; tr < MAXT; ++tr) sz[tr] += part[1 + tr][64 * w + 16 * g + t];
+          for (int tr = 0; tr < MAXT; ++tr) sz[tr] += part[1 + tr][64 * w + 16 * g + t];
+        }
+      double v;
+      if constexpr (FORM == FORM_PRIMAL) v = (ww_s[t] - s2 / dd) / lam;
+      else v = s2;
+      info[b * n_cand + sl * W + t] = dead ? nan : v;
+      for (int tr = 0; tr < nt; ++tr) {
+        double u;
+        if constexpr (FORM == FORM_PRIMAL) u = (wr_s[tr][t] - sz[tr]) / lam;
+        else u = sz[tr];
+        score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u;
       }
-    double v;
-    if constexpr (FORM == FORM_PRIMAL) v = (ww_s[t] - s2 / dd) / lam;
-    else v = s2;
-    info[b * n_cand + sl * W + t] = dead ? nan : v;
-    for (int tr = 0; tr < nt; ++tr) {
-      double u;
-      if constexpr (FORM == FORM_PRIMAL) u = (wr_s[tr][t] - sz[tr]) / lam;
-      else u = sz[tr];
-      score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u;
+    }
+  } else {
+    // the plain statistics of this lane's SNP, the same sums
+    double v = 0.0, u[MAXT] = {0.0, 0.0, 0.0, 0.0};
+    if (fin) {
+      double s2 = 0.0, sz[MAXT] = {0.0, 0.0, 0.0, 0.0};
+      for (int w = 0; w < STH / 64; ++w)
+        for (int g = 0; g < 4; ++g) {
+          s2 += part[0][64 * w + 16 * g + t];
+#pragma unroll
+          for (int tr = 0; tr < MAXT; ++tr) sz[tr] += part[1 + tr][64 * w + 16 * g + t];
+        }
+      if constexpr (FORM == FORM_PRIMAL) v = (ww_s[t] - s2 / dd) / lam;
+      else v = s2;
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr) {
+        if constexpr (FORM == FORM_PRIMAL) u[tr] = (wr_s[tr][t] - sz[tr]) / lam;
+        else u[tr] = sz[tr];
+      }
+    }
+    // The covariates' share: a_j = Q~_T^T V^{-1} w_j from T = S^T s_j (S = L^{-1} R of the covariates, k_covar's),
+    // then C y = a_j and v_P = v - y.y, u_P = u - y.(C^{-1} h_t).
+    // T for the slab's 16 SNPs on fp64 MFMA, rows of S (global / L2) against the same rows of the solved V:
+    // wave q takes the 4-row groups pad / 4 + q, + 8, .. of the real rows in order (a function of the
+    // system alone); a row outside them counts as zero.
+    const double* ks = cv.ks + b * COVAR_KS;
+    dead = dead || ks[KS_BAD] != 0.0 || !((double)nT - sc[SC_MUF] - (double)cv.nc > 0.0);
+    const double* sq = cv.sq + b * ns * W;
+    v4d tacc = {0.0, 0.0, 0.0, 0.0};
+    const int64_t g1 = (pad + nrow + 3) / 4;
+    // (TKC groups per step, their loads issued together; a slot past the last group multiplies zeros)
+    constexpr int TKC = 16;
+    for (int64_t g0 = pad / 4 + q; g0 < g1; g0 += TKC * (STH / 64)) {
+      double sa[TKC], sv[TKC];
+#pragma unroll
+      for (int e = 0; e < TKC; ++e) {
+        const int64_t g = g0 + e * (STH / 64), r = 4 * g + lg;
+        sa[e] = g < g1 && sys_real(r, pad, nrow) ? sq[r * W + lc] : 0.0;
+        sv[e] = g < g1 ? V[r * W + lc] : 0.0;
+      }
+#pragma unroll
+      for (int e = 0; e < TKC; ++e) tacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[e], sv[e], tacc, 0, 0, 0);
+    }
+    // SNP form: (Q~_T^T x_T,j)_i, thread (covariate i = t / 16, SNP ta): one chain over the train rows in
+    // order, the genotypes unpacked from the packed row (Q~_T sums to zero there: w_j's centre drops out)
+    double qx = 0.0;
+    if constexpr (FORM == FORM_PRIMAL) {
+      if (t < W * W && tp < cv.nc) {
+        const double* qi = cv.qT + (gblup ? 0 : (int64_t)W * nTp) + (int64_t)tp * nTp;
+        // (16 rows per step, the next step's loads in flight under the step's chain, as the w.r chains of
+        // phase 1; a padding row has genotype and covariate zero and adds nothing)
+        double qa[16], qb[16];
+        uint32_t xa, xb;
+        auto ld = [&](double (&qv)[16], uint32_t& x, int64_t g) {
+          x = crow[g];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) qv[e] = qi[16 * g + e];
+        };
+        auto use = [&](const double (&qv)[16], uint32_t x) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) qx = __builtin_fma((double)((x >> (2 * e)) & 3u), qv[e], qx);
+        };
+        const int64_t ng = nTp / 16;
+        ld(qa, xa, 0);
+        for (int64_t g = 0; g < ng; g += 2) {
+          if (g + 1 < ng) ld(qb, xb, g + 1);
+          use(qa, xa);
+          if (g + 1 < ng) {
+            if (g + 2 < ng) ld(qa, xa, g + 2);
+            use(qb, xb);
+          }
+        }
+      }
+    }
+    // staging in the buffers the sums above are done with: the waves' tiles and Q~^T x in part, C and
+    // C^{-1} h_t in ired
+    double* tps = &part[0][0];
+    double* cfs = reinterpret_cast<double*>(&ired[0][0]);
+    static_assert(sizeof(part) >= (STH / 64 + 1) * W * W * 8 && sizeof(ired) >= (W * W + MAXT * W) * 8,
+                  "the covariates' staging fits part / ired");
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tps[q * W * W + (lg + 4 * r) * W + lc] = tacc[r];   // tile element [covariate][SNP]
+    if (t < W * W) {
+      tps[(STH / 64) * W * W + t] = qx;
+      cfs[t] = cv.cf[b * W * W + t];
+    } else if (t < W * W + MAXT * W) {
+      cfs[t] = cv.ch[b * MAXT * W + t - W * W];
+    }
+    __syncthreads();
+    if (fin) {
+      double a[W];
+#pragma unroll
+      for (int i = 0; i < W; ++i) {
+        double T = 0.0;
+        for (int w = 0; w < STH / 64; ++w) T += tps[w * W * W + i * W + t];
+        if constexpr (FORM == FORM_PRIMAL) a[i] = (tps[(STH / 64) * W * W + i * W + t] - T / dd) / lam;
+        else a[i] = T;
+        if (i >= cv.nc) a[i] = 0.0;
+      }
+      // C y = a_j (k_covar's own substitution: column by column), y.y and y.(C^{-1} h_t) on the way
+      double yy = 0.0, yh[MAXT] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const double yk = a[k] / cfs[k * W + k];
+#pragma unroll
+        for (int i = k + 1; i < W; ++i) a[i] = __builtin_fma(-cfs[i * W + k], yk, a[i]);
+        yy = __builtin_fma(yk, yk, yy);
+#pragma unroll
+        for (int tr = 0; tr < MAXT; ++tr) yh[tr] = __builtin_fma(yk, cfs[W * W + tr * W + k], yh[tr]);
+      }
+      // a SNP in the span of the covariates (or constant over the reference rows): exact zeros
+      const double vp = v - yy;
+      const bool span = !(vp > COVAR_PIV_RTOL * v);
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr) u[tr] = span ? 0.0 : u[tr] - yh[tr];
+      v = span ? 0.0 : vp;
+      info[b * n_cand + sl * W + t] = dead ? nan : v;
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr)
+        if (tr < nt) score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u[tr];
     }
   }
   if (sl != 0 || !qout) return;
@@ -295,6 +432,7 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
     double qv;
     if constexpr (FORM == FORM_PRIMAL) qv = (syy - dd * szz) / lam;
     else qv = szz;
+    if constexpr (COV) qv = qv - cv.ks[b * COVAR_KS + KS_HB + t];   // q_P = q - h_t^T b_t
     qout[b * nt + t] = dead ? nan : qv;
   }
 }
@@ -302,16 +440,22 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
 }  // namespace
 
 hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
-                           const SlabPlan& p, double* vscr, double* score, double* info, double* q, hipStream_t s) {
+                           const SlabPlan& p, double* vscr, const ScoreCov* cov, double* score, double* info,
+                           double* q, hipStream_t s) {
   if (c.B < 1 || n_cand < 1) return hipSuccess;
   if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
-  using Kern = decltype(&k_snpscore<FORM_DUAL, false>);
-  const Kern kern[4] = {k_snpscore<FORM_DUAL, false>, k_snpscore<FORM_DUAL, true>, k_snpscore<FORM_PRIMAL, false>,
-                        k_snpscore<FORM_PRIMAL, true>};
+  if (cov && (!cov->sq || !cov->cf || !cov->ch || !cov->ks || !cov->qT || cov->nc < 1 || cov->nc > COVAR_W))
+    return hipErrorInvalidValue;
+  using Kern = decltype(&k_snpscore<FORM_DUAL, false, false>);
+  const Kern plain[4] = {k_snpscore<FORM_DUAL, false, false>, k_snpscore<FORM_DUAL, true, false>,
+                         k_snpscore<FORM_PRIMAL, false, false>, k_snpscore<FORM_PRIMAL, true, false>};
+  const Kern adj[4] = {k_snpscore<FORM_DUAL, false, true>, k_snpscore<FORM_DUAL, true, true>,
+                       k_snpscore<FORM_PRIMAL, false, true>, k_snpscore<FORM_PRIMAL, true, true>};
+  const ScoreCov cv = cov ? *cov : ScoreCov{};
   const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
-    hipLaunchKernelGGL(k, grid, dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr, score, info, q);
+    hipLaunchKernelGGL(k, grid, dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr, cv, score, info, q);
   };
-  return launch_slabs(kern, c, p, vscr, (n_cand + SCORE_W - 1) / SCORE_W, launch);
+  return launch_slabs(cov ? adj : plain, c, p, vscr, (n_cand + SCORE_W - 1) / SCORE_W, launch);
 }
 
 }  // namespace tblup

@@ -407,9 +407,19 @@ hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32
 // listed SNPs), right-hand sides from the split's 2-bit packed rows, then k_reliab's forward substitution
 // (fwd_subst.h).  p / vscr: as launch_reliab.  The same bits either way, and for a SNP wherever it stands in
 // the list.  NaN for a model with d = 0 or a flagged index.
+// With covariates (cov non-null: launch_covar's keep buffers of the same chunk, qT and n_cov as launch_covar
+// has them): score / info / q hold u_P = u - (C^-1 a_j).(C^-1 h_t), v_P = v - |C^-1 a_j|^2 and
+// q_P = q - h_t^T b_t with a_j = Q~_T^T V^-1 w_j from the cross product S^T s_j on fp64 MFMA; u_P = v_P = 0
+// exactly where v_P <= COVAR_PIV_RTOL v; NaN also for a model whose ks is flagged and for N - r - n_cov <= 0.
+// Without: the plain statistics, the same bits as before.
 constexpr int SCORE_W = 16;
+struct ScoreCov {
+  const double *sq, *cf, *ch, *ks, *qT;
+  int nc;
+};
 hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
-                           const SlabPlan& p, double* vscr, double* score, double* info, double* q, hipStream_t s);
+                           const SlabPlan& p, double* vscr, const ScoreCov* cov, double* score, double* info,
+                           double* q, hipStream_t s);
 
 // ---- launchers (k_covar.hip): fixed-effect covariates fitted by GLS from a chunk's factor ----
 // qT [2][COVAR_W][nTp] / qV [2][COVAR_W][nV]: the call's covariates of the split's train / validation rows,
@@ -426,8 +436,18 @@ constexpr int COVAR_W = 16;
 // Q~^T V^-1 Q~ (1 - R^2 of the column on the earlier ones): below it the effects have no digit left at the
 // tests' 1e-9, and an exactly repeated column leaves rounding noise of either sign, ~1e-16 of the entry
 constexpr double COVAR_PIV_RTOL = 1e-12;
+// Keep mode of launch_covar (all four pointers or none): what the model's GLS step computed stays on the
+// device for launch_snpscore's and launch_loglik's covariate adjustment.  sq [B][ns][COVAR_W] = S = L^-1 R
+// (zero at padding rows and at columns past n_cov; without LDS it is vscr itself, the model's slice),
+// cf [B][COVAR_W][COVAR_W] the factor C of G = C C^T (row-major, lower, identity past n_cov),
+// ch [B][MAXT][COVAR_W] = C^-1 h_t, ks [B][COVAR_KS] = {log|G|, bad flag, h_t^T b_t per trait}.  With keep,
+// z2 may be null: z* is then not formed.
+struct CovKeep {
+  double *sq = nullptr, *cf = nullptr, *ch = nullptr, *ks = nullptr;
+};
+enum { KS_LOGG = 0, KS_BAD = 1, KS_HB = 2, COVAR_KS = KS_HB + MAXT };
 hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, const SlabPlan& p, double* vscr,
-                        double* bhat, double* z2, hipStream_t s);
+                        double* bhat, double* z2, const CovKeep& keep, hipStream_t s);
 hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const double* qV, const double* bhat, int n_cov,
                               double* fit, hipStream_t s);
 
@@ -436,7 +456,12 @@ hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const doub
 // z and the scalars that the chunk's pipeline left in c (SNP form: also the split's yT / ymu); one
 // workgroup per model, fixed-order sums, so a model's bits do not depend on the chunk around it.
 // NaN for d = 0, a flagged index or a quadratic form that is not positive and finite.
-hipError_t launch_loglik(const CholLaunch& c, double* loglik, double* sigma2, hipStream_t s);
+// With covariates (ks non-null: launch_covar's keep.ks of the same chunk at the same h2; lqq [2] =
+// log|Q~_T^T Q~_T| of the gblup and of the snp plane, NaN for a plane that is not of full rank):
+// q_P = q - h_t^T b_t, dof = N - r - n_cov, log|A^T V A| = log|V| - r log lambda + log|G| - lqq.  NaN also
+// for a model whose ks is flagged and for dof <= 0.  With ks null: the plain likelihood, the same bits.
+hipError_t launch_loglik(const CholLaunch& c, const double* ks, const double* lqq, int n_cov, double* loglik,
+                         double* sigma2, hipStream_t s);
 
 // ---- launcher (k_model.hip): EBVs of any animals of the panel from fitted models ----
 // ebv[(m * nt + t) * n_pred + v] = intercept[m * nt + t] + sum_j (x[animals[v], idx_j] - center_j)

@@ -270,7 +270,7 @@ class GpuBlupEngine:
                 None, None, None, _ptr(rel)))
         return rel
 
-    def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto"):
+    def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto", covariates=None):
         """Mixed-model score statistics of the panel's SNPs `snps` (column ids: any order, repeats
         allowed, negatives wrap, in or out of the models; None: every column) against the model each
         selected-index set fits on (train, valid): a tblup_amd.model.SnpScores from
@@ -278,24 +278,39 @@ class GpuBlupEngine:
         (B, nt, n_cand), info v = w_j' V^-1 w_j (B, n_cand), q = r_t' V^-1 r_t (B, nt) and dof = N - r.
         u / d is the SNP's back-solved BLUP effect to first order (fit()'s effect for a SNP of the
         model).  h2 in (0, 1).  A degenerate model panel gives NaN; a (model, SNP) value does not
-        depend on the list it comes in.  An empty list runs nothing: q is then NaN."""
+        depend on the list it comes in.  An empty list runs nothing: q is then NaN.
+        covariates: an (n_animals, c) matrix Q as fit(covariates=) takes it -- the statistics are then those of
+        the model with Q fitted beside the panel (tblup_snp_score_cov_batch): u_P, v_P, q_P with V^-1 replaced
+        by P = V^-1 - V^-1 Q~ (Q~' V^-1 Q~)^-1 Q~' V^-1, dof = N - r - c, and `cov_effects` (B, nt, c)
+        bit-identical to fit(covariates=Q)'s.  u_P / v_P is the GLS effect of the SNP fitted as one more
+        covariate.  Collinear covariates give NaN for the model; a listed SNP in the span of the covariates
+        gives u_P = v_P = 0, so NaN statistics."""
         from .model import SnpScores
         self._settle()
         cand = _as_int64(np.arange(self.n_snps) if snps is None else snps)
         if cand.ndim != 1:
             raise ValueError("snps must be a 1-D list of column ids")
+        qc = None if covariates is None else self._covariates(covariates)
         sid = self.split_id(train, valid)
         idx, offsets = concat_genomes(genomes)
         B, nt, m = len(genomes), self.n_traits, len(cand)
         score = np.empty((B, nt, m), dtype=np.float64)
         info = np.empty((B, m), dtype=np.float64)
         q = np.full((B, nt), np.nan)
+        snp = np.array([self._fitted_branch(k, branch) == "snp" for k in np.diff(offsets)], dtype=bool)
+        dof = len(_as_int64(train)) - snp.astype(np.float64)
+        wrapped = np.where(cand < 0, cand + self.n_snps, cand)
+        if qc is not None:
+            nc = qc.shape[1]
+            cov_eff = np.full((B, nt, nc), np.nan)
+            _native.check("tblup_snp_score_cov_batch", self._lib.tblup_snp_score_cov_batch(
+                self._ctx, sid, _ptr(qc), nc, _ptr(cand) if m else None, m, _ptr(idx), _ptr(offsets), B, float(h2),
+                _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q), _ptr(cov_eff)))
+            return SnpScores(score, info, q, (dof - nc).reshape(B), wrapped, cov_effects=cov_eff)
         _native.check("tblup_snp_score_batch", self._lib.tblup_snp_score_batch(
             self._ctx, sid, _ptr(cand) if m else None, m, _ptr(idx), _ptr(offsets), B, float(h2),
             _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q)))
-        snp = np.array([self._fitted_branch(k, branch) == "snp" for k in np.diff(offsets)], dtype=bool)
-        dof = len(_as_int64(train)) - snp.astype(np.float64)
-        return SnpScores(score, info, q, dof.reshape(B), np.where(cand < 0, cand + self.n_snps, cand))
+        return SnpScores(score, info, q, dof.reshape(B), wrapped)
 
     # ------------------------------------------------- variance ratio by (RE)ML
     def log_likelihood(self, genomes, train, valid, h2, branch="auto", return_sigma2=False):
@@ -306,12 +321,24 @@ class GpuBlupEngine:
         (0, 1).  Returns (G, B) -- (B,) for a scalar -- with the trait axis appended for several traits,
         as evaluate(return_ebv=True) shapes its output; return_sigma2=True: (loglik, sigma2_g), the
         profiled genetic variance in the same shape (sigma2_e = (1 - h2) / h2 * sigma2_g).  A degenerate
-        panel gives NaN, not an error; a model's value does not depend on the batch it comes in."""
+        panel gives NaN, not an error; a model's value does not depend on the batch it comes in.
+        With fixed-effect covariates: log_likelihood_cov."""
         ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False)
         return (ll, s2) if return_sigma2 else ll
 
-    def _loglik(self, genomes, train, valid, h2, branch, want_fitness):
+    def log_likelihood_cov(self, genomes, train, valid, h2, covariates, branch="auto", return_sigma2=False):
+        """log_likelihood for the model that fit(covariates=) fits (this method's signature is that one's with
+        `covariates` added; log_likelihood's own stays as it is): covariates is the (n_animals, c) matrix Q as
+        fit takes it, and the value is the restricted likelihood of the N - r - c error contrasts of the model
+        with Q fitted beside the panel (tblup_loglik_cov_batch; include/tblup_gpu.h has the definition), with
+        sigma2_g = q_P / (N - r - c).  Under gblup a mean is fitted only if Q carries a column of ones.
+        Collinear covariates, or c >= N - r, give NaN; NaN / Inf in Q is a ValueError."""
+        ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False, covariates)
+        return (ll, s2) if return_sigma2 else ll
+
+    def _loglik(self, genomes, train, valid, h2, branch, want_fitness, covariates=None):
         self._settle()
+        qc = None if covariates is None else self._covariates(covariates)
         idx, offsets = concat_genomes(genomes)
         B, nt = len(genomes), self.n_traits
         h = np.asarray(h2, dtype=np.float64)
@@ -327,7 +354,12 @@ class GpuBlupEngine:
         ll = np.empty((G, B, nt), dtype=np.float64)
         s2 = np.empty((G, B, nt), dtype=np.float64)
         fit = np.empty((G, B), dtype=np.float64) if want_fitness else None
-        if B and G:
+        if B and G and qc is not None:
+            sid = self.split_id(train, valid)
+            _native.check("tblup_loglik_cov_batch", self._lib.tblup_loglik_cov_batch(
+                self._ctx, sid, _ptr(qc), qc.shape[1], _ptr(idx), _ptr(offsets), B, _ptr(hm), G, _native.BRANCH[branch],
+                _ptr(fit) if want_fitness else None, _ptr(ll), _ptr(s2), None))
+        elif B and G:
             sid = self.split_id(train, valid)
             _native.check("tblup_loglik_batch", self._lib.tblup_loglik_batch(
                 self._ctx, sid, _ptr(idx), _ptr(offsets), B, _ptr(hm), G, _native.BRANCH[branch],
@@ -351,14 +383,24 @@ class GpuBlupEngine:
         is an end of `grid`: the maximum lies outside it or at its edge) and `step`, the spacing of the
         last round's values.  A model whose likelihood is NaN everywhere stays NaN.
         The profile is not guaranteed to be unimodal: the answer is the best point seen, a local
-        maximum when the grid is too coarse to separate two."""
+        maximum when the grid is too coarse to separate two.
+        With fixed-effect covariates: estimate_h2_cov."""
+        return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, None)
+
+    def estimate_h2_cov(self, genomes, train, valid, covariates, branch="auto", grid=np.linspace(0.02, 0.98, 25),
+                        refine=3, points=9):
+        """estimate_h2 on log_likelihood_cov: the h2 of the model that fit(covariates=) fits -- the value to
+        pass to fit(covariates=) and snp_scores(covariates=).  The same search, the same returned fields."""
+        return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, covariates)
+
+    def _estimate_h2(self, genomes, train, valid, branch, grid, refine, points, covariates):
         grid = np.asarray(grid, dtype=np.float64)
         if grid.ndim != 1 or len(grid) < 2 or not np.all(np.diff(grid) > 0):
             raise ValueError("grid must be 1-D, ascending, with at least two values")
         if points < 3:
             raise ValueError("points must be at least 3")
         B, nt = len(genomes), self.n_traits
-        ll0, s20, _ = self._loglik(genomes, train, valid, grid, branch, False)
+        ll0, s20, _ = self._loglik(genomes, train, valid, grid, branch, False, covariates)
         ll0, s20 = ll0.reshape(len(grid), B, nt), s20.reshape(len(grid), B, nt)
         out = {k: np.full((B, nt), np.nan) for k in ("h2", "loglik", "sigma2_g", "sigma2_e", "step")}
         out["at_bound"] = np.zeros((B, nt), dtype=bool)
@@ -380,7 +422,7 @@ class GpuBlupEngine:
                     break
                 lo, hi = h[np.maximum(i - 1, 0), cols], h[np.minimum(i + 1, len(h) - 1), cols]
                 h = np.linspace(lo, hi, points)      # (points, B), both ends exact
-                ll, s2, _ = self._loglik(genomes, train, valid, h, branch, False)
+                ll, s2, _ = self._loglik(genomes, train, valid, h, branch, False, covariates)
                 ll, s2 = ll.reshape(points, B, nt)[:, :, t], s2.reshape(points, B, nt)[:, :, t]
             dead = np.isnan(best[1])
             hb = np.where(dead, np.nan, best[0])

@@ -423,26 +423,36 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
-    def snp_scores(self, population, snps=None, final=True, train=None, valid=None):
+    def snp_scores(self, population, snps=None, final=True, train=None, valid=None, covariates=None):
         """Mixed-model score statistics (tblup_amd.model.SnpScores) of the SNPs `snps` (column ids of the
         evaluator's data; None: every column) against every individual's model: GpuBlupEngine.snp_scores
-        with fit_models' split and genome conventions.  No RNG, no collective: under torch.distributed
-        every rank computes what it is given."""
+        with fit_models' split and genome conventions.  covariates: an (animals, c) matrix of fixed-effect
+        covariates, one row per animal of the evaluator's data -- the statistics are then those of the model
+        that fit_models(covariates=) fits.  No RNG, no collective: under torch.distributed every rank computes
+        what it is given."""
         genomes, train, valid = self._model_setup(population, final, train, valid)
-        return self.engine.snp_scores(genomes, train, valid, self.h2, snps)
+        if covariates is None:
+            return self.engine.snp_scores(genomes, train, valid, self.h2, snps)
+        return self.engine.snp_scores(genomes, train, valid, self.h2, snps, covariates=covariates)
 
     def log_likelihood(self, population, h2, final=True, train=None, valid=None, **kw):
         """Profile (restricted) log-likelihood of every individual's model at `h2` (a scalar, a (G,)
-        grid or a (G, B) matrix): GpuBlupEngine.log_likelihood with fit_models' split and genome
-        conventions.  No RNG, no collective: under torch.distributed every rank computes what it is given."""
+        grid or a (G, B) matrix): GpuBlupEngine.log_likelihood (its keywords pass through; with
+        covariates=Q, an (animals, c) matrix: log_likelihood_cov, the model fit_models(covariates=) fits) with fit_models' split and genome conventions.  No RNG, no collective: under torch.distributed every rank computes what it is given."""
         genomes, train, valid = self._model_setup(population, final, train, valid)
+        if kw.get("covariates") is not None:
+            return self.engine.log_likelihood_cov(genomes, train, valid, h2, **kw)
+        kw.pop("covariates", None)
         return self.engine.log_likelihood(genomes, train, valid, h2, **kw)
 
     def estimate_h2(self, population, final=True, train=None, valid=None, **kw):
         """The h2 that maximises each individual's profile (restricted) likelihood on the panel it
-        selected: GpuBlupEngine.estimate_h2 (its keywords pass through) with fit_models' split and genome
+        selected: GpuBlupEngine.estimate_h2 (its keywords pass through; with covariates=Q: estimate_h2_cov) with fit_models' split and genome
         conventions.  The evaluator's own h2 is not consulted.  No RNG, no collective."""
         genomes, train, valid = self._model_setup(population, final, train, valid)
+        if kw.get("covariates") is not None:
+            return self.engine.estimate_h2_cov(genomes, train, valid, **kw)
+        kw.pop("covariates", None)
         return self.engine.estimate_h2(genomes, train, valid, **kw)
 
     def predict(self, models, animals):

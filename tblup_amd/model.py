@@ -137,23 +137,31 @@ class SnpScores:
         dof   (B,)             N - r: the train animals, minus one under snp (the fitted intercept)
         snps  (n_cand,)        the listed columns, wrapped to [0, P)
 
+    With fixed-effect covariates Q (snp_scores(covariates=), tblup_snp_score_cov_batch) the same fields hold
+    the statistics adjusted for them -- u_P = w_j' P r_t, v_P = w_j' P w_j, q_P = r_t' P r_t with
+    P = V^-1 - V^-1 Q~ (Q~' V^-1 Q~)^-1 Q~' V^-1, dof = N - r - c -- and `cov_effects` (B, nt, c) the GLS
+    effects of the covariates in the model without the SNP (fit(covariates=)'s); it is None otherwise.
+
     The derived statistics are plain numpy and need neither the GPU nor the library; all three give NaN
-    where v == 0 (a column that is constant over the reference rows)."""
+    where v == 0 (a column that is constant over the reference rows, or in the span of the covariates)."""
 
-    __slots__ = ("score", "info", "q", "dof", "snps")
+    __slots__ = ("score", "info", "q", "dof", "snps", "cov_effects")
 
-    def __init__(self, score, info, q, dof, snps):
+    def __init__(self, score, info, q, dof, snps, cov_effects=None):
         self.score = np.asarray(score, dtype=np.float64)
         self.info = np.asarray(info, dtype=np.float64)
         self.q = np.asarray(q, dtype=np.float64)
         self.dof = np.asarray(dof, dtype=np.float64)
         self.snps = np.asarray(snps, dtype=np.int64)
+        self.cov_effects = None if cov_effects is None else np.asarray(cov_effects, dtype=np.float64)
         if self.score.ndim != 3:
             raise ValueError("score must have shape (models, n_traits, n_cand)")
         B, nt, m = self.score.shape
         if self.info.shape != (B, m) or self.q.shape != (B, nt) or self.dof.shape != (B,) or self.snps.shape != (m,):
             raise ValueError("info (B, n_cand), q (B, n_traits), dof (B,) and snps (n_cand,) must match score %s"
                              % (self.score.shape,))
+        if self.cov_effects is not None and (self.cov_effects.ndim != 3 or self.cov_effects.shape[:2] != (B, nt)):
+            raise ValueError("cov_effects must have shape (models, n_traits, n_cov)")
 
     def _uv(self):
         v = np.where(self.info == 0, np.nan, self.info)[:, None, :]

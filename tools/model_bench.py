@@ -24,10 +24,16 @@ numbers go to PERFLOG.md.  One JSON line per part:
            and snp_scores() of 16 listed SNPs -- the same substitution, one slab per model -- alternated in one
            process; k_covar beside k_snpscore, the second k_solve and k_cov_fitness per launch come from a
            --stats run of this part
+  score_cov   config 2 again: snp_scores(covariates=Q) with 16 covariates (tblup_snp_score_cov_batch) beside
+           snp_scores() on the same 2,000-SNP list as `score`, alternated in one process: the ratio is the cost of
+           the covariate adjustment (k_covar in keep mode once per chunk, then S^T s_j, the SNP form's Q~^T x_j
+           chains and the 16-step solve per slab)
+  loglik_cov  config 2 again: tblup_loglik_cov_batch beside tblup_loglik_batch at the same 8 grid points,
+           alternated (per grid point: one k_covar launch more per pass)
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,score_cov,loglik_cov] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -225,6 +231,75 @@ def covar_vs_fit(eng, genomes, T, V, n, P, reps, n_cov=16):
                     "--stats"}
 
 
+def bench_cov(n, n_cov=16):
+    """The covariates of the score_cov / loglik_cov parts (covar_vs_fit's draw)."""
+    rng = np.random.default_rng(77)
+    q = rng.standard_normal((n, n_cov))
+    q[:, 0] = rng.random(n) < 0.5
+    return q
+
+
+def score_cov_vs_score(eng, genomes, T, V, n, P, ns, reps, n_cand=2000, n_cov=16):
+    """snp_scores(covariates=Q) against snp_scores() on score_vs_reliability's list, and evaluate(), alternated."""
+    cand = np.random.default_rng(99).choice(P, n_cand, replace=False)
+    q = bench_cov(n, n_cov)
+    te, ts, tc = [], [], []
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        plain = eng.snp_scores(genomes, T, V, 0.4, cand)
+        t.append(time.perf_counter())
+        adj = eng.snp_scores(genomes, T, V, 0.4, cand, covariates=q)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for lst, i in ((te, 0), (ts, 1), (tc, 2)):
+                lst.append(t[i + 1] - t[i])
+    nslab = (n_cand + 15) // 16
+    return {"evaluate_ms": med_ms(te), "score_ms": med_ms(ts), "score_cov_ms": med_ms(tc), "n_cand": n_cand,
+            "n_cov": n_cov, "score_cov_over_score": round(med_ms(tc) / med_ms(ts), 4),
+            "extra_over_evaluate_ratio": round((med_ms(tc) - med_ms(te)) / (med_ms(ts) - med_ms(te)), 4),
+            "derived_flop_share": round(32.0 / ns, 4), "slab_launch_workgroups": len(genomes) * nslab,
+            "score_ms_all": [round(x * 1e3, 3) for x in ts], "score_cov_ms_all": [round(x * 1e3, 3) for x in tc],
+            "finite": bool(np.all(np.isfinite(adj.score)) and np.all(np.isfinite(adj.info))),
+            "median_info_ratio": float(np.median(adj.info / plain.info)),
+            "note": "each call is the whole evaluation plus its kernels and the D2H copy of its outputs; the adjusted "
+                    "call adds one k_covar launch per chunk; the kernels alone: --stats"}
+
+
+def loglik_cov_vs_loglik(eng, genomes, T, V, n, reps, grid_n=8, n_cov=16):
+    """tblup_loglik_cov_batch against tblup_loglik_batch at grid_n grid points (the C entries, alternated)."""
+    from tblup_amd.engine import concat_genomes
+    from tblup_amd import _native
+    _ptr = _native.ptr
+    sid = eng.split_id(T, V)
+    idx, off = concat_genomes(genomes)
+    B, nt = len(genomes), eng.n_traits
+    q = np.ascontiguousarray(bench_cov(n, n_cov))
+    hg = np.ascontiguousarray(np.repeat(np.linspace(0.1, 0.8, grid_n)[:, None], B, axis=1))
+    ll, s2 = np.empty((grid_n, B, nt)), np.empty((grid_n, B, nt))
+    llc, s2c = np.empty((grid_n, B, nt)), np.empty((grid_n, B, nt))
+    tp, tc = [], []
+    for r in range(reps + 2):
+        t0 = time.perf_counter()
+        _native.check("tblup_loglik_batch", eng._lib.tblup_loglik_batch(
+            eng._ctx, sid, _ptr(idx), _ptr(off), B, _ptr(hg), grid_n, 0, None, _ptr(ll), _ptr(s2)))
+        t1 = time.perf_counter()
+        _native.check("tblup_loglik_cov_batch", eng._lib.tblup_loglik_cov_batch(
+            eng._ctx, sid, _ptr(q), n_cov, _ptr(idx), _ptr(off), B, _ptr(hg), grid_n, 0, None, _ptr(llc), _ptr(s2c), None))
+        t2 = time.perf_counter()
+        if r >= 2:
+            tp.append(t1 - t0)
+            tc.append(t2 - t1)
+    return {"loglik_%d_ms" % grid_n: med_ms(tp), "loglik_cov_%d_ms" % grid_n: med_ms(tc), "n_cov": n_cov,
+            "per_grid_point_ms": round(med_ms(tp) / grid_n, 4), "per_grid_point_cov_ms": round(med_ms(tc) / grid_n, 4),
+            "extra_per_point_ms": round((med_ms(tc) - med_ms(tp)) / grid_n, 4),
+            "loglik_ms_all": [round(x * 1e3, 3) for x in tp], "loglik_cov_ms_all": [round(x * 1e3, 3) for x in tc],
+            "finite": bool(np.all(np.isfinite(llc)) and np.all(np.isfinite(s2c))),
+            "note": "every call ends in the stream's synchronisation; the adjusted call adds one k_covar launch "
+                    "(keep mode, no z*) per pass; the kernels alone: --stats"}
+
+
 def loglik_vs_eval(eng, genomes, T, V, reps, grid_n=8):
     """tblup_eval_batch against tblup_loglik_batch at 1 and grid_n grid points (the C entries, alternated),
     then one estimate_h2 with the defaults."""
@@ -350,6 +425,16 @@ def main():
             st = covar_vs_fit(eng, genomes, T, V, n, P, args.reps)
             print(json.dumps({"part": "covar", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **st}))
+    if parts & {"score_cov", "loglik_cov"}:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            head = {"config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024}
+            if "score_cov" in parts:
+                print(json.dumps({"part": "score_cov", **head,
+                                  **score_cov_vs_score(eng, genomes, T, V, n, P, 1024, args.reps)}))
+            if "loglik_cov" in parts:
+                print(json.dumps({"part": "loglik_cov", **head, **loglik_cov_vs_loglik(eng, genomes, T, V, n, args.reps)}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
