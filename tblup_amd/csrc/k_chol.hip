@@ -496,10 +496,26 @@ __device__ __forceinline__ void i8_tt2d_pk64(const uint8_t* sa, const uint8_t* s
 // GEMM1: acc[cb] -= sum_k L_J[c][k] L_I[i][k] over the nL Lt tiles starting at ltJ / ltI (k < 128 nL)
 // for the wave's 16 columns i and the NCB row blocks cb0 .. cb0+NCB-1, on 32-row stages: only A
 // (the Lt_J stage every wave reads) goes through the LDS ring (2 x 32 KiB); each wave's B operand
-// (its own 16 columns of Lt_I) is loaded straight into registers one stage ahead.  (A 16-row A+B
-// ring has twice the barriers and measured 2% slower.)  Every accumulator element's chain of MFMAs
-// is the same whatever NCB / cb0 and wherever the L range is split, so partial sums handed from
-// one launch to the next reproduce the one-workgroup result bit for bit.
+// (its own 16 columns of Lt_I) is loaded straight into registers: k-step kk of stage s, once its
+// MFMAs are issued, reloads bc[kk] for stage s + 1.  (A 16-row A+B ring has twice the barriers and
+// measured 2% slower.)  Every accumulator element's chain of MFMAs is the same whatever NCB / cb0 and
+// wherever the L range is split, so partial sums handed from one launch to the next reproduce the
+// one-workgroup result bit for bit.
+//
+// Waits.  The vector-memory queue of a wave completes in order.  At the top of stage s it holds,
+// oldest first, A(s) x 4 (LDS-DMA, inline asm: the compiler does not count them) and B(s) x 8; the
+// stage's own wait is vmcnt(8): the four A ops, nothing younger.  A(s + 1) x 4 follows the barrier,
+// and k-step kk waits for bc[kk] with the compiler's vmcnt(7) -- it counts the 8 B loads it sees; the
+// 4 A ops it does not see make that stricter than needed (exact: 11), never laxer -- so a B load has
+// 3 to 4 k-steps (24 to 32 MFMAs of its wave) in flight before anything waits on it.  For the count
+// to hold the B loads are unconditional and pinned behind their k-step by scheduling barriers:
+// under `if (more)` the wait-count pass may not count a load as issued and emitted vmcnt(7 - kk),
+// which from k-step 2 on waited for the loads just issued and drained the queue at k-step 7; left
+// free, max-ILP bunches the loads at the stage's end and spills, and the scratch reloads bring
+// vmcnt(0) into the loop (tools/stage_waits.py --check guards both).  The last stage therefore
+// reloads its own B rows (address clamped to stage s): 8 loads per call, L2 hits, never read -- the
+// compiler tracks them as pending writes of bc[], so no later use of those registers can pass them,
+// and a later counted wait only finds older ops in the queue, which makes it wait for more.
 //
 // r0 (a multiple of 4): leading contraction rows skipped -- the SNP form's leading padding rows,
 // whose columns of block column 0 are exact zeros (sys_real), so only a range that starts at L = 0
@@ -533,14 +549,16 @@ __device__ __forceinline__ void gemm1_a32(const double* __restrict__ ltJ, const 
   for (int kk = 0; kk < 8; ++kk) bc[kk] = bcol[src_of(s0) + 4 * kk * TILE];
   int s = s0;
   if (kf > 0) {   // the first stage from k-step kf
-    // the next stage's A issued before this short stage's wait, not after it (its 4 LDS-DMA ops
-    // stay outstanding: vmcnt(4))
+    // the next stage's A issued before this short stage's wait, not after it.  The queue is then
+    // A(s) x 4, B(s) x 8, A(s + 1) x 4, and only A(s) has to be complete: vmcnt(12) leaves this stage's
+    // 8 B loads (the compiler's own waits cover them) and the next stage's 4 LDS-DMA ops outstanding;
+    // without a next stage the queue is A(s) x 4, B(s) x 8 and vmcnt(8) leaves the 8 B loads.
     const bool more = s + 1 < nst;
     if (more) {
       issue_a(s + 1);
-      asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
     } else {
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();
     const double* bs = bcol + src_of(more ? s + 1 : s);
@@ -553,12 +571,15 @@ __device__ __forceinline__ void gemm1_a32(const double* __restrict__ ltJ, const 
         for (int cb = 0; cb < NCB; ++cb)
           acc[cb] = mfma64_nega(As[lt_off(k, 16 * (cb0 + cb) + (l & 15))], bc[kk], acc[cb]);
       }
+      // conditional here (once per call, not in the loop): unconditional loads in this stage, pinned
+      // or not, spill (scratch 28 -> 208 B per lane)
       if (more) bc[kk] = bs[4 * kk * TILE];
     }
     ++s;
   }
   for (; s < nst; ++s) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    // the queue here, oldest first: A(s) x 4, B(s) x 8 -- only the LDS-DMA ops have to be complete
+    asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     const bool more = s + 1 < nst;
     if (more) issue_a(s + 1);
@@ -570,8 +591,11 @@ __device__ __forceinline__ void gemm1_a32(const double* __restrict__ ltJ, const 
 #pragma unroll
       for (int cb = 0; cb < NCB; ++cb)
         acc[cb] = mfma64_nega(As[lt_off(k, 16 * (cb0 + cb) + (l & 15))], bc[kk], acc[cb]);
-      // B of the next stage into the register this k-step has consumed
-      if (more) bc[kk] = bs[4 * kk * TILE];
+      // B of the next stage into the register this k-step has consumed: unconditional and pinned
+      // behind its k-step (see above)
+      __builtin_amdgcn_sched_barrier(0);
+      bc[kk] = bs[4 * kk * TILE];
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
