@@ -346,6 +346,46 @@ int tblup_loglik_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int6
                            double* fitness, double* loglik, double* sigma2_g, double* cov_effects);
 
 /*
+ * Uncertainty under the model with fixed-effect covariates that tblup_fit_cov_batch fits: the reliabilities of
+ * tblup_reliability_batch with the covariates' effects estimated, not known, the error variance of a predicted
+ * value and the sampling covariance of the covariates' effects.  Notation is tblup_reliability_batch's and
+ * tblup_fit_cov_batch's: V = K_TT + lambda I, k_Ta, K_aa, Q~ (centred by the train means m under snp, as given
+ * under gblup), G = Q~_T^T V^{-1} Q~_T = C C^T.  Under snp the intercept mean(y_T) is still taken as known; under
+ * gblup a mean is fitted only through a column of ones in Q.  For a listed animal a (any row of the panel, in any
+ * or no split role), with P as tblup_snp_score_cov_batch defines it:
+ *   a_a          = Q~_T^T V^{-1} k_Ta                                           (n_cov values)
+ *   reliability  : out, batch x n_pred:  (k_Ta^T V^{-1} k_Ta - |C^{-1} a_a|^2) / K_aa = k_Ta^T P k_Ta / K_aa
+ *                  = 1 - PEV(g^_a - g_a) / (sigma2_g K_aa) with b estimated; never above tblup_reliability_batch's
+ *   pev_total    : optional out, batch x n_pred:  K_aa - k_Ta^T V^{-1} k_Ta + |C^{-1} (q~_a - a_a)|^2, q~_a = q_a - m:
+ *                  the error variance of q~_a^T b^ + g^_a as a predictor of q~_a^T b + g_a, in units of sigma2_g
+ *   cov_cov      : optional out, batch x n_cov x n_cov (compact, row-major):  G^{-1}, in units of sigma2_g:
+ *                  Var(b^_t) = sigma2_g,t G^{-1}, sigma2_g,t being tblup_loglik_cov_batch's
+ *   fitness      : optional out, batch: tblup_fit_cov_batch's, bit for bit
+ *   cov_effects / cov_center / intercept / center / effects : optional as a group (all NULL or none):
+ *                  tblup_fit_cov_batch's, bit for bit
+ * From the factor, with s_a the animal's solved column (tblup_reliability_batch) and S = L^{-1} R the covariates'
+ * slab (tblup_fit_cov_batch):
+ *   kernel form (M = V, R = Q~_T):  a_a = S^T s_a,  k_Ta^T V^{-1} k_Ta = |s_a|^2
+ *   SNP form (M = W_T^T W_T / d + lambda I_k, R = W_T^T Q~_T; V^{-1} W_T = W_T M^{-1}, k_Ta = W_T w_a / d):
+ *     a_a = S^T s_a / d,  k_Ta^T V^{-1} k_Ta = K_aa - lambda |s_a|^2 / d
+ * No phenotype enters reliability, pev_total or cov_cov: with several traits one value per (model, animal).
+ * A model whose G has a pivot that is not positive (tblup_fit_cov_batch's rule) and finite, d = 0 or a flagged
+ * index gives NaN in every output of that model; K_aa = 0 gives NaN for that animal: not errors.  cov / n_cov
+ * and their errors are tblup_fit_cov_batch's; animals and theirs tblup_reliability_batch's; idx / offsets / h2 /
+ * branch, the index rules and the chunking tblup_fit_batch's.  batch == 0 returns 0 and writes nothing, as does
+ * n_pred == 0 when none of cov_cov, fitness and the model group is asked for; n_pred == 0 with one of them given
+ * still fills it.  The second solve behind the model group and fitness runs only when one of them is given.
+ * A (model, animal) value depends neither on the list, the slab, the batch, the chunking nor on where the
+ * right-hand sides live (TBLUP_RELIAB_LDS, TBLUP_SCORE_LDS): fixed-order sums, no atomics.  Host pointers,
+ * synchronous.
+ */
+int tblup_reliability_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov,
+                                const int64_t* animals, int64_t n_pred, const int64_t* idx, const int64_t* offsets,
+                                int64_t batch, double h2, int branch, double* fitness, double* cov_effects,
+                                double* cov_center, double* intercept, double* center, double* effects,
+                                double* reliability, double* pev_total, double* cov_cov);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

@@ -8,6 +8,8 @@
 //   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
 //   tblup_snp_score_cov_batch  k_covar in keep mode, k_snpscore's covariate-adjusted launches
 //   tblup_loglik_cov_batch     the pipeline once per h2 row, k_covar in keep mode and k_loglik behind each
+//   tblup_reliability_cov_batch  k_covar in keep mode, k_reliab's covariate-adjusted launches, k_cov_cov;
+//                                tblup_fit_cov_batch's second pass when the model or its fitness is wanted
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -144,6 +146,30 @@ struct LogLikCovBufs {   // tblup_loglik_cov_batch
   }
 };
 
+struct ReliabCovBufs {   // tblup_reliability_cov_batch
+  ReliabBufs r;
+  CovKeepBufs k;
+  double *qa, *pev, *cc;            // the listed animals' covariates, both planes [2][n_rel][COVAR_W]; pev_total
+                                    // [B][n_rel] and cov_cov [B][n_cov][n_cov] where wanted
+  double *qV, *z2, *fit0, *ebv2;    // tblup_fit_cov_batch's second pass (CovBufs'), where wanted
+  static ReliabCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, int64_t n_cov,
+                             bool model, bool full, bool pev, bool cc) {
+    const EvalDims& d = hb.d;
+    const size_t Bt = (size_t)B * d.nt;
+    ReliabCovBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), CovKeepBufs::carve(cv, hb, B, n_cov, 1)};
+    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
+    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
+    b.cc = cc ? cv.take<double>((size_t)B * n_cov * n_cov) : nullptr;
+    if (full) {
+      b.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
+      b.z2 = cv.take<double>(Bt * hb.sd.ns);
+      b.fit0 = cv.take<double>((size_t)B);
+      b.ebv2 = cv.take<double>(Bt * d.nV);
+    }
+    return b;
+  }
+};
+
 // The argument checks every covariate entry shares (tblup_fit_cov_batch's)
 int check_cov(const tblup_ctx* c, const double* cov, int64_t n_cov) {
   if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
@@ -272,13 +298,123 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
       if (model)
         if (int rc = rb.m.enqueue(hb, ck, cl, center, effects)) return rc;
       HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.an, n_pred, rb.plan,
-                           rb.vscr, rb.rel, s));
+                           rb.vscr, nullptr, rb.rel, s));
       HIPCHK(hipMemcpyAsync(reliability + ck.b0 * n_pred, rb.rel, (size_t)ck.B * n_pred * 8, hipMemcpyDeviceToHost, s));
       return 0;
     });
   });
   if (!rc && model) fill_intercepts(hb, intercept);
   return rc;
+}
+
+int tblup_reliability_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* animals,
+                                int64_t n_pred, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                                int branch, double* fitness, double* cov_effects, double* cov_center,
+                                double* intercept, double* center, double* effects, double* reliability,
+                                double* pev_total, double* cov_cov) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_cov(c, cov, n_cov)) return rc;
+  if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
+  const bool model = cov_effects || cov_center || intercept || center || effects;
+  if (model && !(cov_effects && cov_center && intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "cov_effects/cov_center/intercept/center/effects are given together or not at all");
+  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
+  std::vector<int32_t> a32((size_t)n_pred);
+  for (int64_t i = 0; i < n_pred; ++i) {
+    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
+    a32[i] = (int32_t)animals[i];
+  }
+  // the second solve (the model of the adjusted phenotype and its fitness) runs only for a caller who wants it
+  const bool full = model || fitness;
+  if (batch == 0 || (n_pred == 0 && !full && !cov_cov)) return 0;
+  if (n_pred > 0 && !reliability) return fail(TBLUP_ERR_ARG, "null reliability");
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  fitness = hb.fitness_or_own(fitness);
+  const EvalDims& d = hb.d;
+  const int nt = d.nt, nc = (int)n_cov;
+  const CovPlanes cp = gather_cov(hb, cov, n_cov, full);
+  // q~_a of the listed animals: plane 0 as given, plane 1 centred by the train means, zero past n_cov
+  std::vector<double> h_qa((size_t)2 * n_pred * COVAR_W, 0.0);
+  for (int64_t v = 0; v < n_pred; ++v)
+    for (int64_t j = 0; j < n_cov; ++j) {
+      const double q = cov[animals[v] * n_cov + j];
+      h_qa[v * COVAR_W + j] = q;
+      h_qa[(n_pred + v) * COVAR_W + j] = q - cp.m[j];
+    }
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
+    return ReliabCovBufs::carve(cv, hb, B, sk, n_pred, n_cov, model, full, pev_total != nullptr, cov_cov != nullptr);
+  };
+  // per chunk, behind the pipeline: k_covar keeps the model's GLS step, k_reliab's covariate-adjusted launches
+  // and k_cov_cov read it; a caller who wants the model or its fitness gets tblup_fit_cov_batch's own second
+  // pass (the one-workgroup solve on z*, k_cov_fitness, k_effects) behind them
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const ReliabCovBufs rb = carve(cv, B, ck.sum_k);
+    const CovKeepBufs& kb = rb.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    if (n_pred > 0) {
+      HIPCHK(hipMemcpyAsync(rb.r.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(rb.qa, h_qa.data(), h_qa.size() * 8, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(hipMemcpyAsync(kb.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    if (full) HIPCHK(hipMemcpyAsync(rb.qV, cp.qV.data(), cp.qV.size() * 8, hipMemcpyHostToDevice, s));
+    const auto after = [&](const CholLaunch& cl) -> int {
+      HIPCHK(launch_covar(cl, kb.qT, nc, kb.plan, kb.vscr(), kb.b, rb.z2, kb.keep, s));
+      const ReliabCov rcv{kb.keep.sq, kb.keep.cf, kb.keep.ks, rb.qa, nc, rb.pev};
+      HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.r.an, n_pred,
+                           rb.r.plan, rb.r.vscr, &rcv, rb.r.rel, s));
+      if (n_pred > 0) {
+        HIPCHK(hipMemcpyAsync(reliability + b0 * n_pred, rb.r.rel, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
+        if (pev_total)
+          HIPCHK(hipMemcpyAsync(pev_total + b0 * n_pred, rb.pev, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
+      }
+      if (cov_cov) {
+        HIPCHK(launch_cov_cov(kb.keep.cf, kb.keep.ks, B, nc, rb.cc, s));
+        HIPCHK(hipMemcpyAsync(cov_cov + b0 * nc * nc, rb.cc, (size_t)B * nc * nc * 8, hipMemcpyDeviceToHost, s));
+      }
+      return 0;
+    };
+    if (!full) return factor_pass(hb, ck, cv, rq, fitness, nullptr, after);
+    // tblup_fit_cov_batch's chunk: the pipeline with the one-workgroup solve, then the second pass on z*
+    double* d_fit = rq.d_fit;
+    Carve cvp = cv;
+    rq.mode = ChunkMode::NoChain;
+    rq.d_fit = rb.fit0;
+    ChunkRes res;
+    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+    if (int rc = after(res.cl)) return rc;
+    CholLaunch cl2 = res.cl;
+    cl2.z = rb.z2;
+    HIPCHK(launch_solve(cl2, nullptr, rb.fit0, rb.ebv2, s));
+    HIPCHK(launch_cov_fitness(cl2, rb.ebv2, rb.qV, kb.b, nc, d_fit, s));
+    if (model) {
+      if (int rc = rb.r.m.enqueue(hb, ck, cl2, center, effects)) return rc;
+      HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, kb.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    return 0;
+  });
+  if (rc || !model) return rc;
+  // tblup_fit_cov_batch's post-pass: intercepts, cov_center, and NaN throughout for a model whose covariate
+  // effects are NaN
+  fill_intercepts(hb, intercept);
+  const double nan = std::nan("");
+  for (int64_t b = 0; b < batch; ++b) {
+    const int mode = branch_of(c, offsets[b + 1] - offsets[b], branch);
+    bool dead = false;
+    for (int64_t i = 0; i < nt * n_cov; ++i) dead = dead || std::isnan(cov_effects[b * nt * n_cov + i]);
+    for (int64_t j = 0; j < n_cov; ++j) cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cp.m[j] : 0.0);
+    if (dead) {
+      for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
+      for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+    }
+  }
+  return 0;
 }
 
 int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64_t n_cand, const int64_t* idx,

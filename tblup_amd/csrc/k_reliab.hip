@@ -25,6 +25,20 @@
 // place in the list, of its slab or of the chunking.
 // V lives in LDS when ns x 16 doubles fit beside the staging buffers (ns <= 1024), else in a
 // workspace slice of the workgroup's own -- the same arithmetic in the same order.
+//
+// COV instances (tblup_reliability_cov_batch): the reliabilities under the model with fixed-effect covariates
+// Q~ that k_covar fits, from what its keep mode left in the workspace -- S = L^{-1} R of the covariates, the
+// factor C of G = Q~_T^T V^{-1} Q~_T and the bad flag.  With s_a the animal's solved column and
+// kVk = k_Ta^T V^{-1} k_Ta (kernel form |s_a|^2; SNP form K_aa - lambda |s_a|^2 / d, K_aa = w_a.w_a / d):
+//   a_a = Q~_T^T V^{-1} k_Ta:  kernel form S^T s_a;  SNP form S^T s_a / d   (V^{-1} W_T = W_T M^{-1}, R = W_T^T Q~_T)
+//   rel_cov = (kVk - |C^{-1} a_a|^2) / K_aa,   pev_total = K_aa - kVk + |C^{-1} (q~_a - a_a)|^2
+// behind phase 2, with the same sum for |s_a|^2 as the plain instances:
+//   T = S^T s for the slab's 16 animals on fp64 MFMA, k_snpscore's cross product (wave q over the 4-row groups
+//     pad / 4 + q, + 8, .. of the real rows in order, S from global / L2); the 8 tiles are staged in the head of V
+//     itself, which is done with by then, and added in wave order: no LDS beyond the plain instances';
+//   thread (animal, covariate) of the first four waves: a_a, q~_a - a_a (q~_a from the call's [n_pred][16] array of
+//     the model's branch), the two substitutions C y = a_a and C x = q~_a - a_a column by column by lane shuffles.
+// NaN also for a model whose G has no positive pivot.  k_cov_cov inverts C into G^{-1} per model.
 #include <algorithm>
 
 #include "fwd_subst.h"
@@ -40,11 +54,11 @@ constexpr int RKS = RKC + 16;     // its row stride (bytes): 16 animals' 16-B re
 constexpr int RPARTS = RTH / RELIAB_W;
 static_assert(RELIAB_W == FWD_W, "k_reliab's slab is the substitution's 16 right-hand sides");
 
-template <int FORM, bool VLDS>
+template <int FORM, bool VLDS, bool COV>
 __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __restrict__ geno,
                                                 const int32_t* __restrict__ csA,
                                                 const int32_t* __restrict__ animals, int64_t n_pred, int64_t slab0,
-                                                int64_t nslab, double* __restrict__ vscr,
+                                                int64_t nslab, double* __restrict__ vscr, ReliabCov cv,
                                                 double* __restrict__ rel) {
   extern __shared__ __attribute__((aligned(16))) double dyn[];
   __shared__ double nrm[RTH];
@@ -168,6 +182,86 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
   double nacc = 0.0;
   fwd_subst16(Lb, Db, V, NT, J0, J1, pad, q, lc, lg, [&](int, double v) { nacc = __builtin_fma(v, v, nacc); });
   nrm[t] = nacc;
+  if constexpr (COV) {
+    // The covariates' share: a_a = Q~_T^T V^{-1} k_Ta from T = S^T s_a (S = L^{-1} R of the covariates, k_covar's
+    // keep mode) -- k_snpscore's cross product: rows of S (global / L2) against the same rows of the solved V on
+    // fp64 MFMA, wave q over the 4-row groups pad / 4 + q, + 8, .. of the real rows in order (a function of the
+    // system alone); a row outside them counts as zero.
+    const double* sq = cv.sq + b * ns * W;
+    v4d tacc = {0.0, 0.0, 0.0, 0.0};
+    const int64_t g1 = (pad + nrow + 3) / 4;
+    constexpr int TKC = 8;   // groups per step, their loads issued together (16 spills beside the substitution's ring)
+    for (int64_t g0 = pad / 4 + q; g0 < g1; g0 += TKC * (RTH / 64)) {
+      double sa[TKC], sv[TKC];
+#pragma unroll
+      for (int e = 0; e < TKC; ++e) {
+        const int64_t g = g0 + e * (RTH / 64), r = 4 * g + lg;
+        sa[e] = g < g1 && sys_real(r, pad, nrow) ? sq[r * W + lc] : 0.0;
+        sv[e] = g < g1 ? V[r * W + lc] : 0.0;
+      }
+#pragma unroll
+      for (int e = 0; e < TKC; ++e) tacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[e], sv[e], tacc, 0, 0, 0);
+    }
+    // the solved V is done with: its first 8 x 256 doubles (ns >= TILE rows of 16) stage the waves' tiles,
+    // element [covariate][animal] -- no LDS beyond the plain instances'
+    static_assert((RTH / 64) * W * W <= TILE * W, "the waves' tiles fit the smallest V");
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) V[q * W * W + (lg + 4 * r) * W + lc] = tacc[r];
+    __syncthreads();
+    // thread (animal an = t / 16, covariate i = t % 16) of the first four waves: a_a (SNP form: S^T s_a / d) and
+    // e_a = q~_a - a_a, the tiles added in wave order; then C y = a_a and C x = e_a column by column
+    // (k_covar's own substitution, the solved entries passed by lane shuffles), y.y and x.x on the way
+    if (t < W * W) {
+      const int i = t & (W - 1), an = t >> 4;
+      const int64_t va = sl * W + an;
+      const bool live = va < n_pred;
+      double T = 0.0;
+      for (int w = 0; w < RTH / 64; ++w) T += V[w * W * W + i * W + an];
+      if constexpr (FORM == FORM_PRIMAL) T = T / dd;
+      const bool in = i < cv.nc;
+      const double qv = live && in ? cv.qa[((gblup ? 0 : n_pred) + va) * W + i] : 0.0;
+      double a = in ? T : 0.0, e = in ? qv - T : 0.0;
+      double crow[W];   // row i of C
+#pragma unroll
+      for (int k = 0; k < W; ++k) crow[k] = cv.cf[(b * W + i) * W + k];
+      double cii = 1.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) cii = (k == i) ? crow[k] : cii;
+      double yy = 0.0, xx = 0.0;
+#pragma unroll
+      for (int k = 0; k < W; ++k) {
+        const double yk = __shfl(a / cii, k, W), xk = __shfl(e / cii, k, W);
+        if (i > k) {
+          a = __builtin_fma(-crow[k], yk, a);
+          e = __builtin_fma(-crow[k], xk, e);
+        }
+        yy = __builtin_fma(yk, yk, yy);
+        xx = __builtin_fma(xk, xk, xx);
+      }
+      if (i == 0 && live) {
+        double s2 = 0.0;
+        for (int w = 0; w < RTH / 64; ++w)
+          for (int g = 0; g < 4; ++g) s2 += nrm[64 * w + 16 * g + an];
+        // kVk = k_Ta^T V^{-1} k_Ta and K_aa; SNP form: K_aa - kVk = lambda |s_a|^2 / d
+        const double dn = den[an];
+        double r, pv;
+        if constexpr (FORM == FORM_PRIMAL) {
+          const double kaa = dn / dd, gap = lam * s2 / dd;
+          r = ((kaa - gap) - yy) / kaa;
+          pv = gap + xx;
+        } else {
+          r = (s2 - yy) / dn;
+          pv = (dn - s2) + xx;
+        }
+        if (dd == 0.0 || dn == 0.0 || sc[SC_BAD] != 0.0 || cv.ks[b * COVAR_KS + KS_BAD] != 0.0)
+          r = pv = __builtin_nan("");
+        rel[b * n_pred + va] = r;
+        if (cv.pev) cv.pev[b * n_pred + va] = pv;
+      }
+    }
+    return;
+  }
   __syncthreads();
   if (t < W && sl * W + t < n_pred) {
     double s2 = 0.0;
@@ -178,6 +272,38 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
     else r = s2 / den[t];
     if (dd == 0.0 || den[t] == 0.0 || sc[SC_BAD] != 0.0) r = __builtin_nan("");
     rel[b * n_pred + sl * W + t] = r;
+  }
+}
+
+// cov_cov = G^{-1} = C^{-T} C^{-1} of every model from the factor k_covar keeps (identity past nc): thread j < 16
+// solves C x = e_j (column j of C^{-1}), thread (i, j) one chain over k = max(i, j) .. nc - 1 in order -- the
+// same bits at (i, j) and (j, i).  NaN for a model whose ks is flagged.
+__global__ __launch_bounds__(COVAR_W* COVAR_W) void k_cov_cov(const double* __restrict__ cf,
+                                                               const double* __restrict__ ks, int nc,
+                                                               double* __restrict__ cc) {
+  constexpr int W = COVAR_W;
+  __shared__ double ci[W][W];   // C^{-1}, row-major
+  const int t = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const double* C = cf + b * W * W;
+  if (t < W) {
+    double x[W];
+#pragma unroll
+    for (int i = 0; i < W; ++i) x[i] = i == t ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < W; ++k) {
+      const double xk = x[k] / C[k * W + k];
+#pragma unroll
+      for (int i = k + 1; i < W; ++i) x[i] = __builtin_fma(-C[i * W + k], xk, x[i]);
+      ci[k][t] = xk;
+    }
+  }
+  __syncthreads();
+  const int i = t >> 4, j = t & 15;
+  if (i < nc && j < nc) {
+    double acc = 0.0;
+    for (int k = i > j ? i : j; k < nc; ++k) acc = __builtin_fma(ci[k][i], ci[k][j], acc);
+    cc[(b * nc + i) * nc + j] = ks[b * COVAR_KS + KS_BAD] != 0.0 ? __builtin_nan("") : acc;
   }
 }
 
@@ -192,15 +318,28 @@ SlabPlan slab_plan(const SysDims& sd, int64_t B, int64_t n_items, bool lds_knob,
 }
 
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
-                         int64_t n_pred, const SlabPlan& p, double* vscr, double* rel, hipStream_t s) {
+                         int64_t n_pred, const SlabPlan& p, double* vscr, const ReliabCov* cov, double* rel,
+                         hipStream_t s) {
   if (c.B < 1 || n_pred < 1) return hipSuccess;
-  using Kern = decltype(&k_reliab<FORM_DUAL, false>);
-  const Kern kern[4] = {k_reliab<FORM_DUAL, false>, k_reliab<FORM_DUAL, true>, k_reliab<FORM_PRIMAL, false>,
-                        k_reliab<FORM_PRIMAL, true>};
+  if (cov && (!cov->sq || !cov->cf || !cov->ks || !cov->qa || cov->nc < 1 || cov->nc > COVAR_W))
+    return hipErrorInvalidValue;
+  using Kern = decltype(&k_reliab<FORM_DUAL, false, false>);
+  const Kern plain[4] = {k_reliab<FORM_DUAL, false, false>, k_reliab<FORM_DUAL, true, false>,
+                         k_reliab<FORM_PRIMAL, false, false>, k_reliab<FORM_PRIMAL, true, false>};
+  const Kern adj[4] = {k_reliab<FORM_DUAL, false, true>, k_reliab<FORM_DUAL, true, true>,
+                       k_reliab<FORM_PRIMAL, false, true>, k_reliab<FORM_PRIMAL, true, true>};
+  const ReliabCov cv = cov ? *cov : ReliabCov{};
   const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
-    hipLaunchKernelGGL(k, grid, dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn, vscr, rel);
+    hipLaunchKernelGGL(k, grid, dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn, vscr, cv, rel);
   };
-  return launch_slabs(kern, c, p, vscr, (n_pred + RELIAB_W - 1) / RELIAB_W, launch);
+  return launch_slabs(cov ? adj : plain, c, p, vscr, (n_pred + RELIAB_W - 1) / RELIAB_W, launch);
+}
+
+hipError_t launch_cov_cov(const double* cf, const double* ks, int64_t B, int n_cov, double* cc, hipStream_t s) {
+  if (B < 1) return hipSuccess;
+  if (!cf || !ks || !cc || n_cov < 1 || n_cov > COVAR_W || B > 0x7fffffff) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_cov_cov, dim3((unsigned)B), dim3(COVAR_W * COVAR_W), 0, s, cf, ks, n_cov, cc);
+  return hipGetLastError();
 }
 
 }  // namespace tblup

@@ -396,9 +396,22 @@ SlabPlan slab_plan(const SysDims& sd, int64_t B, int64_t n_items, bool lds_knob,
 // (model, slab of RELIAB_W listed animals), a blocked forward substitution on fp64 MFMA.  p / vscr: the
 // list's slab_plan and its scratch() doubles (null with LDS).
 // The same bits either way, and for an animal wherever it stands in the list.
+// With covariates (cov non-null: sq / cf / ks launch_covar's keep buffers of the same chunk; qa [2][n_pred][16]
+// the listed animals' covariates, plane 0 as given (gblup models), plane 1 centred by the train means (snp
+// models), zero past nc): rel holds (k_Ta^T V^-1 k_Ta - |C^-1 a_a|^2) / K_aa and pev (may be null)
+// K_aa - k_Ta^T V^-1 k_Ta + |C^-1 (q~_a - a_a)|^2, with a_a = Q~_T^T V^-1 k_Ta from the cross product S^T s_a on
+// fp64 MFMA (SNP form: / d); NaN also for a model whose ks is flagged.  Without: the plain reliabilities, the
+// same bits as before.  launch_cov_cov: cc [B][n_cov][n_cov] = G^-1 = C^-T C^-1 from the kept factor.
 constexpr int RELIAB_W = 16;
+struct ReliabCov {
+  const double *sq, *cf, *ks, *qa;
+  int nc;
+  double* pev;
+};
 hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
-                         int64_t n_pred, const SlabPlan& p, double* vscr, double* rel, hipStream_t s);
+                         int64_t n_pred, const SlabPlan& p, double* vscr, const ReliabCov* cov, double* rel,
+                         hipStream_t s);
+hipError_t launch_cov_cov(const double* cf, const double* ks, int64_t B, int n_cov, double* cc, hipStream_t s);
 
 // ---- launcher (k_score.hip): mixed-model score statistics of listed SNPs from a chunk's factor ----
 // score[(b * nt + t) * n_cand + v] = w_j^T V^-1 r_t, info[b * n_cand + v] = w_j^T V^-1 w_j for column

@@ -169,7 +169,8 @@ class GpuBlupEngine:
         then those of the adjusted phenotype y* = y - (Q - cov_center) cov_effects (PanelModel.adjust);
         return_ebv=True also returns the validation EBVs of y*, (B, n_valid) or (B, nt, n_valid), as
         (models, ebv).  Collinear covariates give a NaN model, not an error; NaN / Inf in Q is a ValueError.
-        Not combined with reliability_of."""
+        Not combined with reliability_of: reliability_cov(covariates=Q, return_models=True) gives the reliabilities
+        under the covariate model and these models from one pass."""
         self._settle()
         if covariates is not None:
             if reliability_of is not None:
@@ -255,7 +256,7 @@ class GpuBlupEngine:
         definition).  It needs no phenotype: with several traits it is still one number per (model,
         animal).  The snp branch's intercept is taken as known.  The factor behind it is not kept, so
         candidates must be rows of this engine's panel.  A degenerate panel gives NaN; an animal's
-        value does not depend on the list it comes in."""
+        value does not depend on the list it comes in.  With fixed-effect covariates: reliability_cov."""
         self._settle()
         an = _as_int64(animals)
         if an.ndim != 1:
@@ -269,6 +270,49 @@ class GpuBlupEngine:
                 self._ctx, sid, _ptr(an), len(an), _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], None,
                 None, None, None, _ptr(rel)))
         return rel
+
+    def reliability_cov(self, genomes, train, valid, h2, animals, covariates, branch="auto", return_pev=False,
+                        return_cov_cov=False, return_models=False):
+        """reliability() under the model with fixed-effect covariates that fit(covariates=) fits (a method of
+        its own, as log_likelihood_cov and estimate_h2_cov are: reliability()'s parameters stay what they were).
+        covariates: an (n_animals, c) matrix Q as fit(covariates=) takes it.  Returns a
+        tblup_amd.model.CovReliability from tblup_reliability_cov_batch (include/tblup_gpu.h has the
+        definitions): `reliability` (B, n_pred) with the covariates' effects estimated, not known (never above
+        the plain value); with return_pev `pev_total` (B, n_pred), the error variance of the predicted value
+        (q_a - cov_center) cov_effects + g_a in units of sigma2_g; with return_cov_cov `cov_cov` (B, c, c) =
+        (Q~' V^-1 Q~)^-1, whose cov_stderr(sigma2_g) gives the standard errors of cov_effects (sigma2_g from
+        log_likelihood_cov(return_sigma2=True)); with return_models `models`, bit-identical to
+        fit(covariates=Q)'s, from the same pass.  Collinear covariates give NaN for the model, K_aa = 0 NaN for
+        the animal; NaN / Inf in Q is a ValueError."""
+        self._settle()
+        an = _as_int64(animals)
+        if an.ndim != 1:
+            raise ValueError("animals must be a 1-D list of row ids")
+        want_pev, want_cc, want_models = bool(return_pev), bool(return_cov_cov), bool(return_models)
+        from .model import CovReliability
+        q = self._covariates(covariates)
+        B, nt, nc, m = len(genomes), self.n_traits, q.shape[1], len(an)
+        rel = np.empty((B, m), dtype=np.float64)
+        pev = np.empty((B, m), dtype=np.float64) if want_pev else None
+        cc = np.empty((B, nc, nc), dtype=np.float64) if want_cc else None
+        outs = (_ptr(an) if m else None, m), (_ptr(rel), _ptr(pev) if want_pev else None, _ptr(cc) if want_cc else None)
+
+        def entry(sid, idx, offsets, *model):
+            _native.check("tblup_reliability_cov_batch", self._lib.tblup_reliability_cov_batch(
+                self._ctx, sid, _ptr(q), nc, *outs[0], idx, offsets, B, float(h2), _native.BRANCH[branch], *model,
+                *outs[1]))
+        models = None
+        if want_models:
+            cov_eff = np.empty((B, nt, nc), dtype=np.float64)
+            cov_cen = np.empty((B, nc), dtype=np.float64)
+
+            def call(sid, idx, offsets, fit, *model):
+                entry(sid, idx, offsets, fit, _ptr(cov_eff), _ptr(cov_cen), *model)
+            models = self._fit_models(genomes, train, valid, h2, branch, call, cov_effects=cov_eff, cov_center=cov_cen)
+        elif B:
+            idx, offsets = concat_genomes(genomes)
+            entry(self.split_id(train, valid), _ptr(idx), _ptr(offsets), None, None, None, None, None, None)
+        return CovReliability(rel, pev, cc, models)
 
     def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto", covariates=None):
         """Mixed-model score statistics of the panel's SNPs `snps` (column ids: any order, repeats

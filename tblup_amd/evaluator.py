@@ -423,6 +423,14 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
+    def reliability_cov(self, population, animals, covariates, final=True, train=None, valid=None, **kw):
+        """The tblup_amd.model.CovReliability of `animals` under every individual's model with the fixed-effect
+        covariates that fit_models(covariates=) fits: GpuBlupEngine.reliability_cov (return_pev / return_cov_cov /
+        return_models pass through) with fit_models' split and genome conventions.  covariates: an (animals, c)
+        matrix, one row per animal of the evaluator's data.  No RNG, no collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.reliability_cov(genomes, train, valid, self.h2, animals, covariates, **kw)
+
     def snp_scores(self, population, snps=None, final=True, train=None, valid=None, covariates=None):
         """Mixed-model score statistics (tblup_amd.model.SnpScores) of the SNPs `snps` (column ids of the
         evaluator's data; None: every column) against every individual's model: GpuBlupEngine.snp_scores

@@ -186,3 +186,51 @@ class SnpScores:
         q = self.q[:, :, None]
         with np.errstate(all="ignore"):
             return self.dof[:, None, None] / 2 * np.log(q / (q - u * u / v))
+
+
+class CovReliability:
+    """Uncertainty under the model with fixed-effect covariates (GpuBlupEngine.reliability_cov(covariates=),
+    tblup_reliability_cov_batch; include/tblup_gpu.h has the definitions).  For B models, n_pred listed animals and
+    c covariates:
+
+        reliability (B, n_pred)  1 - PEV(g^_a - g_a) / (sigma2_g K_aa) with the covariates' effects estimated
+        pev_total   (B, n_pred)  error variance of (q_a - cov_center) cov_effects + g_a, in units of sigma2_g
+                                 (None unless return_pev)
+        cov_cov     (B, c, c)    (Q~' V^-1 Q~)^-1: Var(cov_effects[t]) = sigma2_g[t] * cov_cov (None unless
+                                 return_cov_cov)
+        models      B PanelModels, fit(covariates=)'s bit for bit (None unless return_models)
+
+    No phenotype enters the first three: with several traits they are one value per (model, animal)."""
+
+    __slots__ = ("reliability", "pev_total", "cov_cov", "models")
+
+    def __init__(self, reliability, pev_total=None, cov_cov=None, models=None):
+        self.reliability = np.asarray(reliability, dtype=np.float64)
+        if self.reliability.ndim != 2:
+            raise ValueError("reliability must have shape (models, n_pred)")
+        B = self.reliability.shape[0]
+        self.pev_total = None if pev_total is None else np.asarray(pev_total, dtype=np.float64)
+        if self.pev_total is not None and self.pev_total.shape != self.reliability.shape:
+            raise ValueError("pev_total must have reliability's shape %s" % (self.reliability.shape,))
+        self.cov_cov = None if cov_cov is None else np.asarray(cov_cov, dtype=np.float64)
+        if self.cov_cov is not None and (self.cov_cov.ndim != 3 or self.cov_cov.shape[0] != B
+                                         or self.cov_cov.shape[1] != self.cov_cov.shape[2]):
+            raise ValueError("cov_cov must have shape (models, c, c)")
+        self.models = None if models is None else list(models)
+        if self.models is not None and len(self.models) != B:
+            raise ValueError("models must hold one model per row of reliability")
+
+    def cov_stderr(self, sigma2_g):
+        """sqrt(sigma2_g * diag cov_cov): the standard errors of cov_effects, (B, nt, c).  sigma2_g: (B,) for one
+        trait or (B, nt), as log_likelihood_cov(return_sigma2=True) gives it at one h2.  Host numpy."""
+        if self.cov_cov is None:
+            raise ValueError("cov_cov was not asked for (return_cov_cov=True)")
+        B = self.cov_cov.shape[0]
+        s2 = np.asarray(sigma2_g, dtype=np.float64)
+        if s2.ndim == 1:
+            s2 = s2[:, None]
+        if s2.ndim != 2 or s2.shape[0] != B:
+            raise ValueError("sigma2_g must have shape (models,) or (models, n_traits), got %s" % (s2.shape,))
+        diag = np.einsum("bii->bi", self.cov_cov)
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(s2[:, :, None] * diag[:, None, :])

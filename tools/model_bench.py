@@ -30,10 +30,15 @@ numbers go to PERFLOG.md.  One JSON line per part:
            chains and the 16-step solve per slab)
   loglik_cov  config 2 again: tblup_loglik_cov_batch beside tblup_loglik_batch at the same 8 grid points,
            alternated (per grid point: one k_covar launch more per pass)
+  reliab_cov  config 2 again: reliability_cov(covariates=Q) with 16 covariates (tblup_reliability_cov_batch) beside
+           reliability() for all 2,000 animals under the 256 models, alternated in one process: the ratio is the cost
+           of the covariate adjustment (k_covar in keep mode once per chunk, then S^T s_a and the two 16-step solves
+           per slab); k_reliab's adjusted and plain launches and the k_covar keep launch come from a --stats run of
+           this part (the --stats reader lists them apart)
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,score_cov,loglik_cov] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,score_cov,loglik_cov,reliab_cov] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -267,6 +272,37 @@ def score_cov_vs_score(eng, genomes, T, V, n, P, ns, reps, n_cand=2000, n_cov=16
                     "call adds one k_covar launch per chunk; the kernels alone: --stats"}
 
 
+def reliab_cov_vs_reliab(eng, genomes, T, V, n, ns, reps, n_cov=16):
+    """reliability_cov(covariates=Q) against reliability() for all n animals, and evaluate(), alternated."""
+    herd = np.arange(n)
+    q = bench_cov(n, n_cov)
+    te, tr, tc = [], [], []
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        plain = eng.reliability(genomes, T, V, 0.4, herd)
+        t.append(time.perf_counter())
+        adj = eng.reliability_cov(genomes, T, V, 0.4, herd, covariates=q, return_pev=True, return_cov_cov=True)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for lst, i in ((te, 0), (tr, 1), (tc, 2)):
+                lst.append(t[i + 1] - t[i])
+    nslab = (n + 15) // 16
+    return {"evaluate_ms": med_ms(te), "reliability_ms": med_ms(tr), "reliability_cov_ms": med_ms(tc), "animals": n,
+            "n_cov": n_cov, "reliab_cov_over_reliab": round(med_ms(tc) / med_ms(tr), 4),
+            "extra_over_evaluate_ratio": round((med_ms(tc) - med_ms(te)) / (med_ms(tr) - med_ms(te)), 4),
+            "derived_flop_share": round(32.0 / ns, 4), "slab_launch_workgroups": len(genomes) * nslab,
+            "reliability_ms_all": [round(x * 1e3, 3) for x in tr], "reliability_cov_ms_all": [round(x * 1e3, 3) for x in tc],
+            "finite": bool(np.all(np.isfinite(adj.reliability)) and np.all(np.isfinite(adj.pev_total))
+                           and np.all(np.isfinite(adj.cov_cov))),
+            "never_above_plain": bool(np.all(adj.reliability <= plain + 1e-9)),
+            "median_reliability_drop": float(np.median(plain - adj.reliability)),
+            "note": "each call is the whole evaluation plus its kernels and the D2H copy of its outputs; the adjusted "
+                    "call adds one k_covar launch (keep mode, no z*) and one k_cov_cov launch per chunk; the kernels "
+                    "alone: --stats"}
+
+
 def loglik_cov_vs_loglik(eng, genomes, T, V, n, reps, grid_n=8, n_cov=16):
     """tblup_loglik_cov_batch against tblup_loglik_batch at grid_n grid points (the C entries, alternated)."""
     from tblup_amd.engine import concat_genomes
@@ -357,7 +393,11 @@ def stats_share(path):
     out = {"part": "rocprof", "total_kernel_ms": round(tot / 1e6, 3), "kernels": {}}
     for r in rows:
         name = r["Name"]
-        for key in ("k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        # the covariate-adjusted k_reliab instances and k_covar's keep mode (third template argument) apart
+        for key, alias in (("k_reliab", "k_reliab_cov"), ("k_covar", "k_covar_keep")):
+            if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith(",true"):
+                name = name.replace(key + "<", alias + "<")
+        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -435,6 +475,12 @@ def main():
                                   **score_cov_vs_score(eng, genomes, T, V, n, P, 1024, args.reps)}))
             if "loglik_cov" in parts:
                 print(json.dumps({"part": "loglik_cov", **head, **loglik_cov_vs_loglik(eng, genomes, T, V, n, args.reps)}))
+    if "reliab_cov" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            print(json.dumps({"part": "reliab_cov", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **reliab_cov_vs_reliab(eng, genomes, T, V, n, 1024, args.reps)}))
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
