@@ -300,6 +300,47 @@ int tblup_fit_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t
                         double* cov_effects, double* cov_center, double* intercept, double* center, double* effects);
 
 /*
+ * A class fixed effect (herd, herd-year-season, batch, pen, sex x farm ..) beside the covariates:
+ * tblup_fit_cov_batch with the fixed design F = [Q, Z], Q the n_cov dense covariates (0 <= n_cov <= 16; cov may be
+ * NULL when n_cov is 0) and Z the one-hot columns of one factor.  group is int64 [n]: every animal's level code in
+ * [0, n_levels), or -1 for an animal without one, which is allowed only outside the split's train and validation
+ * rows.  The branch's centring rule applies to Z as it does to Q:
+ *   gblup : nothing is centred and no mean is fitted.  Z has one column per level, in ascending code order; the
+ *           level effects are the group means of the model (a column of ones in Q is then collinear: a NaN model).
+ *           n_cov + n_levels columns.
+ *   snp   : every column is centred by its mean over the train rows, the intercept stays mean(y_T).  Z drops the
+ *           lowest level, the reference level, whose effect is exactly 0; the centre of level l is its share
+ *           n_l / n_T of the train rows.  n_cov + n_levels - 1 columns.
+ * With F~ the centred design, b_t = (F~_T^T V^{-1} F~_T)^{-1} F~_T^T V^{-1} r_t and y*_t = y_t - F~ b_t exactly as
+ * tblup_fit_cov_batch has them for Q~; which level is the reference changes the reported effects and nothing else.
+ * A model has at most TBLUP_MAX_FIXED = 128 columns.
+ *   group_effects : out, batch x n_traits x n_levels: the level effects (0 at the reference level under snp)
+ *   group_center  : out, batch x n_levels: the levels' shares of the train rows under snp, all zero for a gblup model
+ *   cov_effects / cov_center : out, as tblup_fit_cov_batch (may be NULL when n_cov is 0)
+ *   fitness / ebv / intercept / center / effects : tblup_fit_cov_batch's, for phenotype y*
+ * so that the value of an animal of level g is tblup_fit_cov_batch's plus
+ *   sum_l ([g == l] - group_center[l]) group_effects[t][l].
+ * A model of 1 .. 16 columns runs tblup_fit_cov_batch's own kernels on the expanded design: its outputs are that
+ * entry's on [Q, Z] bit for bit.  A wider one runs the same GLS step in 16-column slabs: S = L^{-1} R slab by slab
+ * (a level's right-hand side in the SNP form is the allele count of each selected SNP over the level's train animals
+ * minus s_i n_l / n_T: exact integers, one fp64 combination), G and h_t on fp64 MFMA (SNP form: F~_T^T F~_T and
+ * F~_T^T r_t once per call, on the host in long double), a blocked Cholesky of G in 16 x 16 blocks under
+ * tblup_fit_cov_batch's pivot rule, the two triangular solves, the corrected z and the second pass.
+ * TBLUP_ERR_ARG: n_cov outside [0, 16]; n_levels < 1; a code outside [-1, n_levels); -1 on a split row; a level
+ * with no train row; more than 128 columns for a model of the batch; NaN or Inf in cov.  A degenerate model (d = 0,
+ * a flagged index, a pivot of G failing the rule: a covariate equal to a level's indicator, a column of ones beside
+ * gblup levels) is NaN in every output of that model: not an error.  Everything else -- idx / offsets / h2 / branch,
+ * the empty batch, the context without a panel, the chunking, the bits' independence of the batch, the chunking
+ * and TBLUP_SCORE_LDS -- is tblup_fit_cov_batch's.  Host pointers, synchronous.
+ */
+#define TBLUP_MAX_FIXED 128
+int tblup_fit_group_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                          int64_t n_levels, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                          int branch, double* fitness, double* ebv, double* cov_effects, double* cov_center,
+                          double* group_effects, double* group_center, double* intercept, double* center,
+                          double* effects);
+
+/*
  * The score statistics of tblup_snp_score_batch and the likelihood of tblup_loglik_batch for the model with
  * fixed-effect covariates that tblup_fit_cov_batch fits: cov, n_cov, Q~, G = Q~_T^T V^{-1} Q~_T = C C^T,
  * h_t = Q~_T^T V^{-1} r_t and b_t = G^{-1} h_t as documented there, and with

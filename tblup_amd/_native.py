@@ -19,6 +19,7 @@ MAX_TRAITS = 4
 RELIAB_SLAB = 16   # animals per k_reliab workgroup (RELIAB_W, csrc/tblup_internal.h)
 SCORE_SLAB = 16    # listed SNPs per k_snpscore workgroup (SCORE_W, csrc/tblup_internal.h)
 MAX_COV = 16       # fixed-effect covariates per call (COVAR_W, csrc/tblup_internal.h)
+MAX_FIXED = 128    # fixed columns of a model with a class factor: covariates + levels (TBLUP_MAX_FIXED)
 ERR_ARG = -1     # TBLUP_ERR_ARG: invalid argument
 ERR_STATE = -4   # TBLUP_ERR_STATE: call out of order
 ERR_INDEX = -5   # TBLUP_ERR_INDEX: numpy's IndexError for data[:, indices]
@@ -47,6 +48,8 @@ SIGNATURES = {
     "tblup_fit_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP, _DP, _DP, _DP]),
     "tblup_fit_cov_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int,
                                        _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
+    "tblup_fit_group_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64,
+                                         _c.c_double, _c.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     "tblup_reliability_batch": (_c.c_int, [_P, _c.c_int, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _c.c_double,
                                            _c.c_int, _DP, _DP, _DP, _DP, _DP]),
     "tblup_loglik_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _DP, _c.c_int64, _c.c_int, _DP, _DP,

@@ -10,6 +10,8 @@
 //   tblup_loglik_cov_batch     the pipeline once per h2 row, k_covar in keep mode and k_loglik behind each
 //   tblup_reliability_cov_batch  k_covar in keep mode, k_reliab's covariate-adjusted launches, k_cov_cov;
 //                                tblup_fit_cov_batch's second pass when the model or its fitness is wanted
+//   tblup_fit_group_batch      models of up to 16 columns: tblup_fit_cov_batch on the expanded design; wider ones:
+//                              k_fixed_subst, k_fixed_gls, a second solve, k_fixed_fitness, k_effects when wanted
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -103,6 +105,37 @@ struct CovBufs {   // tblup_fit_cov_batch
     return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<double>((size_t)2 * COVAR_W * d.nTp),
             cv.take<double>((size_t)2 * COVAR_W * d.nV), cv.take<double>(Bt * n_cov), cv.take<double>(Bt * hb.sd.ns),
             cv.take<double>((size_t)B), cv.take<double>(Bt * d.nV), carve_slices(cv, p)};
+  }
+};
+
+struct FixedBufs {   // tblup_fit_group_batch, the models of more than COVAR_W columns (k_fixed.hip)
+  ModelBufs m;
+  SlabPlan plan;            // a Cw-item list; the slices of a plan without LDS are S's own slabs
+  double *qT, *qV;          // CovBufs'
+  int32_t *gT, *gV, *lst, *lpos;   // level codes of the train / validation rows; the train rows by level
+  double *share, *ff, *fr;  // FixedDesign's
+  double* S;                // [B][Cw / 16][ns][16]
+  double *b, *z2;           // the fitted effects [B][nt][Cw]; z of the adjusted phenotype [B][nt][ns]
+  double *fit0, *ebv2;      // CovBufs'
+  static FixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t L, int64_t Cw, bool model) {
+    const EvalDims& d = hb.d;
+    const size_t Bt = (size_t)B * d.nt;
+    FixedBufs f{ModelBufs::carve(cv, hb, sum_k, model), plan_slabs(hb, B, Cw, hb.c->score_lds)};
+    f.qT = cv.take<double>((size_t)2 * COVAR_W * d.nTp);
+    f.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
+    f.gT = cv.take<int32_t>((size_t)d.nTp);
+    f.gV = cv.take<int32_t>((size_t)d.nV);
+    f.lst = cv.take<int32_t>((size_t)L + 1);
+    f.lpos = cv.take<int32_t>((size_t)d.nT);
+    f.share = cv.take<double>((size_t)L);
+    f.ff = cv.take<double>((size_t)Cw * Cw);
+    f.fr = cv.take<double>((size_t)MAXT * Cw);
+    f.S = cv.take<double>((size_t)B * Cw * hb.sd.ns);
+    f.b = cv.take<double>(Bt * Cw);
+    f.z2 = cv.take<double>(Bt * hb.sd.ns);
+    f.fit0 = cv.take<double>((size_t)B);
+    f.ebv2 = cv.take<double>(Bt * d.nV);
+    return f;
   }
 };
 
@@ -232,6 +265,135 @@ double log_det_qq(const double* q, int64_t nT, int64_t nTp, int64_t n_cov) {
     a[k][k] = ckk;
   }
   return (double)ld;
+}
+
+// The class factor of a tblup_fit_group_batch call on the host: the split rows' codes, the train rows by level,
+// the levels' shares, and the snp design's cross products F~_T^T F~_T and F~_T^T r_t (long double, once per call:
+// a row has n_cov + 1 non-zeros before centring, so they cost n_T (n_cov + 1)^2, not n_T C^2).
+struct GroupDesign {
+  int nc, L, Cw;
+  CovPlanes cp;
+  std::vector<int32_t> gT, gV, lst, lpos;
+  std::vector<double> share, ff, fr;
+};
+GroupDesign gather_group(const HostBatch& hb, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
+                         int64_t Cw) {
+  const EvalDims& d = hb.d;
+  const std::vector<int64_t>& T = hb.sp->train;
+  const int nt = d.nt;
+  GroupDesign g{(int)n_cov, (int)L, (int)Cw, gather_cov(hb, cov, n_cov, true)};
+  g.gT.assign((size_t)d.nTp, -1);
+  g.gV.assign((size_t)d.nV, -1);
+  g.lst.assign((size_t)L + 1, 0);
+  g.lpos.resize((size_t)d.nT);
+  g.share.resize((size_t)L);
+  for (int64_t i = 0; i < d.nT; ++i) ++g.lst[(g.gT[i] = (int32_t)group[T[i]]) + 1];
+  for (int64_t i = 0; i < d.nV; ++i) g.gV[i] = (int32_t)group[hb.sp->valid[i]];
+  for (int64_t l = 0; l < L; ++l) {
+    g.share[l] = (double)((long double)g.lst[l + 1] / (long double)d.nT);
+    g.lst[l + 1] += g.lst[l];
+  }
+  std::vector<int32_t> at(g.lst.begin(), g.lst.end() - 1);
+  for (int64_t i = 0; i < d.nT; ++i) g.lpos[at[g.gT[i]]++] = (int32_t)i;
+  // the snp design: columns 0 .. n_cov - 1 the covariates centred by their train means, then levels 1 .. L - 1
+  // centred by their shares.  U = F_T^T F_T uncentred, F~^T F~ = U - n_T m m^T with m the train means.
+  const int64_t C = n_cov + L - 1;
+  std::vector<long double> U((size_t)C * C, 0.0L), m((size_t)C, 0.0L), fr((size_t)nt * C, 0.0L), sr((size_t)nt, 0.0L);
+  for (int64_t j = 0; j < n_cov; ++j) m[j] = g.cp.m[j];
+  for (int64_t l = 1; l < L; ++l) m[n_cov + l - 1] = g.share[l];
+  for (int64_t i = 0; i < d.nT; ++i) {
+    const double* q = cov + T[i] * n_cov;   // (not read when n_cov is 0)
+    const int64_t zl = g.gT[i] >= 1 ? n_cov + g.gT[i] - 1 : -1;
+    for (int64_t a = 0; a < n_cov; ++a) {
+      for (int64_t e = 0; e <= a; ++e) U[a * C + e] += (long double)q[a] * (long double)q[e];
+      if (zl >= 0) U[zl * C + a] += q[a];
+    }
+    if (zl >= 0) U[zl * C + zl] += 1.0L;
+    for (int t = 0; t < nt; ++t) {
+      const long double r = (long double)(hb.c->pheno[T[i] * nt + t] - hb.sp->meanyT[t]);
+      sr[t] += r;
+      for (int64_t a = 0; a < n_cov; ++a) fr[t * C + a] += (long double)q[a] * r;
+      if (zl >= 0) fr[t * C + zl] += r;
+    }
+  }
+  g.ff.assign((size_t)Cw * Cw, 0.0);
+  g.fr.assign((size_t)MAXT * Cw, 0.0);
+  if (C <= Cw) {
+    for (int64_t a = 0; a < C; ++a)
+      for (int64_t e = 0; e <= a; ++e)
+        g.ff[a * Cw + e] = g.ff[e * Cw + a] = (double)(U[a * C + e] - (long double)d.nT * m[a] * m[e]);
+    for (int t = 0; t < nt; ++t)
+      for (int64_t a = 0; a < C; ++a) g.fr[t * Cw + a] = (double)(fr[t * C + a] - m[a] * sr[t]);
+  }
+  return g;
+}
+
+// The models of more than COVAR_W fixed columns of a tblup_fit_group_batch call, as a batch of their own:
+// bout [batch][nt][Cw] the fitted effects by column (zero past a model's own), everything else
+// tblup_fit_cov_batch's.  A model whose effects are NaN is NaN in intercept and center too.
+int fit_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
+                   int64_t Cw, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2, int branch,
+                   double* fitness, double* ebv, double* bout, double* intercept, double* center, double* effects) {
+  const bool model = intercept != nullptr;
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  if (!hb.sp) return 0;
+  const EvalDims& d = hb.d;
+  const int nt = d.nt;
+  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return FixedBufs::carve(cv, hb, B, sk, L, Cw, model); };
+  // per chunk: tblup_fit_cov_batch's, with k_fixed's three kernels in place of k_covar and k_cov_fitness
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const FixedBufs fb = carve(cv, B, ck.sum_k);
+    if (int rc = ws_check(c, cv)) return rc;
+    const auto up = [&](void* dst, const void* src, size_t bytes) {
+      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIPCHK(up(fb.qT, g.cp.qT.data(), g.cp.qT.size() * 8));
+    HIPCHK(up(fb.qV, g.cp.qV.data(), g.cp.qV.size() * 8));
+    HIPCHK(up(fb.gT, g.gT.data(), g.gT.size() * 4));
+    HIPCHK(up(fb.gV, g.gV.data(), g.gV.size() * 4));
+    HIPCHK(up(fb.lst, g.lst.data(), g.lst.size() * 4));
+    HIPCHK(up(fb.lpos, g.lpos.data(), g.lpos.size() * 4));
+    HIPCHK(up(fb.share, g.share.data(), g.share.size() * 8));
+    HIPCHK(up(fb.ff, g.ff.data(), g.ff.size() * 8));
+    HIPCHK(up(fb.fr, g.fr.data(), g.fr.size() * 8));
+    const FixedDesign fd{fb.qT, fb.qV, fb.gT, fb.gV, fb.lst, fb.lpos, fb.share, fb.ff, fb.fr, g.nc, g.L, g.Cw};
+    double* d_fit = rq.d_fit;
+    Carve cvp = cv;
+    rq.mode = ChunkMode::NoChain;
+    rq.d_fit = fb.fit0;
+    ChunkRes res;
+    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+    HIPCHK(launch_fixed_subst(res.cl, fd, fb.plan, fb.S, s));
+    HIPCHK(launch_fixed_gls(res.cl, fd, fb.S, fb.b, fb.z2, s));
+    CholLaunch cl2 = res.cl;
+    cl2.z = fb.z2;
+    HIPCHK(launch_solve(cl2, nullptr, fb.fit0, fb.ebv2, s));
+    HIPCHK(launch_fixed_fitness(cl2, fd, fb.ebv2, fb.b, d_fit, s));
+    if (model)
+      if (int rc = fb.m.enqueue(hb, ck, cl2, center, effects)) return rc;
+    HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, fb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    if (ebv) HIPCHK(hipMemcpyAsync(ebv + b0 * nt * d.nV, fb.ebv2, (size_t)B * nt * d.nV * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    return 0;
+  });
+  if (rc || !model) return rc;
+  fill_intercepts(hb, intercept);
+  const double nan = std::nan("");
+  for (int64_t b = 0; b < batch; ++b) {
+    // (a model without a fixed column has no effect to tell by: its fitness tells)
+    const bool gblup = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1;
+    bool dead = fixed_cols(gblup, (int)n_cov, (int)L) == 0 && std::isnan(fitness[b]);
+    for (int64_t i = 0; i < nt * Cw; ++i) dead = dead || std::isnan(bout[b * nt * Cw + i]);
+    if (!dead) continue;
+    for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
+    for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+  }
+  return 0;
 }
 
 struct PredictBufs {   // tblup_predict_batch: no pipeline, these are the chunk
@@ -567,6 +729,130 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
     if (dead && model) {
       for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
       for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+    }
+  }
+  return 0;
+}
+
+int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                          int64_t n_levels, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                          int branch, double* fitness, double* ebv, double* cov_effects, double* cov_center,
+                          double* group_effects, double* group_center, double* intercept, double* center,
+                          double* effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (n_cov < 0 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 0 <= n_cov <= 16");
+  if (n_cov > 0)
+    if (int rc = check_cov(c, cov, n_cov)) return rc;
+  if (n_levels < 1) return fail(TBLUP_ERR_ARG, "need n_levels >= 1");
+  if (!group) return fail(TBLUP_ERR_ARG, "null group");
+  for (int64_t i = 0; i < c->n; ++i)
+    if (group[i] < -1 || group[i] >= n_levels) return fail(TBLUP_ERR_ARG, "a level code lies outside [-1, n_levels)");
+  const bool model = intercept || center || effects;
+  if (model && !(intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  if (batch > 0 && (!group_effects || !group_center)) return fail(TBLUP_ERR_ARG, "null group_effects/group_center");
+  if (batch > 0 && n_cov > 0 && (!cov_effects || !cov_center))
+    return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
+  const int64_t L = n_levels, nc = n_cov;
+  std::vector<long double> share((size_t)std::min<int64_t>(L, c->n + 1), 0.0L);
+  std::vector<double> cov_m((size_t)nc);   // the covariates' means over the train rows (gather_cov's)
+  int64_t nT = 0, nV = 0;
+  int nt = 1;
+  {
+    HostBatch hb;
+    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+    if (!hb.sp) return 0;
+    nT = hb.d.nT, nV = hb.d.nV, nt = hb.d.nt;
+    if (L > nT) return fail(TBLUP_ERR_ARG, "a level has no train row");
+    for (int64_t i = 0; i < nT; ++i) {
+      if (group[hb.sp->train[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
+      share[group[hb.sp->train[i]]] += 1.0L;
+    }
+    for (int64_t i = 0; i < nV; ++i)
+      if (group[hb.sp->valid[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
+    for (int64_t l = 0; l < L; ++l) {
+      if (share[l] == 0.0L) return fail(TBLUP_ERR_ARG, "a level has no train row");
+      share[l] /= (long double)nT;
+    }
+    for (int64_t j = 0; j < nc; ++j) {
+      long double acc = 0.0L;
+      for (int64_t i = 0; i < nT; ++i) acc += cov[hb.sp->train[i] * nc + j];
+      cov_m[j] = (double)(acc / (long double)nT);
+    }
+  }
+  // A model's columns follow its branch: n_cov + L under gblup, one less under snp (the reference level).
+  // Routes: 0 / 1 the gblup / snp models of 1 .. 16 columns, through tblup_fit_cov_batch on the expanded design
+  // (the same bits as that entry gives); 2 the others, one batch of both branches through k_fixed.
+  const int64_t cols[2] = {fixed_cols(true, (int)nc, (int)L), fixed_cols(false, (int)nc, (int)L)};
+  std::vector<int64_t> of[3];
+  int64_t wide_cols = 0;
+  for (int64_t b = 0; b < batch; ++b) {
+    const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
+    if (cols[br] > FIXED_MAX)
+      return fail(TBLUP_ERR_ARG, "more than 128 fixed columns (n_cov + levels; one less under snp)");
+    const bool narrow = cols[br] >= 1 && cols[br] <= COVAR_W;
+    of[narrow ? br : 2].push_back(b);
+    if (!narrow) wide_cols = std::max(wide_cols, cols[br]);
+  }
+  const int64_t total = offsets[batch];
+  const double nan = std::nan("");
+  for (int route = 0; route < 3; ++route) {
+    const std::vector<int64_t>& mb = of[route];
+    const int64_t Bs = (int64_t)mb.size();
+    if (!Bs) continue;
+    // the route's models as a batch of their own
+    std::vector<int64_t> so((size_t)Bs + 1, 0), si;
+    for (int64_t i = 0; i < Bs; ++i) {
+      si.insert(si.end(), idx + offsets[mb[i]], idx + offsets[mb[i] + 1]);
+      so[i + 1] = (int64_t)si.size();
+    }
+    const int64_t st = so[Bs];
+    const int64_t Cw = route == 2 ? std::max<int64_t>(COVAR_W, round_up(wide_cols, COVAR_W)) : cols[route];
+    std::vector<double> fit((size_t)Bs), ev(ebv ? (size_t)Bs * nt * nV : 0), bo((size_t)Bs * nt * Cw);
+    std::vector<double> icpt(model ? (size_t)Bs * nt : 0), cen(model ? (size_t)st : 0), eff(model ? (size_t)nt * st : 0);
+    double* evp = ebv ? ev.data() : nullptr;
+    double *ip = model ? icpt.data() : nullptr, *cp = model ? cen.data() : nullptr, *ep = model ? eff.data() : nullptr;
+    int rc;
+    if (route == 2) {
+      rc = fit_fixed_wide(c, split_id, cov, nc, group, L, Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
+                          bo.data(), ip, cp, ep);
+    } else {
+      // the expanded design [Q, Z]: every level under gblup, all but the lowest under snp; an animal without
+      // a level (outside the split) has a row of zeros in Z
+      std::vector<double> x((size_t)c->n * Cw, 0.0), xc((size_t)Bs * Cw);   // xc: that entry's centres (cov_m, share)
+      for (int64_t a = 0; a < c->n; ++a) {
+        for (int64_t j = 0; j < nc; ++j) x[a * Cw + j] = cov[a * nc + j];
+        const int64_t z = group[a] - route;
+        if (z >= 0) x[a * Cw + nc + z] = 1.0;
+      }
+      rc = tblup_fit_cov_batch(c, split_id, x.data(), Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
+                               bo.data(), xc.data(), ip, cp, ep);
+    }
+    if (rc) return rc;
+    for (int64_t i = 0; i < Bs; ++i) {
+      const int64_t b = mb[i];
+      const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
+      const int64_t k = offsets[b + 1] - offsets[b];
+      bool dead = cols[br] == 0 && std::isnan(fit[i]);
+      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
+      if (fitness) fitness[b] = fit[i];
+      if (ebv) std::copy(evp + i * nt * nV, evp + (i + 1) * nt * nV, ebv + b * nt * nV);
+      for (int64_t j = 0; j < nc; ++j)
+        cov_center[b * nc + j] = dead ? nan : (br == 1 ? cov_m[j] : 0.0);
+      for (int64_t l = 0; l < L; ++l) group_center[b * L + l] = dead ? nan : (br == 1 ? (double)share[l] : 0.0);
+      for (int t = 0; t < nt; ++t) {
+        const double* bt = bo.data() + (i * nt + t) * Cw;
+        for (int64_t j = 0; j < nc; ++j) cov_effects[(b * nt + t) * nc + j] = dead ? nan : bt[j];
+        for (int64_t l = 0; l < L; ++l)
+          group_effects[(b * nt + t) * L + l] = dead ? nan : (l - br < 0 ? 0.0 : bt[nc + l - br]);
+        if (model) {
+          intercept[b * nt + t] = ip[i * nt + t];
+          std::copy(ep + t * st + so[i], ep + t * st + so[i] + k, effects + t * total + offsets[b]);
+        }
+      }
+      if (model) std::copy(cp + so[i], cp + so[i] + k, center + offsets[b]);
     }
   }
   return 0;

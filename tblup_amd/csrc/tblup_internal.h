@@ -464,6 +464,35 @@ hipError_t launch_covar(const CholLaunch& c, const double* qT, int n_cov, const 
 hipError_t launch_cov_fitness(const CholLaunch& c, const double* ebv, const double* qV, const double* bhat, int n_cov,
                               double* fit, hipStream_t s);
 
+// ---- launchers (k_fixed.hip): a wide fixed design [Q, Z] fitted by GLS from a chunk's factor ----
+// tblup_fit_group_batch's models of more than COVAR_W columns: n_cov dense covariates and the one-hot
+// columns Z of a class factor of L levels, FIXED_MAX columns at most.  Column j of a model's design: covariate
+// j for j < nc (qT / qV, launch_covar's planes), else level j - nc under gblup (as given) and level
+// j - nc + 1 under snp (the lowest level is the reference; centred by the level's share of the train rows).
+//   gT [nTp] / gV [nV]  level codes of the split's train / validation rows (-1 at padding rows)
+//   lst [L + 1], lpos [n_T]  the train rows' positions by level, ascending inside a level (CSR)
+//   share [L]           n_l / n_T
+//   ff [Cw][Cw], fr [MAXT][Cw]  SNP form: F~_T^T F~_T and F~_T^T r_t of the snp design, once per call
+// Cw: the column stride of the call's buffers, a multiple of 16 that holds every model's columns.
+// launch_fixed_subst: S = L^-1 R into sbuf [B][Cw / 16][ns][16], one workgroup per (model, slab of 16 columns);
+// p: the plan of a Cw-item list, its slices being sbuf's own slabs.  launch_fixed_gls: G, its blocked Cholesky,
+// bhat [B][nt][Cw] (zero past the model's columns) and z2 [B][nt][ns], one workgroup per model.
+// launch_fixed_fitness: launch_cov_fitness for this design.  NaN as launch_covar.
+constexpr int FIXED_MAX = 128;
+struct FixedDesign {
+  const double *qT, *qV;
+  const int32_t *gT, *gV, *lst, *lpos;
+  const double *share, *ff, *fr;
+  int nc, L, Cw;
+};
+__host__ __device__ __forceinline__ int fixed_cols(bool gblup, int nc, int L) { return nc + L - (gblup ? 0 : 1); }
+hipError_t launch_fixed_subst(const CholLaunch& c, const FixedDesign& f, const SlabPlan& p, double* sbuf,
+                              hipStream_t s);
+hipError_t launch_fixed_gls(const CholLaunch& c, const FixedDesign& f, const double* sbuf, double* bhat, double* z2,
+                            hipStream_t s);
+hipError_t launch_fixed_fitness(const CholLaunch& c, const FixedDesign& f, const double* ebv, const double* bhat,
+                                double* fit, hipStream_t s);
+
 // ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
 // loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,
 // z and the scalars that the chunk's pipeline left in c (SNP form: also the split's yT / ymu); one

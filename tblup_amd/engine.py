@@ -136,9 +136,10 @@ class GpuBlupEngine:
         return [self.split_id(t, v, pinned) for t, v in splits]
 
     # -------------------------------------------------------------- evaluation
-    def evaluate(self, genomes, train, valid, h2, branch="auto", return_ebv=False):
+    def evaluate(self, genomes, train, valid, h2, branch="auto", return_ebv=False, groups=None):
         """Fitness |pearson(EBV_V, y_V)| for each selected-index set (evaluator.py:244-314);
         multi-trait: the mean over traits, EBVs (B, t, n_valid)."""
+        self._no_groups(groups, "evaluate()")
         self._settle()
         sid = self.split_id(train, valid)
         idx, offsets = concat_genomes(genomes)
@@ -154,7 +155,8 @@ class GpuBlupEngine:
         return (fit, ebv) if return_ebv else fit
 
     # ------------------------------------------------------- taking the model out
-    def fit(self, genomes, train, valid, h2, branch="auto", reliability_of=None, covariates=None, return_ebv=False):
+    def fit(self, genomes, train, valid, h2, branch="auto", reliability_of=None, covariates=None, return_ebv=False,
+            groups=None):
         """evaluate() plus what it fitted: one PanelModel per selected-index set (tblup_fit_batch),
         whose `fitness` is evaluate()'s value bit for bit.  Out-of-range indices raise
         TblupIndexError; a degenerate panel gives NaN effects, not an error.
@@ -170,8 +172,22 @@ class GpuBlupEngine:
         return_ebv=True also returns the validation EBVs of y*, (B, n_valid) or (B, nt, n_valid), as
         (models, ebv).  Collinear covariates give a NaN model, not an error; NaN / Inf in Q is a ValueError.
         Not combined with reliability_of: reliability_cov(covariates=Q, return_models=True) gives the reliabilities
-        under the covariate model and these models from one pass."""
+        under the covariate model and these models from one pass.
+        groups: an (n_animals,) array of integer or string labels of one class factor (herd, batch, pen ..), with
+        or without covariates -- its levels, np.unique of the train rows' labels, are fitted as fixed effects
+        beside them (tblup_fit_group_batch; include/tblup_gpu.h has the model).  Under gblup every level has a
+        column and the level effects are the model's group means (a column of ones in Q is then collinear: a NaN
+        model); under snp the columns are centred, the lowest level is the reference with effect 0 and the
+        intercept stays mean(y_T).  A model has at most 128 columns, covariates and levels together (one level
+        less under snp).  Every model carries `group_levels` (L,), `group_effects` (nt, L) and `group_center`
+        (L,), and y* = PanelModel.adjust(y, covariates, groups).  A validation animal whose label no train animal
+        has is a ValueError that names the label; elsewhere such an animal is simply not used.  h2 is the
+        caller's own: the likelihood entries do not take groups.  Not combined with reliability_of."""
         self._settle()
+        if groups is not None:
+            if reliability_of is not None:
+                raise ValueError("reliability_of is not supported together with groups")
+            return self._fit_group(genomes, train, valid, h2, branch, covariates, groups, return_ebv)
         if covariates is not None:
             if reliability_of is not None:
                 raise ValueError("reliability_of is not supported together with covariates")
@@ -248,6 +264,59 @@ class GpuBlupEngine:
         models = self._fit_models(genomes, train, valid, h2, branch, call, cov_effects=cov_eff, cov_center=cov_cen)
         return (models, ebv) if return_ebv else models
 
+    @staticmethod
+    def _no_groups(groups, what):
+        if groups is not None:
+            raise ValueError(f"{what} does not take groups: the class factor is fitted by fit(groups=) only")
+
+    def _groups(self, groups, train, valid):
+        """(levels, codes) of a `groups` argument: the sorted distinct labels of the train rows and every
+        animal's level code as int64, -1 for a label that is not among them."""
+        g = np.asarray(groups)
+        if g.dtype.kind == "O":
+            g = g.astype(str)
+        if g.ndim != 1 or g.shape[0] != self.n_animals:
+            raise ValueError(f"groups must have one label per animal ({self.n_animals}), got shape {g.shape}")
+        if g.dtype.kind not in "iuUS":
+            raise ValueError(f"groups must be integer or string labels, got dtype {g.dtype}")
+        T, V = _as_int64(train), _as_int64(valid)
+        levels = np.unique(g[T])
+        if not len(levels):
+            raise ValueError("groups needs at least one train animal")
+        at = np.minimum(np.searchsorted(levels, g), len(levels) - 1)
+        codes = np.where(levels[at] == g, at, -1).astype(np.int64)
+        unseen = codes[V] < 0
+        if np.any(unseen):
+            raise ValueError("validation animal %d has the label %r, which no train animal has"
+                             % (int(V[unseen][0]), g[V][unseen][0].item()))
+        return levels, np.ascontiguousarray(codes)
+
+    def _fit_group(self, genomes, train, valid, h2, branch, covariates, groups, return_ebv):
+        levels, codes = self._groups(groups, train, valid)
+        q = None if covariates is None else self._covariates(covariates)
+        B, nt, nc, L, n_valid = len(genomes), self.n_traits, 0 if q is None else q.shape[1], len(levels), len(valid)
+        for g in genomes:
+            cols = nc + L - (self._fitted_branch(len(g), branch) == "snp")
+            if cols > _native.MAX_FIXED:
+                raise ValueError(f"a model would have {cols} fixed columns ({nc} covariates, {L} levels); the limit "
+                                 f"is {_native.MAX_FIXED}")
+        cov_eff = np.empty((B, nt, nc), dtype=np.float64)
+        cov_cen = np.empty((B, nc), dtype=np.float64)
+        grp_eff = np.empty((B, nt, L), dtype=np.float64)
+        grp_cen = np.empty((B, L), dtype=np.float64)
+        ebv = np.empty((B, n_valid) if nt == 1 else (B, nt, n_valid), dtype=np.float64) if return_ebv else None
+
+        def call(sid, idx, offsets, fit, *model):
+            _native.check("tblup_fit_group_batch", self._lib.tblup_fit_group_batch(
+                self._ctx, sid, _ptr(q) if nc else None, nc, _ptr(codes), L, idx, offsets, B, float(h2),
+                _native.BRANCH[branch], fit, _ptr(ebv) if return_ebv else None, _ptr(cov_eff) if nc else None,
+                _ptr(cov_cen) if nc else None, _ptr(grp_eff), _ptr(grp_cen), *model))
+        extra = dict(group_levels=np.broadcast_to(levels, (B, L)), group_effects=grp_eff, group_center=grp_cen)
+        if nc:
+            extra.update(cov_effects=cov_eff, cov_center=cov_cen)
+        models = self._fit_models(genomes, train, valid, h2, branch, call, **extra)
+        return (models, ebv) if return_ebv else models
+
     def reliability(self, genomes, train, valid, h2, animals, branch="auto"):
         """Reliability (squared accuracy, 1 - PEV / (sigma_g^2 K_aa)) of the genomic value of each of
         `animals` (row ids of this engine's panel: any order, repeats allowed, any or no split role)
@@ -272,7 +341,7 @@ class GpuBlupEngine:
         return rel
 
     def reliability_cov(self, genomes, train, valid, h2, animals, covariates, branch="auto", return_pev=False,
-                        return_cov_cov=False, return_models=False):
+                        return_cov_cov=False, return_models=False, groups=None):
         """reliability() under the model with fixed-effect covariates that fit(covariates=) fits (a method of
         its own, as log_likelihood_cov and estimate_h2_cov are: reliability()'s parameters stay what they were).
         covariates: an (n_animals, c) matrix Q as fit(covariates=) takes it.  Returns a
@@ -284,6 +353,7 @@ class GpuBlupEngine:
         log_likelihood_cov(return_sigma2=True)); with return_models `models`, bit-identical to
         fit(covariates=Q)'s, from the same pass.  Collinear covariates give NaN for the model, K_aa = 0 NaN for
         the animal; NaN / Inf in Q is a ValueError."""
+        self._no_groups(groups, "reliability_cov()")
         self._settle()
         an = _as_int64(animals)
         if an.ndim != 1:
@@ -314,7 +384,7 @@ class GpuBlupEngine:
             entry(self.split_id(train, valid), _ptr(idx), _ptr(offsets), None, None, None, None, None, None)
         return CovReliability(rel, pev, cc, models)
 
-    def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto", covariates=None):
+    def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto", covariates=None, groups=None):
         """Mixed-model score statistics of the panel's SNPs `snps` (column ids: any order, repeats
         allowed, negatives wrap, in or out of the models; None: every column) against the model each
         selected-index set fits on (train, valid): a tblup_amd.model.SnpScores from
@@ -329,6 +399,7 @@ class GpuBlupEngine:
         bit-identical to fit(covariates=Q)'s.  u_P / v_P is the GLS effect of the SNP fitted as one more
         covariate.  Collinear covariates give NaN for the model; a listed SNP in the span of the covariates
         gives u_P = v_P = 0, so NaN statistics."""
+        self._no_groups(groups, "snp_scores()")
         from .model import SnpScores
         self._settle()
         cand = _as_int64(np.arange(self.n_snps) if snps is None else snps)
@@ -370,13 +441,15 @@ class GpuBlupEngine:
         ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False)
         return (ll, s2) if return_sigma2 else ll
 
-    def log_likelihood_cov(self, genomes, train, valid, h2, covariates, branch="auto", return_sigma2=False):
+    def log_likelihood_cov(self, genomes, train, valid, h2, covariates, branch="auto", return_sigma2=False,
+                           groups=None):
         """log_likelihood for the model that fit(covariates=) fits (this method's signature is that one's with
         `covariates` added; log_likelihood's own stays as it is): covariates is the (n_animals, c) matrix Q as
         fit takes it, and the value is the restricted likelihood of the N - r - c error contrasts of the model
         with Q fitted beside the panel (tblup_loglik_cov_batch; include/tblup_gpu.h has the definition), with
         sigma2_g = q_P / (N - r - c).  Under gblup a mean is fitted only if Q carries a column of ones.
         Collinear covariates, or c >= N - r, give NaN; NaN / Inf in Q is a ValueError."""
+        self._no_groups(groups, "log_likelihood_cov()")
         ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False, covariates)
         return (ll, s2) if return_sigma2 else ll
 
@@ -432,9 +505,10 @@ class GpuBlupEngine:
         return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, None)
 
     def estimate_h2_cov(self, genomes, train, valid, covariates, branch="auto", grid=np.linspace(0.02, 0.98, 25),
-                        refine=3, points=9):
+                        refine=3, points=9, groups=None):
         """estimate_h2 on log_likelihood_cov: the h2 of the model that fit(covariates=) fits -- the value to
         pass to fit(covariates=) and snp_scores(covariates=).  The same search, the same returned fields."""
+        self._no_groups(groups, "estimate_h2_cov()")
         return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, covariates)
 
     def _estimate_h2(self, genomes, train, valid, branch, grid, refine, points, covariates):
@@ -518,8 +592,9 @@ class GpuBlupEngine:
         return fit
 
     def evaluate_folds_device(self, split_ids, d_idx_ptr, d_off_ptr, h_offsets, h2, d_fit_ptr, stream_ptr=None,
-                              branch="auto"):
+                              branch="auto", groups=None):
         """Asynchronous evaluate_folds on device-resident buffers (d_fit: n_splits x B)."""
+        self._no_groups(groups, "evaluate_folds_device()")
         self._settle()
         sids = np.ascontiguousarray(split_ids, dtype=np.int32)
         h_off = _as_int64(h_offsets)
@@ -529,8 +604,9 @@ class GpuBlupEngine:
             ctypes.c_void_p(stream_ptr) if stream_ptr else None))
 
     def evaluate_device(self, split_id, d_idx_ptr, d_off_ptr, h_offsets, h2, d_fit_ptr, d_ebv_ptr=None,
-                        stream_ptr=None, branch="auto"):
+                        stream_ptr=None, branch="auto", groups=None):
         """Asynchronous evaluation on device-resident buffers (raw device pointers)."""
+        self._no_groups(groups, "evaluate_device()")
         self._settle()
         h_off = _as_int64(h_offsets)
         B = len(h_off) - 1

@@ -140,7 +140,9 @@ class ParallelEvaluator(Evaluator):
     def genomes_to_evaluate(self, population):
         raise NotImplementedError()
 
-    def evaluate(self, previous_population, next_population, generation):
+    def evaluate(self, previous_population, next_population, generation, groups=None):
+        if groups is not None:
+            raise ValueError("evaluate() does not take groups: the class factor is fitted by fit_models(groups=) only")
         if self.engine is None:
             raise AttributeError("Workers are not set up.")
 
@@ -336,9 +338,9 @@ class BlupParallelEvaluator(ParallelEvaluator):
             return None
         return local
 
-    def evaluate(self, previous_population, next_population, generation):
+    def evaluate(self, previous_population, next_population, generation, groups=None):
         """evaluator.py:359-378."""
-        super().evaluate(previous_population, next_population, generation)
+        super().evaluate(previous_population, next_population, generation, groups=groups)
         fits = self._take_spec(next_population, generation)
         if fits is not None:   # the children's fitnesses, computed while their genomes were copied
             for i, f in enumerate(fits):
@@ -395,7 +397,8 @@ class BlupParallelEvaluator(ParallelEvaluator):
             valid = self.testing_indices if final else self.validation_indices
         return genomes, train, valid
 
-    def fit_models(self, population, final=True, train=None, valid=None, reliability_of=None, covariates=None):
+    def fit_models(self, population, final=True, train=None, valid=None, reliability_of=None, covariates=None,
+                   groups=None):
         """The fitted model (tblup_amd.model.PanelModel) of every individual, in population order.
 
         final=True is evaluate_testing's set-up -- train = T u V, valid = the testing animals, the
@@ -406,9 +409,15 @@ class BlupParallelEvaluator(ParallelEvaluator):
         (GpuBlupEngine.fit).
         covariates: an (animals, c) matrix of fixed-effect covariates, one row per animal of the evaluator's
         data -- fitted beside the genomic effects (GpuBlupEngine.fit); not with reliability_of.
+        groups: an (animals,) array of integer or string labels of one class factor, one per animal of the
+        evaluator's data -- its levels are fitted as fixed effects, with or without covariates
+        (GpuBlupEngine.fit(groups=)); not with reliability_of.
         Draws no RNG and uses no collective: under torch.distributed every rank fits the population
         it is given (call it on one rank, or with that rank's share)."""
         genomes, train, valid = self._model_setup(population, final, train, valid)
+        if groups is not None:
+            return self.engine.fit(genomes, train, valid, self.h2, reliability_of=reliability_of, covariates=covariates,
+                                   groups=groups)
         if covariates is not None:
             return self.engine.fit(genomes, train, valid, self.h2, reliability_of=reliability_of, covariates=covariates)
         if reliability_of is None:
@@ -431,13 +440,15 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability_cov(genomes, train, valid, self.h2, animals, covariates, **kw)
 
-    def snp_scores(self, population, snps=None, final=True, train=None, valid=None, covariates=None):
+    def snp_scores(self, population, snps=None, final=True, train=None, valid=None, covariates=None, groups=None):
         """Mixed-model score statistics (tblup_amd.model.SnpScores) of the SNPs `snps` (column ids of the
         evaluator's data; None: every column) against every individual's model: GpuBlupEngine.snp_scores
         with fit_models' split and genome conventions.  covariates: an (animals, c) matrix of fixed-effect
         covariates, one row per animal of the evaluator's data -- the statistics are then those of the model
         that fit_models(covariates=) fits.  No RNG, no collective: under torch.distributed every rank computes
         what it is given."""
+        if groups is not None:
+            raise ValueError("snp_scores() does not take groups: the class factor is fitted by fit_models(groups=) only")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if covariates is None:
             return self.engine.snp_scores(genomes, train, valid, self.h2, snps)
@@ -447,6 +458,8 @@ class BlupParallelEvaluator(ParallelEvaluator):
         """Profile (restricted) log-likelihood of every individual's model at `h2` (a scalar, a (G,)
         grid or a (G, B) matrix): GpuBlupEngine.log_likelihood (its keywords pass through; with
         covariates=Q, an (animals, c) matrix: log_likelihood_cov, the model fit_models(covariates=) fits) with fit_models' split and genome conventions.  No RNG, no collective: under torch.distributed every rank computes what it is given."""
+        if kw.pop("groups", None) is not None:
+            raise ValueError("log_likelihood() does not take groups: the class factor is fitted by fit_models(groups=) only")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if kw.get("covariates") is not None:
             return self.engine.log_likelihood_cov(genomes, train, valid, h2, **kw)
@@ -457,6 +470,8 @@ class BlupParallelEvaluator(ParallelEvaluator):
         """The h2 that maximises each individual's profile (restricted) likelihood on the panel it
         selected: GpuBlupEngine.estimate_h2 (its keywords pass through; with covariates=Q: estimate_h2_cov) with fit_models' split and genome
         conventions.  The evaluator's own h2 is not consulted.  No RNG, no collective."""
+        if kw.pop("groups", None) is not None:
+            raise ValueError("estimate_h2() does not take groups: the class factor is fitted by fit_models(groups=) only")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if kw.get("covariates") is not None:
             return self.engine.estimate_h2_cov(genomes, train, valid, **kw)

@@ -13,6 +13,9 @@ library to be applied to a genotype matrix.
 A model fitted with fixed-effect covariates (`GpuBlupEngine.fit(..., covariates=Q)`,
 tblup_fit_cov_batch) also carries their GLS effects and centre; the value of an animal with
 covariates q is then the genomic value above plus sum_i (q_i - cov_center[i]) * cov_effects[t][i].
+A model fitted with a class factor (`fit(..., groups=labels)`, tblup_fit_group_batch) carries the fitted
+levels, their effects and centres as well: an animal of level g adds
+sum_l ([g == group_levels[l]] - group_center[l]) * group_effects[t][l], and NaN if g is not a fitted level.
 """
 import numpy as np
 
@@ -21,12 +24,15 @@ class PanelModel:
     """indices (k,) wrapped to [0, P); center (k,) = 2p of each column over the branch's reference
     rows; effects (nt, k); intercept (nt,); h2, branch ("gblup" / "snp": the branch that was fitted)
     and the fit's validation fitness.  cov_effects (nt, c) and cov_center (c,): the fitted fixed-effect
-    covariates, or None for a model without any."""
+    covariates, or None for a model without any.  group_levels (L,) the sorted labels of a fitted class factor,
+    group_effects (nt, L) and group_center (L,): their effects (0 at the reference level under snp) and centres
+    (the levels' shares of the train rows under snp, zero under gblup), or None for a model without one."""
 
-    __slots__ = ("indices", "center", "effects", "intercept", "h2", "branch", "fitness", "cov_effects", "cov_center")
+    __slots__ = ("indices", "center", "effects", "intercept", "h2", "branch", "fitness", "cov_effects", "cov_center",
+                 "group_levels", "group_effects", "group_center")
 
     def __init__(self, indices, center, effects, intercept, h2=float("nan"), branch="snp", fitness=float("nan"),
-                 cov_effects=None, cov_center=None):
+                 cov_effects=None, cov_center=None, group_levels=None, group_effects=None, group_center=None):
         idx = np.asarray(indices)
         if idx.ndim != 1 or idx.size < 1 or not np.issubdtype(idx.dtype, np.integer):
             raise ValueError("indices must be a non-empty 1-D integer array")
@@ -63,10 +69,30 @@ class PanelModel:
                 raise ValueError(f"cov_effects must have shape ({eff.shape[0]}, c) and cov_center (c,), got "
                                  f"{ce.shape} and {cc.shape}")
             self.cov_effects, self.cov_center = np.ascontiguousarray(ce), cc
+        given = [a is not None for a in (group_levels, group_effects, group_center)]
+        if any(given) and not all(given):
+            raise ValueError("group_levels, group_effects and group_center are given together or not at all")
+        self.group_levels = self.group_effects = self.group_center = None
+        if all(given):
+            gl = np.asarray(group_levels)
+            ge = np.asarray(group_effects, dtype=np.float64)
+            if ge.ndim == 1:
+                ge = ge[None, :]
+            gc = np.ascontiguousarray(np.atleast_1d(np.asarray(group_center, dtype=np.float64)))
+            if gl.ndim != 1 or gl.size < 1 or ge.shape != (eff.shape[0], gl.size) or gc.shape != (gl.size,):
+                raise ValueError(f"group_levels must be (L,), group_effects ({eff.shape[0]}, L) and group_center (L,), "
+                                 f"got {gl.shape}, {ge.shape} and {gc.shape}")
+            if gl.size > 1 and not np.all(gl[1:] > gl[:-1]):
+                raise ValueError("group_levels must be sorted and distinct (np.unique's order)")
+            self.group_levels, self.group_effects, self.group_center = gl, np.ascontiguousarray(ge), gc
 
     @property
     def n_covariates(self):
         return 0 if self.cov_effects is None else self.cov_effects.shape[1]
+
+    @property
+    def n_levels(self):
+        return 0 if self.group_levels is None else self.group_levels.shape[0]
 
     @property
     def n_traits(self):
@@ -83,11 +109,38 @@ class PanelModel:
             raise ValueError(f"covariates must have shape ({rows}, {self.n_covariates}), got {q.shape}")
         return self.cov_effects @ (q - self.cov_center).T
 
-    def adjust(self, y, covariates):
-        """The phenotype adjusted for the fitted fixed effects, y* = y - (Q - cov_center) cov_effects: y is
-        (animals,) for one trait, else (animals, n_traits); covariates (animals, c).  Host numpy."""
+    def _group_part(self, groups, rows):
+        """(Z - group_center) group_effects^T as (n_traits, animals); NaN for a label that is not a fitted level."""
+        if self.group_levels is None:
+            raise ValueError("the model was fitted without groups")
+        g = np.asarray(groups)
+        if g.dtype.kind == "O":
+            g = g.astype(str)
+        if g.shape != (rows,):
+            raise ValueError(f"groups must have shape ({rows},), got {g.shape}")
+        if (g.dtype.kind in "US") != (self.group_levels.dtype.kind in "US"):
+            raise ValueError("groups must be labels of the kind the model was fitted with (%s)" % self.group_levels.dtype)
+        at = np.minimum(np.searchsorted(self.group_levels, g), self.n_levels - 1)
+        known = self.group_levels[at] == g
+        out = self.group_effects[:, at] - (self.group_effects @ self.group_center)[:, None]
+        out[:, ~known] = np.nan
+        return out
+
+    def _fixed_part(self, covariates, groups, rows):
+        part = np.zeros((self.n_traits, rows))
+        if covariates is not None:
+            part = part + self._cov_part(covariates, rows)
+        if groups is not None:
+            part = part + self._group_part(groups, rows)
+        return part
+
+    def adjust(self, y, covariates=None, groups=None):
+        """The phenotype adjusted for the fitted fixed effects, y* = y - (Q - cov_center) cov_effects
+        - (Z - group_center) group_effects: y is (animals,) for one trait, else (animals, n_traits); covariates
+        (animals, c) and groups (animals,) labels, each for a model fitted with it (an animal whose label is not a
+        fitted level gets NaN).  Host numpy."""
         y = np.asarray(y, dtype=np.float64)
-        part = self._cov_part(covariates, y.shape[0])
+        part = self._fixed_part(covariates, groups, y.shape[0])
         if y.ndim == 1:
             if self.n_traits != 1:
                 raise ValueError("y must be (animals, n_traits)")
@@ -96,11 +149,13 @@ class PanelModel:
             raise ValueError("y must be (animals, n_traits)")
         return y - part.T
 
-    def predict(self, genotypes, covariates=None):
+    def predict(self, genotypes, covariates=None, groups=None):
         """EBVs of the rows of an (animals x P) {0,1,2} genotype matrix: (animals,) for one trait,
         else (n_traits, animals) -- the shapes GpuBlupEngine.predict gives per model.  Host numpy.
         covariates (animals, c): the fitted fixed effects (Q - cov_center) cov_effects are added (a model
-        fitted with covariates; without the argument it returns the genomic value and intercept alone)."""
+        fitted with covariates; without the argument it returns the genomic value and intercept alone).
+        groups (animals,) labels: the fitted class effects (Z - group_center) group_effects are added in the same
+        way; an animal whose label is not a fitted level gets NaN."""
         g = np.asarray(genotypes)
         if g.ndim != 2:
             raise ValueError("genotypes must be 2-D (animals x SNPs)")
@@ -108,20 +163,25 @@ class PanelModel:
             raise IndexError(f"index {int(self.indices.max())} is out of bounds for axis 1 with size {g.shape[1]}")
         xc = g[:, self.indices].astype(np.float64) - self.center
         out = self.effects @ xc.T + self.intercept[:, None]
-        if covariates is not None:
-            out = out + self._cov_part(covariates, g.shape[0])
+        if covariates is not None or groups is not None:
+            out = out + self._fixed_part(covariates, groups, g.shape[0])
         return out[0] if self.n_traits == 1 else out
 
     def save(self, path):
         """Write the model as an .npz (numpy appends the suffix when it is missing)."""
         extra = {} if self.cov_effects is None else {"cov_effects": self.cov_effects, "cov_center": self.cov_center}
+        if self.group_levels is not None:
+            extra.update(group_levels=self.group_levels, group_effects=self.group_effects,
+                         group_center=self.group_center)
         np.savez(path, indices=self.indices, center=self.center, effects=self.effects, intercept=self.intercept,
                  h2=np.float64(self.h2), branch=np.array(self.branch), fitness=np.float64(self.fitness), **extra)
 
     @classmethod
     def load(cls, path):
         with np.load(path, allow_pickle=False) as z:
-            cov = {k: z[k] for k in ("cov_effects", "cov_center") if k in z.files}   # (files without them: no covariates)
+            # (files without them: no covariates, no class factor)
+            cov = {k: z[k] for k in ("cov_effects", "cov_center", "group_levels", "group_effects", "group_center")
+                   if k in z.files}
             return cls(z["indices"], z["center"], z["effects"], z["intercept"], float(z["h2"]), str(z["branch"]),
                        float(z["fitness"]), **cov)
 

@@ -24,6 +24,10 @@ numbers go to PERFLOG.md.  One JSON line per part:
            and snp_scores() of 16 listed SNPs -- the same substitution, one slab per model -- alternated in one
            process; k_covar beside k_snpscore, the second k_solve and k_cov_fitness per launch come from a
            --stats run of this part
+  group    config 2 again: fit(groups=) with 64 levels, fit(covariates=Q, groups=) with 112 levels + 16 covariates
+           (tblup_fit_group_batch: 63 and 127 columns under snp), fit(covariates=Q) with 16 covariates and fit(),
+           alternated in one process; k_fixed_subst, k_fixed_gls and k_fixed_fitness per launch beside k_covar and
+           k_snpscore come from a --stats run of this part (run it with `--only group,covar`)
   score_cov   config 2 again: snp_scores(covariates=Q) with 16 covariates (tblup_snp_score_cov_batch) beside
            snp_scores() on the same 2,000-SNP list as `score`, alternated in one process: the ratio is the cost of
            the covariate adjustment (k_covar in keep mode once per chunk, then S^T s_j, the SNP form's Q~^T x_j
@@ -38,7 +42,7 @@ numbers go to PERFLOG.md.  One JSON line per part:
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,score_cov,loglik_cov,reliab_cov] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -236,6 +240,36 @@ def covar_vs_fit(eng, genomes, T, V, n, P, reps, n_cov=16):
                     "--stats"}
 
 
+def group_vs_fit(eng, genomes, T, V, n, reps):
+    """fit(groups=) at 64 levels and at 112 levels + 16 covariates against fit(covariates=16 columns) and fit(),
+    alternated on one engine.  Labels uniform over the levels, every level on a train animal."""
+    rng = np.random.default_rng(78)
+    q = bench_cov(n)
+    g64, g112 = rng.integers(0, 64, n), rng.integers(0, 112, n)
+    g64[T[:64]], g112[T[:112]] = np.arange(64), np.arange(112)
+    ts = {"fit_ms": [], "fit_cov16_ms": [], "fit_group64_ms": [], "fit_group112_cov16_ms": []}
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.fit(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        eng.fit(genomes, T, V, 0.4, covariates=q)
+        t.append(time.perf_counter())
+        m64 = eng.fit(genomes, T, V, 0.4, groups=g64)
+        t.append(time.perf_counter())
+        m128 = eng.fit(genomes, T, V, 0.4, covariates=q, groups=g112)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for i, key in enumerate(ts):
+                ts[key].append(t[i + 1] - t[i])
+    out = {k: med_ms(v) for k, v in ts.items()}
+    out.update({k + "_all": [round(x * 1e3, 3) for x in v] for k, v in ts.items()})
+    out["columns"] = {"group64": 63, "group112_cov16": 127}
+    out["finite"] = bool(all(np.all(np.isfinite(m.group_effects)) for m in m64 + m128))
+    out["note"] = ("each call is the whole evaluation plus its kernels, the D2H copies and the PanelModel objects; the "
+                   "covariate and group calls run the one-workgroup k_solve twice; the kernels alone: --stats")
+    return out
+
+
 def bench_cov(n, n_cov=16):
     """The covariates of the score_cov / loglik_cov parts (covar_vs_fit's draw)."""
     rng = np.random.default_rng(77)
@@ -397,7 +431,7 @@ def stats_share(path):
         for key, alias in (("k_reliab", "k_reliab_cov"), ("k_covar", "k_covar_keep")):
             if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith(",true"):
                 name = name.replace(key + "<", alias + "<")
-        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -465,6 +499,12 @@ def main():
             st = covar_vs_fit(eng, genomes, T, V, n, P, args.reps)
             print(json.dumps({"part": "covar", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **st}))
+    if "group" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            print(json.dumps({"part": "group", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **group_vs_fit(eng, genomes, T, V, n, args.reps)}))
     if parts & {"score_cov", "loglik_cov"}:
         n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
