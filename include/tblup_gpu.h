@@ -387,6 +387,44 @@ int tblup_loglik_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int6
                            double* fitness, double* loglik, double* sigma2_g, double* cov_effects);
 
 /*
+ * The same two for the model with a class fixed effect that tblup_fit_group_batch fits: cov, n_cov, group, n_levels
+ * and the design F = [Q, Z] as documented there (gblup: nothing centred, every level a column; snp: every column
+ * centred by its train mean, the lowest level dropped), C_m = n_cov + n_levels - [snp] columns for a model, at most
+ * TBLUP_MAX_FIXED.  With F~_T in place of Q~_T and C_m in place of c the statistics and the likelihood are exactly
+ * tblup_snp_score_cov_batch's and tblup_loglik_cov_batch's:
+ *   G = F~_T^T V^{-1} F~_T = C C^T,  h_t = F~_T^T V^{-1} r_t,  P = V^{-1} - V^{-1} F~_T G^{-1} F~_T^T V^{-1},
+ *   dof = N - r - C_m,  log|A^T V A| = log|V| - r log lambda + log|G| - log|F~_T^T F~_T|.
+ * C_m, so dof and log|F~_T^T F~_T|, differ between the gblup and the snp models of one batch.
+ *   score / info / q, loglik / sigma2_g, fitness : as the covariate entries have them
+ *   cov_effects   : optional out, [n_h2 x] batch x n_traits x n_cov
+ *   group_effects : optional out, [n_h2 x] batch x n_traits x n_levels: tblup_fit_group_batch's at this h2, bit
+ *                   for bit (NaN throughout for a model that entry gives NaN)
+ * A batch model of 1 .. 16 columns runs the covariate entries' own kernels on the expanded design: its outputs are
+ * tblup_snp_score_cov_batch's / tblup_loglik_cov_batch's on [Q, Z] bit for bit.  A wider one runs
+ * tblup_fit_group_batch's GLS step and keeps it -- S = L^{-1} R in 16-column slabs, C, C^{-1} h_t,
+ * {log|G|, h_t^T b_t} -- and behind it
+ *   the score statistics: T = S^T s_j (C_m x 16 per slab of listed SNPs) on fp64 MFMA, one wave per column slab over
+ *     the real rows in order; SNP form a_j = (F~_T^T x_T,j - T / d) / lambda, a level's row of F~_T^T x_T,j being the
+ *     exact allele count of SNP j over the level's train animals minus its share of the SNP's train sum; C y = a_j
+ *     column by column with |y|^2 and y.(C^{-1} h_t) on the way; v_P <= 1e-12 v gives exact zeros;
+ *   the likelihood: k_loglik with the model's own C_m and log|F~_T^T F~_T| of its plane, once per call on the host
+ *     in long double under the pivot rule (NaN for a plane that is not of full rank).
+ * Argument errors are tblup_fit_group_batch's (a code outside [-1, n_levels), -1 on a split row, a level without a
+ * train row, more than 128 columns for a model of the batch, NaN in cov); everything else -- the empty calls, h2 in
+ * (0, 1), the chunking, NaN and no error for a degenerate model or dof <= 0, the bits' independence of the list,
+ * the slab, the batch, the chunking, TBLUP_SCORE_LDS and TBLUP_WORKSPACE_MB -- is the covariate entries'.
+ * Host pointers, synchronous.
+ */
+int tblup_snp_score_group_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                                int64_t n_levels, const int64_t* snps, int64_t n_cand, const int64_t* idx,
+                                const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                                double* score, double* info, double* q, double* cov_effects, double* group_effects);
+int tblup_loglik_group_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                             int64_t n_levels, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                             const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
+                             double* sigma2_g, double* cov_effects, double* group_effects);
+
+/*
  * Uncertainty under the model with fixed-effect covariates that tblup_fit_cov_batch fits: the reliabilities of
  * tblup_reliability_batch with the covariates' effects estimated, not known, the error variance of a predicted
  * value and the sampling covariance of the covariates' effects.  Notation is tblup_reliability_batch's and

@@ -12,6 +12,10 @@
 //                                tblup_fit_cov_batch's second pass when the model or its fitness is wanted
 //   tblup_fit_group_batch      models of up to 16 columns: tblup_fit_cov_batch on the expanded design; wider ones:
 //                              k_fixed_subst, k_fixed_gls, a second solve, k_fixed_fitness, k_effects when wanted
+//   tblup_snp_score_group_batch  models of up to 16 columns: tblup_snp_score_cov_batch on the expanded design; wider
+//                              ones: k_fixed_subst, k_fixed_gls in keep mode, k_snpscore's wide-design launches
+//   tblup_loglik_group_batch   the same routes: tblup_loglik_cov_batch, or per h2 row k_fixed_subst, k_fixed_gls in
+//                              keep mode and k_loglik with the model's own column count
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -241,28 +245,34 @@ CovPlanes gather_cov(const HostBatch& hb, const double* cov, int64_t n_cov, bool
 
 // log|Q~_T^T Q~_T| of a plane of qT in long double, by Cholesky under k_covar's pivot rule (COVAR_PIV_RTOL of
 // the pivot's own diagonal entry); NaN for a plane that is not of full rank
+double log_det_chol(long double* a, int64_t n);
 double log_det_qq(const double* q, int64_t nT, int64_t nTp, int64_t n_cov) {
-  long double a[COVAR_W][COVAR_W];
+  long double a[COVAR_W * COVAR_W];
   for (int64_t i = 0; i < n_cov; ++i)
     for (int64_t j = 0; j <= i; ++j) {
       long double acc = 0.0L;
       for (int64_t r = 0; r < nT; ++r) acc += (long double)q[i * nTp + r] * (long double)q[j * nTp + r];
-      a[i][j] = acc;
+      a[i * n_cov + j] = acc;
     }
+  return log_det_chol(a, n_cov);
+}
+// log|A| of a symmetric n x n matrix given by its lower triangle (row-major, stride n; overwritten by the factor),
+// under the pivot rule above; NaN for one that is not of full rank
+double log_det_chol(long double* a, int64_t n) {
   long double ld = 0.0L;
-  for (int64_t k = 0; k < n_cov; ++k) {
-    const long double gkk = a[k][k];
+  for (int64_t k = 0; k < n; ++k) {
+    const long double gkk = a[k * n + k];
     long double p = gkk;
-    for (int64_t m = 0; m < k; ++m) p -= a[k][m] * a[k][m];
+    for (int64_t m = 0; m < k; ++m) p -= a[k * n + m] * a[k * n + m];
     if (!(p > (long double)COVAR_PIV_RTOL * gkk) || !std::isfinite((double)p)) return std::nan("");
     const long double ckk = std::sqrt(p);
     ld += 2.0L * std::log(ckk);
-    for (int64_t i = k + 1; i < n_cov; ++i) {
-      long double v = a[i][k];
-      for (int64_t m = 0; m < k; ++m) v -= a[i][m] * a[k][m];
-      a[i][k] = v / ckk;
+    for (int64_t i = k + 1; i < n; ++i) {
+      long double v = a[i * n + k];
+      for (int64_t m = 0; m < k; ++m) v -= a[i * n + m] * a[k * n + m];
+      a[i * n + k] = v / ckk;
     }
-    a[k][k] = ckk;
+    a[k * n + k] = ckk;
   }
   return (double)ld;
 }
@@ -328,6 +338,88 @@ GroupDesign gather_group(const HostBatch& hb, const double* cov, int64_t n_cov, 
   return g;
 }
 
+// log|F~_T^T F~_T| of the gblup design (plane 0: [Q, Z] as given, every level) and of the snp design (plane 1:
+// centred, the lowest level dropped) in long double under log_det_qq's rule, once per call; NaN for a plane that
+// is not of full rank, and for one that no model of the call has (need).  A row has n_cov + 1 non-zeros.  The snp
+// plane sums the covariates centred, as log_det_qq does on gather_cov's centred plane, so a covariate whose mean is
+// far above its spread loses nothing: Q~^T Z~ = Q~^T Z because Q~_T sums to zero, and Z~^T Z~ = diag(n_l) - n_l n_e / n_T
+// from the integer counts.
+void group_log_dets(const HostBatch& hb, const double* cov, const GroupDesign& g, const bool (&need)[2],
+                    double (&lqq)[2]) {
+  const std::vector<int64_t>& T = hb.sp->train;
+  const int64_t nT = hb.d.nT, nc = g.nc, L = g.L;
+  lqq[0] = lqq[1] = std::nan("");
+  for (int plane = 0; plane < 2; ++plane) {
+    if (!need[plane]) continue;
+    const int64_t l0 = plane, C = nc + L - l0;   // the first level with a column; the plane's columns
+    std::vector<long double> A((size_t)C * C, 0.0L), q((size_t)nc);
+    for (int64_t i = 0; i < nT; ++i) {
+      for (int64_t a = 0; a < nc; ++a)
+        q[a] = (long double)cov[T[i] * nc + a] - (plane ? (long double)g.cp.m[a] : 0.0L);
+      const int64_t zl = g.gT[i] >= l0 ? nc + g.gT[i] - l0 : -1;
+      for (int64_t a = 0; a < nc; ++a) {
+        for (int64_t e = 0; e <= a; ++e) A[a * C + e] += q[a] * q[e];
+        if (zl >= 0) A[zl * C + a] += q[a];
+      }
+      if (zl >= 0) A[zl * C + zl] += 1.0L;
+    }
+    if (plane)
+      for (int64_t a = nc; a < C; ++a)
+        for (int64_t e = nc; e <= a; ++e) {
+          const long double na = g.lst[a - nc + l0 + 1] - g.lst[a - nc + l0], ne = g.lst[e - nc + l0 + 1] - g.lst[e - nc + l0];
+          A[a * C + e] -= na * ne / (long double)nT;
+        }
+    lqq[plane] = log_det_chol(A.data(), C);
+  }
+}
+
+// What k_fixed_subst and k_fixed_gls in keep mode leave of a chunk's wide GLS step for the score statistics and the
+// likelihood under the class factor (FixedBufs without the second pass).  passes: the h2 rows whose effects are kept.
+struct FixedKeepBufs {
+  SlabPlan plan;            // FixedBufs'
+  double* qT;
+  int32_t *gT, *lst, *lpos;
+  double *share, *ff, *fr;
+  double* S;                // [B][Cw / 16][ns][16]
+  double* b;                // the fitted effects [passes][B][nt][Cw]
+  FixedKeep keep;
+  double* lqq;              // log|F~_T^T F~_T| of the two planes
+  static FixedKeepBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t L, int64_t Cw, int64_t passes) {
+    const EvalDims& d = hb.d;
+    FixedKeepBufs f{plan_slabs(hb, B, Cw, hb.c->score_lds)};
+    f.qT = cv.take<double>((size_t)2 * COVAR_W * d.nTp);
+    f.gT = cv.take<int32_t>((size_t)d.nTp);
+    f.lst = cv.take<int32_t>((size_t)L + 1);
+    f.lpos = cv.take<int32_t>((size_t)d.nT);
+    f.share = cv.take<double>((size_t)L);
+    f.ff = cv.take<double>((size_t)Cw * Cw);
+    f.fr = cv.take<double>((size_t)MAXT * Cw);
+    f.S = cv.take<double>((size_t)B * Cw * hb.sd.ns);
+    f.b = cv.take<double>((size_t)passes * B * d.nt * Cw);
+    f.keep.cf = cv.take<double>((size_t)B * Cw * Cw);
+    f.keep.ch = cv.take<double>((size_t)B * MAXT * Cw);
+    f.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
+    f.lqq = cv.take<double>(2);
+    return f;
+  }
+  FixedDesign design(const GroupDesign& g) const {
+    return {qT, nullptr, gT, nullptr, lst, lpos, share, ff, fr, g.nc, g.L, g.Cw};
+  }
+  int upload(const GroupDesign& g, hipStream_t s) const {
+    const auto up = [&](void* dst, const void* src, size_t bytes) {
+      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+    };
+    HIPCHK(up(qT, g.cp.qT.data(), g.cp.qT.size() * 8));
+    HIPCHK(up(gT, g.gT.data(), g.gT.size() * 4));
+    HIPCHK(up(lst, g.lst.data(), g.lst.size() * 4));
+    HIPCHK(up(lpos, g.lpos.data(), g.lpos.size() * 4));
+    HIPCHK(up(share, g.share.data(), g.share.size() * 8));
+    HIPCHK(up(ff, g.ff.data(), g.ff.size() * 8));
+    HIPCHK(up(fr, g.fr.data(), g.fr.size() * 8));
+    return 0;
+  }
+};
+
 // The models of more than COVAR_W fixed columns of a tblup_fit_group_batch call, as a batch of their own:
 // bout [batch][nt][Cw] the fitted effects by column (zero past a model's own), everything else
 // tblup_fit_cov_batch's.  A model whose effects are NaN is NaN in intercept and center too.
@@ -368,7 +460,7 @@ int fit_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov,
     ChunkRes res;
     if (int rc = run_chunk(c, rq, cvp, res)) return rc;
     HIPCHK(launch_fixed_subst(res.cl, fd, fb.plan, fb.S, s));
-    HIPCHK(launch_fixed_gls(res.cl, fd, fb.S, fb.b, fb.z2, s));
+    HIPCHK(launch_fixed_gls(res.cl, fd, fb.S, fb.b, fb.z2, FixedKeep{}, s));
     CholLaunch cl2 = res.cl;
     cl2.z = fb.z2;
     HIPCHK(launch_solve(cl2, nullptr, fb.fit0, fb.ebv2, s));
@@ -394,6 +486,231 @@ int fit_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov,
     for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
   }
   return 0;
+}
+
+// The argument checks the class-factor entries share (tblup_fit_group_batch's), before the split is known
+int check_group(const tblup_ctx* c, const double* cov, int64_t n_cov, const int64_t* group, int64_t n_levels) {
+  if (n_cov < 0 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 0 <= n_cov <= 16");
+  if (n_cov > 0)
+    if (int rc = check_cov(c, cov, n_cov)) return rc;
+  if (n_levels < 1) return fail(TBLUP_ERR_ARG, "need n_levels >= 1");
+  if (!group) return fail(TBLUP_ERR_ARG, "null group");
+  for (int64_t i = 0; i < c->n; ++i)
+    if (group[i] < -1 || group[i] >= n_levels) return fail(TBLUP_ERR_ARG, "a level code lies outside [-1, n_levels)");
+  return 0;
+}
+
+// ... and against the split: every animal of the split has a level and every level a train row.  share [L] the
+// levels' shares n_l / n_T, cov_m the covariates' means over the train rows (gather_cov's).
+struct GroupSplit {
+  std::vector<long double> share;
+  std::vector<double> cov_m;
+  int64_t nT = 0, nV = 0;
+  int nt = 1;
+};
+int check_group_split(const HostBatch& hb, const double* cov, int64_t nc, const int64_t* group, int64_t L,
+                      GroupSplit& gs) {
+  const int64_t nT = gs.nT = hb.d.nT, nV = gs.nV = hb.d.nV;
+  gs.nt = hb.d.nt;
+  gs.share.assign((size_t)std::min<int64_t>(L, hb.c->n + 1), 0.0L);
+  gs.cov_m.resize((size_t)nc);
+  if (L > nT) return fail(TBLUP_ERR_ARG, "a level has no train row");
+  for (int64_t i = 0; i < nT; ++i) {
+    if (group[hb.sp->train[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
+    gs.share[group[hb.sp->train[i]]] += 1.0L;
+  }
+  for (int64_t i = 0; i < nV; ++i)
+    if (group[hb.sp->valid[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
+  for (int64_t l = 0; l < L; ++l) {
+    if (gs.share[l] == 0.0L) return fail(TBLUP_ERR_ARG, "a level has no train row");
+    gs.share[l] /= (long double)nT;
+  }
+  for (int64_t j = 0; j < nc; ++j) {
+    long double acc = 0.0L;
+    for (int64_t i = 0; i < nT; ++i) acc += cov[hb.sp->train[i] * nc + j];
+    gs.cov_m[j] = (double)(acc / (long double)nT);
+  }
+  return 0;
+}
+
+// A model's columns follow its branch: n_cov + L under gblup, one less under snp (the reference level).
+// Routes: 0 / 1 the gblup / snp models of 1 .. 16 columns, which run the covariate entry on the expanded design;
+// 2 the others, one batch of both branches through k_fixed.
+struct GroupRoutes {
+  int64_t cols[2] = {0, 0};
+  std::vector<int64_t> of[3];
+  int64_t wide_cols = 0;
+  // the column stride of a route's effects
+  int64_t width(int route) const {
+    return route == 2 ? std::max<int64_t>(COVAR_W, round_up(wide_cols, COVAR_W)) : cols[route];
+  }
+};
+int route_group(const tblup_ctx* c, const int64_t* offsets, int64_t batch, int branch, int64_t nc, int64_t L,
+                GroupRoutes& gr) {
+  gr.cols[0] = fixed_cols(true, (int)nc, (int)L);
+  gr.cols[1] = fixed_cols(false, (int)nc, (int)L);
+  for (int64_t b = 0; b < batch; ++b) {
+    const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
+    if (gr.cols[br] > FIXED_MAX)
+      return fail(TBLUP_ERR_ARG, "more than 128 fixed columns (n_cov + levels; one less under snp)");
+    const bool narrow = gr.cols[br] >= 1 && gr.cols[br] <= COVAR_W;
+    gr.of[narrow ? br : 2].push_back(b);
+    if (!narrow) gr.wide_cols = std::max(gr.wide_cols, gr.cols[br]);
+  }
+  return 0;
+}
+
+// a route's models as a batch of their own
+struct SubBatch {
+  std::vector<int64_t> so, si;
+};
+SubBatch sub_batch(const int64_t* idx, const int64_t* offsets, const std::vector<int64_t>& mb) {
+  SubBatch sb{std::vector<int64_t>(mb.size() + 1, 0), {}};
+  for (size_t i = 0; i < mb.size(); ++i) {
+    sb.si.insert(sb.si.end(), idx + offsets[mb[i]], idx + offsets[mb[i] + 1]);
+    sb.so[i + 1] = (int64_t)sb.si.size();
+  }
+  return sb;
+}
+
+// the expanded design [Q, Z] of route 0 / 1, [n][Cw]: every level under gblup, all but the lowest under snp; an
+// animal without a level (outside the split) has a row of zeros in Z
+std::vector<double> expand_design(const tblup_ctx* c, const double* cov, int64_t nc, const int64_t* group, int64_t Cw,
+                                  int route) {
+  std::vector<double> x((size_t)c->n * Cw, 0.0);
+  for (int64_t a = 0; a < c->n; ++a) {
+    for (int64_t j = 0; j < nc; ++j) x[a * Cw + j] = cov[a * nc + j];
+    const int64_t z = group[a] - route;
+    if (z >= 0) x[a * Cw + nc + z] = 1.0;
+  }
+  return x;
+}
+
+// a model's fitted effects by column (bt [nt][Cw]) as the covariates' and the levels' (0 at the reference level
+// under snp, br = 1); either output may be null
+void put_effects(const double* bt, int nt, int64_t Cw, int64_t nc, int64_t L, int br, bool dead, double* cov_eff,
+                 double* grp_eff) {
+  const double nan = std::nan("");
+  for (int t = 0; t < nt; ++t) {
+    if (cov_eff)
+      for (int64_t j = 0; j < nc; ++j) cov_eff[t * nc + j] = dead ? nan : bt[t * Cw + j];
+    if (grp_eff)
+      for (int64_t l = 0; l < L; ++l) grp_eff[t * L + l] = dead ? nan : (l - br < 0 ? 0.0 : bt[t * Cw + nc + l - br]);
+  }
+}
+
+struct ScoreFixedBufs {   // tblup_snp_score_group_batch, the models of more than COVAR_W columns
+  ScoreBufs s;
+  FixedKeepBufs k;
+  static ScoreFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cand, int64_t L, int64_t Cw) {
+    const ScoreBufs s = ScoreBufs::carve(cv, hb, B, n_cand);
+    return {s, FixedKeepBufs::carve(cv, hb, B, L, Cw, 1)};
+  }
+};
+
+struct LogLikFixedBufs {   // tblup_loglik_group_batch, the models of more than COVAR_W columns
+  LogLikBufs l;
+  FixedKeepBufs k;
+  static LogLikFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_h2, int64_t L, int64_t Cw) {
+    const LogLikBufs l = LogLikBufs::carve(cv, hb, B, n_h2);
+    return {l, FixedKeepBufs::carve(cv, hb, B, L, Cw, n_h2)};
+  }
+};
+
+// The models of more than COVAR_W fixed columns of a tblup_snp_score_group_batch call, as a batch of their own:
+// tblup_snp_score_cov_batch's chunk with k_fixed_subst and k_fixed_gls (keep mode) in place of k_covar and
+// k_snpscore's FIX instances behind them.  bout [batch][nt][Cw]: fit_fixed_wide's.
+int score_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
+                     int64_t Cw, const std::vector<int32_t>& s32, const int64_t* idx, const int64_t* offsets,
+                     int64_t batch, double h2, int branch, double* fitness, double* score, double* info, double* q,
+                     double* bout) {
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  if (!hb.sp) return 0;
+  const int nt = hb.d.nt;
+  const int64_t n_cand = (int64_t)s32.size();
+  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreFixedBufs::carve(cv, hb, B, n_cand, L, Cw); };
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const ScoreFixedBufs sb = carve(cv, B, ck.sum_k);
+    const FixedKeepBufs& kb = sb.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpyAsync(sb.s.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(g, s)) return rc;
+    const FixedDesign fd = kb.design(g);
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      HIPCHK(launch_fixed_subst(cl, fd, kb.plan, kb.S, s));
+      HIPCHK(launch_fixed_gls(cl, fd, kb.S, kb.b, nullptr, kb.keep, s));
+      const ScoreFixed sf{kb.S, kb.keep.cf, kb.keep.ch, kb.keep.ks, fd};
+      HIPCHK(launch_snpscore_fixed(cl, (const int32_t*)c->colsum_all.p, sb.s.cand, n_cand, sb.s.plan, sb.s.vscr, sf,
+                                   sb.s.sco, sb.s.inf, sb.s.q, s));
+      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.s.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.s.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.s.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, kb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+}
+
+// The same of a tblup_loglik_group_batch call: tblup_loglik_cov_batch's passes with k_fixed_subst and k_fixed_gls
+// (keep mode, no z*) between the pipeline and k_loglik.  h2 [n_h2][batch]; bout [n_h2][batch][nt][Cw].
+int loglik_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
+                      int64_t Cw, const int64_t* idx, const int64_t* offsets, int64_t batch, const double* h2,
+                      int64_t n_h2, int branch, double* fitness, double* loglik, double* sigma2_g, double* bout) {
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
+  if (!hb.sp) return 0;
+  const int nt = hb.d.nt;
+  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
+  const int cols[2] = {fixed_cols(true, (int)n_cov, (int)L), fixed_cols(false, (int)n_cov, (int)L)};
+  // log|F~_T^T F~_T| does not depend on h2: once per call, for the planes that the batch has models of
+  bool need[2] = {false, false};
+  for (int64_t b = 0; b < batch; ++b) need[branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1] = true;
+  double lqq[2];
+  group_log_dets(hb, cov, g, need, lqq);
+  // (a plane without a model is not read; its count only has to pass the launcher's range check)
+  const int kcols[2] = {need[0] ? cols[0] : 0, need[1] ? cols[1] : 0};
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikFixedBufs::carve(cv, hb, B, n_h2, L, Cw); };
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
+    const LogLikFixedBufs lf = carve(cv, B, ck.sum_k);
+    const LogLikBufs& lb = lf.l;
+    const FixedKeepBufs& kb = lf.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(g, s)) return rc;
+    HIPCHK(hipMemcpyAsync(kb.lqq, lqq, sizeof(lqq), hipMemcpyHostToDevice, s));
+    const FixedDesign fd = kb.design(g);
+    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+      for (int64_t gi = 0; gi < n_h2; ++gi) {
+        Carve cvp = cv;
+        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
+        rq.d_h2 = lb.h2 + gi * B;
+        rq.d_fit = lb.fits + gi * B;
+        ChunkRes res;
+        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+        seqs.push_back(res.chain_seq);
+        if (redo) continue;
+        HIPCHK(launch_fixed_subst(res.cl, fd, kb.plan, kb.S, s));
+        HIPCHK(launch_fixed_gls(res.cl, fd, kb.S, kb.b + gi * B * nt * Cw, nullptr, kb.keep, s));
+        HIPCHK(launch_loglik_fixed(res.cl, kb.keep.ks, kb.lqq, kcols, lb.ll + gi * B * nt, lb.s2 + gi * B * nt, s));
+      }
+      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
+        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
+      };
+      HIPCHK(out(fitness + b0, pitch, lb.fits, row));
+      if (redo) return 0;
+      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
+      HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
+      HIPCHK(out(bout + b0 * nt * Cw, pitch * nt * Cw, kb.b, rowt * Cw));
+      return 0;
+    });
+  });
 }
 
 struct PredictBufs {   // tblup_predict_batch: no pipeline, these are the chunk
@@ -742,13 +1059,7 @@ int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t
   clear_error();
   if (int rc = check_ctx(c)) return rc;
   if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
-  if (n_cov < 0 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 0 <= n_cov <= 16");
-  if (n_cov > 0)
-    if (int rc = check_cov(c, cov, n_cov)) return rc;
-  if (n_levels < 1) return fail(TBLUP_ERR_ARG, "need n_levels >= 1");
-  if (!group) return fail(TBLUP_ERR_ARG, "null group");
-  for (int64_t i = 0; i < c->n; ++i)
-    if (group[i] < -1 || group[i] >= n_levels) return fail(TBLUP_ERR_ARG, "a level code lies outside [-1, n_levels)");
+  if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
   const bool model = intercept || center || effects;
   if (model && !(intercept && center && effects))
     return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
@@ -756,60 +1067,32 @@ int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t
   if (batch > 0 && n_cov > 0 && (!cov_effects || !cov_center))
     return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
   const int64_t L = n_levels, nc = n_cov;
-  std::vector<long double> share((size_t)std::min<int64_t>(L, c->n + 1), 0.0L);
-  std::vector<double> cov_m((size_t)nc);   // the covariates' means over the train rows (gather_cov's)
-  int64_t nT = 0, nV = 0;
-  int nt = 1;
+  GroupSplit gs;
   {
     HostBatch hb;
     if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
     if (!hb.sp) return 0;
-    nT = hb.d.nT, nV = hb.d.nV, nt = hb.d.nt;
-    if (L > nT) return fail(TBLUP_ERR_ARG, "a level has no train row");
-    for (int64_t i = 0; i < nT; ++i) {
-      if (group[hb.sp->train[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
-      share[group[hb.sp->train[i]]] += 1.0L;
-    }
-    for (int64_t i = 0; i < nV; ++i)
-      if (group[hb.sp->valid[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
-    for (int64_t l = 0; l < L; ++l) {
-      if (share[l] == 0.0L) return fail(TBLUP_ERR_ARG, "a level has no train row");
-      share[l] /= (long double)nT;
-    }
-    for (int64_t j = 0; j < nc; ++j) {
-      long double acc = 0.0L;
-      for (int64_t i = 0; i < nT; ++i) acc += cov[hb.sp->train[i] * nc + j];
-      cov_m[j] = (double)(acc / (long double)nT);
-    }
+    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
   }
-  // A model's columns follow its branch: n_cov + L under gblup, one less under snp (the reference level).
-  // Routes: 0 / 1 the gblup / snp models of 1 .. 16 columns, through tblup_fit_cov_batch on the expanded design
-  // (the same bits as that entry gives); 2 the others, one batch of both branches through k_fixed.
-  const int64_t cols[2] = {fixed_cols(true, (int)nc, (int)L), fixed_cols(false, (int)nc, (int)L)};
-  std::vector<int64_t> of[3];
-  int64_t wide_cols = 0;
-  for (int64_t b = 0; b < batch; ++b) {
-    const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
-    if (cols[br] > FIXED_MAX)
-      return fail(TBLUP_ERR_ARG, "more than 128 fixed columns (n_cov + levels; one less under snp)");
-    const bool narrow = cols[br] >= 1 && cols[br] <= COVAR_W;
-    of[narrow ? br : 2].push_back(b);
-    if (!narrow) wide_cols = std::max(wide_cols, cols[br]);
-  }
+  const std::vector<long double>& share = gs.share;
+  const std::vector<double>& cov_m = gs.cov_m;
+  const int64_t nV = gs.nV;
+  const int nt = gs.nt;
+  // Routes 0 / 1 through tblup_fit_cov_batch on the expanded design (the same bits as that entry gives); 2 through
+  // k_fixed.
+  GroupRoutes gr;
+  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
+  const int64_t(&cols)[2] = gr.cols;
   const int64_t total = offsets[batch];
   const double nan = std::nan("");
   for (int route = 0; route < 3; ++route) {
-    const std::vector<int64_t>& mb = of[route];
+    const std::vector<int64_t>& mb = gr.of[route];
     const int64_t Bs = (int64_t)mb.size();
     if (!Bs) continue;
-    // the route's models as a batch of their own
-    std::vector<int64_t> so((size_t)Bs + 1, 0), si;
-    for (int64_t i = 0; i < Bs; ++i) {
-      si.insert(si.end(), idx + offsets[mb[i]], idx + offsets[mb[i] + 1]);
-      so[i + 1] = (int64_t)si.size();
-    }
+    const SubBatch sub = sub_batch(idx, offsets, mb);
+    const std::vector<int64_t>&so = sub.so, &si = sub.si;
     const int64_t st = so[Bs];
-    const int64_t Cw = route == 2 ? std::max<int64_t>(COVAR_W, round_up(wide_cols, COVAR_W)) : cols[route];
+    const int64_t Cw = gr.width(route);
     std::vector<double> fit((size_t)Bs), ev(ebv ? (size_t)Bs * nt * nV : 0), bo((size_t)Bs * nt * Cw);
     std::vector<double> icpt(model ? (size_t)Bs * nt : 0), cen(model ? (size_t)st : 0), eff(model ? (size_t)nt * st : 0);
     double* evp = ebv ? ev.data() : nullptr;
@@ -819,14 +1102,8 @@ int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t
       rc = fit_fixed_wide(c, split_id, cov, nc, group, L, Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
                           bo.data(), ip, cp, ep);
     } else {
-      // the expanded design [Q, Z]: every level under gblup, all but the lowest under snp; an animal without
-      // a level (outside the split) has a row of zeros in Z
-      std::vector<double> x((size_t)c->n * Cw, 0.0), xc((size_t)Bs * Cw);   // xc: that entry's centres (cov_m, share)
-      for (int64_t a = 0; a < c->n; ++a) {
-        for (int64_t j = 0; j < nc; ++j) x[a * Cw + j] = cov[a * nc + j];
-        const int64_t z = group[a] - route;
-        if (z >= 0) x[a * Cw + nc + z] = 1.0;
-      }
+      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
+      std::vector<double> xc((size_t)Bs * Cw);   // that entry's centres (cov_m, share)
       rc = tblup_fit_cov_batch(c, split_id, x.data(), Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
                                bo.data(), xc.data(), ip, cp, ep);
     }
@@ -842,11 +1119,9 @@ int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t
       for (int64_t j = 0; j < nc; ++j)
         cov_center[b * nc + j] = dead ? nan : (br == 1 ? cov_m[j] : 0.0);
       for (int64_t l = 0; l < L; ++l) group_center[b * L + l] = dead ? nan : (br == 1 ? (double)share[l] : 0.0);
+      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, nc ? cov_effects + b * nt * nc : nullptr,
+                  group_effects + b * nt * L);
       for (int t = 0; t < nt; ++t) {
-        const double* bt = bo.data() + (i * nt + t) * Cw;
-        for (int64_t j = 0; j < nc; ++j) cov_effects[(b * nt + t) * nc + j] = dead ? nan : bt[j];
-        for (int64_t l = 0; l < L; ++l)
-          group_effects[(b * nt + t) * L + l] = dead ? nan : (l - br < 0 ? 0.0 : bt[nc + l - br]);
         if (model) {
           intercept[b * nt + t] = ip[i * nt + t];
           std::copy(ep + t * st + so[i], ep + t * st + so[i] + k, effects + t * total + offsets[b]);
@@ -959,6 +1234,126 @@ int tblup_loglik_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_
       return 0;
     });
   });
+}
+
+int tblup_snp_score_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                                int64_t n_levels, const int64_t* snps, int64_t n_cand, const int64_t* idx,
+                                const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                                double* score, double* info, double* q, double* cov_effects, double* group_effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
+  if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
+  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
+  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  if (batch == 0 || n_cand == 0) return 0;
+  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
+  const int64_t L = n_levels, nc = n_cov;
+  GroupSplit gs;
+  {
+    HostBatch hb;
+    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
+  }
+  const int nt = gs.nt;
+  GroupRoutes gr;
+  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
+  std::vector<int32_t> s32((size_t)n_cand);
+  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
+  for (int route = 0; route < 3; ++route) {
+    const std::vector<int64_t>& mb = gr.of[route];
+    const int64_t Bs = (int64_t)mb.size();
+    if (!Bs) continue;
+    const SubBatch sub = sub_batch(idx, offsets, mb);
+    const int64_t Cw = gr.width(route);
+    std::vector<double> fit((size_t)Bs), sco((size_t)Bs * nt * n_cand), inf((size_t)Bs * n_cand), qs((size_t)Bs * nt),
+        bo((size_t)Bs * nt * Cw);
+    int rc;
+    if (route == 2) {
+      rc = score_fixed_wide(c, split_id, cov, nc, group, L, Cw, s32, sub.si.data(), sub.so.data(), Bs, h2, branch,
+                            fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
+    } else {
+      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
+      rc = tblup_snp_score_cov_batch(c, split_id, x.data(), Cw, snps, n_cand, sub.si.data(), sub.so.data(), Bs, h2,
+                                     branch, fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
+    }
+    if (rc) return rc;
+    for (int64_t i = 0; i < Bs; ++i) {
+      const int64_t b = mb[i];
+      const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
+      bool dead = gr.cols[br] == 0 && std::isnan(fit[i]);
+      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
+      if (fitness) fitness[b] = fit[i];
+      std::copy(sco.begin() + i * nt * n_cand, sco.begin() + (i + 1) * nt * n_cand, score + b * nt * n_cand);
+      std::copy(inf.begin() + i * n_cand, inf.begin() + (i + 1) * n_cand, info + b * n_cand);
+      if (q) std::copy(qs.begin() + i * nt, qs.begin() + (i + 1) * nt, q + b * nt);
+      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, cov_effects ? cov_effects + b * nt * nc : nullptr,
+                  group_effects ? group_effects + b * nt * L : nullptr);
+    }
+  }
+  return 0;
+}
+
+int tblup_loglik_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                             int64_t n_levels, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                             const double* h2, int64_t n_h2, int branch, double* fitness, double* loglik,
+                             double* sigma2_g, double* cov_effects, double* group_effects) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
+  if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
+  if (batch == 0 || n_h2 == 0) return 0;
+  if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
+  for (int64_t i = 0; i < n_h2 * batch; ++i)
+    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  const int64_t L = n_levels, nc = n_cov;
+  GroupSplit gs;
+  {
+    HostBatch hb;
+    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
+    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
+  }
+  const int nt = gs.nt;
+  GroupRoutes gr;
+  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
+  for (int route = 0; route < 3; ++route) {
+    const std::vector<int64_t>& mb = gr.of[route];
+    const int64_t Bs = (int64_t)mb.size();
+    if (!Bs) continue;
+    const SubBatch sub = sub_batch(idx, offsets, mb);
+    const int64_t Cw = gr.width(route);
+    // the route's h2 columns; its results [n_h2][Bs][..]
+    std::vector<double> hs((size_t)n_h2 * Bs), fit(hs.size()), ll(hs.size() * nt), s2(ll.size()), bo(ll.size() * Cw);
+    for (int64_t g = 0; g < n_h2; ++g)
+      for (int64_t i = 0; i < Bs; ++i) hs[g * Bs + i] = h2[g * batch + mb[i]];
+    int rc;
+    if (route == 2) {
+      rc = loglik_fixed_wide(c, split_id, cov, nc, group, L, Cw, sub.si.data(), sub.so.data(), Bs, hs.data(), n_h2,
+                             branch, fit.data(), ll.data(), s2.data(), bo.data());
+    } else {
+      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
+      rc = tblup_loglik_cov_batch(c, split_id, x.data(), Cw, sub.si.data(), sub.so.data(), Bs, hs.data(), n_h2, branch,
+                                  fit.data(), ll.data(), s2.data(), bo.data());
+    }
+    if (rc) return rc;
+    for (int64_t g = 0; g < n_h2; ++g)
+      for (int64_t i = 0; i < Bs; ++i) {
+        const int64_t b = mb[i], at = g * Bs + i, to = g * batch + b;
+        const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
+        bool dead = gr.cols[br] == 0 && std::isnan(fit[at]);
+        for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[at * nt * Cw + e]);
+        if (fitness) fitness[to] = fit[at];
+        std::copy(ll.begin() + at * nt, ll.begin() + (at + 1) * nt, loglik + to * nt);
+        if (sigma2_g) std::copy(s2.begin() + at * nt, s2.begin() + (at + 1) * nt, sigma2_g + to * nt);
+        put_effects(bo.data() + at * nt * Cw, nt, Cw, nc, L, br, dead,
+                    cov_effects ? cov_effects + to * nt * nc : nullptr,
+                    group_effects ? group_effects + to * nt * L : nullptr);
+      }
+  }
+  return 0;
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,

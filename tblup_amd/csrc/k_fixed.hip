@@ -24,6 +24,11 @@
 //     threads update the trailing lower triangle, one fma chain over the block's 16 columns per entry.
 //   C y = h_t, C^T b_t = y: thread (trait, row), a column per step.  z* = z - S b (SNP form: / d), one chain over the
 //     model's columns in order.
+//   Keep mode (FixedKeep non-null: tblup_snp_score_group_batch, tblup_loglik_group_batch), what k_covar's keep mode is
+//     for 16 columns: C (row-major with the call's stride, identity past the model's columns), C^{-1} h_t and
+//     {log|G| = 2 sum log C_kk, the bad flag, h_t^T b_t = |C^{-1} h_t|^2 per trait} go to the workspace, the sums one
+//     chain over the model's columns in order; S is already there.  z* is skipped when z2 is null.  b and z* are
+//     the same bits with or without it.
 // k_fixed_fitness: k_cov_fitness with a level column as a lookup: y*_V = y_V - (q~_V b_Q + b_level - sum_l m_l b_l).
 // No flags, no atomics, every loop bounded by the system's shape and the model's own column count, every sum in a
 // fixed order: a model's bits are a function of the model, the design and the system alone.
@@ -155,9 +160,10 @@ __global__ __launch_bounds__(XTH) void k_fixed_subst(CholLaunch c, FixedDesign f
   }
 }
 
-template <int FORM>
+template <int FORM, bool KEEP>
 __global__ __launch_bounds__(XTH) void k_fixed_gls(CholLaunch c, FixedDesign f, const double* __restrict__ sbuf,
-                                                   double* __restrict__ bhat, double* __restrict__ z2) {
+                                                   double* __restrict__ bhat, double* __restrict__ z2,
+                                                   FixedKeep keep) {
   extern __shared__ __attribute__((aligned(16))) double G[];   // [GS][GS], the model's columns rounded up to 16
   __shared__ double gd[FIXED_MAX];            // the diagonal of G before the factorisation
   __shared__ double hs[MAXT][FIXED_MAX];      // h_t
@@ -321,6 +327,31 @@ __global__ __launch_bounds__(XTH) void k_fixed_gls(CholLaunch c, FixedDesign f, 
     __syncthreads();
     if (i < GS) bs[tr][i] = bv;
     if (tr < nt && i < f.Cw) bhat[(b * nt + tr) * f.Cw + i] = bv;
+    if constexpr (KEEP) {
+      // C^{-1} h_t; h_t^T b_t = |C^{-1} h_t|^2 and log|G| = 2 sum log C_kk, each one chain over the model's columns
+      if (i < f.Cw) keep.ch[(b * MAXT + tr) * f.Cw + i] = i < GS ? ys[tr][i] : 0.0;
+      double* ks = keep.ks + b * COVAR_KS;
+      if (i == 0) {
+        double hb = 0.0;
+        for (int k = 0; k < Cm; ++k) hb = __builtin_fma(ys[tr][k], ys[tr][k], hb);
+        ks[KS_HB + tr] = hb;
+      }
+      if (t == 1) {
+        double slog = 0.0;
+        for (int k = 0; k < Cm; ++k) slog += log(G[k * GS + k]);
+        ks[KS_LOGG] = 2.0 * slog;
+        ks[KS_BAD] = bad ? 1.0 : 0.0;
+      }
+    }
+  }
+  if constexpr (KEEP) {
+    // C, row-major with the call's stride: identity past the model's blocks
+    double* cf = keep.cf + b * (int64_t)f.Cw * f.Cw;
+    for (int e = t; e < f.Cw * f.Cw; e += XTH) {
+      const int i = e / f.Cw, j = e % f.Cw;
+      cf[e] = (i < GS && j <= i) ? G[i * GS + j] : (i == j ? 1.0 : 0.0);
+    }
+    if (!z2) return;
   }
   __syncthreads();
 
@@ -403,14 +434,19 @@ hipError_t launch_fixed_subst(const CholLaunch& c, const FixedDesign& f, const S
 }
 
 hipError_t launch_fixed_gls(const CholLaunch& c, const FixedDesign& f, const double* sbuf, double* bhat, double* z2,
-                            hipStream_t s) {
+                            const FixedKeep& keep, hipStream_t s) {
   if (c.B < 1) return hipSuccess;
-  if (!design_ok(c, f) || !sbuf || !bhat || !z2) return hipErrorInvalidValue;
-  const auto k = c.sd.form == FORM_PRIMAL ? k_fixed_gls<FORM_PRIMAL> : k_fixed_gls<FORM_DUAL>;
+  // keep mode: every buffer or none
+  const bool kp = keep.cf || keep.ch || keep.ks;
+  if (kp && !(keep.cf && keep.ch && keep.ks)) return hipErrorInvalidValue;
+  if (!design_ok(c, f) || !sbuf || !bhat || (!kp && !z2)) return hipErrorInvalidValue;
+  const bool primal = c.sd.form == FORM_PRIMAL;
+  const auto k = kp ? (primal ? k_fixed_gls<FORM_PRIMAL, true> : k_fixed_gls<FORM_DUAL, true>)
+                    : (primal ? k_fixed_gls<FORM_PRIMAL, false> : k_fixed_gls<FORM_DUAL, false>);
   const size_t shm = (size_t)f.Cw * f.Cw * 8;
   hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(k, dim3((unsigned)c.B), dim3(XTH), shm, s, c, f, sbuf, bhat, z2);
+  hipLaunchKernelGGL(k, dim3((unsigned)c.B), dim3(XTH), shm, s, c, f, sbuf, bhat, z2, keep);
   return hipGetLastError();
 }
 

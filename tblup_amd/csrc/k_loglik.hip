@@ -19,6 +19,8 @@
 //   q_P = q - h_t^T b_t,  dof = N - r - c,  log|A^T V A| = log|V| - r log lambda + log|G| - log|Q~_T^T Q~_T|
 //   l_R = -1/2 [ dof (log 2 pi + 1 + log(q_P / dof)) + log|A^T V A| ],  sigma2_g = q_P / dof
 // log|Q~_T^T Q~_T| does not depend on h2: the host's, one value per branch (lqq; NaN: not of full rank).
+// c is a count per branch (nc_gblup, nc_snp): the covariate entries pass the same count twice, the wide design
+// [Q, Z] of tblup_loglik_group_batch has one column less under snp (launch_loglik_fixed).
 #include "tblup_internal.h"
 
 namespace tblup {
@@ -34,7 +36,7 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 __global__ __launch_bounds__(LL_THREADS) void k_loglik(CholLaunch c, const double* __restrict__ ks,
-                                                       const double* __restrict__ lqq, int nc,
+                                                       const double* __restrict__ lqq, int nc_gblup, int nc_snp,
                                                        double* __restrict__ loglik, double* __restrict__ sigma2) {
   __shared__ double part[LL_WAVES][LL_SUMS];
   const int t = threadIdx.x;
@@ -100,8 +102,9 @@ __global__ __launch_bounds__(LL_THREADS) void k_loglik(CholLaunch c, const doubl
   bool ok = d > 0.0 && sc[SC_BAD] == 0.0;
   if (ks) {
     const double* kb = ks + b * COVAR_KS;
-    const double lq = lqq[(int)sc[SC_MODE] == 1 ? 0 : 1];
-    df = df - (double)nc;
+    const bool gblup = (int)sc[SC_MODE] == 1;
+    const double lq = lqq[gblup ? 0 : 1];
+    df = df - (double)(gblup ? nc_gblup : nc_snp);
     q = q - kb[KS_HB + t];
     ldg = kb[KS_LOGG] - lq;
     ok = ok && kb[KS_BAD] == 0.0 && lq == lq;
@@ -120,7 +123,17 @@ hipError_t launch_loglik(const CholLaunch& c, const double* ks, const double* lq
                          double* sigma2, hipStream_t s) {
   if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
   if (ks && (!lqq || n_cov < 1 || n_cov > COVAR_W)) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_loglik, dim3((unsigned)c.B), dim3(LL_THREADS), 0, s, c, ks, lqq, n_cov, loglik, sigma2);
+  hipLaunchKernelGGL(k_loglik, dim3((unsigned)c.B), dim3(LL_THREADS), 0, s, c, ks, lqq, n_cov, n_cov, loglik, sigma2);
+  return hipGetLastError();
+}
+
+hipError_t launch_loglik_fixed(const CholLaunch& c, const double* ks, const double* lqq, const int (&cols)[2],
+                               double* loglik, double* sigma2, hipStream_t s) {
+  if (c.d.nt < 1 || c.d.nt > MAXT || !ks || !lqq) return hipErrorInvalidValue;
+  for (int n : cols)
+    if (n < 0 || n > FIXED_MAX) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_loglik, dim3((unsigned)c.B), dim3(LL_THREADS), 0, s, c, ks, lqq, cols[0], cols[1], loglik,
+                     sigma2);
   return hipGetLastError();
 }
 

@@ -44,7 +44,25 @@
 //   one lane per SNP: a_j, C y = a_j column by column, u_P and v_P; v_P <= COVAR_PIV_RTOL v gives exact zeros.
 // The staging reuses part (tiles, Q~^T x) and ired (C, C^{-1} h_t): no static LDS beyond the plain instances'.
 // NaN also for a model whose G has no positive pivot and for N - r - c <= 0.
+//
+// FIX instances (tblup_snp_score_group_batch): the same statistics for the wide fixed design F~ = [Q~, Z~] of up to
+// FIXED_MAX = 128 columns that k_fixed.hip fits, from what k_fixed_subst and k_fixed_gls (keep mode) left in the
+// workspace -- S slab-major [Cw / 16][ns][16], C [Cw][Cw], C^{-1} h_t and {log|G|, bad flag, h_t^T b_t}.  Phase 1,
+// the substitution and the sums for u, v, q are the plain instances'; behind them, for the model's own Cm columns:
+//   T = S^T s, Cm x 16, on fp64 MFMA: wave q takes the design's column slab q over all real 4-row groups in order, so
+//     the waves' tiles are T itself and nothing is summed across waves;
+//   thread (SNP, r of 32) holds a_j at the columns r, r + 32, ..; SNP form: its own entries of F~_T^T x_T,j -- a
+//     covariate's the COV chain, a level's the exact allele count of SNP j over the level's train animals (lst /
+//     lpos) minus the level's share of the SNP's train sum, integers and one fp64 combination: all levels together
+//     one pass over n_T per SNP;
+//   C y = a_j column by column: the owner of row k hands y_k to the SNP's 32 threads through a double-buffered LDS
+//     slot (one barrier a column), every thread updates its rows below k with its column of C streamed from
+//     global / L2 a step ahead; thread (SNP, 0) takes y.y and y.(C^{-1} h_t) on the way, one chain over the model's
+//     columns in order; v_P <= COVAR_PIV_RTOL v gives exact zeros.
+// The staging reuses part (T) and ired (C^{-1} h_t); 256 bytes of static LDS (the column slot) come on top, in these
+// instances only.  NaN as the COV instances, with Cm in place of c.
 #include <algorithm>
+#include <type_traits>
 
 #include "fwd_subst.h"
 #include "i8_tile.h"
@@ -59,10 +77,16 @@ constexpr int SKC = 8;                  // SNP form: 16-B loads per operand in f
 static_assert(SCORE_W == FWD_W, "a slab is the substitution's 16 right-hand sides");
 static_assert(SCORE_W * MAXT == 64, "w.r chains: one wave, one lane per (SNP, trait)");
 
-template <int FORM, bool VLDS, bool COV>
+// ADJ: the fixed effects the statistics are adjusted for, and the struct that carries them
+// (plain ints: an unnamed enum in the kernel's signature is mangled differently by the host and the device pass)
+constexpr int ADJ_NONE = 0, ADJ_COV = 1, ADJ_FIX = 2;
+template <int ADJ>
+using ScoreAdj = std::conditional_t<ADJ == ADJ_FIX, ScoreFixed, ScoreCov>;
+
+template <int FORM, bool VLDS, int ADJ>
 __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* __restrict__ csA,
                                                   const int32_t* __restrict__ cand, int64_t n_cand, int64_t slab0,
-                                                  int64_t nslab, double* __restrict__ vscr, ScoreCov cv,
+                                                  int64_t nslab, double* __restrict__ vscr, ScoreAdj<ADJ> cv,
                                                   double* __restrict__ score, double* __restrict__ info,
                                                   double* __restrict__ qout) {
   extern __shared__ __attribute__((aligned(16))) double dyn[];
@@ -244,7 +268,7 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
   bool dead = !(dd > 0.0) || sc[SC_BAD] != 0.0;
   const double nan = __builtin_nan("");
   const bool fin = t < W && sl * W + t < n_cand;   // this lane finishes a listed SNP
-  if constexpr (!COV) {
+  if constexpr (ADJ == ADJ_NONE) {
     if (fin) {
       double s2 = 0.0, sz[MAXT] = {0.0, 0.0, 0.0, 0.0};
       for (int w = 0; w < STH / 64; ++w)
@@ -264,7 +288,7 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
         score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u;
       }
     }
-  } else {
+  } else if constexpr (ADJ == ADJ_COV) {
     // the plain statistics of this lane's SNP, the same sums
     double v = 0.0, u[MAXT] = {0.0, 0.0, 0.0, 0.0};
     if (fin) {
@@ -385,6 +409,185 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
       for (int tr = 0; tr < MAXT; ++tr)
         if (tr < nt) score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u[tr];
     }
+  } else {
+    // the plain statistics of this lane's SNP, the same sums
+    double v = 0.0, u[MAXT] = {0.0, 0.0, 0.0, 0.0};
+    if (fin) {
+      double s2 = 0.0, sz[MAXT] = {0.0, 0.0, 0.0, 0.0};
+      for (int w = 0; w < STH / 64; ++w)
+        for (int g = 0; g < 4; ++g) {
+          s2 += part[0][64 * w + 16 * g + t];
+#pragma unroll
+          for (int tr = 0; tr < MAXT; ++tr) sz[tr] += part[1 + tr][64 * w + 16 * g + t];
+        }
+      if constexpr (FORM == FORM_PRIMAL) v = (ww_s[t] - s2 / dd) / lam;
+      else v = s2;
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr) {
+        if constexpr (FORM == FORM_PRIMAL) u[tr] = (wr_s[tr][t] - sz[tr]) / lam;
+        else u[tr] = sz[tr];
+      }
+    }
+    // The wide design's share: a_j = F~_T^T V^{-1} w_j for the model's Cm columns, C y = a_j, and the COV
+    // instances' u_P, v_P.
+    const FixedDesign& f = cv.f;
+    const int Cw = f.Cw;
+    const int Cm = std::min(fixed_cols(gblup, f.nc, f.L), Cw), nb = (Cm + W - 1) / W;
+    const double* ks = cv.ks + b * COVAR_KS;
+    dead = dead || ks[KS_BAD] != 0.0 || !((double)nT - sc[SC_MUF] - (double)Cm > 0.0);
+    // T = S^T s, Cm x 16, on fp64 MFMA: wave q takes the design's column slab q (S slab-major: the slab's [ns][16]
+    // from global / L2) over all 4-row groups of the real rows in order, so its tile is rows 16 q .. 16 q + 15 of T
+    // itself; a row outside the real ones counts as zero.
+    v4d tacc = {0.0, 0.0, 0.0, 0.0};
+    if (q < nb) {
+      const double* sq = cv.sbuf + (b * (Cw / W) + q) * ns * W;
+      const int64_t g1 = (pad + nrow + 3) / 4;
+      // (TKC groups per step, their loads issued together; a slot past the last group multiplies zeros)
+      constexpr int TKC = 16;
+      for (int64_t g0 = pad / 4; g0 < g1; g0 += TKC) {
+        double sa[TKC], sv[TKC];
+#pragma unroll
+        for (int e = 0; e < TKC; ++e) {
+          const int64_t g = g0 + e, r = 4 * g + lg;
+          sa[e] = g < g1 && sys_real(r, pad, nrow) ? sq[r * W + lc] : 0.0;
+          sv[e] = g < g1 ? V[r * W + lc] : 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < TKC; ++e) tacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[e], sv[e], tacc, 0, 0, 0);
+      }
+    }
+    // staging in the buffers the sums above are done with: T in part, C^{-1} h_t in ired
+    __shared__ double ycol[2][W];   // the solve's current column of y, double-buffered
+    double* tps = &part[0][0];
+    double* chs = reinterpret_cast<double*>(&ired[0][0]);
+    static_assert(sizeof(part) >= FIXED_MAX * W * 8 && sizeof(ired) >= MAXT * FIXED_MAX * 8 &&
+                      STH == MAXT * FIXED_MAX && STH / 64 * W >= FIXED_MAX,
+                  "the wide design's staging fits part / ired; a wave per column slab");
+    __syncthreads();
+    if (q < nb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) tps[(W * q + lg + 4 * r) * W + lc] = tacc[r];   // T[column][SNP]
+    }
+    {
+      const int tr = t / FIXED_MAX, i = t % FIXED_MAX;
+      chs[t] = i < Cw ? cv.ch[(b * MAXT + tr) * Cw + i] : 0.0;
+    }
+    __syncthreads();
+    // Thread (SNP ta, tp) holds a_j at the columns tp, tp + 32, .. (FIXED_MAX / SPARTS of them).  SNP form:
+    // a = (F~_T^T x_T,j - T / d) / lambda with F~_T^T x_T,j the thread's own: a covariate's (tp < nc, the COV
+    // instances' chain over the train rows in order), a level's the exact allele count of SNP j over the level's
+    // train animals (lst / lpos; integers: any order) minus the level's share of the SNP's train sum -- k_fixed_subst's
+    // right-hand side.  F~_T sums to zero over the train rows there: w_j's centre drops out.
+    constexpr int NR = FIXED_MAX / SPARTS;
+    double a[NR];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const int i = tp + SPARTS * m;
+      a[m] = i < Cm ? tps[i * W + ta] : 0.0;
+    }
+    if constexpr (FORM == FORM_PRIMAL) {
+      double qx = 0.0;
+      if (tp < f.nc) {
+        const double* qi = f.qT + (gblup ? 0 : (int64_t)COVAR_W * nTp) + (int64_t)tp * nTp;
+        double qa[16], qb[16];
+        uint32_t xa, xb;
+        auto ld = [&](double (&qv)[16], uint32_t& x, int64_t g) {
+          x = crow[g];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) qv[e] = qi[16 * g + e];
+        };
+        auto use = [&](const double (&qv)[16], uint32_t x) {
+#pragma unroll
+          for (int e = 0; e < 16; ++e) qx = __builtin_fma((double)((x >> (2 * e)) & 3u), qv[e], qx);
+        };
+        const int64_t ng = nTp / 16;
+        ld(qa, xa, 0);
+        for (int64_t g = 0; g < ng; g += 2) {
+          if (g + 1 < ng) ld(qb, xb, g + 1);
+          use(qa, xa);
+          if (g + 1 < ng) {
+            if (g + 2 < ng) ld(qa, xa, g + 2);
+            use(qb, xb);
+          }
+        }
+      }
+      const uint8_t* xb8 = reinterpret_cast<const uint8_t*>(crow);
+      const double sTj = (double)cs[col];
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int i = tp + SPARTS * m;
+        double fx = qx;   // (a covariate's column has m = 0)
+        if (i >= f.nc && i < Cm) {
+          const int lev = i - f.nc + (gblup ? 0 : 1);
+          const int p1 = f.lst[lev + 1];
+          int cnt = 0, p = f.lst[lev];
+          for (; p + 4 <= p1; p += 4) {
+            int an[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) an[e] = f.lpos[p + e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) cnt += (xb8[an[e] >> 2] >> (2 * (an[e] & 3))) & 3;
+          }
+          for (; p < p1; ++p) {
+            const int an = f.lpos[p];
+            cnt += (xb8[an >> 2] >> (2 * (an & 3))) & 3;
+          }
+          fx = (double)cnt - sTj * (gblup ? 0.0 : f.share[lev]);
+        }
+        a[m] = i < Cm ? (fx - a[m] / dd) / lam : 0.0;
+      }
+    }
+    // C y = a_j column by column (k_fixed_gls's substitution), C streamed from global / L2 a column ahead: the owner
+    // of row k hands y_k to the SNP's other threads through LDS, every thread updates its rows below k; thread
+    // (SNP ta, 0) takes y.y and y.(C^{-1} h_t) on the way, one chain over the model's columns in order
+    const double* Cb = cv.cf + b * (int64_t)Cw * Cw;
+    double yy = 0.0, yh[MAXT] = {0.0, 0.0, 0.0, 0.0};
+    double cn[NR];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const int i = tp + SPARTS * m;
+      cn[m] = i < Cm ? Cb[(int64_t)i * Cw] : 0.0;
+    }
+    for (int k = 0; k < Cm; ++k) {
+      double cc[NR];
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int i = tp + SPARTS * m;
+        cc[m] = cn[m];
+        cn[m] = (i > k && i < Cm) ? Cb[(int64_t)i * Cw + k + 1] : 0.0;
+      }
+      if (tp == k % SPARTS) {
+        double ak = 0.0, ckk = 1.0;
+#pragma unroll
+        for (int m = 0; m < NR; ++m)
+          if (m == k / SPARTS) ak = a[m], ckk = cc[m];
+        ycol[k & 1][ta] = ak / ckk;
+      }
+      __syncthreads();
+      const double yk = ycol[k & 1][ta];
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int i = tp + SPARTS * m;
+        if (i > k && i < Cm) a[m] = __builtin_fma(-cc[m], yk, a[m]);
+      }
+      if (tp == 0) {
+        yy = __builtin_fma(yk, yk, yy);
+#pragma unroll
+        for (int tr = 0; tr < MAXT; ++tr) yh[tr] = __builtin_fma(yk, chs[tr * FIXED_MAX + k], yh[tr]);
+      }
+    }
+    if (fin) {
+      // a SNP in the span of the design (or constant over the reference rows): exact zeros
+      const double vp = v - yy;
+      const bool span = !(vp > COVAR_PIV_RTOL * v);
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr) u[tr] = span ? 0.0 : u[tr] - yh[tr];
+      v = span ? 0.0 : vp;
+      info[b * n_cand + sl * W + t] = dead ? nan : v;
+#pragma unroll
+      for (int tr = 0; tr < MAXT; ++tr)
+        if (tr < nt) score[(b * nt + tr) * n_cand + sl * W + t] = dead ? nan : u[tr];
+    }
   }
   if (sl != 0 || !qout) return;
 
@@ -432,9 +635,22 @@ __global__ __launch_bounds__(STH) void k_snpscore(CholLaunch c, const int32_t* _
     double qv;
     if constexpr (FORM == FORM_PRIMAL) qv = (syy - dd * szz) / lam;
     else qv = szz;
-    if constexpr (COV) qv = qv - cv.ks[b * COVAR_KS + KS_HB + t];   // q_P = q - h_t^T b_t
+    if constexpr (ADJ != ADJ_NONE) qv = qv - cv.ks[b * COVAR_KS + KS_HB + t];   // q_P = q - h_t^T b_t
     qout[b * nt + t] = dead ? nan : qv;
   }
+}
+
+// the list's slabs through the <FORM, VLDS> instance of mode ADJ that the chunk and the plan select
+template <int ADJ>
+hipError_t launch_adj(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand, const SlabPlan& p,
+                      double* vscr, const ScoreAdj<ADJ>& cv, double* score, double* info, double* q, hipStream_t s) {
+  using Kern = decltype(&k_snpscore<FORM_DUAL, false, ADJ>);
+  const Kern kern[4] = {k_snpscore<FORM_DUAL, false, ADJ>, k_snpscore<FORM_DUAL, true, ADJ>,
+                        k_snpscore<FORM_PRIMAL, false, ADJ>, k_snpscore<FORM_PRIMAL, true, ADJ>};
+  const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
+    hipLaunchKernelGGL(k, grid, dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr, cv, score, info, q);
+  };
+  return launch_slabs(kern, c, p, vscr, (n_cand + SCORE_W - 1) / SCORE_W, launch);
 }
 
 }  // namespace
@@ -446,16 +662,20 @@ hipError_t launch_snpscore(const CholLaunch& c, const int32_t* csA, const int32_
   if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
   if (cov && (!cov->sq || !cov->cf || !cov->ch || !cov->ks || !cov->qT || cov->nc < 1 || cov->nc > COVAR_W))
     return hipErrorInvalidValue;
-  using Kern = decltype(&k_snpscore<FORM_DUAL, false, false>);
-  const Kern plain[4] = {k_snpscore<FORM_DUAL, false, false>, k_snpscore<FORM_DUAL, true, false>,
-                         k_snpscore<FORM_PRIMAL, false, false>, k_snpscore<FORM_PRIMAL, true, false>};
-  const Kern adj[4] = {k_snpscore<FORM_DUAL, false, true>, k_snpscore<FORM_DUAL, true, true>,
-                       k_snpscore<FORM_PRIMAL, false, true>, k_snpscore<FORM_PRIMAL, true, true>};
-  const ScoreCov cv = cov ? *cov : ScoreCov{};
-  const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
-    hipLaunchKernelGGL(k, grid, dim3(STH), shm, s, c, csA, cand, n_cand, s0, sn, vscr, cv, score, info, q);
-  };
-  return launch_slabs(cov ? adj : plain, c, p, vscr, (n_cand + SCORE_W - 1) / SCORE_W, launch);
+  if (cov) return launch_adj<ADJ_COV>(c, csA, cand, n_cand, p, vscr, *cov, score, info, q, s);
+  return launch_adj<ADJ_NONE>(c, csA, cand, n_cand, p, vscr, ScoreCov{}, score, info, q, s);
+}
+
+hipError_t launch_snpscore_fixed(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
+                                 const SlabPlan& p, double* vscr, const ScoreFixed& fx, double* score, double* info,
+                                 double* q, hipStream_t s) {
+  if (c.B < 1 || n_cand < 1) return hipSuccess;
+  if (c.d.nt < 1 || c.d.nt > MAXT) return hipErrorInvalidValue;
+  const FixedDesign& f = fx.f;
+  if (!fx.sbuf || !fx.cf || !fx.ch || !fx.ks || !f.qT || !f.lst || !f.lpos || !f.share || f.nc < 0 || f.nc > COVAR_W ||
+      f.L < 1 || f.Cw < SCORE_W || f.Cw > FIXED_MAX || f.Cw % SCORE_W != 0)
+    return hipErrorInvalidValue;
+  return launch_adj<ADJ_FIX>(c, csA, cand, n_cand, p, vscr, fx, score, info, q, s);
 }
 
 }  // namespace tblup

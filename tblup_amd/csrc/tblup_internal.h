@@ -488,10 +488,28 @@ struct FixedDesign {
 __host__ __device__ __forceinline__ int fixed_cols(bool gblup, int nc, int L) { return nc + L - (gblup ? 0 : 1); }
 hipError_t launch_fixed_subst(const CholLaunch& c, const FixedDesign& f, const SlabPlan& p, double* sbuf,
                               hipStream_t s);
+// Keep mode of launch_fixed_gls (all three pointers or none), CovKeep for the wide design: cf [B][Cw][Cw] the
+// factor C of G = C C^T (row-major, lower, identity past the model's columns), ch [B][MAXT][Cw] = C^-1 h_t,
+// ks [B][COVAR_KS] = {log|G| summed over the model's own columns in order, bad flag, h_t^T b_t per trait}; S stays
+// in sbuf as launch_fixed_subst left it.  With keep, z2 may be null: z* is then not formed.  bhat and z2 are the
+// same bits with or without it.
+struct FixedKeep {
+  double *cf = nullptr, *ch = nullptr, *ks = nullptr;
+};
 hipError_t launch_fixed_gls(const CholLaunch& c, const FixedDesign& f, const double* sbuf, double* bhat, double* z2,
-                            hipStream_t s);
+                            const FixedKeep& keep, hipStream_t s);
 hipError_t launch_fixed_fitness(const CholLaunch& c, const FixedDesign& f, const double* ebv, const double* bhat,
                                 double* fit, hipStream_t s);
+// launch_snpscore for a model with the wide design (k_score.hip's FIX instances): u_P, v_P, q_P as its covariate
+// form has them with F~ in place of Q~, from sbuf (launch_fixed_subst's) and launch_fixed_gls's keep buffers of the
+// same chunk; f as those two launches had it (qV / gV / ff / fr are not read).  NaN also for N - r - C_m <= 0.
+struct ScoreFixed {
+  const double *sbuf, *cf, *ch, *ks;
+  FixedDesign f;
+};
+hipError_t launch_snpscore_fixed(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
+                                 const SlabPlan& p, double* vscr, const ScoreFixed& fx, double* score, double* info,
+                                 double* q, hipStream_t s);
 
 // ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
 // loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,
@@ -504,6 +522,11 @@ hipError_t launch_fixed_fitness(const CholLaunch& c, const FixedDesign& f, const
 // for a model whose ks is flagged and for dof <= 0.  With ks null: the plain likelihood, the same bits.
 hipError_t launch_loglik(const CholLaunch& c, const double* ks, const double* lqq, int n_cov, double* loglik,
                          double* sigma2, hipStream_t s);
+// The same with a column count per plane (the wide design: ks launch_fixed_gls's keep.ks, lqq [2] =
+// log|F~_T^T F~_T|): dof = N - r - cols[0] for a gblup model, N - r - cols[1] for an snp model, each in
+// [0, FIXED_MAX].
+hipError_t launch_loglik_fixed(const CholLaunch& c, const double* ks, const double* lqq, const int (&cols)[2],
+                               double* loglik, double* sigma2, hipStream_t s);
 
 // ---- launcher (k_model.hip): EBVs of any animals of the panel from fitted models ----
 // ebv[(m * nt + t) * n_pred + v] = intercept[m * nt + t] + sum_j (x[animals[v], idx_j] - center_j)

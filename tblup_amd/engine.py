@@ -181,8 +181,9 @@ class GpuBlupEngine:
         intercept stays mean(y_T).  A model has at most 128 columns, covariates and levels together (one level
         less under snp).  Every model carries `group_levels` (L,), `group_effects` (nt, L) and `group_center`
         (L,), and y* = PanelModel.adjust(y, covariates, groups).  A validation animal whose label no train animal
-        has is a ValueError that names the label; elsewhere such an animal is simply not used.  h2 is the
-        caller's own: the likelihood entries do not take groups.  Not combined with reliability_of."""
+        has is a ValueError that names the label; elsewhere such an animal is simply not used.  The h2 of this
+        model is estimate_h2_group()'s; snp_scores_group() tests SNPs against it.  Not combined with
+        reliability_of."""
         self._settle()
         if groups is not None:
             if reliability_of is not None:
@@ -264,10 +265,16 @@ class GpuBlupEngine:
         models = self._fit_models(genomes, train, valid, h2, branch, call, cov_effects=cov_eff, cov_center=cov_cen)
         return (models, ebv) if return_ebv else models
 
-    @staticmethod
-    def _no_groups(groups, what):
+    _GROUP_FORMS = {"snp_scores()": "snp_scores_group()", "log_likelihood_cov()": "log_likelihood_group()",
+                    "estimate_h2_cov()": "estimate_h2_group()"}
+
+    @classmethod
+    def _no_groups(cls, groups, what):
         if groups is not None:
-            raise ValueError(f"{what} does not take groups: the class factor is fitted by fit(groups=) only")
+            own = cls._GROUP_FORMS.get(what)
+            raise ValueError(f"{what} does not take groups: " + (f"the class factor's form is {own}" if own else
+                             "the class factor is known to fit(groups=), snp_scores_group(), log_likelihood_group() "
+                             "and estimate_h2_group() only"))
 
     def _groups(self, groups, train, valid):
         """(levels, codes) of a `groups` argument: the sorted distinct labels of the train rows and every
@@ -291,15 +298,21 @@ class GpuBlupEngine:
                              % (int(V[unseen][0]), g[V][unseen][0].item()))
         return levels, np.ascontiguousarray(codes)
 
-    def _fit_group(self, genomes, train, valid, h2, branch, covariates, groups, return_ebv):
+    def _group_design(self, genomes, train, valid, branch, covariates, groups):
+        """(levels, codes, Q or None, columns (B,)) of a class-factor call, validated: _groups' labels, the
+        covariates and every model's column count (covariates + levels, one less under snp) against the limit."""
         levels, codes = self._groups(groups, train, valid)
         q = None if covariates is None else self._covariates(covariates)
+        nc, L = 0 if q is None else q.shape[1], len(levels)
+        cols = np.array([nc + L - (self._fitted_branch(len(g), branch) == "snp") for g in genomes], dtype=np.int64)
+        if len(cols) and cols.max() > _native.MAX_FIXED:
+            raise ValueError(f"a model would have {cols.max()} fixed columns ({nc} covariates, {L} levels); the limit "
+                             f"is {_native.MAX_FIXED}")
+        return levels, codes, q, cols
+
+    def _fit_group(self, genomes, train, valid, h2, branch, covariates, groups, return_ebv):
+        levels, codes, q, _ = self._group_design(genomes, train, valid, branch, covariates, groups)
         B, nt, nc, L, n_valid = len(genomes), self.n_traits, 0 if q is None else q.shape[1], len(levels), len(valid)
-        for g in genomes:
-            cols = nc + L - (self._fitted_branch(len(g), branch) == "snp")
-            if cols > _native.MAX_FIXED:
-                raise ValueError(f"a model would have {cols} fixed columns ({nc} covariates, {L} levels); the limit "
-                                 f"is {_native.MAX_FIXED}")
         cov_eff = np.empty((B, nt, nc), dtype=np.float64)
         cov_cen = np.empty((B, nc), dtype=np.float64)
         grp_eff = np.empty((B, nt, L), dtype=np.float64)
@@ -427,6 +440,39 @@ class GpuBlupEngine:
             _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q)))
         return SnpScores(score, info, q, dof.reshape(B), wrapped)
 
+    def snp_scores_group(self, genomes, train, valid, h2, groups, snps=None, branch="auto", covariates=None):
+        """snp_scores() under the model with a class fixed effect that fit(groups=) fits (a method of its own, as
+        log_likelihood_cov and estimate_h2_cov are: snp_scores(groups=) keeps raising).  groups and the optional
+        covariates are fit()'s: (n_animals,) integer or string labels of one factor, an (n_animals, c) matrix Q.
+        Returns a tblup_amd.model.SnpScores from tblup_snp_score_group_batch (include/tblup_gpu.h has the
+        definitions): u_P, v_P, q_P with the fixed design F = [Q, Z] in place of Q, dof = N - r - C_m per model
+        (C_m its column count: covariates + levels, one less under snp), `group_levels` (L,) and `group_effects`
+        (B, nt, L) bit-identical to fit(groups=)'s, and `cov_effects` when there are covariates.  u_P / v_P is the GLS
+        effect of the SNP fitted as one more covariate beside the factor.  A design that is collinear over the train
+        rows, or C_m >= N - r, gives NaN for the model; a listed SNP in the span of the design gives u_P = v_P = 0."""
+        from .model import SnpScores
+        self._settle()
+        cand = _as_int64(np.arange(self.n_snps) if snps is None else snps)
+        if cand.ndim != 1:
+            raise ValueError("snps must be a 1-D list of column ids")
+        levels, codes, qc, cols = self._group_design(genomes, train, valid, branch, covariates, groups)
+        sid = self.split_id(train, valid)
+        idx, offsets = concat_genomes(genomes)
+        B, nt, m, nc, L = len(genomes), self.n_traits, len(cand), 0 if qc is None else qc.shape[1], len(levels)
+        score = np.empty((B, nt, m), dtype=np.float64)
+        info = np.empty((B, m), dtype=np.float64)
+        q = np.full((B, nt), np.nan)
+        cov_eff = np.full((B, nt, nc), np.nan)
+        grp_eff = np.full((B, nt, L), np.nan)
+        snp = np.array([self._fitted_branch(k, branch) == "snp" for k in np.diff(offsets)], dtype=bool)
+        dof = len(_as_int64(train)) - snp.astype(np.float64) - cols
+        _native.check("tblup_snp_score_group_batch", self._lib.tblup_snp_score_group_batch(
+            self._ctx, sid, _ptr(qc) if nc else None, nc, _ptr(codes), L, _ptr(cand) if m else None, m, _ptr(idx),
+            _ptr(offsets), B, float(h2), _native.BRANCH[branch], None, _ptr(score), _ptr(info), _ptr(q),
+            _ptr(cov_eff) if nc else None, _ptr(grp_eff)))
+        return SnpScores(score, info, q, dof.reshape(B), np.where(cand < 0, cand + self.n_snps, cand),
+                         cov_effects=cov_eff if nc else None, group_effects=grp_eff, group_levels=levels)
+
     # ------------------------------------------------- variance ratio by (RE)ML
     def log_likelihood(self, genomes, train, valid, h2, branch="auto", return_sigma2=False):
         """Profile (restricted) log-likelihood of h2 for the model each selected-index set fits on
@@ -453,9 +499,22 @@ class GpuBlupEngine:
         ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False, covariates)
         return (ll, s2) if return_sigma2 else ll
 
-    def _loglik(self, genomes, train, valid, h2, branch, want_fitness, covariates=None):
+    def log_likelihood_group(self, genomes, train, valid, h2, groups, covariates=None, branch="auto",
+                             return_sigma2=False):
+        """log_likelihood for the model that fit(groups=) fits (a method of its own: log_likelihood_cov(groups=)
+        keeps raising): groups and the optional covariates as fit() takes them, and the value is the restricted
+        likelihood of the N - r - C_m error contrasts of the model with the fixed design [Q, Z] fitted beside the panel
+        (tblup_loglik_group_batch; include/tblup_gpu.h has the definition), with sigma2_g = q_P / (N - r - C_m).
+        h2 as log_likelihood takes it.  A design that is collinear over the train rows, or C_m >= N - r, gives NaN."""
+        ll, s2, _ = self._loglik(genomes, train, valid, h2, branch, False, covariates, groups)
+        return (ll, s2) if return_sigma2 else ll
+
+    def _loglik(self, genomes, train, valid, h2, branch, want_fitness, covariates=None, groups=None):
         self._settle()
-        qc = None if covariates is None else self._covariates(covariates)
+        if groups is not None:
+            levels, codes, qc, _ = self._group_design(genomes, train, valid, branch, covariates, groups)
+        else:
+            qc = None if covariates is None else self._covariates(covariates)
         idx, offsets = concat_genomes(genomes)
         B, nt = len(genomes), self.n_traits
         h = np.asarray(h2, dtype=np.float64)
@@ -471,7 +530,13 @@ class GpuBlupEngine:
         ll = np.empty((G, B, nt), dtype=np.float64)
         s2 = np.empty((G, B, nt), dtype=np.float64)
         fit = np.empty((G, B), dtype=np.float64) if want_fitness else None
-        if B and G and qc is not None:
+        if B and G and groups is not None:
+            sid = self.split_id(train, valid)
+            nc = 0 if qc is None else qc.shape[1]
+            _native.check("tblup_loglik_group_batch", self._lib.tblup_loglik_group_batch(
+                self._ctx, sid, _ptr(qc) if nc else None, nc, _ptr(codes), len(levels), _ptr(idx), _ptr(offsets), B,
+                _ptr(hm), G, _native.BRANCH[branch], _ptr(fit) if want_fitness else None, _ptr(ll), _ptr(s2), None, None))
+        elif B and G and qc is not None:
             sid = self.split_id(train, valid)
             _native.check("tblup_loglik_cov_batch", self._lib.tblup_loglik_cov_batch(
                 self._ctx, sid, _ptr(qc), qc.shape[1], _ptr(idx), _ptr(offsets), B, _ptr(hm), G, _native.BRANCH[branch],
@@ -511,14 +576,20 @@ class GpuBlupEngine:
         self._no_groups(groups, "estimate_h2_cov()")
         return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, covariates)
 
-    def _estimate_h2(self, genomes, train, valid, branch, grid, refine, points, covariates):
+    def estimate_h2_group(self, genomes, train, valid, groups, covariates=None, branch="auto",
+                          grid=np.linspace(0.02, 0.98, 25), refine=3, points=9):
+        """estimate_h2 on log_likelihood_group: the h2 of the model that fit(groups=) fits -- the value to pass to
+        fit(groups=) and snp_scores_group().  The same search, the same returned fields."""
+        return self._estimate_h2(genomes, train, valid, branch, grid, refine, points, covariates, groups)
+
+    def _estimate_h2(self, genomes, train, valid, branch, grid, refine, points, covariates, groups=None):
         grid = np.asarray(grid, dtype=np.float64)
         if grid.ndim != 1 or len(grid) < 2 or not np.all(np.diff(grid) > 0):
             raise ValueError("grid must be 1-D, ascending, with at least two values")
         if points < 3:
             raise ValueError("points must be at least 3")
         B, nt = len(genomes), self.n_traits
-        ll0, s20, _ = self._loglik(genomes, train, valid, grid, branch, False, covariates)
+        ll0, s20, _ = self._loglik(genomes, train, valid, grid, branch, False, covariates, groups)
         ll0, s20 = ll0.reshape(len(grid), B, nt), s20.reshape(len(grid), B, nt)
         out = {k: np.full((B, nt), np.nan) for k in ("h2", "loglik", "sigma2_g", "sigma2_e", "step")}
         out["at_bound"] = np.zeros((B, nt), dtype=bool)
@@ -540,7 +611,7 @@ class GpuBlupEngine:
                     break
                 lo, hi = h[np.maximum(i - 1, 0), cols], h[np.minimum(i + 1, len(h) - 1), cols]
                 h = np.linspace(lo, hi, points)      # (points, B), both ends exact
-                ll, s2, _ = self._loglik(genomes, train, valid, h, branch, False, covariates)
+                ll, s2, _ = self._loglik(genomes, train, valid, h, branch, False, covariates, groups)
                 ll, s2 = ll.reshape(points, B, nt)[:, :, t], s2.reshape(points, B, nt)[:, :, t]
             dead = np.isnan(best[1])
             hb = np.where(dead, np.nan, best[0])

@@ -448,18 +448,39 @@ class BlupParallelEvaluator(ParallelEvaluator):
         that fit_models(covariates=) fits.  No RNG, no collective: under torch.distributed every rank computes
         what it is given."""
         if groups is not None:
-            raise ValueError("snp_scores() does not take groups: the class factor is fitted by fit_models(groups=) only")
+            raise ValueError("snp_scores() does not take groups: the class factor's form is snp_scores_group()")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if covariates is None:
             return self.engine.snp_scores(genomes, train, valid, self.h2, snps)
         return self.engine.snp_scores(genomes, train, valid, self.h2, snps, covariates=covariates)
+
+    def snp_scores_group(self, population, groups, snps=None, final=True, train=None, valid=None, covariates=None):
+        """snp_scores under the model with the class factor that fit_models(groups=) fits:
+        GpuBlupEngine.snp_scores_group with fit_models' split and genome conventions.  groups: an (animals,) array of
+        labels, covariates: an optional (animals, c) matrix, one row per animal of the evaluator's data.  No RNG, no
+        collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.snp_scores_group(genomes, train, valid, self.h2, groups, snps, covariates=covariates)
+
+    def log_likelihood_group(self, population, h2, groups, final=True, train=None, valid=None, **kw):
+        """log_likelihood under the model that fit_models(groups=) fits: GpuBlupEngine.log_likelihood_group (its
+        keywords pass through) with fit_models' split and genome conventions.  No RNG, no collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.log_likelihood_group(genomes, train, valid, h2, groups, **kw)
+
+    def estimate_h2_group(self, population, groups, final=True, train=None, valid=None, **kw):
+        """estimate_h2 under the model that fit_models(groups=) fits -- the h2 to construct the evaluator with for
+        that model: GpuBlupEngine.estimate_h2_group (its keywords pass through) with fit_models' split and genome
+        conventions.  The evaluator's own h2 is not consulted.  No RNG, no collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.estimate_h2_group(genomes, train, valid, groups, **kw)
 
     def log_likelihood(self, population, h2, final=True, train=None, valid=None, **kw):
         """Profile (restricted) log-likelihood of every individual's model at `h2` (a scalar, a (G,)
         grid or a (G, B) matrix): GpuBlupEngine.log_likelihood (its keywords pass through; with
         covariates=Q, an (animals, c) matrix: log_likelihood_cov, the model fit_models(covariates=) fits) with fit_models' split and genome conventions.  No RNG, no collective: under torch.distributed every rank computes what it is given."""
         if kw.pop("groups", None) is not None:
-            raise ValueError("log_likelihood() does not take groups: the class factor is fitted by fit_models(groups=) only")
+            raise ValueError("log_likelihood() does not take groups: the class factor's form is log_likelihood_group()")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if kw.get("covariates") is not None:
             return self.engine.log_likelihood_cov(genomes, train, valid, h2, **kw)
@@ -471,7 +492,7 @@ class BlupParallelEvaluator(ParallelEvaluator):
         selected: GpuBlupEngine.estimate_h2 (its keywords pass through; with covariates=Q: estimate_h2_cov) with fit_models' split and genome
         conventions.  The evaluator's own h2 is not consulted.  No RNG, no collective."""
         if kw.pop("groups", None) is not None:
-            raise ValueError("estimate_h2() does not take groups: the class factor is fitted by fit_models(groups=) only")
+            raise ValueError("estimate_h2() does not take groups: the class factor's form is estimate_h2_group()")
         genomes, train, valid = self._model_setup(population, final, train, valid)
         if kw.get("covariates") is not None:
             return self.engine.estimate_h2_cov(genomes, train, valid, **kw)

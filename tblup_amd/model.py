@@ -201,13 +201,16 @@ class SnpScores:
     the statistics adjusted for them -- u_P = w_j' P r_t, v_P = w_j' P w_j, q_P = r_t' P r_t with
     P = V^-1 - V^-1 Q~ (Q~' V^-1 Q~)^-1 Q~' V^-1, dof = N - r - c -- and `cov_effects` (B, nt, c) the GLS
     effects of the covariates in the model without the SNP (fit(covariates=)'s); it is None otherwise.
+    With a class factor (snp_scores_group, tblup_snp_score_group_batch) the adjustment is for the fixed design
+    [Q, Z], dof = N - r - C_m with C_m the model's column count, and `group_levels` (L,) / `group_effects` (B, nt, L)
+    are fit(groups=)'s levels and level effects; both are None otherwise.
 
     The derived statistics are plain numpy and need neither the GPU nor the library; all three give NaN
     where v == 0 (a column that is constant over the reference rows, or in the span of the covariates)."""
 
-    __slots__ = ("score", "info", "q", "dof", "snps", "cov_effects")
+    __slots__ = ("score", "info", "q", "dof", "snps", "cov_effects", "group_effects", "group_levels")
 
-    def __init__(self, score, info, q, dof, snps, cov_effects=None):
+    def __init__(self, score, info, q, dof, snps, cov_effects=None, group_effects=None, group_levels=None):
         self.score = np.asarray(score, dtype=np.float64)
         self.info = np.asarray(info, dtype=np.float64)
         self.q = np.asarray(q, dtype=np.float64)
@@ -222,6 +225,12 @@ class SnpScores:
                              % (self.score.shape,))
         if self.cov_effects is not None and (self.cov_effects.ndim != 3 or self.cov_effects.shape[:2] != (B, nt)):
             raise ValueError("cov_effects must have shape (models, n_traits, n_cov)")
+        self.group_effects = None if group_effects is None else np.asarray(group_effects, dtype=np.float64)
+        self.group_levels = None if group_levels is None else np.asarray(group_levels)
+        if (self.group_effects is None) != (self.group_levels is None):
+            raise ValueError("group_effects and group_levels are given together")
+        if self.group_effects is not None and self.group_effects.shape != (B, nt, len(self.group_levels)):
+            raise ValueError("group_effects must have shape (models, n_traits, n_levels)")
 
     def _uv(self):
         v = np.where(self.info == 0, np.nan, self.info)[:, None, :]

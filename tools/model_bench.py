@@ -39,10 +39,18 @@ numbers go to PERFLOG.md.  One JSON line per part:
            of the covariate adjustment (k_covar in keep mode once per chunk, then S^T s_a and the two 16-step solves
            per slab); k_reliab's adjusted and plain launches and the k_covar keep launch come from a --stats run of
            this part (the --stats reader lists them apart)
+  score_group  config 2 again: snp_scores_group() at 64 levels (63 columns under snp) and at 112 levels + 16 covariates
+           (127 columns) (tblup_snp_score_group_batch) beside snp_scores() and snp_scores(covariates=16 columns) on the
+           same 2,000-SNP list, alternated in one process; beside each ratio the derived flop share of the
+           adjustment over the plain substitution, 2 C_m / ns + C_m^2 / ns^2; k_snpscore's plain, 16-column and
+           wide launches, k_fixed_subst and k_fixed_gls (keep mode) come from a --stats run of this part
+  loglik_group  config 2 again: tblup_loglik_group_batch at 64 levels and at 112 levels + 16 covariates beside
+           tblup_loglik_cov_batch (16 covariates) at the same 8 grid points and fit(groups=) at both designs, alternated;
+           one estimate_h2_group with the defaults (25 + 3 x 9 passes) at 64 levels
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov,score_group,loglik_group] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -243,10 +251,8 @@ def covar_vs_fit(eng, genomes, T, V, n, P, reps, n_cov=16):
 def group_vs_fit(eng, genomes, T, V, n, reps):
     """fit(groups=) at 64 levels and at 112 levels + 16 covariates against fit(covariates=16 columns) and fit(),
     alternated on one engine.  Labels uniform over the levels, every level on a train animal."""
-    rng = np.random.default_rng(78)
     q = bench_cov(n)
-    g64, g112 = rng.integers(0, 64, n), rng.integers(0, 112, n)
-    g64[T[:64]], g112[T[:112]] = np.arange(64), np.arange(112)
+    g64, g112 = bench_groups(n, T)
     ts = {"fit_ms": [], "fit_cov16_ms": [], "fit_group64_ms": [], "fit_group112_cov16_ms": []}
     for r in range(reps + 2):
         t = [time.perf_counter()]
@@ -267,6 +273,113 @@ def group_vs_fit(eng, genomes, T, V, n, reps):
     out["finite"] = bool(all(np.all(np.isfinite(m.group_effects)) for m in m64 + m128))
     out["note"] = ("each call is the whole evaluation plus its kernels, the D2H copies and the PanelModel objects; the "
                    "covariate and group calls run the one-workgroup k_solve twice; the kernels alone: --stats")
+    return out
+
+
+def bench_groups(n, T):
+    """group_vs_fit's labels: 64 and 112 levels, uniform, every level on a train animal."""
+    rng = np.random.default_rng(78)
+    g64, g112 = rng.integers(0, 64, n), rng.integers(0, 112, n)
+    g64[T[:64]], g112[T[:112]] = np.arange(64), np.arange(112)
+    return g64, g112
+
+
+def score_group_vs_score(eng, genomes, T, V, n, P, ns, reps, n_cand=2000):
+    """snp_scores_group() at 64 levels and at 112 levels + 16 covariates against snp_scores() and
+    snp_scores(covariates=16 columns) on score_vs_reliability's list, and evaluate(), alternated."""
+    cand = np.random.default_rng(99).choice(P, n_cand, replace=False)
+    q = bench_cov(n)
+    g64, g112 = bench_groups(n, T)
+    ts = {"evaluate_ms": [], "score_ms": [], "score_cov16_ms": [], "score_group64_ms": [], "score_group112_cov16_ms": []}
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        plain = eng.snp_scores(genomes, T, V, 0.4, cand)
+        t.append(time.perf_counter())
+        eng.snp_scores(genomes, T, V, 0.4, cand, covariates=q)
+        t.append(time.perf_counter())
+        s64 = eng.snp_scores_group(genomes, T, V, 0.4, g64, cand)
+        t.append(time.perf_counter())
+        s128 = eng.snp_scores_group(genomes, T, V, 0.4, g112, cand, covariates=q)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for i, key in enumerate(ts):
+                ts[key].append(t[i + 1] - t[i])
+    out = {k: med_ms(v) for k, v in ts.items()}
+    out.update({k + "_all": [round(x * 1e3, 3) for x in v] for k, v in ts.items() if k != "evaluate_ms"})
+    share = lambda c: round(2.0 * c / ns + float(c) * c / (ns * ns), 4)
+    out.update({"n_cand": n_cand, "columns": {"cov16": 16, "group64": 63, "group112_cov16": 127},
+                "over_score": {k: round(out[k + "_ms"] / out["score_ms"], 4)
+                               for k in ("score_cov16", "score_group64", "score_group112_cov16")},
+                "derived_flop_share": {"cov16": share(16), "group64": share(63), "group112_cov16": share(127)},
+                "slab_launch_workgroups": len(genomes) * ((n_cand + 15) // 16),
+                "finite": bool(all(np.all(np.isfinite(s.score)) and np.all(np.isfinite(s.info)) for s in (s64, s128))),
+                "median_info_ratio": {"group64": float(np.median(s64.info / plain.info)),
+                                      "group112_cov16": float(np.median(s128.info / plain.info))},
+                "note": "each call is the whole evaluation plus its kernels and the D2H copy of its outputs; a group "
+                        "call adds one k_fixed_subst and one k_fixed_gls (keep mode) launch per chunk; the kernels "
+                        "alone: --stats"})
+    return out
+
+
+def loglik_group_vs_cov(eng, genomes, T, V, n, reps, grid_n=8):
+    """tblup_loglik_group_batch at 64 levels and at 112 levels + 16 covariates against tblup_loglik_cov_batch at
+    grid_n grid points (the C entries) and fit(groups=) at both designs, alternated; one estimate_h2_group."""
+    from tblup_amd.engine import concat_genomes
+    from tblup_amd import _native
+    _ptr = _native.ptr
+    sid = eng.split_id(T, V)
+    idx, off = concat_genomes(genomes)
+    B, nt = len(genomes), eng.n_traits
+    q = np.ascontiguousarray(bench_cov(n))
+    g64, g112 = (np.ascontiguousarray(g, dtype=np.int64) for g in bench_groups(n, T))
+    hg = np.ascontiguousarray(np.repeat(np.linspace(0.1, 0.8, grid_n)[:, None], B, axis=1))
+    ll = {k: np.empty((grid_n, B, nt)) for k in ("cov", "g64", "g128")}
+    s2 = np.empty((grid_n, B, nt))
+
+    def group(codes, L, cov, nc, out):
+        _native.check("tblup_loglik_group_batch", eng._lib.tblup_loglik_group_batch(
+            eng._ctx, sid, _ptr(cov) if nc else None, nc, _ptr(codes), L, _ptr(idx), _ptr(off), B, _ptr(hg), grid_n, 0,
+            None, _ptr(out), _ptr(s2), None, None))
+
+    ts = {"loglik_cov16": [], "loglik_group64": [], "loglik_group112_cov16": [], "fit_group64": [],
+          "fit_group112_cov16": []}
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        _native.check("tblup_loglik_cov_batch", eng._lib.tblup_loglik_cov_batch(
+            eng._ctx, sid, _ptr(q), 16, _ptr(idx), _ptr(off), B, _ptr(hg), grid_n, 0, None, _ptr(ll["cov"]), _ptr(s2),
+            None))
+        t.append(time.perf_counter())
+        group(g64, 64, None, 0, ll["g64"])
+        t.append(time.perf_counter())
+        group(g112, 112, q, 16, ll["g128"])
+        t.append(time.perf_counter())
+        eng.fit(genomes, T, V, 0.4, groups=g64)
+        t.append(time.perf_counter())
+        eng.fit(genomes, T, V, 0.4, covariates=q, groups=g112)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for i, key in enumerate(ts):
+                ts[key].append(t[i + 1] - t[i])
+    t0 = time.perf_counter()
+    est = eng.estimate_h2_group(genomes, T, V, g64)
+    t_est = time.perf_counter() - t0
+    out = {}
+    for k, v in ts.items():
+        if k.startswith("loglik"):
+            out[k + "_%d_ms" % grid_n] = med_ms(v)
+            out[k + "_per_grid_point_ms"] = round(med_ms(v) / grid_n, 4)
+        else:
+            out[k + "_ms"] = med_ms(v)
+        out[k + "_ms_all"] = [round(x * 1e3, 3) for x in v]
+    out.update({"finite": bool(all(np.all(np.isfinite(a)) for a in ll.values())),
+                "estimate_h2_group_ms": round(t_est * 1e3, 2), "estimate_h2_passes": 25 + 3 * 9,
+                "estimate_h2_group_ms_per_pass": round(t_est * 1e3 / (25 + 3 * 9), 3),
+                "h2_median": float(np.nanmedian(est["h2"])), "at_bound": int(np.sum(est["at_bound"])),
+                "note": "every call ends in the stream's synchronisation; a group pass adds one k_fixed_subst and one "
+                        "k_fixed_gls (keep mode, no z*) launch; fit(groups=) is one pass with the second solve and the "
+                        "PanelModel objects; the kernels alone: --stats"})
     return out
 
 
@@ -428,10 +541,13 @@ def stats_share(path):
     for r in rows:
         name = r["Name"]
         # the covariate-adjusted k_reliab instances and k_covar's keep mode (third template argument) apart
-        for key, alias in (("k_reliab", "k_reliab_cov"), ("k_covar", "k_covar_keep")):
-            if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith(",true"):
+        # ... k_fixed_gls's keep mode (second) and k_snpscore's 16-column and wide instances (third: 1, 2) too
+        for key, alias, last in (("k_reliab", "k_reliab_cov", "true"), ("k_covar", "k_covar_keep", "true"),
+                                 ("k_fixed_gls", "k_fixed_gls_keep", "true"), ("k_snpscore", "k_snpscore_cov", "1"),
+                                 ("k_snpscore", "k_snpscore_fix", "2")):
+            if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith("," + last):
                 name = name.replace(key + "<", alias + "<")
-        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_fixed_gls_keep", "k_snpscore_cov", "k_snpscore_fix", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -515,6 +631,17 @@ def main():
                                   **score_cov_vs_score(eng, genomes, T, V, n, P, 1024, args.reps)}))
             if "loglik_cov" in parts:
                 print(json.dumps({"part": "loglik_cov", **head, **loglik_cov_vs_loglik(eng, genomes, T, V, n, args.reps)}))
+    if parts & {"score_group", "loglik_group"}:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            head = {"config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024}
+            if "score_group" in parts:
+                print(json.dumps({"part": "score_group", **head,
+                                  **score_group_vs_score(eng, genomes, T, V, n, P, 1024, args.reps)}), flush=True)
+            if "loglik_group" in parts:
+                print(json.dumps({"part": "loglik_group", **head,
+                                  **loglik_group_vs_cov(eng, genomes, T, V, n, args.reps)}), flush=True)
     if "reliab_cov" in parts:
         n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
