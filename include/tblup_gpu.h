@@ -465,6 +465,50 @@ int tblup_reliability_cov_batch(tblup_ctx* ctx, int split_id, const double* cov,
                                 double* reliability, double* pev_total, double* cov_cov);
 
 /*
+ * The same for the model with a class fixed effect that tblup_fit_group_batch fits: cov, n_cov, group, n_levels and
+ * the design F = [Q, Z] as documented there, C_m = n_cov + n_levels - [snp] columns for a model, at most
+ * TBLUP_MAX_FIXED.  With F~ in place of Q~ the three statistics are exactly tblup_reliability_cov_batch's:
+ * G = F~_T^T V^{-1} F~_T = C C^T and, for a listed animal a (any row of the panel, in any split role or none) with
+ * design row f~_a,
+ *   a_a          = F~_T^T V^{-1} k_Ta                                           (C_m values)
+ *   reliability  : out, batch x n_pred:  (k_Ta^T V^{-1} k_Ta - |C^{-1} a_a|^2) / K_aa: the level effects estimated,
+ *                  not known; never above tblup_reliability_cov_batch's on Q alone
+ *   pev_total    : optional out, batch x n_pred:  K_aa - k_Ta^T V^{-1} k_Ta + |C^{-1} (f~_a - a_a)|^2: the error variance
+ *                  of a predicted record of the animal in its own level, in units of sigma2_g
+ *   fixed_cov    : optional out, batch x (n_cov + n_levels) x (n_cov + n_levels), covariates then levels:  G^{-1}, in
+ *                  units of sigma2_g.  Under snp the row and the column of the reference level (the lowest) are exact
+ *                  zeros: its effect is 0 by construction
+ *   fitness      : optional out, batch: tblup_fit_group_batch's, bit for bit
+ *   cov_effects / cov_center / group_effects / group_center / intercept / center / effects : optional as a group
+ *                  (all NULL or none; cov_effects / cov_center only with n_cov > 0): tblup_fit_group_batch's, bit for bit
+ * f~_a: a covariate's entry is tblup_reliability_cov_batch's q~_a; a level's is [code_a == level] under gblup and
+ * [code_a == level] - share_level under snp, the lowest level dropped.  A listed animal whose code is -1 (a label that
+ * no train animal has) is not an argument error: its reliability needs no design row and is defined, its pev_total is
+ * NaN.  On a row of the split -1 stays the argument error it is in tblup_fit_group_batch.
+ * From the factor, with s_a the animal's solved column and S = L^{-1} R in 16-column slabs (tblup_fit_group_batch):
+ *   kernel form:  a_a = S^T s_a          SNP form:  a_a = S^T s_a / d
+ * (no allele counts per level are needed, unlike tblup_snp_score_group_batch's SNP form).  A batch model of 1 .. 16
+ * columns runs tblup_reliability_cov_batch's own kernels on the expanded design: its outputs are that entry's on
+ * [Q, Z] bit for bit, fixed_cov scattered to the layout above.  A wider one keeps tblup_fit_group_batch's GLS step --
+ * S, C, the bad flag -- and behind it T = S^T s_a (C_m x 16 per slab of listed animals) on fp64 MFMA, one wave per
+ * column slab over the real rows in order; C y = a_a and C x = f~_a - a_a together, column by column, with |y|^2 and
+ * |x|^2 on the way; and G^{-1} from C^{-1}, formed in place in LDS, G^{-1}(i, j) one chain over k >= max(i, j) in order
+ * (the same bits at (i, j) and (j, i)).
+ * NaN in every output of a model whose design is collinear over the train rows (a covariate equal to a level's
+ * indicator, a column of ones beside gblup levels), with d = 0 or a flagged index; K_aa = 0 gives NaN for the
+ * animal: not errors.  Argument errors are tblup_fit_group_batch's and, for animals, tblup_reliability_batch's; the
+ * empty-call rules, the second solve only when fitness or the model group is given, the chunking and the bits'
+ * independence of the list, the slab, the batch, the chunking, TBLUP_RELIAB_LDS, TBLUP_SCORE_LDS and
+ * TBLUP_WORKSPACE_MB are tblup_reliability_cov_batch's.  Host pointers, synchronous.
+ */
+int tblup_reliability_group_batch(tblup_ctx* ctx, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                                  int64_t n_levels, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                                  const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                                  double* cov_effects, double* cov_center, double* group_effects,
+                                  double* group_center, double* intercept, double* center, double* effects,
+                                  double* reliability, double* pev_total, double* fixed_cov);
+
+/*
  * EBVs of `n_pred` animals of the context's panel under `batch` fitted models (the formula above
  * on the device panel): ebv is batch x n_traits x n_pred.  `animals` are row ids in any order, may
  * repeat and need not belong to any split; no split is needed, only a panel (TBLUP_ERR_STATE on a

@@ -68,6 +68,9 @@ SIGNATURES = {
     "tblup_reliability_cov_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _c.c_int64, _I64P, _I64P,
                                                _c.c_int64, _c.c_double, _c.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP,
                                                _DP, _DP]),
+    "tblup_reliability_group_batch": (_c.c_int, [_P, _c.c_int, _DP, _c.c_int64, _I64P, _c.c_int64, _I64P, _c.c_int64,
+                                                 _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP, _DP, _DP, _DP,
+                                                 _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     "tblup_predict_batch": (_c.c_int, [_P, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _DP, _DP, _DP, _c.c_int64,
                                        _DP]),
     "tblup_eval_batch_device": (_c.c_int, [_P, _c.c_int, _P, _P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _P, _P,

@@ -16,6 +16,9 @@
 //                              ones: k_fixed_subst, k_fixed_gls in keep mode, k_snpscore's wide-design launches
 //   tblup_loglik_group_batch   the same routes: tblup_loglik_cov_batch, or per h2 row k_fixed_subst, k_fixed_gls in
 //                              keep mode and k_loglik with the model's own column count
+//   tblup_reliability_group_batch  the same routes: tblup_reliability_cov_batch, or k_fixed_subst, k_fixed_gls in keep
+//                              mode, k_reliab's wide-design launches and k_fixed_cov; tblup_fit_group_batch's second
+//                              pass when the model or its fitness is wanted
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -713,6 +716,139 @@ int loglik_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_c
   });
 }
 
+struct ReliabFixedBufs {   // tblup_reliability_group_batch, the models of more than COVAR_W columns
+  ReliabBufs r;
+  FixedKeepBufs k;
+  double* qa;                       // ReliabCovBufs'
+  int32_t* ga;                      // the listed animals' level codes [n_rel]
+  double *pev, *fc;                 // pev_total [B][n_rel] and fixed_cov [B][n_cov + L][n_cov + L] where wanted
+  double* qV;                       // tblup_fit_group_batch's second pass (FixedBufs'), where wanted
+  int32_t* gV;
+  double *z2, *fit0, *ebv2;
+  static ReliabFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, int64_t n_cov,
+                               int64_t L, int64_t Cw, bool model, bool full, bool pev, bool fc) {
+    const EvalDims& d = hb.d;
+    const size_t Bt = (size_t)B * d.nt, Co = (size_t)(n_cov + L);
+    ReliabFixedBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), FixedKeepBufs::carve(cv, hb, B, L, Cw, 1)};
+    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
+    b.ga = cv.take<int32_t>((size_t)n_rel);
+    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
+    b.fc = fc ? cv.take<double>((size_t)B * Co * Co) : nullptr;
+    if (full) {
+      b.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
+      b.gV = cv.take<int32_t>((size_t)d.nV);
+      b.z2 = cv.take<double>(Bt * hb.sd.ns);
+      b.fit0 = cv.take<double>((size_t)B);
+      b.ebv2 = cv.take<double>(Bt * d.nV);
+    }
+    return b;
+  }
+};
+
+// The models of more than COVAR_W fixed columns of a tblup_reliability_group_batch call, as a batch of their own:
+// tblup_reliability_cov_batch's chunk with k_fixed_subst and k_fixed_gls (keep mode) in place of k_covar, k_reliab's
+// FIX instances and k_fixed_cov behind them, and fit_fixed_wide's second pass when the model or its fitness is wanted
+// (full).  a32 / animals: the list; rel / pev [batch][n_pred], fc [batch][(n_cov + L)^2] (pev, fc: null when not
+// wanted); bout [batch][nt][Cw] and intercept / center / effects: fit_fixed_wide's, with model.
+int reliab_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
+                      int64_t Cw, const std::vector<int32_t>& a32, const int64_t* animals, const int64_t* idx,
+                      const int64_t* offsets, int64_t batch, double h2, int branch, bool full, double* fitness,
+                      double* rel, double* pev, double* fc, double* bout, double* intercept, double* center,
+                      double* effects) {
+  const bool model = intercept != nullptr;
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+  if (!hb.sp) return 0;
+  fitness = hb.fitness_or_own(fitness);
+  const EvalDims& d = hb.d;
+  const int nt = d.nt;
+  const int64_t n_pred = (int64_t)a32.size(), Co = n_cov + L;
+  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
+  // f~_a of the listed animals: the covariates as tblup_reliability_cov_batch lays them out, the level codes
+  std::vector<double> h_qa((size_t)2 * n_pred * COVAR_W, 0.0);
+  std::vector<int32_t> h_ga((size_t)n_pred);
+  for (int64_t v = 0; v < n_pred; ++v) {
+    for (int64_t j = 0; j < n_cov; ++j) {
+      const double q = cov[animals[v] * n_cov + j];
+      h_qa[v * COVAR_W + j] = q;
+      h_qa[(n_pred + v) * COVAR_W + j] = q - g.cp.m[j];
+    }
+    h_ga[v] = (int32_t)group[animals[v]];
+  }
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
+    return ReliabFixedBufs::carve(cv, hb, B, sk, n_pred, n_cov, L, Cw, model, full, pev != nullptr, fc != nullptr);
+  };
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const ReliabFixedBufs rb = carve(cv, B, ck.sum_k);
+    const FixedKeepBufs& kb = rb.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    if (n_pred > 0) {
+      HIPCHK(hipMemcpyAsync(rb.r.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(rb.qa, h_qa.data(), h_qa.size() * 8, hipMemcpyHostToDevice, s));
+      HIPCHK(hipMemcpyAsync(rb.ga, h_ga.data(), h_ga.size() * 4, hipMemcpyHostToDevice, s));
+    }
+    if (int rc = kb.upload(g, s)) return rc;
+    FixedDesign fd = kb.design(g);
+    if (full) {
+      HIPCHK(hipMemcpyAsync(rb.qV, g.cp.qV.data(), g.cp.qV.size() * 8, hipMemcpyHostToDevice, s));
+      if (!g.gV.empty()) HIPCHK(hipMemcpyAsync(rb.gV, g.gV.data(), g.gV.size() * 4, hipMemcpyHostToDevice, s));
+      fd.qV = rb.qV;
+      fd.gV = rb.gV;
+    }
+    const auto after = [&](const CholLaunch& cl) -> int {
+      HIPCHK(launch_fixed_subst(cl, fd, kb.plan, kb.S, s));
+      HIPCHK(launch_fixed_gls(cl, fd, kb.S, kb.b, rb.z2, kb.keep, s));
+      const ReliabFixed rf{kb.S, kb.keep.cf, kb.keep.ks, rb.qa, rb.ga, fd, rb.pev};
+      HIPCHK(launch_reliab_fixed(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.r.an, n_pred,
+                                 rb.r.plan, rb.r.vscr, rf, rb.r.rel, s));
+      if (n_pred > 0) {
+        HIPCHK(hipMemcpyAsync(rel + b0 * n_pred, rb.r.rel, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
+        if (pev) HIPCHK(hipMemcpyAsync(pev + b0 * n_pred, rb.pev, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
+      }
+      if (fc) {
+        HIPCHK(launch_fixed_cov(cl, fd, kb.keep.cf, kb.keep.ks, rb.fc, s));
+        HIPCHK(hipMemcpyAsync(fc + b0 * Co * Co, rb.fc, (size_t)B * Co * Co * 8, hipMemcpyDeviceToHost, s));
+      }
+      return 0;
+    };
+    if (!full) return factor_pass(hb, ck, cv, rq, fitness, nullptr, after);
+    // fit_fixed_wide's chunk: the pipeline with the one-workgroup solve, then the second pass on z*
+    double* d_fit = rq.d_fit;
+    Carve cvp = cv;
+    rq.mode = ChunkMode::NoChain;
+    rq.d_fit = rb.fit0;
+    ChunkRes res;
+    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+    if (int rc = after(res.cl)) return rc;
+    CholLaunch cl2 = res.cl;
+    cl2.z = rb.z2;
+    HIPCHK(launch_solve(cl2, nullptr, rb.fit0, rb.ebv2, s));
+    HIPCHK(launch_fixed_fitness(cl2, fd, rb.ebv2, kb.b, d_fit, s));
+    if (model) {
+      if (int rc = rb.r.m.enqueue(hb, ck, cl2, center, effects)) return rc;
+      HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, kb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    return 0;
+  });
+  if (rc || !model) return rc;
+  // fit_fixed_wide's post-pass
+  fill_intercepts(hb, intercept);
+  const double nan = std::nan("");
+  for (int64_t b = 0; b < batch; ++b) {
+    const bool gblup = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1;
+    bool dead = fixed_cols(gblup, (int)n_cov, (int)L) == 0 && std::isnan(fitness[b]);
+    for (int64_t i = 0; i < nt * Cw; ++i) dead = dead || std::isnan(bout[b * nt * Cw + i]);
+    if (!dead) continue;
+    for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
+    for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+  }
+  return 0;
+}
+
 struct PredictBufs {   // tblup_predict_batch: no pipeline, these are the chunk
   int32_t* an;                      // the animal list [n_pred]
   int64_t *idx, *off;               // the models' index lists and offsets
@@ -1352,6 +1488,120 @@ int tblup_loglik_group_batch(tblup_ctx* c, int split_id, const double* cov, int6
                     cov_effects ? cov_effects + to * nt * nc : nullptr,
                     group_effects ? group_effects + to * nt * L : nullptr);
       }
+  }
+  return 0;
+}
+
+int tblup_reliability_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
+                                  int64_t n_levels, const int64_t* animals, int64_t n_pred, const int64_t* idx,
+                                  const int64_t* offsets, int64_t batch, double h2, int branch, double* fitness,
+                                  double* cov_effects, double* cov_center, double* group_effects, double* group_center,
+                                  double* intercept, double* center, double* effects, double* reliability,
+                                  double* pev_total, double* fixed_cov) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
+  if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
+  // (without covariates cov_effects / cov_center are not looked at, as tblup_fit_group_batch)
+  const bool cov_out = n_cov > 0 && (cov_effects || cov_center);
+  const bool model = cov_out || group_effects || group_center || intercept || center || effects;
+  if (model && !(group_effects && group_center && intercept && center && effects &&
+                 (n_cov == 0 || (cov_effects && cov_center))))
+    return fail(TBLUP_ERR_ARG,
+                "cov_effects/cov_center/group_effects/group_center/intercept/center/effects are given together or not "
+                "at all");
+  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
+  std::vector<int32_t> a32((size_t)n_pred);
+  for (int64_t i = 0; i < n_pred; ++i) {
+    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
+    a32[i] = (int32_t)animals[i];
+  }
+  // the second solve (the model of the adjusted phenotype and its fitness) runs only for a caller who wants it
+  const bool full = model || fitness;
+  if (batch == 0 || (n_pred == 0 && !full && !fixed_cov)) return 0;
+  if (n_pred > 0 && !reliability) return fail(TBLUP_ERR_ARG, "null reliability");
+  const int64_t L = n_levels, nc = n_cov, Co = nc + L;
+  GroupSplit gs;
+  {
+    HostBatch hb;
+    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
+    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
+  }
+  const int nt = gs.nt;
+  GroupRoutes gr;
+  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
+  const int64_t total = offsets[batch];
+  const double nan = std::nan("");
+  for (int route = 0; route < 3; ++route) {
+    const std::vector<int64_t>& mb = gr.of[route];
+    const int64_t Bs = (int64_t)mb.size();
+    if (!Bs) continue;
+    const SubBatch sub = sub_batch(idx, offsets, mb);
+    const std::vector<int64_t>& so = sub.so;
+    const int64_t st = so[Bs], Cw = gr.width(route), Cm = gr.cols[route == 2 ? 0 : route];
+    // A route that is the whole batch (its models are then in batch order) writes the per-animal outputs, and the
+    // wide route fixed_cov, straight into the caller's arrays: at 128 columns fixed_cov is 128 KiB a model.  Else the
+    // route's own: fixed_cov compact [Cm][Cm] from the covariate entry, in the caller's layout from k_fixed_cov.
+    const bool whole = Bs == batch, fc_own = fixed_cov && !(whole && route == 2);
+    const size_t fc_model = (size_t)(route == 2 ? Co * Co : Cm * Cm);
+    std::vector<double> fit(fitness ? (size_t)Bs : 0), rel(whole ? 0 : (size_t)Bs * n_pred),
+        pev(pev_total && !whole ? (size_t)Bs * n_pred : 0), fc(fc_own ? (size_t)Bs * fc_model : 0),
+        bo(model ? (size_t)Bs * nt * Cw : 0), xc(model ? (size_t)Bs * Cw : 0), icpt(model ? (size_t)Bs * nt : 0),
+        cen(model ? (size_t)st : 0), eff(model ? (size_t)nt * st : 0);
+    const auto opt = [](std::vector<double>& v, bool on) { return on ? v.data() : nullptr; };
+    double *fp = opt(fit, fitness), *bp = opt(bo, model), *ip = opt(icpt, model), *np = opt(cen, model);
+    double *ep = opt(eff, model), *rp = whole ? reliability : rel.data();
+    double *pp = whole ? pev_total : opt(pev, pev_total), *cp = fc_own ? fc.data() : fixed_cov;
+    int rc;
+    if (route == 2) {
+      rc = reliab_fixed_wide(c, split_id, cov, nc, group, L, Cw, a32, animals, sub.si.data(), so.data(), Bs, h2,
+                             branch, full, fp, rp, pp, cp, bp, ip, np, ep);
+    } else {
+      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
+      rc = tblup_reliability_cov_batch(c, split_id, x.data(), Cw, animals, n_pred, sub.si.data(), so.data(), Bs, h2,
+                                       branch, fp, bp, opt(xc, model), ip, np, ep, rp, pp, cp);
+    }
+    if (rc) return rc;
+    for (int64_t i = 0; i < Bs; ++i) {
+      const int64_t b = mb[i], k = offsets[b + 1] - offsets[b];
+      const int br = branch_of(c, k, branch) == 1 ? 0 : 1;
+      if (fitness) fitness[b] = fit[i];
+      for (int64_t v = 0; v < n_pred; ++v) {
+        reliability[b * n_pred + v] = rp[i * n_pred + v];
+        // an animal whose label no train animal has: no design row, so no predicted record (PanelModel.predict's rule)
+        if (pev_total) pev_total[b * n_pred + v] = group[animals[v]] < 0 ? nan : pp[i * n_pred + v];
+      }
+      if (fc_own) {
+        double* out = fixed_cov + b * Co * Co;
+        if (route == 2) {
+          std::copy(cp + i * Co * Co, cp + (i + 1) * Co * Co, out);
+        } else {
+          // the compact G^-1 of the expanded design at the caller's columns: level l is column nc + l - br, and the
+          // reference level of an snp model keeps its zeros (NaN throughout for a model that is NaN)
+          const double* in = cp + i * Cm * Cm;
+          const bool dead = std::isnan(in[0]);
+          for (int64_t oi = 0; oi < Co; ++oi)
+            for (int64_t oj = 0; oj < Co; ++oj) {
+              const int64_t mi = oi < nc ? oi : oi - br, mj = oj < nc ? oj : oj - br;
+              const bool ref = br == 1 && (oi == nc || oj == nc);
+              out[oi * Co + oj] = dead ? nan : (ref ? 0.0 : in[mi * Cm + mj]);
+            }
+        }
+      }
+      if (!model) continue;
+      bool dead = gr.cols[br] == 0 && std::isnan(fit[i]);
+      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
+      for (int64_t j = 0; j < nc; ++j) cov_center[b * nc + j] = dead ? nan : (br == 1 ? gs.cov_m[j] : 0.0);
+      for (int64_t l = 0; l < L; ++l) group_center[b * L + l] = dead ? nan : (br == 1 ? (double)gs.share[l] : 0.0);
+      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, nc ? cov_effects + b * nt * nc : nullptr,
+                  group_effects + b * nt * L);
+      for (int t = 0; t < nt; ++t) {
+        intercept[b * nt + t] = ip[i * nt + t];
+        std::copy(ep + t * st + so[i], ep + t * st + so[i] + k, effects + t * total + offsets[b]);
+      }
+      std::copy(np + so[i], np + so[i] + k, center + offsets[b]);
+    }
   }
   return 0;
 }

@@ -30,6 +30,7 @@
 //     chain over the model's columns in order; S is already there.  z* is skipped when z2 is null.  b and z* are
 //     the same bits with or without it.
 // k_fixed_fitness: k_cov_fitness with a level column as a lookup: y*_V = y_V - (q~_V b_Q + b_level - sum_l m_l b_l).
+// k_fixed_cov (tblup_reliability_group_batch): G^{-1} from the kept C, one workgroup per model, C^{-1} in place in LDS.
 // No flags, no atomics, every loop bounded by the system's shape and the model's own column count, every sum in a
 // fixed order: a model's bits are a function of the model, the design and the system alone.
 #include <algorithm>
@@ -414,6 +415,54 @@ __global__ __launch_bounds__(XTH) void k_fixed_fitness(CholLaunch c, FixedDesign
   if (t == 0) fit[b] = sc[SC_BAD] != 0.0 ? __builtin_nan("") : (nt == 1) ? fsum : fsum / (double)nt;
 }
 
+// fixed_cov = G^{-1} = C^{-T} C^{-1} of every model from the factor k_fixed_gls keeps (k_cov_cov for the wide
+// design): one workgroup per model, C in LDS.  C^{-1} in place, thread j its column j: the column-by-column solve of
+// C x = e_j with x kept in column j itself -- at step k the threads j < k take x_k = x[k] / C_kk and update their
+// rows below k with column k of C, then thread k turns column k into its own x (x_k = 1 / C_kk, -C_ik x_k below).
+// G^{-1}(i, j) is one chain over k = max(i, j) .. Cm - 1 in order, the same bits at (i, j) and (j, i), written at the
+// caller's [nc + L][nc + L]: covariates then levels, zeros in the row and the column of the level that an snp model
+// drops.  NaN throughout for a model whose ks is flagged.
+__global__ __launch_bounds__(XTH) void k_fixed_cov(CholLaunch c, FixedDesign f, const double* __restrict__ cf,
+                                                   const double* __restrict__ ks, double* __restrict__ fc) {
+  extern __shared__ __attribute__((aligned(16))) double M[];   // [Cw][Cw]
+  const int t = threadIdx.x;
+  const int64_t b = blockIdx.x;
+  const int Cw = f.Cw;
+  const bool gblup = (int)c.scal[b * SCAL + SC_MODE] == 1;
+  const int Cm = cols_of(f, gblup);
+  const double* C = cf + b * (int64_t)Cw * Cw;
+  for (int e = t; e < Cw * Cw; e += XTH) M[e] = C[e];
+  __syncthreads();
+  for (int k = 0; k < Cm; ++k) {
+    const double ckk = M[k * Cw + k];
+    if (t < k) {
+      const double xk = M[k * Cw + t] / ckk;
+      for (int i = k + 1; i < Cm; ++i) M[i * Cw + t] = __builtin_fma(-M[i * Cw + k], xk, M[i * Cw + t]);
+      M[k * Cw + t] = xk;
+    }
+    __syncthreads();
+    if (t == k) {
+      const double xk = 1.0 / ckk;
+      for (int i = k + 1; i < Cm; ++i) M[i * Cw + k] = -M[i * Cw + k] * xk;
+      M[k * Cw + k] = xk;
+    }
+    __syncthreads();
+  }
+  const int Co = f.nc + f.L, drop = gblup ? 0 : 1;
+  const bool bad = ks[b * COVAR_KS + KS_BAD] != 0.0;
+  double* out = fc + b * (int64_t)Co * Co;
+  for (int e = t; e < Co * Co; e += XTH) {
+    const int oi = e / Co, oj = e % Co;
+    // the model's column of an output index; the reference level of an snp model has none
+    const int i = oi < f.nc ? oi : oi - drop, j = oj < f.nc ? oj : oj - drop;
+    const bool ref = drop && (oi == f.nc || oj == f.nc);
+    double acc = 0.0;
+    if (!ref && i < Cm && j < Cm)
+      for (int k = i > j ? i : j; k < Cm; ++k) acc = __builtin_fma(M[k * Cw + i], M[k * Cw + j], acc);
+    out[e] = bad ? __builtin_nan("") : acc;
+  }
+}
+
 bool design_ok(const CholLaunch& c, const FixedDesign& f) {
   return c.d.nt >= 1 && c.d.nt <= MAXT && f.nc >= 0 && f.nc <= COVAR_W && f.L >= 1 && f.Cw >= XW && f.Cw <= FIXED_MAX &&
          f.Cw % XW == 0;
@@ -447,6 +496,17 @@ hipError_t launch_fixed_gls(const CholLaunch& c, const FixedDesign& f, const dou
   hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k, dim3((unsigned)c.B), dim3(XTH), shm, s, c, f, sbuf, bhat, z2, keep);
+  return hipGetLastError();
+}
+
+hipError_t launch_fixed_cov(const CholLaunch& c, const FixedDesign& f, const double* cf, const double* ks, double* fc,
+                            hipStream_t s) {
+  if (c.B < 1) return hipSuccess;
+  if (!design_ok(c, f) || !cf || !ks || !fc || c.B > 0x7fffffff) return hipErrorInvalidValue;
+  const size_t shm = (size_t)f.Cw * f.Cw * 8;
+  hipError_t e = hipFuncSetAttribute((const void*)k_fixed_cov, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_fixed_cov, dim3((unsigned)c.B), dim3(XTH), shm, s, c, f, cf, ks, fc);
   return hipGetLastError();
 }
 

@@ -39,7 +39,23 @@
 //   thread (animal, covariate) of the first four waves: a_a, q~_a - a_a (q~_a from the call's [n_pred][16] array of
 //     the model's branch), the two substitutions C y = a_a and C x = q~_a - a_a column by column by lane shuffles.
 // NaN also for a model whose G has no positive pivot.  k_cov_cov inverts C into G^{-1} per model.
+//
+// FIX instances (tblup_reliability_group_batch): the same two values for the wide fixed design F~ = [Q~, Z~] of up to
+// FIXED_MAX = 128 columns that k_fixed.hip fits, from what k_fixed_subst and k_fixed_gls (keep mode) left in the
+// workspace -- S slab-major [Cw / 16][ns][16], C [Cw][Cw] and the bad flag.  Phase 1, the substitution and the sum
+// for |s_a|^2 are the plain instances'; behind them, for the model's own Cm columns:
+//   T = S^T s, Cm x 16, on fp64 MFMA: wave q takes the design's column slab q over all real 4-row groups in order, so
+//     the waves' tiles are T itself and nothing is summed across waves; T is staged in the head of V;
+//   thread (animal, r of 32) holds a_a and f~_a - a_a at the columns r, r + 32, ..: a covariate's entry of f~_a from
+//     the call's array, a level's from the animal's code and the levels' shares;
+//   C y = a_a and C x = f~_a - a_a together, column by column: the owner of row k hands y_k and x_k to the animal's
+//     32 threads through a double-buffered LDS slot (one barrier a column), every thread updates its rows below k
+//     with its column of C streamed from global / L2 a step ahead; thread (animal, 0) takes |y|^2 and |x|^2 on the
+//     way, each one chain over the model's columns in order.
+// 512 bytes of static LDS (the column slot) come on top, in these instances only.  k_fixed_cov (k_fixed.hip) inverts
+// C into G^{-1} per model.
 #include <algorithm>
+#include <type_traits>
 
 #include "fwd_subst.h"
 #include "i8_tile.h"
@@ -54,11 +70,16 @@ constexpr int RKS = RKC + 16;     // its row stride (bytes): 16 animals' 16-B re
 constexpr int RPARTS = RTH / RELIAB_W;
 static_assert(RELIAB_W == FWD_W, "k_reliab's slab is the substitution's 16 right-hand sides");
 
-template <int FORM, bool VLDS, bool COV>
+// ADJ: the fixed effects the reliabilities are adjusted for, and the struct that carries them (k_snpscore's modes)
+constexpr int ADJ_NONE = 0, ADJ_COV = 1, ADJ_FIX = 2;
+template <int ADJ>
+using ReliabAdj = std::conditional_t<ADJ == ADJ_FIX, ReliabFixed, ReliabCov>;
+
+template <int FORM, bool VLDS, int ADJ>
 __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __restrict__ geno,
                                                 const int32_t* __restrict__ csA,
                                                 const int32_t* __restrict__ animals, int64_t n_pred, int64_t slab0,
-                                                int64_t nslab, double* __restrict__ vscr, ReliabCov cv,
+                                                int64_t nslab, double* __restrict__ vscr, ReliabAdj<ADJ> cv,
                                                 double* __restrict__ rel) {
   extern __shared__ __attribute__((aligned(16))) double dyn[];
   __shared__ double nrm[RTH];
@@ -182,7 +203,7 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
   double nacc = 0.0;
   fwd_subst16(Lb, Db, V, NT, J0, J1, pad, q, lc, lg, [&](int, double v) { nacc = __builtin_fma(v, v, nacc); });
   nrm[t] = nacc;
-  if constexpr (COV) {
+  if constexpr (ADJ == ADJ_COV) {
     // The covariates' share: a_a = Q~_T^T V^{-1} k_Ta from T = S^T s_a (S = L^{-1} R of the covariates, k_covar's
     // keep mode) -- k_snpscore's cross product: rows of S (global / L2) against the same rows of the solved V on
     // fp64 MFMA, wave q over the 4-row groups pad / 4 + q, + 8, .. of the real rows in order (a function of the
@@ -261,6 +282,128 @@ __global__ __launch_bounds__(RTH) void k_reliab(CholLaunch c, const int8_t* __re
       }
     }
     return;
+  } else if constexpr (ADJ == ADJ_FIX) {
+    // The wide design's share: a_a = F~_T^T V^{-1} k_Ta for the model's Cm columns from T = S^T s_a, Cm x 16, on fp64
+    // MFMA -- k_snpscore's FIX cross product: wave q takes the design's column slab q (S slab-major: the slab's
+    // [ns][16] from global / L2) over all 4-row groups of the real rows in order, so its tile is rows 16 q .. 16 q + 15
+    // of T itself and nothing is summed across waves; a row outside the real ones counts as zero.
+    const FixedDesign& f = cv.f;
+    const int Cw = f.Cw;
+    const int Cm = std::min(fixed_cols(gblup, f.nc, f.L), Cw), nb = (Cm + W - 1) / W;
+    v4d tacc = {0.0, 0.0, 0.0, 0.0};
+    if (q < nb) {
+      const double* sq = cv.sbuf + (b * (Cw / W) + q) * ns * W;
+      const int64_t g1 = (pad + nrow + 3) / 4;
+      constexpr int TKC = 8;   // groups per step, their loads issued together (the COV instances' count)
+      for (int64_t g0 = pad / 4; g0 < g1; g0 += TKC) {
+        double sa[TKC], sv[TKC];
+#pragma unroll
+        for (int e = 0; e < TKC; ++e) {
+          const int64_t g = g0 + e, r = 4 * g + lg;
+          sa[e] = g < g1 && sys_real(r, pad, nrow) ? sq[r * W + lc] : 0.0;
+          sv[e] = g < g1 ? V[r * W + lc] : 0.0;
+        }
+#pragma unroll
+        for (int e = 0; e < TKC; ++e) tacc = __builtin_amdgcn_mfma_f64_16x16x4f64(sa[e], sv[e], tacc, 0, 0, 0);
+      }
+    }
+    // the solved V is done with: its first Cw x 16 doubles (ns >= TILE >= Cw rows of 16) stage T, element
+    // [column][animal] -- no dynamic LDS beyond the plain instances'
+    static_assert(FIXED_MAX <= TILE && (RTH / 64) * W >= FIXED_MAX && FIXED_MAX % RPARTS == 0,
+                  "T fits the smallest V; a wave per column slab; the solve's rows go round the animal's threads");
+    __shared__ double ycol[2][2][W];   // the solves' current column of y and of x, double-buffered
+    __syncthreads();
+    if (q < nb) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) V[(W * q + lg + 4 * r) * W + lc] = tacc[r];
+    }
+    __syncthreads();
+    // Thread (animal ta, tp of 32) holds a_a (SNP form: T / d) and e_a = f~_a - a_a at the columns tp, tp + 32, ..: a
+    // covariate's entry of f~_a from the call's array of the model's branch, a level's [code == level] minus, under
+    // snp, the level's share (an animal without a level: the centre alone).
+    constexpr int NR = FIXED_MAX / RPARTS;
+    const bool live = va < n_pred;
+    const int code = live ? cv.ga[va] : -1;
+    double a[NR], e[NR];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const int i = tp + RPARTS * m;
+      double T = i < Cm ? V[i * W + ta] : 0.0;
+      if constexpr (FORM == FORM_PRIMAL) T = T / dd;
+      double fv = 0.0;
+      if (i < f.nc) {
+        fv = live ? cv.qa[((gblup ? 0 : n_pred) + va) * COVAR_W + i] : 0.0;
+      } else if (i < Cm) {
+        const int lev = i - f.nc + (gblup ? 0 : 1);
+        fv = (code == lev ? 1.0 : 0.0) - (gblup ? 0.0 : f.share[lev]);
+      }
+      a[m] = i < Cm ? T : 0.0;
+      e[m] = i < Cm ? fv - T : 0.0;
+    }
+    // C y = a_a and C x = e_a together, column by column (k_snpscore's FIX solve): one column of C streamed from
+    // global / L2 a step ahead serves both; the owner of row k hands y_k and x_k to the animal's threads through LDS
+    // (one barrier a column), every thread updates its rows below k; thread (ta, 0) takes y.y and x.x on the way, each
+    // one chain over the model's columns in order
+    const double* Cb = cv.cf + b * (int64_t)Cw * Cw;
+    double yy = 0.0, xx = 0.0;
+    double cn[NR];
+#pragma unroll
+    for (int m = 0; m < NR; ++m) {
+      const int i = tp + RPARTS * m;
+      cn[m] = i < Cm ? Cb[(int64_t)i * Cw] : 0.0;
+    }
+    for (int k = 0; k < Cm; ++k) {
+      double cc[NR];
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int i = tp + RPARTS * m;
+        cc[m] = cn[m];
+        cn[m] = (i > k && i < Cm) ? Cb[(int64_t)i * Cw + k + 1] : 0.0;
+      }
+      if (tp == k % RPARTS) {
+        double ak = 0.0, ek = 0.0, ckk = 1.0;
+#pragma unroll
+        for (int m = 0; m < NR; ++m)
+          if (m == k / RPARTS) ak = a[m], ek = e[m], ckk = cc[m];
+        ycol[k & 1][0][ta] = ak / ckk;
+        ycol[k & 1][1][ta] = ek / ckk;
+      }
+      __syncthreads();
+      const double yk = ycol[k & 1][0][ta], xk = ycol[k & 1][1][ta];
+#pragma unroll
+      for (int m = 0; m < NR; ++m) {
+        const int i = tp + RPARTS * m;
+        if (i > k && i < Cm) {
+          a[m] = __builtin_fma(-cc[m], yk, a[m]);
+          e[m] = __builtin_fma(-cc[m], xk, e[m]);
+        }
+      }
+      if (tp == 0) {
+        yy = __builtin_fma(yk, yk, yy);
+        xx = __builtin_fma(xk, xk, xx);
+      }
+    }
+    if (tp == 0 && live) {
+      double s2 = 0.0;
+      for (int w = 0; w < RTH / 64; ++w)
+        for (int g = 0; g < 4; ++g) s2 += nrm[64 * w + 16 * g + ta];
+      // the COV instances' end, with the model's own columns behind yy and xx
+      const double dn = den[ta];
+      double r, pv;
+      if constexpr (FORM == FORM_PRIMAL) {
+        const double kaa = dn / dd, gap = lam * s2 / dd;
+        r = ((kaa - gap) - yy) / kaa;
+        pv = gap + xx;
+      } else {
+        r = (s2 - yy) / dn;
+        pv = (dn - s2) + xx;
+      }
+      if (dd == 0.0 || dn == 0.0 || sc[SC_BAD] != 0.0 || cv.ks[b * COVAR_KS + KS_BAD] != 0.0)
+        r = pv = __builtin_nan("");
+      rel[b * n_pred + va] = r;
+      if (cv.pev) cv.pev[b * n_pred + va] = pv;
+    }
+    return;
   }
   __syncthreads();
   if (t < W && sl * W + t < n_pred) {
@@ -323,16 +466,33 @@ hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32
   if (c.B < 1 || n_pred < 1) return hipSuccess;
   if (cov && (!cov->sq || !cov->cf || !cov->ks || !cov->qa || cov->nc < 1 || cov->nc > COVAR_W))
     return hipErrorInvalidValue;
-  using Kern = decltype(&k_reliab<FORM_DUAL, false, false>);
-  const Kern plain[4] = {k_reliab<FORM_DUAL, false, false>, k_reliab<FORM_DUAL, true, false>,
-                         k_reliab<FORM_PRIMAL, false, false>, k_reliab<FORM_PRIMAL, true, false>};
-  const Kern adj[4] = {k_reliab<FORM_DUAL, false, true>, k_reliab<FORM_DUAL, true, true>,
-                       k_reliab<FORM_PRIMAL, false, true>, k_reliab<FORM_PRIMAL, true, true>};
+  using Kern = decltype(&k_reliab<FORM_DUAL, false, ADJ_NONE>);
+  const Kern plain[4] = {k_reliab<FORM_DUAL, false, ADJ_NONE>, k_reliab<FORM_DUAL, true, ADJ_NONE>,
+                         k_reliab<FORM_PRIMAL, false, ADJ_NONE>, k_reliab<FORM_PRIMAL, true, ADJ_NONE>};
+  const Kern adj[4] = {k_reliab<FORM_DUAL, false, ADJ_COV>, k_reliab<FORM_DUAL, true, ADJ_COV>,
+                       k_reliab<FORM_PRIMAL, false, ADJ_COV>, k_reliab<FORM_PRIMAL, true, ADJ_COV>};
   const ReliabCov cv = cov ? *cov : ReliabCov{};
   const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
     hipLaunchKernelGGL(k, grid, dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn, vscr, cv, rel);
   };
   return launch_slabs(cov ? adj : plain, c, p, vscr, (n_pred + RELIAB_W - 1) / RELIAB_W, launch);
+}
+
+hipError_t launch_reliab_fixed(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
+                               int64_t n_pred, const SlabPlan& p, double* vscr, const ReliabFixed& fx, double* rel,
+                               hipStream_t s) {
+  if (c.B < 1 || n_pred < 1) return hipSuccess;
+  const FixedDesign& f = fx.f;
+  if (!fx.sbuf || !fx.cf || !fx.ks || !fx.qa || !fx.ga || !f.share || f.nc < 0 || f.nc > COVAR_W || f.L < 1 ||
+      f.Cw < RELIAB_W || f.Cw > FIXED_MAX || f.Cw % RELIAB_W != 0)
+    return hipErrorInvalidValue;
+  using Kern = decltype(&k_reliab<FORM_DUAL, false, ADJ_FIX>);
+  const Kern kern[4] = {k_reliab<FORM_DUAL, false, ADJ_FIX>, k_reliab<FORM_DUAL, true, ADJ_FIX>,
+                        k_reliab<FORM_PRIMAL, false, ADJ_FIX>, k_reliab<FORM_PRIMAL, true, ADJ_FIX>};
+  const auto launch = [&](Kern k, dim3 grid, size_t shm, int64_t s0, int64_t sn) {
+    hipLaunchKernelGGL(k, grid, dim3(RTH), shm, s, c, geno_sm, csA, animals, n_pred, s0, sn, vscr, fx, rel);
+  };
+  return launch_slabs(kern, c, p, vscr, (n_pred + RELIAB_W - 1) / RELIAB_W, launch);
 }
 
 hipError_t launch_cov_cov(const double* cf, const double* ks, int64_t B, int n_cov, double* cc, hipStream_t s) {

@@ -510,6 +510,23 @@ struct ScoreFixed {
 hipError_t launch_snpscore_fixed(const CholLaunch& c, const int32_t* csA, const int32_t* cand, int64_t n_cand,
                                  const SlabPlan& p, double* vscr, const ScoreFixed& fx, double* score, double* info,
                                  double* q, hipStream_t s);
+// launch_reliab for a model with the wide design (k_reliab.hip's FIX instances): rel and pev as its covariate form
+// has them with F~ in place of Q~, from sbuf (launch_fixed_subst's) and launch_fixed_gls's keep buffers of the same
+// chunk; f as those two launches had it (only share, nc, L and Cw are read).  qa [2][n_pred][16]: ReliabCov's;
+// ga [n_pred]: the listed animals' level codes (-1: no level, every level entry of the design row is then its
+// centre alone).  launch_fixed_cov: fc [B][nc + L][nc + L] = G^-1 = C^-T C^-1 from the kept factor, covariates then
+// levels; the reference level's row and column of an snp model are zeros; NaN throughout for a flagged model.
+struct ReliabFixed {
+  const double *sbuf, *cf, *ks, *qa;
+  const int32_t* ga;
+  FixedDesign f;
+  double* pev;
+};
+hipError_t launch_reliab_fixed(const CholLaunch& c, const int8_t* geno_sm, const int32_t* csA, const int32_t* animals,
+                               int64_t n_pred, const SlabPlan& p, double* vscr, const ReliabFixed& fx, double* rel,
+                               hipStream_t s);
+hipError_t launch_fixed_cov(const CholLaunch& c, const FixedDesign& f, const double* cf, const double* ks, double* fc,
+                            hipStream_t s);
 
 // ---- launcher (k_loglik.hip): profile (restricted) log-likelihood of every model of a chunk ----
 // loglik[b * nt + t] and sigma2[b * nt + t] (the profiled sigma2_g) from the pivots on Dinv's diagonals,

@@ -183,11 +183,13 @@ class GpuBlupEngine:
         (L,), and y* = PanelModel.adjust(y, covariates, groups).  A validation animal whose label no train animal
         has is a ValueError that names the label; elsewhere such an animal is simply not used.  The h2 of this
         model is estimate_h2_group()'s; snp_scores_group() tests SNPs against it.  Not combined with
-        reliability_of."""
+        reliability_of: reliability_group(groups=, return_models=True) gives the reliabilities under this model and
+        these models from one pass."""
         self._settle()
         if groups is not None:
             if reliability_of is not None:
-                raise ValueError("reliability_of is not supported together with groups")
+                raise ValueError("reliability_of is not supported together with groups: "
+                                 "reliability_group(return_models=True) gives both from one pass")
             return self._fit_group(genomes, train, valid, h2, branch, covariates, groups, return_ebv)
         if covariates is not None:
             if reliability_of is not None:
@@ -266,15 +268,15 @@ class GpuBlupEngine:
         return (models, ebv) if return_ebv else models
 
     _GROUP_FORMS = {"snp_scores()": "snp_scores_group()", "log_likelihood_cov()": "log_likelihood_group()",
-                    "estimate_h2_cov()": "estimate_h2_group()"}
+                    "estimate_h2_cov()": "estimate_h2_group()", "reliability_cov()": "reliability_group()"}
 
     @classmethod
     def _no_groups(cls, groups, what):
         if groups is not None:
             own = cls._GROUP_FORMS.get(what)
             raise ValueError(f"{what} does not take groups: " + (f"the class factor's form is {own}" if own else
-                             "the class factor is known to fit(groups=), snp_scores_group(), log_likelihood_group() "
-                             "and estimate_h2_group() only"))
+                             "the class factor is known to fit(groups=), snp_scores_group(), log_likelihood_group(), "
+                             "estimate_h2_group() and reliability_group() only"))
 
     def _groups(self, groups, train, valid):
         """(levels, codes) of a `groups` argument: the sorted distinct labels of the train rows and every
@@ -396,6 +398,57 @@ class GpuBlupEngine:
             idx, offsets = concat_genomes(genomes)
             entry(self.split_id(train, valid), _ptr(idx), _ptr(offsets), None, None, None, None, None, None)
         return CovReliability(rel, pev, cc, models)
+
+    def reliability_group(self, genomes, train, valid, h2, animals, groups, covariates=None, branch="auto",
+                          return_pev=False, return_fixed_cov=False, return_models=False):
+        """reliability() under the model with a class fixed effect that fit(groups=) fits (a method of its own, as
+        snp_scores_group and log_likelihood_group are: reliability_cov(groups=) keeps raising).  groups and the
+        optional covariates are fit()'s: (n_animals,) integer or string labels of one factor, an (n_animals, c) matrix
+        Q.  Returns a tblup_amd.model.GroupReliability from tblup_reliability_group_batch (include/tblup_gpu.h has the
+        definitions): `reliability` (B, n_pred) with the level effects (and the covariates') estimated, not known --
+        never above reliability_cov's on Q alone; with return_pev
+        `pev_total` (B, n_pred), the error variance of a predicted record of the animal in its own level in units of
+        sigma2_g; with return_fixed_cov `fixed_cov` (B, c + L, c + L) = (F~' V^-1 F~)^-1, covariates then levels, whose
+        cov_stderr(sigma2_g) / group_stderr(sigma2_g) give the standard errors of cov_effects / group_effects
+        (sigma2_g from log_likelihood_group(return_sigma2=True)); with return_models `models`, bit-identical to
+        fit(groups=)'s, from the same pass.  A listed animal whose label no train animal has keeps its reliability
+        and gets a NaN pev_total (PanelModel.predict's rule); on a validation row such a label stays a ValueError.
+        A design that is collinear over the train rows gives NaN for the model, K_aa = 0 NaN for the animal."""
+        self._settle()
+        an = _as_int64(animals)
+        if an.ndim != 1:
+            raise ValueError("animals must be a 1-D list of row ids")
+        want_pev, want_fc, want_models = bool(return_pev), bool(return_fixed_cov), bool(return_models)
+        from .model import GroupReliability
+        levels, codes, q, _ = self._group_design(genomes, train, valid, branch, covariates, groups)
+        B, nt, nc, L, m = len(genomes), self.n_traits, 0 if q is None else q.shape[1], len(levels), len(an)
+        rel = np.empty((B, m), dtype=np.float64)
+        pev = np.empty((B, m), dtype=np.float64) if want_pev else None
+        fc = np.empty((B, nc + L, nc + L), dtype=np.float64) if want_fc else None
+        head = (_ptr(q) if nc else None, nc, _ptr(codes), L, _ptr(an) if m else None, m)
+        tail = (_ptr(rel), _ptr(pev) if want_pev else None, _ptr(fc) if want_fc else None)
+
+        def entry(sid, idx, offsets, *model):
+            _native.check("tblup_reliability_group_batch", self._lib.tblup_reliability_group_batch(
+                self._ctx, sid, *head, idx, offsets, B, float(h2), _native.BRANCH[branch], *model, *tail))
+        models = None
+        if want_models:
+            cov_eff = np.empty((B, nt, nc), dtype=np.float64)
+            cov_cen = np.empty((B, nc), dtype=np.float64)
+            grp_eff = np.empty((B, nt, L), dtype=np.float64)
+            grp_cen = np.empty((B, L), dtype=np.float64)
+
+            def call(sid, idx, offsets, fit, *model):
+                entry(sid, idx, offsets, fit, _ptr(cov_eff) if nc else None, _ptr(cov_cen) if nc else None,
+                      _ptr(grp_eff), _ptr(grp_cen), *model)
+            extra = dict(group_levels=np.broadcast_to(levels, (B, L)), group_effects=grp_eff, group_center=grp_cen)
+            if nc:
+                extra.update(cov_effects=cov_eff, cov_center=cov_cen)
+            models = self._fit_models(genomes, train, valid, h2, branch, call, **extra)
+        elif B:
+            idx, offsets = concat_genomes(genomes)
+            entry(self.split_id(train, valid), _ptr(idx), _ptr(offsets), *([None] * 8))
+        return GroupReliability(rel, levels, nc, pev, fc, models)
 
     def snp_scores(self, genomes, train, valid, h2, snps=None, branch="auto", covariates=None, groups=None):
         """Mixed-model score statistics of the panel's SNPs `snps` (column ids: any order, repeats

@@ -440,6 +440,14 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability_cov(genomes, train, valid, self.h2, animals, covariates, **kw)
 
+    def reliability_group(self, population, animals, groups, final=True, train=None, valid=None, **kw):
+        """The tblup_amd.model.GroupReliability of `animals` under every individual's model with the class factor that
+        fit_models(groups=) fits: GpuBlupEngine.reliability_group (covariates / return_pev / return_fixed_cov /
+        return_models pass through) with fit_models' split and genome conventions.  groups: an (animals,) array of
+        labels, one per animal of the evaluator's data.  No RNG, no collective."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.reliability_group(genomes, train, valid, self.h2, animals, groups, **kw)
+
     def snp_scores(self, population, snps=None, final=True, train=None, valid=None, covariates=None, groups=None):
         """Mixed-model score statistics (tblup_amd.model.SnpScores) of the SNPs `snps` (column ids of the
         evaluator's data; None: every column) against every individual's model: GpuBlupEngine.snp_scores

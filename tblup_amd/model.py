@@ -303,3 +303,72 @@ class CovReliability:
         diag = np.einsum("bii->bi", self.cov_cov)
         with np.errstate(invalid="ignore"):
             return np.sqrt(s2[:, :, None] * diag[:, None, :])
+
+
+class GroupReliability:
+    """Uncertainty under the model with a class fixed effect (GpuBlupEngine.reliability_group(groups=),
+    tblup_reliability_group_batch; include/tblup_gpu.h has the definitions).  For B models, n_pred listed animals,
+    c covariates and L levels:
+
+        reliability  (B, n_pred)         1 - PEV(g^_a - g_a) / (sigma2_g K_aa) with the covariates' and the levels'
+                                         effects estimated
+        pev_total    (B, n_pred)         error variance of a predicted record of the animal in its own level, in
+                                         units of sigma2_g; NaN for an animal whose label is not a fitted level (None
+                                         unless return_pev)
+        fixed_cov    (B, c + L, c + L)   (F~' V^-1 F~)^-1, covariates then levels: Var of [cov_effects[t],
+                                         group_effects[t]] = sigma2_g[t] * fixed_cov; under snp the reference level's
+                                         row and column are zero (None unless return_fixed_cov)
+        models       B PanelModels, fit(groups=)'s bit for bit (None unless return_models)
+        group_levels (L,)                the fitted levels, np.unique of the train rows' labels
+        n_cov        c
+
+    No phenotype enters the first three: with several traits they are one value per (model, animal)."""
+
+    __slots__ = ("reliability", "pev_total", "fixed_cov", "models", "group_levels", "n_cov")
+
+    def __init__(self, reliability, group_levels, n_cov=0, pev_total=None, fixed_cov=None, models=None):
+        self.reliability = np.asarray(reliability, dtype=np.float64)
+        if self.reliability.ndim != 2:
+            raise ValueError("reliability must have shape (models, n_pred)")
+        B = self.reliability.shape[0]
+        self.group_levels = np.asarray(group_levels)
+        if self.group_levels.ndim != 1 or self.group_levels.size < 1:
+            raise ValueError("group_levels must be a non-empty 1-D array")
+        self.n_cov = int(n_cov)
+        if self.n_cov < 0:
+            raise ValueError("n_cov must not be negative")
+        C = self.n_cov + self.group_levels.size
+        self.pev_total = None if pev_total is None else np.asarray(pev_total, dtype=np.float64)
+        if self.pev_total is not None and self.pev_total.shape != self.reliability.shape:
+            raise ValueError("pev_total must have reliability's shape %s" % (self.reliability.shape,))
+        self.fixed_cov = None if fixed_cov is None else np.asarray(fixed_cov, dtype=np.float64)
+        if self.fixed_cov is not None and self.fixed_cov.shape != (B, C, C):
+            raise ValueError("fixed_cov must have shape (models, n_cov + levels, n_cov + levels) = %s"
+                             % ((B, C, C),))
+        self.models = None if models is None else list(models)
+        if self.models is not None and len(self.models) != B:
+            raise ValueError("models must hold one model per row of reliability")
+
+    def _stderr(self, sigma2_g, lo, hi):
+        if self.fixed_cov is None:
+            raise ValueError("fixed_cov was not asked for (return_fixed_cov=True)")
+        B = self.fixed_cov.shape[0]
+        s2 = np.asarray(sigma2_g, dtype=np.float64)
+        if s2.ndim == 1:
+            s2 = s2[:, None]
+        if s2.ndim != 2 or s2.shape[0] != B:
+            raise ValueError("sigma2_g must have shape (models,) or (models, n_traits), got %s" % (s2.shape,))
+        diag = np.einsum("bii->bi", self.fixed_cov)[:, lo:hi]
+        with np.errstate(invalid="ignore"):
+            return np.sqrt(s2[:, :, None] * diag[:, None, :])
+
+    def cov_stderr(self, sigma2_g):
+        """sqrt(sigma2_g * diag fixed_cov) over the covariates: the standard errors of cov_effects, (B, nt, c).
+        sigma2_g: (B,) for one trait or (B, nt), as log_likelihood_group(return_sigma2=True) gives it at one h2.
+        Host numpy."""
+        return self._stderr(sigma2_g, 0, self.n_cov)
+
+    def group_stderr(self, sigma2_g):
+        """The same over the levels: the standard errors of group_effects, (B, nt, L) -- 0 at the reference level
+        under snp, whose effect is 0 by construction (the others are then errors of contrasts with it)."""
+        return self._stderr(sigma2_g, self.n_cov, self.n_cov + self.group_levels.size)

@@ -47,10 +47,16 @@ numbers go to PERFLOG.md.  One JSON line per part:
   loglik_group  config 2 again: tblup_loglik_group_batch at 64 levels and at 112 levels + 16 covariates beside
            tblup_loglik_cov_batch (16 covariates) at the same 8 grid points and fit(groups=) at both designs, alternated;
            one estimate_h2_group with the defaults (25 + 3 x 9 passes) at 64 levels
+  reliab_group  config 2 again: reliability_group() at 64 levels (63 columns under snp) and at 112 levels + 16 covariates
+           (127 columns) (tblup_reliability_group_batch) beside reliability(), reliability_cov(16 covariates) and
+           fit(groups=) at both designs for all 2,000 animals under the 256 models, alternated in one process; beside
+           each ratio the derived flop share of the adjustment over the plain substitution, 2 C_m / ns + 2 C_m^2 / ns^2
+           (the cross product and the two solves); k_reliab's plain, 16-column and wide launches and k_fixed_cov come
+           from a --stats run of this part
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov,score_group,loglik_group] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov,score_group,loglik_group,reliab_group] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -450,6 +456,54 @@ def reliab_cov_vs_reliab(eng, genomes, T, V, n, ns, reps, n_cov=16):
                     "alone: --stats"}
 
 
+def reliab_group_vs_reliab(eng, genomes, T, V, n, ns, reps):
+    """reliability_group() at 64 levels and at 112 levels + 16 covariates against reliability(),
+    reliability_cov(covariates=16 columns), fit(groups=) at both designs and evaluate(), for all n animals, alternated."""
+    herd = np.arange(n)
+    q = bench_cov(n)
+    g64, g112 = bench_groups(n, T)
+    want = dict(return_pev=True, return_fixed_cov=True)
+    ts = {"evaluate_ms": [], "reliability_ms": [], "reliability_cov16_ms": [], "reliability_group64_ms": [],
+          "reliability_group112_cov16_ms": [], "fit_group64_ms": [], "fit_group112_cov16_ms": []}
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        plain = eng.reliability(genomes, T, V, 0.4, herd)
+        t.append(time.perf_counter())
+        rc = eng.reliability_cov(genomes, T, V, 0.4, herd, covariates=q, return_pev=True, return_cov_cov=True)
+        t.append(time.perf_counter())
+        r64 = eng.reliability_group(genomes, T, V, 0.4, herd, g64, **want)
+        t.append(time.perf_counter())
+        r128 = eng.reliability_group(genomes, T, V, 0.4, herd, g112, covariates=q, **want)
+        t.append(time.perf_counter())
+        eng.fit(genomes, T, V, 0.4, groups=g64)
+        t.append(time.perf_counter())
+        eng.fit(genomes, T, V, 0.4, covariates=q, groups=g112)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for i, key in enumerate(ts):
+                ts[key].append(t[i + 1] - t[i])
+    out = {k: med_ms(v) for k, v in ts.items()}
+    out.update({k + "_all": [round(x * 1e3, 3) for x in v] for k, v in ts.items() if k != "evaluate_ms"})
+    share = lambda c: round(2.0 * c / ns + 2.0 * c * c / (ns * ns), 4)
+    names = ("reliability_cov16", "reliability_group64", "reliability_group112_cov16")
+    out.update({"animals": n, "columns": {"cov16": 16, "group64": 63, "group112_cov16": 127},
+                "over_reliability": {k: round(out[k + "_ms"] / out["reliability_ms"], 4) for k in names},
+                "derived_flop_share": {"cov16": share(16), "group64": share(63), "group112_cov16": share(127)},
+                "slab_launch_workgroups": len(genomes) * ((n + 15) // 16),
+                "finite": bool(all(np.all(np.isfinite(getattr(x, f))) for x in (r64, r128)
+                                   for f in ("reliability", "pev_total", "fixed_cov"))),
+                "never_above_cov": bool(np.all(r128.reliability <= rc.reliability + 1e-9)),
+                "median_reliability_drop": {"cov16": float(np.median(plain - rc.reliability)),
+                                            "group64": float(np.median(plain - r64.reliability)),
+                                            "group112_cov16": float(np.median(plain - r128.reliability))},
+                "note": "each call is the whole evaluation plus its kernels and the D2H copy of its outputs; a group "
+                        "call adds one k_fixed_subst, one k_fixed_gls (keep mode, no z*) and one k_fixed_cov launch per "
+                        "chunk; the kernels alone: --stats"})
+    return out
+
+
 def loglik_cov_vs_loglik(eng, genomes, T, V, n, reps, grid_n=8, n_cov=16):
     """tblup_loglik_cov_batch against tblup_loglik_batch at grid_n grid points (the C entries, alternated)."""
     from tblup_amd.engine import concat_genomes
@@ -542,12 +596,14 @@ def stats_share(path):
         name = r["Name"]
         # the covariate-adjusted k_reliab instances and k_covar's keep mode (third template argument) apart
         # ... k_fixed_gls's keep mode (second) and k_snpscore's 16-column and wide instances (third: 1, 2) too
-        for key, alias, last in (("k_reliab", "k_reliab_cov", "true"), ("k_covar", "k_covar_keep", "true"),
+        # (k_reliab's third argument: true in traces from before its wide instances, then 1 and 2 as k_snpscore's)
+        for key, alias, last in (("k_reliab", "k_reliab_cov", "true"), ("k_reliab", "k_reliab_cov", "1"),
+                                 ("k_reliab", "k_reliab_fix", "2"), ("k_covar", "k_covar_keep", "true"),
                                  ("k_fixed_gls", "k_fixed_gls_keep", "true"), ("k_snpscore", "k_snpscore_cov", "1"),
                                  ("k_snpscore", "k_snpscore_fix", "2")):
             if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith("," + last):
                 name = name.replace(key + "<", alias + "<")
-        for key in ("k_reliab_cov", "k_covar_keep", "k_cov_cov", "k_fixed_gls_keep", "k_snpscore_cov", "k_snpscore_fix", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_reliab_cov", "k_reliab_fix", "k_fixed_cov", "k_covar_keep", "k_cov_cov", "k_fixed_gls_keep", "k_snpscore_cov", "k_snpscore_fix", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -648,6 +704,12 @@ def main():
         with GpuBlupEngine(geno, pheno) as eng:
             print(json.dumps({"part": "reliab_cov", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **reliab_cov_vs_reliab(eng, genomes, T, V, n, 1024, args.reps)}))
+    if "reliab_group" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            print(json.dumps({"part": "reliab_group", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **reliab_group_vs_reliab(eng, genomes, T, V, n, 1024, args.reps)}), flush=True)
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
