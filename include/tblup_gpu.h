@@ -178,6 +178,41 @@ int tblup_reliability_batch(tblup_ctx* ctx, int split_id, const int64_t* animals
                             double* intercept, double* center, double* effects, double* reliability);
 
 /*
+ * Leave-one-out cross-validation of each of `batch` fitted models: every training animal t of the split (in
+ * the split's `train` order) predicted by the model fitted without it, in closed form from the factor that one
+ * evaluation leaves behind -- the k -> n_T limit of k-fold cross-validation at the cost of one pass.  Notation is
+ * tblup_reliability_batch's; c = 0 and mu = 0 under gblup, c = 1 / n_T and mu = mean(y_T) under snp:
+ *   SNP form     h_tt = c + w_t^T (W_T^T W_T + lambda d I)^{-1} w_t,  e_t = y_t - mu - w_t . beta,
+ *                e_loo,t = e_t / (1 - h_tt)
+ *   kernel form  V = K_TT + lambda I, alpha = V^{-1} (y_T - mu):
+ *                e_loo,t = lambda alpha_t / (lambda (V^{-1})_tt - c),  h_tt = 1 + c - lambda (V^{-1})_tt
+ *   y^_loo,t = y_t - e_loo,t
+ * -- equal by the Woodbury identity; the library evaluates whichever form the batch's systems were factored in.
+ * gblup branch: y^_loo,t is the reference's gblup prediction of animal t from a model trained on T \ {t} (K the
+ * GRM over all n animals, as the reference centres it).  snp branch: ridge regression with the fitted model's own
+ * penalty lambda d kept -- d and the centre come from the full training set, the intercept and the centring are
+ * refitted on T \ {t}.  This is not the reference pipeline re-run with t removed: that re-run would also change
+ * p and d.
+ *   fitness      : out, batch: |pearson(y^_loo, y_T)| over the n_T animals, the mean over traits for several
+ *                  traits (tblup_eval_batch's convention and NaN rules)
+ *   loo_pred     : out, batch x n_traits x n_train
+ *   leverage     : optional out (may be NULL), batch x n_train: h_tt, one number per (model, animal) whatever
+ *                  the number of traits
+ *   press        : optional out (may be NULL), batch x n_traits: sum_t e_loo,t^2
+ *   eval_fitness : optional out (may be NULL), batch: the pass's own validation fitness, bit-identical to
+ *                  tblup_eval_batch's
+ * batch == 0 returns 0 and writes nothing; a context without a panel gives TBLUP_ERR_STATE; idx / offsets / h2 /
+ * branch, the index rules (TBLUP_ERR_INDEX) and the chunking are tblup_eval_batch's.  d = 0 (a monomorphic
+ * panel) gives NaN, not an error.  The error of the closed form grows as 1 / (1 - h_tt): near h2 = 1 in the
+ * kernel form, where 1 - h_tt approaches 0, digits are lost in proportion.  LOO under fixed-effect covariates or
+ * a class factor is not built.  An animal's values depend neither on the batch nor on the chunking
+ * (TBLUP_WORKSPACE_MB), and the same call gives the same bits twice.  Host pointers, synchronous.
+ */
+int tblup_loo_batch(tblup_ctx* ctx, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch,
+                    double h2, int branch, double* fitness, double* loo_pred, double* leverage, double* press,
+                    double* eval_fitness);
+
+/*
  * Profile (restricted) log-likelihood of h2 for each of `batch` models, at `n_h2` values each: the
  * evaluation's pipeline once per row of `h2`, plus one reduction over the factor it leaves behind.
  * The model is the reference's own, the one tblup_reliability_batch documents: beta ~ N(0, sigma2_g / d I),

@@ -52,6 +52,8 @@ SIGNATURES = {
                                          _c.c_double, _c.c_int, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP, _DP]),
     "tblup_reliability_batch": (_c.c_int, [_P, _c.c_int, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _c.c_double,
                                            _c.c_int, _DP, _DP, _DP, _DP, _DP]),
+    "tblup_loo_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _c.c_double, _c.c_int, _DP, _DP, _DP, _DP,
+                                   _DP]),
     "tblup_loglik_batch": (_c.c_int, [_P, _c.c_int, _I64P, _I64P, _c.c_int64, _DP, _c.c_int64, _c.c_int, _DP, _DP,
                                       _DP]),
     "tblup_snp_score_batch": (_c.c_int, [_P, _c.c_int, _I64P, _c.c_int64, _I64P, _I64P, _c.c_int64, _c.c_double,

@@ -3,6 +3,7 @@
 // the entry's buffers (a *Bufs struct below; the chunker measures the same carve), runs the pipeline and then:
 //   tblup_fit_batch          k_effects
 //   tblup_reliability_batch  k_reliab's launches, k_effects when the model is wanted too
+//   tblup_loo_batch          k_effects for the solution alone, k_loo's launches, k_loo_fitness
 //   tblup_snp_score_batch    k_snpscore's launches
 //   tblup_loglik_batch       the pipeline once per h2 row, k_loglik behind each
 //   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
@@ -76,6 +77,22 @@ struct ReliabBufs {   // tblup_reliability_batch
     const SlabPlan p = plan_slabs(hb, B, n_rel, hb.c->reliab_lds);
     return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<int32_t>((size_t)n_rel),
             cv.take<double>((size_t)B * n_rel), carve_slices(cv, p)};
+  }
+};
+
+struct LooBufs {   // tblup_loo_batch
+  SlabPlan plan;        // an n_T-item list; the knob is k_reliab's, TBLUP_RELIAB_LDS
+  int32_t* tr;          // the train animals' rows of the panel [n_T]
+  double* alpha;        // the solution k_effects leaves [B][nt][ns]
+  double *pred, *lev;   // y^_loo [B][nt][n_T]; leverages [B][n_T]
+  double *rfit, *press; // |r| and PRESS per (model, trait) [B][nt]
+  double* vscr;         // the slices of one launch's slabs
+  static LooBufs carve(Carve& cv, const HostBatch& hb, int64_t B) {
+    const EvalDims& d = hb.d;
+    const SlabPlan p = plan_slabs(hb, B, d.nT, hb.c->reliab_lds);
+    const size_t Bt = (size_t)B * d.nt;
+    return {p, cv.take<int32_t>((size_t)d.nT), cv.take<double>(Bt * hb.sd.ns), cv.take<double>(Bt * d.nT),
+            cv.take<double>((size_t)B * d.nT), cv.take<double>(Bt), cv.take<double>(Bt), carve_slices(cv, p)};
   }
 };
 
@@ -920,6 +937,52 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
   });
   if (!rc && model) fill_intercepts(hb, intercept);
   return rc;
+}
+
+int tblup_loo_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2,
+                    int branch, double* fitness, double* loo_pred, double* leverage, double* press,
+                    double* eval_fitness) {
+  clear_error();
+  if (int rc = check_ctx(c)) return rc;
+  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (batch > 0 && !loo_pred) return fail(TBLUP_ERR_ARG, "null loo_pred");
+  HostBatch hb;
+  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, fitness != nullptr)) return rc;
+  if (!hb.sp) return 0;
+  const EvalDims& d = hb.d;
+  const int nt = d.nt;
+  const int64_t nT = d.nT;
+  std::vector<int32_t> t32((size_t)nT);
+  for (int64_t i = 0; i < nT; ++i) t32[i] = (int32_t)hb.sp->train[i];
+  std::vector<double> rfit((size_t)batch * nt), own_press(press ? 0 : (size_t)batch * nt);
+  if (!press) press = own_press.data();
+  eval_fitness = hb.fitness_or_own(eval_fitness);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LooBufs::carve(cv, hb, B); };
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const LooBufs lb = carve(cv, B, ck.sum_k);
+    HIPCHK(hipMemcpyAsync(lb.tr, t32.data(), (size_t)nT * 4, hipMemcpyHostToDevice, s));
+    return factor_pass(hb, ck, cv, rq, eval_fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      // neither solve path keeps the solution: k_effects' back substitution does, with nothing else asked of it
+      HIPCHK(launch_effects(cl, (const int32_t*)c->colsum_all.p, nullptr, nullptr, 0, s, lb.alpha));
+      HIPCHK(launch_loo(cl, (const int8_t*)c->geno_sm.p, lb.tr, lb.alpha, lb.plan, lb.vscr, lb.pred, lb.lev, s));
+      HIPCHK(launch_loo_fitness(cl, lb.pred, lb.rfit, lb.press, s));
+      HIPCHK(hipMemcpyAsync(loo_pred + b0 * nt * nT, lb.pred, (size_t)B * nt * nT * 8, hipMemcpyDeviceToHost, s));
+      if (leverage) HIPCHK(hipMemcpyAsync(leverage + b0 * nT, lb.lev, (size_t)B * nT * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(rfit.data() + b0 * nt, lb.rfit, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(press + b0 * nt, lb.press, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+  if (rc) return rc;
+  // the evaluation's convention: the mean of the traits' |r|, added in trait order
+  for (int64_t b = 0; b < batch; ++b) {
+    double fsum = 0.0;
+    for (int t = 0; t < nt; ++t) fsum += rfit[b * nt + t];
+    fitness[b] = nt == 1 ? fsum : fsum / (double)nt;
+  }
+  return 0;
 }
 
 int tblup_reliability_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* animals,

@@ -756,7 +756,7 @@ hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitne
 template <int NTR>
 __global__ __launch_bounds__(NTH) void k_effects(CholLaunch c, const int32_t* __restrict__ csA,
                                                  double* __restrict__ center, double* __restrict__ effects,
-                                                 int64_t plane) {
+                                                 int64_t plane, double* __restrict__ alpha_out) {
   extern __shared__ double dyn[];  // alpha[nt][ns]
   __shared__ double vsh[MAXT][TPAD];
   const int64_t nT = c.d.nT, ns = c.sd.ns;
@@ -798,6 +798,10 @@ __global__ __launch_bounds__(NTH) void k_effects(CholLaunch c, const int32_t* __
     __syncthreads();
   }
 
+  // the solution itself, for a launch that reads it (k_loo); without center nothing else is wanted
+  if (alpha_out != nullptr)
+    for (int64_t i = t; i < nt * ns; i += NTH) alpha_out[b * nt * ns + i] = alpha[i];
+  if (center == nullptr) return;
   const int64_t kk = (int64_t)sc[SC_K], o0 = c.off[b];
   const bool gblup = (int)sc[SC_MODE] == 1;
   const int32_t* cs = gblup ? csA : c.ft.csT[fo];
@@ -843,7 +847,7 @@ __global__ __launch_bounds__(NTH) void k_effects(CholLaunch c, const int32_t* __
 }
 
 hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
-                          hipStream_t s) {
+                          hipStream_t s, double* alpha) {
   const size_t shm = (size_t)c.d.nt * (size_t)c.sd.ns * sizeof(double);
   if (shm > 150 * 1024) return hipErrorInvalidValue;   // (k_solve's own LDS bound is tighter)
   auto launch = [&](const void* fn, auto kernel) -> hipError_t {
@@ -851,7 +855,7 @@ hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* cente
       hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm);
       if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(kernel, dim3((unsigned)c.B), dim3(NTH), shm, s, c, csA, center, effects, plane);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c.B), dim3(NTH), shm, s, c, csA, center, effects, plane, alpha);
     return hipGetLastError();
   };
   switch (c.d.nt) {

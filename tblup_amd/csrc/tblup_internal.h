@@ -366,8 +366,10 @@ hipError_t launch_solve(const CholLaunch& c, const SolveChain* ch, double* fitne
 // rows -- csA over all n animals for gblup, the split's counts for snp -- divided once by their
 // number) and effects[t * plane + off[b] + j], trait-major planes.  SNP form: the solved beta without
 // its padding rows; kernel form: W_T^T alpha / d over the split's 2-bit packed rows.
+// alpha (may be null): also the solution itself, [B][nt][ns] in z's layout (SNP form: beta at rows pad .. pad + k - 1;
+// kernel form: alpha_t = (V^-1 (y_T - mu))_t at the train rows); with center null only alpha is written.
 hipError_t launch_effects(const CholLaunch& c, const int32_t* csA, double* center, double* effects, int64_t plane,
-                          hipStream_t s);
+                          hipStream_t s, double* alpha = nullptr);
 
 // ---- the slab kernels behind a chunk's factor: k_reliab, k_snpscore, k_covar (fwd_subst.h) ----
 // Each walks a list (animals, SNPs, covariates) in slabs of 16 right-hand sides, one workgroup per (model,
@@ -412,6 +414,20 @@ hipError_t launch_reliab(const CholLaunch& c, const int8_t* geno_sm, const int32
                          int64_t n_pred, const SlabPlan& p, double* vscr, const ReliabCov* cov, double* rel,
                          hipStream_t s);
 hipError_t launch_cov_cov(const double* cf, const double* ks, int64_t B, int n_cov, double* cc, hipStream_t s);
+
+// ---- launchers (k_loo.hip): leave-one-out cross-validation of a chunk's models from its factor ----
+// For training animal ti (position in the split's `train` order; train [n_T] its rows of geno_sm) under model b of the
+// chunk whose pipeline left L, Dinv, u, scal in c and whose solution launch_effects left in alpha [B][nt][ns]:
+// lev[b * n_T + ti] = h_tt and pred[(b * nt + t) * n_T + ti] = y_t - e_loo,t, the prediction of the animal by the
+// model fitted without it (the snp branch keeps the penalty lambda d and refits the intercept and the centring).
+// One workgroup per (model, slab of LOO_W training animals) through fwd_subst.h; p / vscr: as launch_reliab, the
+// plan of an n_T-item list.  The same bits either way, whatever the batch and the chunking.  NaN for a model with
+// d = 0 or a flagged index.  launch_loo_fitness: rfit[b * nt + t] = |pearson(pred, y_T)| (pearson_dev.h) and
+// press[b * nt + t] = sum_t e_loo,t^2 over the n_T values in order, one workgroup per (model, trait).
+constexpr int LOO_W = 16;
+hipError_t launch_loo(const CholLaunch& c, const int8_t* geno_sm, const int32_t* train, const double* alpha,
+                      const SlabPlan& p, double* vscr, double* pred, double* lev, hipStream_t s);
+hipError_t launch_loo_fitness(const CholLaunch& c, const double* pred, double* rfit, double* press, hipStream_t s);
 
 // ---- launcher (k_score.hip): mixed-model score statistics of listed SNPs from a chunk's factor ----
 // score[(b * nt + t) * n_cand + v] = w_j^T V^-1 r_t, info[b * n_cand + v] = w_j^T V^-1 w_j for column

@@ -355,6 +355,40 @@ class GpuBlupEngine:
                 None, None, None, _ptr(rel)))
         return rel
 
+    def loo(self, genomes, train, valid, h2, branch="auto", return_leverage=False, covariates=None, groups=None):
+        """Leave-one-out cross-validation of the model each selected-index set fits on (train, valid): every
+        training animal predicted by the model fitted without it, in closed form from the factor one evaluation
+        leaves behind (tblup_loo_batch; include/tblup_gpu.h has the definitions) -- the k -> n_T limit of IntraGCV
+        at the cost of one pass.  Returns a tblup_amd.model.LooResult: `fitness` (B,) = |pearson(pred, y_T)| (the
+        mean over traits), `pred` (B, n_T) or (B, t, n_T) in `train` order, `press`, `eval_fitness` (evaluate()'s
+        value bit for bit) and, with return_leverage, `leverage` (B, n_T), the h_tt that mark influential records.
+        gblup branch: pred is the reference's gblup prediction of animal t from a model trained on T without t.
+        snp branch: ridge regression with the fitted model's own penalty lambda d kept -- d and the centre come from
+        the full training set, the intercept and the centring are refitted without t.  That is not the reference
+        pipeline re-run with t removed, which would also change p and d.  A degenerate panel gives NaN; an
+        animal's values do not depend on the batch.  The closed form loses digits as 1 / (1 - h_tt), so towards
+        h2 = 1.  LOO under fixed effects (covariates=, groups=) is not built: ValueError."""
+        if covariates is not None or groups is not None:
+            raise ValueError("LOO under fixed effects (covariates= / groups=) is not built: loo() cross-validates the "
+                             "plain model only")
+        from .model import LooResult
+        self._settle()
+        T = _as_int64(train)
+        sid = self.split_id(T, valid)
+        idx, offsets = concat_genomes(genomes)
+        B, nt, nT = len(genomes), self.n_traits, len(T)
+        fit, efit = np.empty(B, dtype=np.float64), np.empty(B, dtype=np.float64)
+        pred = np.empty((B, nt, nT), dtype=np.float64)
+        press = np.empty((B, nt), dtype=np.float64)
+        lev = np.empty((B, nT), dtype=np.float64) if return_leverage else None
+        if B:
+            _native.check("tblup_loo_batch", self._lib.tblup_loo_batch(
+                self._ctx, sid, _ptr(idx), _ptr(offsets), B, float(h2), _native.BRANCH[branch], _ptr(fit), _ptr(pred),
+                _ptr(lev) if return_leverage else None, _ptr(press), _ptr(efit)))
+        if nt == 1:
+            pred, press = pred[:, 0, :], press[:, 0]
+        return LooResult(fit, pred, press, lev, efit, T)
+
     def reliability_cov(self, genomes, train, valid, h2, animals, covariates, branch="auto", return_pev=False,
                         return_cov_cov=False, return_models=False, groups=None):
         """reliability() under the model with fixed-effect covariates that fit(covariates=) fits (a method of

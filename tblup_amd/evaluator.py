@@ -432,6 +432,14 @@ class BlupParallelEvaluator(ParallelEvaluator):
         genomes, train, valid = self._model_setup(population, final, train, valid)
         return self.engine.reliability(genomes, train, valid, self.h2, animals)
 
+    def loo(self, population, final=True, train=None, valid=None, **kw):
+        """The tblup_amd.model.LooResult of every individual's model: each training animal predicted by the model
+        fitted without it (GpuBlupEngine.loo; branch / return_leverage pass through) with fit_models' split and
+        genome conventions.  It ranks nothing: the DE loop's fitness stays evaluate()'s.  No RNG, no collective:
+        under torch.distributed every rank computes what it is given."""
+        genomes, train, valid = self._model_setup(population, final, train, valid)
+        return self.engine.loo(genomes, train, valid, self.h2, **kw)
+
     def reliability_cov(self, population, animals, covariates, final=True, train=None, valid=None, **kw):
         """The tblup_amd.model.CovReliability of `animals` under every individual's model with the fixed-effect
         covariates that fit_models(covariates=) fits: GpuBlupEngine.reliability_cov (return_pev / return_cov_cov /

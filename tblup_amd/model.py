@@ -372,3 +372,52 @@ class GroupReliability:
         """The same over the levels: the standard errors of group_effects, (B, nt, L) -- 0 at the reference level
         under snp, whose effect is 0 by construction (the others are then errors of contrasts with it)."""
         return self._stderr(sigma2_g, self.n_cov, self.n_cov + self.group_levels.size)
+
+
+class LooResult:
+    """Leave-one-out cross-validation of fitted models (GpuBlupEngine.loo, tblup_loo_batch; include/tblup_gpu.h has
+    the definitions).  For B models, n_T training animals in `train` order and t traits:
+
+        fitness      (B,)                   |pearson(pred, y_T)|, the mean over traits for several traits
+        pred         (B, n_T) / (B, t, n_T) every training animal predicted by the model fitted without it
+        press        (B,) / (B, t)          sum over the animals of (y_T - pred)^2
+        leverage     (B, n_T)               h_tt, the diagonal of the smoother (None unless return_leverage); no
+                                            phenotype enters: one value per (model, animal) for any number of traits
+        eval_fitness (B,)                   the same pass's validation fitness, evaluate()'s bit for bit
+        train        (n_T,)                 the animals' row ids, the order of pred's and leverage's last axis"""
+
+    __slots__ = ("fitness", "pred", "press", "leverage", "eval_fitness", "train")
+
+    def __init__(self, fitness, pred, press, leverage, eval_fitness, train):
+        self.fitness = np.asarray(fitness, dtype=np.float64)
+        self.pred = np.asarray(pred, dtype=np.float64)
+        self.train = np.asarray(train, dtype=np.int64)
+        if self.fitness.ndim != 1 or self.train.ndim != 1:
+            raise ValueError("fitness must have shape (models,) and train (n_train,)")
+        B, nT = self.fitness.shape[0], self.train.shape[0]
+        if self.pred.ndim not in (2, 3) or self.pred.shape[0] != B or self.pred.shape[-1] != nT:
+            raise ValueError("pred must have shape (models, n_train) or (models, n_traits, n_train)")
+        self.press = np.asarray(press, dtype=np.float64)
+        if self.press.shape != self.pred.shape[:-1]:
+            raise ValueError("press must have shape %s" % (self.pred.shape[:-1],))
+        self.leverage = None if leverage is None else np.asarray(leverage, dtype=np.float64)
+        if self.leverage is not None and self.leverage.shape != (B, nT):
+            raise ValueError("leverage must have shape (models, n_train)")
+        self.eval_fitness = np.asarray(eval_fitness, dtype=np.float64)
+        if self.eval_fitness.shape != (B,):
+            raise ValueError("eval_fitness must have shape (models,)")
+
+    def residuals(self, y):
+        """y_T - pred, the leave-one-out errors, in pred's shape.  y: the phenotypes of every animal of the panel,
+        (n,) or (n, t) as the engine took them.  Host numpy."""
+        y = np.asarray(y, dtype=np.float64)
+        if y.ndim == 2 and y.shape[1] == 1:
+            y = y[:, 0]
+        yT = y[self.train]
+        if self.pred.ndim == 2:
+            if yT.ndim != 1:
+                raise ValueError("one trait was fitted: y must be (n,)")
+            return yT[None, :] - self.pred
+        if yT.ndim != 2 or yT.shape[1] != self.pred.shape[1]:
+            raise ValueError("y must be (n, %d)" % self.pred.shape[1])
+        return yT.T[None, :, :] - self.pred

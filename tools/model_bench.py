@@ -53,10 +53,15 @@ numbers go to PERFLOG.md.  One JSON line per part:
            each ratio the derived flop share of the adjustment over the plain substitution, 2 C_m / ns + 2 C_m^2 / ns^2
            (the cross product and the two solves); k_reliab's plain, 16-column and wide launches and k_fixed_cov come
            from a --stats run of this part
+  loo      config 2 again: loo() of the 256 models (1,280 training animals each) beside reliability() of the same
+           1,280 animals -- as many right-hand sides through the same substitution -- evaluate() and the 5-fold
+           IntraGCV entry (evaluate_folds on a partition of the train set), alternated in one process; and the
+           kernel-form stand-in of `dual` (768 training animals, unit-column right-hand sides); k_loo, k_loo_fitness
+           and k_reliab per launch come from a --stats run of this part
   --stats CSV   the k_effects / k_predict / k_reliab / k_snpscore / k_loglik share of a `rocprofv3 --kernel-trace --stats` run of
            `model_bench.py --only fit,predict` (a run of its own): reads its kernel_stats CSV
 
-    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov,score_group,loglik_group,reliab_group] [--reps 7]
+    python tools/model_bench.py [--only fit,predict,dual,reliability,loglik,score,covar,group,score_cov,loglik_cov,reliab_cov,score_group,loglik_group,reliab_group,loo] [--reps 7]
     rocprofv3 --kernel-trace --stats -d DIR -o trace --output-format csv -- python tools/model_bench.py --only fit,predict --reps 3
     python tools/model_bench.py --stats DIR/.../trace_kernel_stats.csv
 """
@@ -504,6 +509,52 @@ def reliab_group_vs_reliab(eng, genomes, T, V, n, ns, reps):
     return out
 
 
+def loo_vs_reliability(eng, genomes, T, V, ns, reps, folds=5):
+    """loo() against reliability() of the n_T training animals (as many right-hand sides through the same
+    substitution), evaluate() and the `folds`-fold IntraGCV entry (evaluate_folds on a partition of T), alternated
+    on one engine."""
+    T = np.asarray(T)
+    parts = np.array_split(T, folds)
+    splits = [(np.concatenate([p for j, p in enumerate(parts) if j != f]), parts[f]) for f in range(folds)]
+    ts = {"evaluate_ms": [], "reliability_nT_ms": [], "loo_ms": [], "folds_ms": []}
+    res = None
+    for r in range(reps + 2):
+        t = [time.perf_counter()]
+        fit = eng.evaluate(genomes, T, V, 0.4)
+        t.append(time.perf_counter())
+        eng.reliability(genomes, T, V, 0.4, T)
+        t.append(time.perf_counter())
+        res = eng.loo(genomes, T, V, 0.4, return_leverage=True)
+        t.append(time.perf_counter())
+        cv = eng.evaluate_folds(genomes, splits, 0.4)
+        t.append(time.perf_counter())
+        if r >= 2:
+            for i, key in enumerate(ts):
+                ts[key].append(t[i + 1] - t[i])
+    out = {k: med_ms(v) for k, v in ts.items()}
+    out.update({k + "_all": [round(x * 1e3, 3) for x in v] for k, v in ts.items()})
+    B, nT = len(genomes), len(T)
+    flop = float(B) * nT * ns * ns
+    out.update({"right_hand_sides": nT, "folds": folds,
+                "loo_extra_ms_over_evaluate": round(out["loo_ms"] - out["evaluate_ms"], 4),
+                "reliability_extra_ms_over_evaluate": round(out["reliability_nT_ms"] - out["evaluate_ms"], 4),
+                "loo_over_evaluate": round(out["loo_ms"] / out["evaluate_ms"], 4),
+                "folds_over_evaluate": round(out["folds_ms"] / out["evaluate_ms"], 4),
+                "substitution_flop": flop, "substitution_floor_ms": round(flop / (F64_MFMA_TFS * 1e12) * 1e3, 3),
+                "slab_launch_workgroups": B * ((nT + 15) // 16),
+                "eval_fitness_bit_equal": bool(np.array_equal(res.eval_fitness, fit, equal_nan=True)),
+                "finite": bool(np.all(np.isfinite(res.pred)) and np.all(np.isfinite(res.leverage))),
+                "loo_fitness_median": float(np.nanmedian(res.fitness)),
+                "folds_fitness_median": float(np.nanmedian(cv.mean(axis=0))),
+                "evaluate_fitness_median": float(np.nanmedian(fit)),
+                "leverage_max": float(np.nanmax(res.leverage)),
+                "note": "each call is the whole evaluation plus its kernels and the D2H copy of its outputs; loo adds "
+                        "k_effects (the solution alone), k_loo and k_loo_fitness; the floor is derived for the full "
+                        "substitution (flop / measured fp64 MFMA peak; the kernel form's unit columns need half of it); "
+                        "the kernels alone: --stats"})
+    return out
+
+
 def loglik_cov_vs_loglik(eng, genomes, T, V, n, reps, grid_n=8, n_cov=16):
     """tblup_loglik_cov_batch against tblup_loglik_batch at grid_n grid points (the C entries, alternated)."""
     from tblup_amd.engine import concat_genomes
@@ -603,7 +654,7 @@ def stats_share(path):
                                  ("k_snpscore", "k_snpscore_fix", "2")):
             if key + "<" in name and name.split(key + "<")[1].split(">")[0].replace(" ", "").endswith("," + last):
                 name = name.replace(key + "<", alias + "<")
-        for key in ("k_reliab_cov", "k_reliab_fix", "k_fixed_cov", "k_covar_keep", "k_cov_cov", "k_fixed_gls_keep", "k_snpscore_cov", "k_snpscore_fix", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
+        for key in ("k_loo_fitness", "k_loo", "k_reliab_cov", "k_reliab_fix", "k_fixed_cov", "k_covar_keep", "k_cov_cov", "k_fixed_gls_keep", "k_snpscore_cov", "k_snpscore_fix", "k_fixed_subst", "k_fixed_gls", "k_fixed_fitness", "k_effects", "k_predict", "k_reliab", "k_snpscore", "k_loglik", "k_covar", "k_cov_fitness", "k_solve", "k_chol_offdiag", "k_chol_diag"):
             if key + "<" in name or key + "(" in name:
                 e = out["kernels"].setdefault(key, {"calls": 0, "total_ms": 0.0})
                 e["calls"] += int(r["Calls"])
@@ -710,6 +761,18 @@ def main():
         with GpuBlupEngine(geno, pheno) as eng:
             print(json.dumps({"part": "reliab_group", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
                               **reliab_group_vs_reliab(eng, genomes, T, V, n, 1024, args.reps)}), flush=True)
+    if "loo" in parts:
+        n, P, k, pop, nT, nV = 2000, 50_000, 1000, 256, 1280, 320
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            print(json.dumps({"part": "loo", "config": "config2", "models": pop, "k": k, "form": "snp", "ns": 1024,
+                              **loo_vs_reliability(eng, genomes, T, V, 1024, args.reps)}), flush=True)
+        n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
+        geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
+        with GpuBlupEngine(geno, pheno) as eng:
+            print(json.dumps({"part": "loo", "config": "config4-shaped stand-in: %d x %d, k=%d (gblup), n_T=%d"
+                              % (n, P, k, nT), "models": pop, "k": k, "form": "kernel", "ns": 768,
+                              **loo_vs_reliability(eng, genomes, T, V, 768, args.reps)}), flush=True)
     if "dual" in parts:
         n, P, k, pop, nT, nV = 1200, 20_000, 1500, 32, 768, 192
         geno, pheno, T, V, genomes = workload(n, P, k, pop, nT, nV)
