@@ -6,20 +6,21 @@
 //   tblup_loo_batch          k_effects for the solution alone, k_loo's launches, k_loo_fitness
 //   tblup_snp_score_batch    k_snpscore's launches
 //   tblup_loglik_batch       the pipeline once per h2 row, k_loglik behind each
-//   tblup_fit_cov_batch      k_covar, a second solve, k_cov_fitness, k_effects when the model is wanted
-//   tblup_snp_score_cov_batch  k_covar in keep mode, k_snpscore's covariate-adjusted launches
-//   tblup_loglik_cov_batch     the pipeline once per h2 row, k_covar in keep mode and k_loglik behind each
-//   tblup_reliability_cov_batch  k_covar in keep mode, k_reliab's covariate-adjusted launches, k_cov_cov;
-//                                tblup_fit_cov_batch's second pass when the model or its fitness is wanted
-//   tblup_fit_group_batch      models of up to 16 columns: tblup_fit_cov_batch on the expanded design; wider ones:
-//                              k_fixed_subst, k_fixed_gls, a second solve, k_fixed_fitness, k_effects when wanted
-//   tblup_snp_score_group_batch  models of up to 16 columns: tblup_snp_score_cov_batch on the expanded design; wider
-//                              ones: k_fixed_subst, k_fixed_gls in keep mode, k_snpscore's wide-design launches
-//   tblup_loglik_group_batch   the same routes: tblup_loglik_cov_batch, or per h2 row k_fixed_subst, k_fixed_gls in
-//                              keep mode and k_loglik with the model's own column count
-//   tblup_reliability_group_batch  the same routes: tblup_reliability_cov_batch, or k_fixed_subst, k_fixed_gls in keep
-//                              mode, k_reliab's wide-design launches and k_fixed_cov; tblup_fit_group_batch's second
-//                              pass when the model or its fitness is wanted
+// and under fixed effects, with the model's GLS step in front (CovGls: k_covar, the narrow step of up to 16 columns;
+// FixedGls: k_fixed_subst and k_fixed_gls, the wide one of up to 128):
+//   tblup_fit_cov_batch / fit_fixed_wide                the step, then the second pass: a solve on the adjusted
+//                                                       phenotype, the step's fitness kernel, k_effects when wanted
+//   tblup_snp_score_cov_batch / score_fixed_wide        the step in keep mode, k_snpscore's adjusted launches
+//   tblup_loglik_cov_batch / loglik_fixed_wide          per h2 row the step in keep mode and k_loglik
+//   tblup_reliability_cov_batch / reliab_fixed_wide     the step in keep mode, k_reliab's adjusted launches, k_cov_cov /
+//                                                       k_fixed_cov; the second pass when the model or its fitness is
+//                                                       wanted
+// What the variants share is written once: the two GLS steps' buffers, uploads, launches and consumer views (CovGls,
+// FixedGls), the second pass and its host post-pass (second_pass, finish_second, post_model), the h2-grid loop
+// (h2_grid) and the argument checks (check_*).  The narrow and the wide step run different kernels on different
+// layouts, so an entry keeps one body for each.
+// tblup_*_group_batch route a batch by its models' column counts (for_each_route): the narrow ones through the
+// covariate entry on the expanded design, the wide ones through the *_fixed_wide function, results scattered back.
 // tblup_predict_batch (k_predict) runs no pipeline: its own chunks, of PredictBufs alone.
 #include <algorithm>
 #include <cmath>
@@ -106,6 +107,15 @@ struct ScoreBufs {   // tblup_snp_score_batch
     return {p, cv.take<int32_t>((size_t)n_cand), cv.take<double>(B * nt * n_cand), cv.take<double>((size_t)B * n_cand),
             cv.take<double>(B * nt), carve_slices(cv, p)};
   }
+  // the chunk's stretch of the statistics to the host (q null: not wanted)
+  int copy_out(const HostBatch& hb, const Chunk& ck, int64_t n_cand, double* score, double* info, double* q_out) const {
+    const hipStream_t s = hb.c->stream;
+    const int64_t b0 = ck.b0, B = ck.B, nt = hb.d.nt;
+    HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sco, (size_t)(B * nt * n_cand) * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(info + b0 * n_cand, inf, (size_t)(B * n_cand) * 8, hipMemcpyDeviceToHost, s));
+    if (q_out) HIPCHK(hipMemcpyAsync(q_out + b0 * nt, q, (size_t)(B * nt) * 8, hipMemcpyDeviceToHost, s));
+    return 0;
+  }
 };
 
 struct LogLikBufs {   // tblup_loglik_batch, every pass of the chunk
@@ -115,118 +125,6 @@ struct LogLikBufs {   // tblup_loglik_batch, every pass of the chunk
     return {cv.take<double>(n), cv.take<double>(n), cv.take<double>(n * hb.d.nt), cv.take<double>(n * hb.d.nt)};
   }
 };
-
-struct CovBufs {   // tblup_fit_cov_batch
-  ModelBufs m;
-  SlabPlan plan;       // one slab per model: a COVAR_W-item list; the knob is k_snpscore's, TBLUP_SCORE_LDS
-  double *qT, *qV;     // the covariates of the train and of the validation rows, both planes
-  double *b, *z2;      // their fitted effects [B][nt][n_cov]; z of the adjusted phenotype [B][nt][ns]
-  double *fit0, *ebv2, *vscr;   // the first pass's fitness (not returned); the second solve's EBVs; the slices
-  static CovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_cov, bool model) {
-    const EvalDims& d = hb.d;
-    const SlabPlan p = plan_slabs(hb, B, COVAR_W, hb.c->score_lds);
-    const size_t Bt = (size_t)B * d.nt;
-    return {ModelBufs::carve(cv, hb, sum_k, model), p, cv.take<double>((size_t)2 * COVAR_W * d.nTp),
-            cv.take<double>((size_t)2 * COVAR_W * d.nV), cv.take<double>(Bt * n_cov), cv.take<double>(Bt * hb.sd.ns),
-            cv.take<double>((size_t)B), cv.take<double>(Bt * d.nV), carve_slices(cv, p)};
-  }
-};
-
-struct FixedBufs {   // tblup_fit_group_batch, the models of more than COVAR_W columns (k_fixed.hip)
-  ModelBufs m;
-  SlabPlan plan;            // a Cw-item list; the slices of a plan without LDS are S's own slabs
-  double *qT, *qV;          // CovBufs'
-  int32_t *gT, *gV, *lst, *lpos;   // level codes of the train / validation rows; the train rows by level
-  double *share, *ff, *fr;  // FixedDesign's
-  double* S;                // [B][Cw / 16][ns][16]
-  double *b, *z2;           // the fitted effects [B][nt][Cw]; z of the adjusted phenotype [B][nt][ns]
-  double *fit0, *ebv2;      // CovBufs'
-  static FixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t L, int64_t Cw, bool model) {
-    const EvalDims& d = hb.d;
-    const size_t Bt = (size_t)B * d.nt;
-    FixedBufs f{ModelBufs::carve(cv, hb, sum_k, model), plan_slabs(hb, B, Cw, hb.c->score_lds)};
-    f.qT = cv.take<double>((size_t)2 * COVAR_W * d.nTp);
-    f.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
-    f.gT = cv.take<int32_t>((size_t)d.nTp);
-    f.gV = cv.take<int32_t>((size_t)d.nV);
-    f.lst = cv.take<int32_t>((size_t)L + 1);
-    f.lpos = cv.take<int32_t>((size_t)d.nT);
-    f.share = cv.take<double>((size_t)L);
-    f.ff = cv.take<double>((size_t)Cw * Cw);
-    f.fr = cv.take<double>((size_t)MAXT * Cw);
-    f.S = cv.take<double>((size_t)B * Cw * hb.sd.ns);
-    f.b = cv.take<double>(Bt * Cw);
-    f.z2 = cv.take<double>(Bt * hb.sd.ns);
-    f.fit0 = cv.take<double>((size_t)B);
-    f.ebv2 = cv.take<double>(Bt * d.nV);
-    return f;
-  }
-};
-
-// What k_covar keeps of a chunk's GLS step for the covariate-adjusted score statistics and likelihood
-// (CovKeep): one slab per model, planned as CovBufs plans it.  passes: the h2 rows whose effects are kept.
-struct CovKeepBufs {
-  SlabPlan plan;
-  double* qT;            // the covariates of the train rows, both planes
-  double* b;             // their fitted effects [passes][B][nt][n_cov]
-  CovKeep keep;          // keep.sq doubles as the slices of a plan without LDS
-  double* lqq;           // log|Q~_T^T Q~_T| of the two planes
-  static CovKeepBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cov, int64_t passes) {
-    const SlabPlan p = plan_slabs(hb, B, COVAR_W, hb.c->score_lds);
-    CovKeepBufs k{p, cv.take<double>((size_t)2 * COVAR_W * hb.d.nTp),
-                  cv.take<double>((size_t)passes * B * hb.d.nt * n_cov), {}, nullptr};
-    k.keep.sq = cv.take<double>((size_t)B * hb.sd.ns * COVAR_W);
-    k.keep.cf = cv.take<double>((size_t)B * COVAR_W * COVAR_W);
-    k.keep.ch = cv.take<double>((size_t)B * MAXT * COVAR_W);
-    k.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
-    k.lqq = cv.take<double>(2);
-    return k;
-  }
-  double* vscr() const { return plan.lds ? nullptr : keep.sq; }
-};
-
-struct ScoreCovBufs {   // tblup_snp_score_cov_batch
-  ScoreBufs s;
-  CovKeepBufs k;
-  static ScoreCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cand, int64_t n_cov) {
-    const ScoreBufs s = ScoreBufs::carve(cv, hb, B, n_cand);
-    return {s, CovKeepBufs::carve(cv, hb, B, n_cov, 1)};
-  }
-};
-
-struct LogLikCovBufs {   // tblup_loglik_cov_batch
-  LogLikBufs l;
-  CovKeepBufs k;
-  static LogLikCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_h2, int64_t n_cov) {
-    const LogLikBufs l = LogLikBufs::carve(cv, hb, B, n_h2);
-    return {l, CovKeepBufs::carve(cv, hb, B, n_cov, n_h2)};
-  }
-};
-
-struct ReliabCovBufs {   // tblup_reliability_cov_batch
-  ReliabBufs r;
-  CovKeepBufs k;
-  double *qa, *pev, *cc;            // the listed animals' covariates, both planes [2][n_rel][COVAR_W]; pev_total
-                                    // [B][n_rel] and cov_cov [B][n_cov][n_cov] where wanted
-  double *qV, *z2, *fit0, *ebv2;    // tblup_fit_cov_batch's second pass (CovBufs'), where wanted
-  static ReliabCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, int64_t n_cov,
-                             bool model, bool full, bool pev, bool cc) {
-    const EvalDims& d = hb.d;
-    const size_t Bt = (size_t)B * d.nt;
-    ReliabCovBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), CovKeepBufs::carve(cv, hb, B, n_cov, 1)};
-    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
-    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
-    b.cc = cc ? cv.take<double>((size_t)B * n_cov * n_cov) : nullptr;
-    if (full) {
-      b.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
-      b.z2 = cv.take<double>(Bt * hb.sd.ns);
-      b.fit0 = cv.take<double>((size_t)B);
-      b.ebv2 = cv.take<double>(Bt * d.nV);
-    }
-    return b;
-  }
-};
-
 // The argument checks every covariate entry shares (tblup_fit_cov_batch's)
 int check_cov(const tblup_ctx* c, const double* cov, int64_t n_cov) {
   if (n_cov < 1 || n_cov > COVAR_W) return fail(TBLUP_ERR_ARG, "need 1 <= n_cov <= 16");
@@ -393,44 +291,110 @@ void group_log_dets(const HostBatch& hb, const double* cov, const GroupDesign& g
   }
 }
 
-// What k_fixed_subst and k_fixed_gls in keep mode leave of a chunk's wide GLS step for the score statistics and the
-// likelihood under the class factor (FixedBufs without the second pass).  passes: the h2 rows whose effects are kept.
-struct FixedKeepBufs {
-  SlabPlan plan;            // FixedBufs'
-  double* qT;
-  int32_t *gT, *lst, *lpos;
-  double *share, *ff, *fr;
-  double* S;                // [B][Cw / 16][ns][16]
-  double* b;                // the fitted effects [passes][B][nt][Cw]
+// The second pass's device buffers, held by a GLS step carved with `second`: the covariates of the validation rows
+// (both planes), z of the adjusted phenotype [B][nt][ns], the first pass's fitness (not returned), the second
+// solve's EBVs [B][nt][nV]
+struct Second {
+  double *qV = nullptr, *z2 = nullptr, *fit0 = nullptr, *ebv2 = nullptr;
+  static Second carve(Carve& cv, const HostBatch& hb, int64_t B, bool wanted) {
+    if (!wanted) return {};
+    const size_t Bt = (size_t)B * hb.d.nt;
+    return {cv.take<double>((size_t)2 * COVAR_W * hb.d.nV), cv.take<double>(Bt * hb.sd.ns), cv.take<double>((size_t)B),
+            cv.take<double>(Bt * hb.d.nV)};
+  }
+};
+
+// The narrow GLS step of a chunk (k_covar): one slab per model, a COVAR_W-item list; the knob is k_snpscore's,
+// TBLUP_SCORE_LDS.  keep: what k_covar leaves for the adjusted score statistics, likelihood and reliabilities
+// (CovKeep) and log|Q~_T^T Q~_T|; keep.sq then doubles as the slices of a plan without LDS.  passes: the h2 rows
+// whose effects are kept.  second: the second pass's buffers.
+struct CovGls {
+  SlabPlan plan;
+  int nc;
+  double *qT, *b;       // the covariates of the train rows, both planes; their fitted effects [passes][B][nt][nc]
+  CovKeep keep;
+  double *lqq, *vscr;   // log|Q~_T^T Q~_T| of the two planes (keep); the slices
+  Second p2;
+  static CovGls carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cov, bool keep, int64_t passes,
+                      bool second) {
+    CovGls g{plan_slabs(hb, B, COVAR_W, hb.c->score_lds), (int)n_cov};
+    g.qT = cv.take<double>((size_t)2 * COVAR_W * hb.d.nTp);
+    g.b = cv.take<double>((size_t)passes * B * hb.d.nt * n_cov);
+    if (keep) {
+      g.keep.sq = cv.take<double>((size_t)B * hb.sd.ns * COVAR_W);
+      g.keep.cf = cv.take<double>((size_t)B * COVAR_W * COVAR_W);
+      g.keep.ch = cv.take<double>((size_t)B * MAXT * COVAR_W);
+      g.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
+      g.lqq = cv.take<double>(2);
+      g.vscr = g.plan.lds ? nullptr : g.keep.sq;
+    } else {
+      g.vscr = carve_slices(cv, g.plan);
+    }
+    g.p2 = Second::carve(cv, hb, B, second);
+    return g;
+  }
+  int upload(const CovPlanes& cp, hipStream_t s) const {
+    HIPCHK(hipMemcpyAsync(qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    if (p2.qV) HIPCHK(hipMemcpyAsync(p2.qV, cp.qV.data(), cp.qV.size() * 8, hipMemcpyHostToDevice, s));
+    return 0;
+  }
+  // the step on cl's factor and z: the effects into row `pass`, z* where the second pass's buffers were carved
+  int enqueue(const CholLaunch& cl, int64_t pass, hipStream_t s) const {
+    HIPCHK(launch_covar(cl, qT, nc, plan, vscr, b + pass * cl.B * cl.d.nt * nc, p2.z2, keep, s));
+    return 0;
+  }
+  // the second pass's fitness, on the launch whose z is z*
+  hipError_t fitness(const CholLaunch& cl2, double* d_fit, hipStream_t s) const {
+    return launch_cov_fitness(cl2, p2.ebv2, p2.qV, b, nc, d_fit, s);
+  }
+  ScoreCov score() const { return {keep.sq, keep.cf, keep.ch, keep.ks, qT, nc}; }
+  ReliabCov reliab(const double* qa, double* pev) const { return {keep.sq, keep.cf, keep.ks, qa, nc, pev}; }
+};
+
+// The wide GLS step of a chunk (k_fixed_subst, k_fixed_gls): a Cw-item list; S's own slabs serve as the slices of
+// a plan without LDS.  keep / passes / second: CovGls's.
+struct FixedGls {
+  SlabPlan plan;
+  int nc, L, Cw;
+  double* qT;                      // CovGls's
+  int32_t *gT, *gV, *lst, *lpos;   // level codes of the train / validation (second) rows; the train rows by level
+  double *share, *ff, *fr;         // FixedDesign's
+  double *S, *b;                   // [B][Cw / 16][ns][16]; the fitted effects [passes][B][nt][Cw]
   FixedKeep keep;
-  double* lqq;              // log|F~_T^T F~_T| of the two planes
-  static FixedKeepBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t L, int64_t Cw, int64_t passes) {
+  double* lqq;                     // log|F~_T^T F~_T| of the two planes (keep)
+  Second p2;
+  static FixedGls carve(Carve& cv, const HostBatch& hb, int64_t B, const GroupDesign& g, bool keep, int64_t passes,
+                        bool second) {
     const EvalDims& d = hb.d;
-    FixedKeepBufs f{plan_slabs(hb, B, Cw, hb.c->score_lds)};
+    const size_t L = (size_t)g.L, Cw = (size_t)g.Cw;
+    FixedGls f{plan_slabs(hb, B, g.Cw, hb.c->score_lds), g.nc, g.L, g.Cw};
     f.qT = cv.take<double>((size_t)2 * COVAR_W * d.nTp);
     f.gT = cv.take<int32_t>((size_t)d.nTp);
-    f.lst = cv.take<int32_t>((size_t)L + 1);
+    f.gV = second ? cv.take<int32_t>((size_t)d.nV) : nullptr;
+    f.lst = cv.take<int32_t>(L + 1);
     f.lpos = cv.take<int32_t>((size_t)d.nT);
-    f.share = cv.take<double>((size_t)L);
-    f.ff = cv.take<double>((size_t)Cw * Cw);
+    f.share = cv.take<double>(L);
+    f.ff = cv.take<double>(Cw * Cw);
     f.fr = cv.take<double>((size_t)MAXT * Cw);
     f.S = cv.take<double>((size_t)B * Cw * hb.sd.ns);
     f.b = cv.take<double>((size_t)passes * B * d.nt * Cw);
-    f.keep.cf = cv.take<double>((size_t)B * Cw * Cw);
-    f.keep.ch = cv.take<double>((size_t)B * MAXT * Cw);
-    f.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
-    f.lqq = cv.take<double>(2);
+    if (keep) {
+      f.keep.cf = cv.take<double>((size_t)B * Cw * Cw);
+      f.keep.ch = cv.take<double>((size_t)B * MAXT * Cw);
+      f.keep.ks = cv.take<double>((size_t)B * COVAR_KS);
+      f.lqq = cv.take<double>(2);
+    }
+    f.p2 = Second::carve(cv, hb, B, second);
     return f;
-  }
-  FixedDesign design(const GroupDesign& g) const {
-    return {qT, nullptr, gT, nullptr, lst, lpos, share, ff, fr, g.nc, g.L, g.Cw};
   }
   int upload(const GroupDesign& g, hipStream_t s) const {
     const auto up = [&](void* dst, const void* src, size_t bytes) {
-      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+      return bytes && dst ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
     };
     HIPCHK(up(qT, g.cp.qT.data(), g.cp.qT.size() * 8));
+    HIPCHK(up(p2.qV, g.cp.qV.data(), g.cp.qV.size() * 8));
     HIPCHK(up(gT, g.gT.data(), g.gT.size() * 4));
+    HIPCHK(up(gV, g.gV.data(), g.gV.size() * 4));
     HIPCHK(up(lst, g.lst.data(), g.lst.size() * 4));
     HIPCHK(up(lpos, g.lpos.data(), g.lpos.size() * 4));
     HIPCHK(up(share, g.share.data(), g.share.size() * 8));
@@ -438,75 +402,247 @@ struct FixedKeepBufs {
     HIPCHK(up(fr, g.fr.data(), g.fr.size() * 8));
     return 0;
   }
+  FixedDesign design() const { return {qT, p2.qV, gT, gV, lst, lpos, share, ff, fr, nc, L, Cw}; }
+  // CovGls::enqueue's, in two launches
+  int enqueue(const CholLaunch& cl, int64_t pass, hipStream_t s) const {
+    const FixedDesign fd = design();
+    HIPCHK(launch_fixed_subst(cl, fd, plan, S, s));
+    HIPCHK(launch_fixed_gls(cl, fd, S, b + pass * cl.B * cl.d.nt * Cw, p2.z2, keep, s));
+    return 0;
+  }
+  hipError_t fitness(const CholLaunch& cl2, double* d_fit, hipStream_t s) const {
+    return launch_fixed_fitness(cl2, design(), p2.ebv2, b, d_fit, s);
+  }
+  ScoreFixed score() const { return {S, keep.cf, keep.ch, keep.ks, design()}; }
+  ReliabFixed reliab(const double* qa, const int32_t* ga, double* pev) const {
+    return {S, keep.cf, keep.ks, qa, ga, design(), pev};
+  }
 };
 
-// The models of more than COVAR_W fixed columns of a tblup_fit_group_batch call, as a batch of their own:
-// bout [batch][nt][Cw] the fitted effects by column (zero past a model's own), everything else
-// tblup_fit_cov_batch's.  A model whose effects are NaN is NaN in intercept and center too.
-int fit_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
-                   int64_t Cw, const int64_t* idx, const int64_t* offsets, int64_t batch, double h2, int branch,
-                   double* fitness, double* ebv, double* bout, double* intercept, double* center, double* effects) {
-  const bool model = intercept != nullptr;
-  HostBatch hb;
-  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-  if (!hb.sp) return 0;
-  const EvalDims& d = hb.d;
-  const int nt = d.nt;
-  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
-  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return FixedBufs::carve(cv, hb, B, sk, L, Cw, model); };
-  // per chunk: tblup_fit_cov_batch's, with k_fixed's three kernels in place of k_covar and k_cov_fitness
-  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
-    const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const FixedBufs fb = carve(cv, B, ck.sum_k);
-    if (int rc = ws_check(c, cv)) return rc;
-    const auto up = [&](void* dst, const void* src, size_t bytes) {
-      return bytes ? hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s) : hipSuccess;
+// An entry's own buffers with its GLS step's behind them (braces: carved left to right)
+template <class Own, class Gls>
+struct WithGls {
+  Own o;
+  Gls k;
+};
+
+struct ReliabCovBufs {   // tblup_reliability_cov_batch
+  ReliabBufs r;
+  CovGls k;
+  double *qa, *pev, *cc;   // the listed animals' covariates, both planes [2][n_rel][COVAR_W]; pev_total [B][n_rel]
+                           // and cov_cov [B][n_cov][n_cov] where wanted
+  static ReliabCovBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, int64_t n_cov,
+                             bool model, bool full, bool pev, bool cc) {
+    ReliabCovBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), CovGls::carve(cv, hb, B, n_cov, true, 1, full)};
+    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
+    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
+    b.cc = cc ? cv.take<double>((size_t)B * n_cov * n_cov) : nullptr;
+    return b;
+  }
+};
+
+struct ReliabFixedBufs {   // tblup_reliability_group_batch, the models of more than COVAR_W columns
+  ReliabBufs r;
+  FixedGls k;
+  double* qa;         // ReliabCovBufs'
+  int32_t* ga;        // the listed animals' level codes [n_rel]
+  double *pev, *fc;   // pev_total [B][n_rel] and fixed_cov [B][n_cov + L][n_cov + L] where wanted
+  static ReliabFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel,
+                               const GroupDesign& g, bool model, bool full, bool pev, bool fc) {
+    const size_t Co = (size_t)(g.nc + g.L);
+    ReliabFixedBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), FixedGls::carve(cv, hb, B, g, true, 1, full)};
+    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
+    b.ga = cv.take<int32_t>((size_t)n_rel);
+    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
+    b.fc = fc ? cv.take<double>((size_t)B * Co * Co) : nullptr;
+    return b;
+  }
+};
+
+// ---- the second pass on the adjusted phenotype ----
+// What a second pass copies to the host, the chunk's stretch of each
+struct SecondOut {
+  const ModelBufs* m;          // k_effects' model into center / effects; null: not wanted
+  double *center, *effects;
+  double* b;                   // the GLS effects [batch][nt][cols] from d_b; null: not wanted
+  const double* d_b;
+  int64_t cols;
+  double *fitness, *ebv;       // ebv [batch][nt][nV]; null: not wanted
+};
+// One chunk of tblup_fit_cov_batch and of every entry that runs its second pass: the pipeline with the
+// one-workgroup solve (nothing to recover; its fitness goes to fit0 and its EBVs are not wanted), after(cl) on the
+// factor and z it leaves -- the GLS step, which writes z*, and whatever else reads the kept step -- then the solve,
+// fitness_launch(cl2, d_fit) and the model of the adjusted phenotype on z*; the copies out, and the host waits.
+int second_pass(const HostBatch& hb, const Chunk& ck, const Carve& cv, ChunkReq& rq, const Second& p2,
+                const std::function<int(const CholLaunch&)>& after,
+                const std::function<hipError_t(const CholLaunch&, double*)>& fitness_launch, const SecondOut& o) {
+  const hipStream_t s = hb.c->stream;
+  const int64_t b0 = ck.b0, B = ck.B, nt = hb.d.nt, nV = hb.d.nV;
+  double* d_fit = rq.d_fit;
+  Carve cvp = cv;
+  rq.mode = ChunkMode::NoChain;
+  rq.d_fit = p2.fit0;
+  ChunkRes res;
+  if (int rc = run_chunk(hb.c, rq, cvp, res)) return rc;
+  if (int rc = after(res.cl)) return rc;
+  CholLaunch cl2 = res.cl;
+  cl2.z = p2.z2;
+  HIPCHK(launch_solve(cl2, nullptr, p2.fit0, p2.ebv2, s));
+  HIPCHK(fitness_launch(cl2, d_fit));
+  if (o.m)
+    if (int rc = o.m->enqueue(hb, ck, cl2, o.center, o.effects)) return rc;
+  if (o.b) HIPCHK(hipMemcpyAsync(o.b + b0 * nt * o.cols, o.d_b, (size_t)(B * nt * o.cols) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(o.fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
+  if (o.ebv) HIPCHK(hipMemcpyAsync(o.ebv + b0 * nt * nV, p2.ebv2, (size_t)(B * nt * nV) * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+  return 0;
+}
+
+// The host post-pass of one model fitted under fixed effects: bt [nt][stride] its effects by column (zero past
+// its own `cols`), fit its fitness.  A model whose effects are NaN (d = 0, a flagged index, a collinear design) is
+// dead; one without a fixed column has no effect to tell by: its NaN fitness tells.  A dead model is NaN in
+// intercept [nt] and center [k] (null: not wanted).  Returns dead.
+bool post_model(const double* bt, int nt, int64_t stride, int64_t cols, double fit, double* intercept, double* center,
+                int64_t k) {
+  bool dead = cols == 0 && std::isnan(fit);
+  for (int64_t i = 0; i < nt * stride; ++i) dead = dead || std::isnan(bt[i]);
+  if (dead && intercept) std::fill(intercept, intercept + nt, std::nan(""));
+  if (dead && center) std::fill(center, center + k, std::nan(""));
+  return dead;
+}
+// ... and the centres of n of its fixed columns: the train means m under snp, 0 under gblup, NaN for a dead model
+void put_centres(double* out, const double* m, int64_t n, bool snp, bool dead) {
+  for (int64_t j = 0; j < n; ++j) out[j] = dead ? std::nan("") : (snp ? m[j] : 0.0);
+}
+// The post-pass of a second-pass entry over its batch: the intercepts, then post_model on every model's effects
+// b [batch][nt][stride] (cols: the fixed columns of a gblup / an snp model), and put_centres on ctr [batch][stride]
+// from m where the entry returns centres.  intercept and center come together (null: no model wanted).
+void finish_second(const HostBatch& hb, const double* fitness, const double* b, int64_t stride, int64_t cols_gblup,
+                   int64_t cols_snp, const double* m, double* ctr, double* intercept, double* center) {
+  const int nt = hb.d.nt;
+  if (intercept) fill_intercepts(hb, intercept);
+  for (int64_t i = 0; i < hb.batch; ++i) {
+    const int64_t k = hb.offsets[i + 1] - hb.offsets[i];
+    const bool snp = branch_of(hb.c, k, hb.branch) == 2;
+    const bool dead = post_model(b + i * nt * stride, nt, stride, snp ? cols_snp : cols_gblup, fitness[i],
+                                 intercept ? intercept + i * nt : nullptr, intercept ? center + hb.offsets[i] : nullptr, k);
+    if (ctr) put_centres(ctr + i * stride, m, stride, snp, dead);
+  }
+}
+
+// ---- the h2-grid loop of the likelihood entries ----
+// One chunk of tblup_loglik_batch and its variants: the chunk's h2 columns up front, the n_h2 passes back to back
+// (each the pipeline at its row of per-system h2, then per_pass(cl, g) on the factor it leaves, without waiting for
+// the solve: the entry's launches up to k_loglik into row g of lb.ll / lb.s2), the results of every pass copied out
+// behind the last.  redo: a chained solve of some pass gave up a wait -- the factors of all but the last pass are
+// gone, so every pass runs again whole with the one-workgroup k_solve (the same bits), for the fitnesses only.
+// fitness behind either pass, the rest behind pass 0 only; a null output is skipped.  extra [n_h2][batch][row]
+// from d_extra: the entry's per-pass effects (xrow doubles a model).
+int h2_grid(const HostBatch& hb, const Chunk& ck, const Carve& cv, ChunkReq& rq, const LogLikBufs& lb, const double* h2,
+            int64_t n_h2, const std::function<int(const CholLaunch& cl, int64_t g)>& per_pass, double* fitness,
+            double* loglik, double* sigma2_g, double* extra = nullptr, const double* d_extra = nullptr,
+            int64_t xrow = 0) {
+  tblup_ctx* c = hb.c;
+  const hipStream_t s = c->stream;
+  const int64_t b0 = ck.b0, B = ck.B, nt = hb.d.nt;
+  const size_t row = (size_t)B * 8, pitch = (size_t)hb.batch * 8;
+  HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
+  return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
+    for (int64_t g = 0; g < n_h2; ++g) {
+      Carve cvp = cv;
+      rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
+      rq.d_h2 = lb.h2 + g * B;
+      rq.d_fit = lb.fits + g * B;
+      ChunkRes res;
+      if (int rc = run_chunk(c, rq, cvp, res)) return rc;
+      seqs.push_back(res.chain_seq);
+      if (!redo)
+        if (int rc = per_pass(res.cl, g)) return rc;
+    }
+    // n_h2 rows of `per` doubles a model to the host
+    const auto out = [&](double* host, const double* dev, int64_t per) {
+      return host ? hipMemcpy2DAsync(host + b0 * per, pitch * per, dev, row * per, row * per, (size_t)n_h2,
+                                     hipMemcpyDeviceToHost, s)
+                  : hipSuccess;
     };
-    HIPCHK(up(fb.qT, g.cp.qT.data(), g.cp.qT.size() * 8));
-    HIPCHK(up(fb.qV, g.cp.qV.data(), g.cp.qV.size() * 8));
-    HIPCHK(up(fb.gT, g.gT.data(), g.gT.size() * 4));
-    HIPCHK(up(fb.gV, g.gV.data(), g.gV.size() * 4));
-    HIPCHK(up(fb.lst, g.lst.data(), g.lst.size() * 4));
-    HIPCHK(up(fb.lpos, g.lpos.data(), g.lpos.size() * 4));
-    HIPCHK(up(fb.share, g.share.data(), g.share.size() * 8));
-    HIPCHK(up(fb.ff, g.ff.data(), g.ff.size() * 8));
-    HIPCHK(up(fb.fr, g.fr.data(), g.fr.size() * 8));
-    const FixedDesign fd{fb.qT, fb.qV, fb.gT, fb.gV, fb.lst, fb.lpos, fb.share, fb.ff, fb.fr, g.nc, g.L, g.Cw};
-    double* d_fit = rq.d_fit;
-    Carve cvp = cv;
-    rq.mode = ChunkMode::NoChain;
-    rq.d_fit = fb.fit0;
-    ChunkRes res;
-    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-    HIPCHK(launch_fixed_subst(res.cl, fd, fb.plan, fb.S, s));
-    HIPCHK(launch_fixed_gls(res.cl, fd, fb.S, fb.b, fb.z2, FixedKeep{}, s));
-    CholLaunch cl2 = res.cl;
-    cl2.z = fb.z2;
-    HIPCHK(launch_solve(cl2, nullptr, fb.fit0, fb.ebv2, s));
-    HIPCHK(launch_fixed_fitness(cl2, fd, fb.ebv2, fb.b, d_fit, s));
-    if (model)
-      if (int rc = fb.m.enqueue(hb, ck, cl2, center, effects)) return rc;
-    HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, fb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    if (ebv) HIPCHK(hipMemcpyAsync(ebv + b0 * nt * d.nV, fb.ebv2, (size_t)B * nt * d.nV * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
+    HIPCHK(out(fitness, lb.fits, 1));
+    if (redo) return 0;
+    HIPCHK(out(loglik, lb.ll, nt));
+    HIPCHK(out(sigma2_g, lb.s2, nt));
+    HIPCHK(out(extra, d_extra, xrow));
     return 0;
   });
-  if (rc || !model) return rc;
-  fill_intercepts(hb, intercept);
-  const double nan = std::nan("");
-  for (int64_t b = 0; b < batch; ++b) {
-    // (a model without a fixed column has no effect to tell by: its fitness tells)
-    const bool gblup = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1;
-    bool dead = fixed_cols(gblup, (int)n_cov, (int)L) == 0 && std::isnan(fitness[b]);
-    for (int64_t i = 0; i < nt * Cw; ++i) dead = dead || std::isnan(bout[b * nt * Cw + i]);
-    if (!dead) continue;
-    for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
-    for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
+}
+
+// ---- argument checks the entries share ----
+int check_panel(const tblup_ctx* c) {
+  return c->n == 0 ? fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)") : 0;
+}
+// the animal list as rows of the panel: a32
+int check_animals(const tblup_ctx* c, const int64_t* animals, int64_t n_pred, std::vector<int32_t>& a32) {
+  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
+  a32.resize((size_t)n_pred);
+  for (int64_t i = 0; i < n_pred; ++i) {
+    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
+    a32[i] = (int32_t)animals[i];
   }
   return 0;
 }
+// the SNP list as columns of the panel: s32
+int check_snps(const tblup_ctx* c, const int64_t* snps, int64_t n_cand, std::vector<int32_t>& s32) {
+  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
+  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  s32.resize((size_t)n_cand);
+  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
+  return 0;
+}
+// lambda = 0 makes the snp branch's V singular: (0, 1) for the entries that need V's inverse, not
+// tblup_eval_batch's (0, 1]
+int check_h2_open(double h2) {
+  return !(h2 > 0.0) || !(h2 < 1.0) ? fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)") : 0;
+}
+int check_h2_grid(const double* h2, int64_t n) {
+  for (int64_t i = 0; i < n; ++i)
+    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  return 0;
+}
+// k_effects' outputs are given together or not at all; model: given
+int check_model_out(const double* intercept, const double* center, const double* effects, bool& model) {
+  model = intercept || center || effects;
+  if (model && !(intercept && center && effects))
+    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  return 0;
+}
+// The fixed-design rows of the listed animals: qa [2][n_pred][COVAR_W] their covariates, plane 0 as given, plane 1
+// centred by the train means m, zero past n_cov; with group, ga [n_pred] their level codes
+std::vector<double> gather_listed(const double* cov, int64_t n_cov, const std::vector<double>& m, const int64_t* animals,
+                                  int64_t n_pred, const int64_t* group = nullptr, std::vector<int32_t>* ga = nullptr) {
+  std::vector<double> qa((size_t)2 * n_pred * COVAR_W, 0.0);
+  if (ga) ga->resize((size_t)n_pred);
+  for (int64_t v = 0; v < n_pred; ++v) {
+    for (int64_t j = 0; j < n_cov; ++j) {
+      const double q = cov[animals[v] * n_cov + j];
+      qa[v * COVAR_W + j] = q;
+      qa[(n_pred + v) * COVAR_W + j] = q - m[j];
+    }
+    if (ga) (*ga)[v] = (int32_t)group[animals[v]];
+  }
+  return qa;
+}
+
+// ---- the class factor: its checks, and the routes of a batch ----
+// The arguments a class-factor entry passes on to its routes
+struct GroupCall {
+  tblup_ctx* c;
+  int split_id;
+  const double* cov;
+  int64_t nc;
+  const int64_t* group;
+  int64_t L;
+  const int64_t *idx, *offsets;
+  int64_t batch;
+  int branch;
+};
 
 // The argument checks the class-factor entries share (tblup_fit_group_batch's), before the split is known
 int check_group(const tblup_ctx* c, const double* cov, int64_t n_cov, const int64_t* group, int64_t n_levels) {
@@ -523,8 +659,7 @@ int check_group(const tblup_ctx* c, const double* cov, int64_t n_cov, const int6
 // ... and against the split: every animal of the split has a level and every level a train row.  share [L] the
 // levels' shares n_l / n_T, cov_m the covariates' means over the train rows (gather_cov's).
 struct GroupSplit {
-  std::vector<long double> share;
-  std::vector<double> cov_m;
+  std::vector<double> share, cov_m;
   int64_t nT = 0, nV = 0;
   int nt = 1;
 };
@@ -532,18 +667,19 @@ int check_group_split(const HostBatch& hb, const double* cov, int64_t nc, const 
                       GroupSplit& gs) {
   const int64_t nT = gs.nT = hb.d.nT, nV = gs.nV = hb.d.nV;
   gs.nt = hb.d.nt;
-  gs.share.assign((size_t)std::min<int64_t>(L, hb.c->n + 1), 0.0L);
+  std::vector<long double> count((size_t)std::min<int64_t>(L, hb.c->n + 1), 0.0L);
   gs.cov_m.resize((size_t)nc);
   if (L > nT) return fail(TBLUP_ERR_ARG, "a level has no train row");
   for (int64_t i = 0; i < nT; ++i) {
     if (group[hb.sp->train[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
-    gs.share[group[hb.sp->train[i]]] += 1.0L;
+    count[group[hb.sp->train[i]]] += 1.0L;
   }
   for (int64_t i = 0; i < nV; ++i)
     if (group[hb.sp->valid[i]] < 0) return fail(TBLUP_ERR_ARG, "an animal of the split has no level (-1)");
+  gs.share.resize((size_t)L);
   for (int64_t l = 0; l < L; ++l) {
-    if (gs.share[l] == 0.0L) return fail(TBLUP_ERR_ARG, "a level has no train row");
-    gs.share[l] /= (long double)nT;
+    if (count[l] == 0.0L) return fail(TBLUP_ERR_ARG, "a level has no train row");
+    gs.share[l] = (double)(count[l] / (long double)nT);
   }
   for (int64_t j = 0; j < nc; ++j) {
     long double acc = 0.0L;
@@ -580,32 +716,6 @@ int route_group(const tblup_ctx* c, const int64_t* offsets, int64_t batch, int b
   return 0;
 }
 
-// a route's models as a batch of their own
-struct SubBatch {
-  std::vector<int64_t> so, si;
-};
-SubBatch sub_batch(const int64_t* idx, const int64_t* offsets, const std::vector<int64_t>& mb) {
-  SubBatch sb{std::vector<int64_t>(mb.size() + 1, 0), {}};
-  for (size_t i = 0; i < mb.size(); ++i) {
-    sb.si.insert(sb.si.end(), idx + offsets[mb[i]], idx + offsets[mb[i] + 1]);
-    sb.so[i + 1] = (int64_t)sb.si.size();
-  }
-  return sb;
-}
-
-// the expanded design [Q, Z] of route 0 / 1, [n][Cw]: every level under gblup, all but the lowest under snp; an
-// animal without a level (outside the split) has a row of zeros in Z
-std::vector<double> expand_design(const tblup_ctx* c, const double* cov, int64_t nc, const int64_t* group, int64_t Cw,
-                                  int route) {
-  std::vector<double> x((size_t)c->n * Cw, 0.0);
-  for (int64_t a = 0; a < c->n; ++a) {
-    for (int64_t j = 0; j < nc; ++j) x[a * Cw + j] = cov[a * nc + j];
-    const int64_t z = group[a] - route;
-    if (z >= 0) x[a * Cw + nc + z] = 1.0;
-  }
-  return x;
-}
-
 // a model's fitted effects by column (bt [nt][Cw]) as the covariates' and the levels' (0 at the reference level
 // under snp, br = 1); either output may be null
 void put_effects(const double* bt, int nt, int64_t Cw, int64_t nc, int64_t L, int br, bool dead, double* cov_eff,
@@ -619,187 +729,239 @@ void put_effects(const double* bt, int nt, int64_t Cw, int64_t nc, int64_t L, in
   }
 }
 
-struct ScoreFixedBufs {   // tblup_snp_score_group_batch, the models of more than COVAR_W columns
-  ScoreBufs s;
-  FixedKeepBufs k;
-  static ScoreFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_cand, int64_t L, int64_t Cw) {
-    const ScoreBufs s = ScoreBufs::carve(cv, hb, B, n_cand);
-    return {s, FixedKeepBufs::carve(cv, hb, B, L, Cw, 1)};
+// One non-empty route of a call, as for_each_route hands it to the entry: its models as a batch of their own
+// (idx / off, Bs of them, route model i is batch model mb[i] of branch br[i]: 0 gblup, 1 snp), the column stride
+// Cw of its effects and, routes 0 / 1, the expanded design x [n][Cw] = [Q, Z]: every level under gblup, all but
+// the lowest under snp; an animal without a level (outside the split) has a row of zeros in Z.
+struct Route {
+  const GroupCall& a;
+  const GroupSplit& gs;
+  int id;
+  const std::vector<int64_t>& mb;
+  int64_t Bs, Cw;
+  int64_t cols[2];   // the fixed columns of a gblup / an snp model
+  std::vector<int64_t> so, si;
+  std::vector<int> br;
+  std::vector<double> x;
+  const int64_t* idx() const { return si.data(); }
+  const int64_t* off() const { return so.data(); }
+  // a row-shaped output of the route, src [n_h2][Bs][len], into the batch's dst [n_h2][batch][len] (null: not wanted)
+  void scatter(const double* src, int64_t len, double* dst, int64_t n_h2 = 1) const {
+    if (!dst) return;
+    for (int64_t g = 0; g < n_h2; ++g)
+      for (int64_t i = 0; i < Bs; ++i)
+        std::copy(src + (g * Bs + i) * len, src + (g * Bs + i + 1) * len, dst + (g * a.batch + mb[i]) * len);
   }
-};
-
-struct LogLikFixedBufs {   // tblup_loglik_group_batch, the models of more than COVAR_W columns
-  LogLikBufs l;
-  FixedKeepBufs k;
-  static LogLikFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t n_h2, int64_t L, int64_t Cw) {
-    const LogLikBufs l = LogLikBufs::carve(cv, hb, B, n_h2);
-    return {l, FixedKeepBufs::carve(cv, hb, B, L, Cw, n_h2)};
-  }
-};
-
-// The models of more than COVAR_W fixed columns of a tblup_snp_score_group_batch call, as a batch of their own:
-// tblup_snp_score_cov_batch's chunk with k_fixed_subst and k_fixed_gls (keep mode) in place of k_covar and
-// k_snpscore's FIX instances behind them.  bout [batch][nt][Cw]: fit_fixed_wide's.
-int score_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
-                     int64_t Cw, const std::vector<int32_t>& s32, const int64_t* idx, const int64_t* offsets,
-                     int64_t batch, double h2, int branch, double* fitness, double* score, double* info, double* q,
-                     double* bout) {
-  HostBatch hb;
-  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-  if (!hb.sp) return 0;
-  const int nt = hb.d.nt;
-  const int64_t n_cand = (int64_t)s32.size();
-  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
-  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreFixedBufs::carve(cv, hb, B, n_cand, L, Cw); };
-  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
-    const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const ScoreFixedBufs sb = carve(cv, B, ck.sum_k);
-    const FixedKeepBufs& kb = sb.k;
-    if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpyAsync(sb.s.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
-    if (int rc = kb.upload(g, s)) return rc;
-    const FixedDesign fd = kb.design(g);
-    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
-      HIPCHK(launch_fixed_subst(cl, fd, kb.plan, kb.S, s));
-      HIPCHK(launch_fixed_gls(cl, fd, kb.S, kb.b, nullptr, kb.keep, s));
-      const ScoreFixed sf{kb.S, kb.keep.cf, kb.keep.ch, kb.keep.ks, fd};
-      HIPCHK(launch_snpscore_fixed(cl, (const int32_t*)c->colsum_all.p, sb.s.cand, n_cand, sb.s.plan, sb.s.vscr, sf,
-                                   sb.s.sco, sb.s.inf, sb.s.q, s));
-      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.s.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.s.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.s.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, kb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
-      return 0;
-    });
-  });
-}
-
-// The same of a tblup_loglik_group_batch call: tblup_loglik_cov_batch's passes with k_fixed_subst and k_fixed_gls
-// (keep mode, no z*) between the pipeline and k_loglik.  h2 [n_h2][batch]; bout [n_h2][batch][nt][Cw].
-int loglik_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
-                      int64_t Cw, const int64_t* idx, const int64_t* offsets, int64_t batch, const double* h2,
-                      int64_t n_h2, int branch, double* fitness, double* loglik, double* sigma2_g, double* bout) {
-  HostBatch hb;
-  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
-  if (!hb.sp) return 0;
-  const int nt = hb.d.nt;
-  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
-  const int cols[2] = {fixed_cols(true, (int)n_cov, (int)L), fixed_cols(false, (int)n_cov, (int)L)};
-  // log|F~_T^T F~_T| does not depend on h2: once per call, for the planes that the batch has models of
-  bool need[2] = {false, false};
-  for (int64_t b = 0; b < batch; ++b) need[branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1] = true;
-  double lqq[2];
-  group_log_dets(hb, cov, g, need, lqq);
-  // (a plane without a model is not read; its count only has to pass the launcher's range check)
-  const int kcols[2] = {need[0] ? cols[0] : 0, need[1] ? cols[1] : 0};
-  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikFixedBufs::carve(cv, hb, B, n_h2, L, Cw); };
-  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
-    const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
-    const LogLikFixedBufs lf = carve(cv, B, ck.sum_k);
-    const LogLikBufs& lb = lf.l;
-    const FixedKeepBufs& kb = lf.k;
-    if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
-    if (int rc = kb.upload(g, s)) return rc;
-    HIPCHK(hipMemcpyAsync(kb.lqq, lqq, sizeof(lqq), hipMemcpyHostToDevice, s));
-    const FixedDesign fd = kb.design(g);
-    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
-      for (int64_t gi = 0; gi < n_h2; ++gi) {
-        Carve cvp = cv;
-        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
-        rq.d_h2 = lb.h2 + gi * B;
-        rq.d_fit = lb.fits + gi * B;
-        ChunkRes res;
-        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-        seqs.push_back(res.chain_seq);
-        if (redo) continue;
-        HIPCHK(launch_fixed_subst(res.cl, fd, kb.plan, kb.S, s));
-        HIPCHK(launch_fixed_gls(res.cl, fd, kb.S, kb.b + gi * B * nt * Cw, nullptr, kb.keep, s));
-        HIPCHK(launch_loglik_fixed(res.cl, kb.keep.ks, kb.lqq, kcols, lb.ll + gi * B * nt, lb.s2 + gi * B * nt, s));
+  // its fitted effects bo [n_h2][Bs][nt][Cw] (fit [n_h2][Bs]: the fitnesses, for post_model) as the batch's
+  // cov_effects [n_h2][batch][nt][nc] and group_effects [n_h2][batch][nt][L], and with centres (n_h2 = 1) those of
+  // the covariates [batch][nc] and of the levels [batch][L]; a null output is skipped
+  void put_fixed(const double* bo, const double* fit, double* cov_eff, double* grp_eff, int64_t n_h2 = 1,
+                 double* cov_center = nullptr, double* group_center = nullptr) const {
+    const int64_t nt = gs.nt, nc = a.nc, L = a.L;
+    for (int64_t g = 0; g < n_h2; ++g)
+      for (int64_t i = 0; i < Bs; ++i) {
+        const int64_t b = mb[i], at = g * Bs + i, to = g * a.batch + b;
+        const double* bt = bo + at * nt * Cw;
+        const bool dead = post_model(bt, (int)nt, Cw, cols[br[i]], fit[at], nullptr, nullptr, 0);
+        put_effects(bt, (int)nt, Cw, nc, L, br[i], dead, cov_eff ? cov_eff + to * nt * nc : nullptr,
+                    grp_eff ? grp_eff + to * nt * L : nullptr);
+        if (cov_center) put_centres(cov_center + b * nc, gs.cov_m.data(), nc, br[i] == 1, dead);
+        if (group_center) put_centres(group_center + b * L, gs.share.data(), L, br[i] == 1, dead);
       }
-      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
-        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
-      };
-      HIPCHK(out(fitness + b0, pitch, lb.fits, row));
-      if (redo) return 0;
-      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
-      HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
-      HIPCHK(out(bout + b0 * nt * Cw, pitch * nt * Cw, kb.b, rowt * Cw));
-      return 0;
-    });
-  });
-}
-
-struct ReliabFixedBufs {   // tblup_reliability_group_batch, the models of more than COVAR_W columns
-  ReliabBufs r;
-  FixedKeepBufs k;
-  double* qa;                       // ReliabCovBufs'
-  int32_t* ga;                      // the listed animals' level codes [n_rel]
-  double *pev, *fc;                 // pev_total [B][n_rel] and fixed_cov [B][n_cov + L][n_cov + L] where wanted
-  double* qV;                       // tblup_fit_group_batch's second pass (FixedBufs'), where wanted
-  int32_t* gV;
-  double *z2, *fit0, *ebv2;
-  static ReliabFixedBufs carve(Carve& cv, const HostBatch& hb, int64_t B, int64_t sum_k, int64_t n_rel, int64_t n_cov,
-                               int64_t L, int64_t Cw, bool model, bool full, bool pev, bool fc) {
-    const EvalDims& d = hb.d;
-    const size_t Bt = (size_t)B * d.nt, Co = (size_t)(n_cov + L);
-    ReliabFixedBufs b{ReliabBufs::carve(cv, hb, B, sum_k, n_rel, model), FixedKeepBufs::carve(cv, hb, B, L, Cw, 1)};
-    b.qa = cv.take<double>((size_t)2 * n_rel * COVAR_W);
-    b.ga = cv.take<int32_t>((size_t)n_rel);
-    b.pev = pev ? cv.take<double>((size_t)B * n_rel) : nullptr;
-    b.fc = fc ? cv.take<double>((size_t)B * Co * Co) : nullptr;
-    if (full) {
-      b.qV = cv.take<double>((size_t)2 * COVAR_W * d.nV);
-      b.gV = cv.take<int32_t>((size_t)d.nV);
-      b.z2 = cv.take<double>(Bt * hb.sd.ns);
-      b.fit0 = cv.take<double>((size_t)B);
-      b.ebv2 = cv.take<double>(Bt * d.nV);
+  }
+};
+// A route's k_effects model where wanted (null pointers else): intercept [Bs][nt], center [st], effects [nt][st]
+struct RouteModel {
+  std::vector<double> icpt, cen, eff;
+  double *ip = nullptr, *cp = nullptr, *ep = nullptr;
+  RouteModel(const Route& r, bool wanted) {
+    if (!wanted) return;
+    const int64_t st = r.so[r.Bs];
+    icpt.resize((size_t)r.Bs * r.gs.nt);
+    cen.resize((size_t)st);
+    eff.resize((size_t)r.gs.nt * st);
+    ip = icpt.data();
+    cp = cen.data();
+    ep = eff.data();
+  }
+  void scatter(const Route& r, double* intercept, double* center, double* effects) const {
+    const int64_t *offsets = r.a.offsets, st = r.so[r.Bs], total = offsets[r.a.batch];
+    r.scatter(ip, r.gs.nt, intercept);
+    for (int64_t i = 0; i < r.Bs; ++i) {
+      const int64_t b = r.mb[i], k = offsets[b + 1] - offsets[b];
+      std::copy(cp + r.so[i], cp + r.so[i] + k, center + offsets[b]);
+      for (int t = 0; t < r.gs.nt; ++t)
+        std::copy(ep + t * st + r.so[i], ep + t * st + r.so[i] + k, effects + t * total + offsets[b]);
     }
-    return b;
   }
 };
 
-// The models of more than COVAR_W fixed columns of a tblup_reliability_group_batch call, as a batch of their own:
-// tblup_reliability_cov_batch's chunk with k_fixed_subst and k_fixed_gls (keep mode) in place of k_covar, k_reliab's
-// FIX instances and k_fixed_cov behind them, and fit_fixed_wide's second pass when the model or its fitness is wanted
-// (full).  a32 / animals: the list; rel / pev [batch][n_pred], fc [batch][(n_cov + L)^2] (pev, fc: null when not
-// wanted); bout [batch][nt][Cw] and intercept / center / effects: fit_fixed_wide's, with model.
-int reliab_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group, int64_t L,
-                      int64_t Cw, const std::vector<int32_t>& a32, const int64_t* animals, const int64_t* idx,
-                      const int64_t* offsets, int64_t batch, double h2, int branch, bool full, double* fitness,
-                      double* rel, double* pev, double* fc, double* bout, double* intercept, double* center,
-                      double* effects) {
+// The class-factor entries' driver: the batch's checks against the split (h2: any of the call's, for the batch's
+// validation), its routes, and `body` on each non-empty one in turn.  An empty batch is no route.
+int for_each_route(const GroupCall& a, double h2, const std::function<int(const Route&)>& body) {
+  GroupSplit gs;
+  {
+    HostBatch hb;
+    if (int rc = open_host_batch(hb, a.c, a.split_id, a.idx, a.offsets, a.batch, h2, a.branch, true)) return rc;
+    if (!hb.sp) return 0;
+    if (int rc = check_group_split(hb, a.cov, a.nc, a.group, a.L, gs)) return rc;
+  }
+  GroupRoutes gr;
+  if (int rc = route_group(a.c, a.offsets, a.batch, a.branch, a.nc, a.L, gr)) return rc;
+  for (int route = 0; route < 3; ++route) {
+    const std::vector<int64_t>& mb = gr.of[route];
+    if (mb.empty()) continue;
+    Route r{a, gs, route, mb, (int64_t)mb.size(), gr.width(route), {gr.cols[0], gr.cols[1]}};
+    r.so.assign(mb.size() + 1, 0);
+    for (size_t i = 0; i < mb.size(); ++i) {
+      const int64_t lo = a.offsets[mb[i]], hi = a.offsets[mb[i] + 1];
+      r.si.insert(r.si.end(), a.idx + lo, a.idx + hi);
+      r.so[i + 1] = (int64_t)r.si.size();
+      r.br.push_back(branch_of(a.c, hi - lo, a.branch) == 1 ? 0 : 1);
+    }
+    if (route < 2) {
+      r.x.assign((size_t)a.c->n * r.Cw, 0.0);
+      for (int64_t an = 0; an < a.c->n; ++an) {
+        for (int64_t j = 0; j < a.nc; ++j) r.x[an * r.Cw + j] = a.cov[an * a.nc + j];
+        const int64_t z = a.group[an] - route;
+        if (z >= 0) r.x[an * r.Cw + a.nc + z] = 1.0;
+      }
+    }
+    if (int rc = body(r)) return rc;
+  }
+  return 0;
+}
+
+// ---- the wide route of the class-factor entries: a route's models through k_fixed ----
+// Opens the route's batch and gathers its design
+int open_wide(const Route& r, double h2, HostBatch& hb, GroupDesign& g) {
+  const GroupCall& a = r.a;
+  if (int rc = open_host_batch(hb, a.c, a.split_id, r.idx(), r.off(), r.Bs, h2, a.branch, true)) return rc;
+  g = gather_group(hb, a.cov, a.nc, a.group, a.L, r.Cw);
+  return 0;
+}
+
+// tblup_fit_group_batch's: tblup_fit_cov_batch's chunk and post-pass with FixedGls in place of CovGls.
+// bout [Bs][nt][Cw] the fitted effects by column (zero past a model's own), everything else that entry's.
+int fit_fixed_wide(const Route& r, double h2, double* fitness, double* ebv, double* bout, double* intercept,
+                   double* center, double* effects) {
   const bool model = intercept != nullptr;
   HostBatch hb;
-  if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-  if (!hb.sp) return 0;
-  fitness = hb.fitness_or_own(fitness);
-  const EvalDims& d = hb.d;
-  const int nt = d.nt;
-  const int64_t n_pred = (int64_t)a32.size(), Co = n_cov + L;
-  const GroupDesign g = gather_group(hb, cov, n_cov, group, L, Cw);
-  // f~_a of the listed animals: the covariates as tblup_reliability_cov_batch lays them out, the level codes
-  std::vector<double> h_qa((size_t)2 * n_pred * COVAR_W, 0.0);
-  std::vector<int32_t> h_ga((size_t)n_pred);
-  for (int64_t v = 0; v < n_pred; ++v) {
-    for (int64_t j = 0; j < n_cov; ++j) {
-      const double q = cov[animals[v] * n_cov + j];
-      h_qa[v * COVAR_W + j] = q;
-      h_qa[(n_pred + v) * COVAR_W + j] = q - g.cp.m[j];
-    }
-    h_ga[v] = (int32_t)group[animals[v]];
-  }
+  GroupDesign g;
+  if (int rc = open_wide(r, h2, hb, g)) return rc;
+  using Bufs = WithGls<ModelBufs, FixedGls>;
   const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
-    return ReliabFixedBufs::carve(cv, hb, B, sk, n_pred, n_cov, L, Cw, model, full, pev != nullptr, fc != nullptr);
+    return Bufs{ModelBufs::carve(cv, hb, sk, model), FixedGls::carve(cv, hb, B, g, false, 1, true)};
+  };
+  const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = hb.c->stream;
+    const Bufs fb = carve(cv, ck.B, ck.sum_k);
+    if (int rc = ws_check(hb.c, cv)) return rc;
+    if (int rc = fb.k.upload(g, s)) return rc;
+    return second_pass(
+        hb, ck, cv, rq, fb.k.p2, [&](const CholLaunch& cl) { return fb.k.enqueue(cl, 0, s); },
+        [&](const CholLaunch& cl2, double* d_fit) { return fb.k.fitness(cl2, d_fit, s); },
+        {model ? &fb.o : nullptr, center, effects, bout, fb.k.b, r.Cw, fitness, ebv});
+  });
+  if (rc || !model) return rc;
+  finish_second(hb, fitness, bout, r.Cw, r.cols[0], r.cols[1], nullptr, nullptr, intercept, center);
+  return 0;
+}
+
+// tblup_snp_score_group_batch's: tblup_snp_score_cov_batch's chunk with FixedGls in place of CovGls and
+// k_snpscore's FIX instances behind it.  bout: fit_fixed_wide's.
+int score_fixed_wide(const Route& r, const std::vector<int32_t>& s32, double h2, double* fitness, double* score,
+                     double* info, double* q, double* bout) {
+  HostBatch hb;
+  GroupDesign g;
+  if (int rc = open_wide(r, h2, hb, g)) return rc;
+  tblup_ctx* c = hb.c;
+  const int64_t nt = hb.d.nt, n_cand = (int64_t)s32.size(), Cw = r.Cw;
+  using Bufs = WithGls<ScoreBufs, FixedGls>;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) {
+    return Bufs{ScoreBufs::carve(cv, hb, B, n_cand), FixedGls::carve(cv, hb, B, g, true, 1, false)};
+  };
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = c->stream;
+    const int64_t b0 = ck.b0, B = ck.B;
+    const Bufs bufs = carve(cv, B, ck.sum_k);
+    const ScoreBufs& sb = bufs.o;
+    const FixedGls& kb = bufs.k;
+    if (int rc = ws_check(c, cv)) return rc;
+    HIPCHK(hipMemcpyAsync(sb.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(g, s)) return rc;
+    return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
+      if (int rc = kb.enqueue(cl, 0, s)) return rc;
+      HIPCHK(launch_snpscore_fixed(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, kb.score(),
+                                   sb.sco, sb.inf, sb.q, s));
+      if (int rc = sb.copy_out(hb, ck, n_cand, score, info, q)) return rc;
+      HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, kb.b, (size_t)(B * nt * Cw) * 8, hipMemcpyDeviceToHost, s));
+      return 0;
+    });
+  });
+}
+
+// tblup_loglik_group_batch's: tblup_loglik_cov_batch's passes with FixedGls in place of CovGls and k_loglik with
+// the model's own column count.  h2 [n_h2][Bs]; bout [n_h2][Bs][nt][Cw].
+int loglik_fixed_wide(const Route& r, const double* h2, int64_t n_h2, double* fitness, double* loglik,
+                      double* sigma2_g, double* bout) {
+  HostBatch hb;
+  GroupDesign g;
+  if (int rc = open_wide(r, h2[0], hb, g)) return rc;
+  const int64_t nt = hb.d.nt;
+  // log|F~_T^T F~_T| does not depend on h2: once per call, for the planes that the batch has models of
+  bool need[2] = {false, false};
+  for (int b : r.br) need[b] = true;
+  double lqq[2];
+  group_log_dets(hb, r.a.cov, g, need, lqq);
+  // (a plane without a model is not read; its count only has to pass the launcher's range check)
+  const int kcols[2] = {need[0] ? (int)r.cols[0] : 0, need[1] ? (int)r.cols[1] : 0};
+  using Bufs = WithGls<LogLikBufs, FixedGls>;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) {
+    return Bufs{LogLikBufs::carve(cv, hb, B, n_h2), FixedGls::carve(cv, hb, B, g, true, n_h2, false)};
+  };
+  return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
+    const hipStream_t s = hb.c->stream;
+    const int64_t B = ck.B;
+    const Bufs bufs = carve(cv, B, ck.sum_k);
+    const LogLikBufs& lb = bufs.o;
+    const FixedGls& kb = bufs.k;
+    if (int rc = ws_check(hb.c, cv)) return rc;
+    if (int rc = kb.upload(g, s)) return rc;
+    HIPCHK(hipMemcpyAsync(kb.lqq, lqq, sizeof(lqq), hipMemcpyHostToDevice, s));
+    const auto per_pass = [&](const CholLaunch& cl, int64_t gi) -> int {
+      if (int rc = kb.enqueue(cl, gi, s)) return rc;
+      HIPCHK(launch_loglik_fixed(cl, kb.keep.ks, kb.lqq, kcols, lb.ll + gi * B * nt, lb.s2 + gi * B * nt, s));
+      return 0;
+    };
+    return h2_grid(hb, ck, cv, rq, lb, h2, n_h2, per_pass, fitness, loglik, sigma2_g, bout, kb.b, nt * r.Cw);
+  });
+}
+
+// tblup_reliability_group_batch's: tblup_reliability_cov_batch's chunk with FixedGls in place of CovGls, k_reliab's
+// FIX instances and k_fixed_cov behind it, and fit_fixed_wide's second pass when the model or its fitness is wanted
+// (full).  a32 / animals: the list; rel / pev [Bs][n_pred], fc [Bs][(n_cov + L)^2] (pev, fc: null when not
+// wanted); bout [Bs][nt][Cw] and intercept / center / effects: fit_fixed_wide's, with model.
+int reliab_fixed_wide(const Route& r, const std::vector<int32_t>& a32, const int64_t* animals, double h2, bool full,
+                      double* fitness, double* rel, double* pev, double* fc, double* bout, double* intercept,
+                      double* center, double* effects) {
+  const bool model = intercept != nullptr;
+  HostBatch hb;
+  GroupDesign g;
+  if (int rc = open_wide(r, h2, hb, g)) return rc;
+  tblup_ctx* c = hb.c;
+  fitness = hb.fitness_or_own(fitness);
+  const int64_t n_pred = (int64_t)a32.size(), Co = r.a.nc + r.a.L;
+  std::vector<int32_t> h_ga;
+  const std::vector<double> h_qa = gather_listed(r.a.cov, r.a.nc, g.cp.m, animals, n_pred, r.a.group, &h_ga);
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
+    return ReliabFixedBufs::carve(cv, hb, B, sk, n_pred, g, model, full, pev != nullptr, fc != nullptr);
   };
   const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
     const int64_t b0 = ck.b0, B = ck.B;
     const ReliabFixedBufs rb = carve(cv, B, ck.sum_k);
-    const FixedKeepBufs& kb = rb.k;
+    const FixedGls& kb = rb.k;
     if (int rc = ws_check(c, cv)) return rc;
     if (n_pred > 0) {
       HIPCHK(hipMemcpyAsync(rb.r.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
@@ -807,62 +969,27 @@ int reliab_fixed_wide(tblup_ctx* c, int split_id, const double* cov, int64_t n_c
       HIPCHK(hipMemcpyAsync(rb.ga, h_ga.data(), h_ga.size() * 4, hipMemcpyHostToDevice, s));
     }
     if (int rc = kb.upload(g, s)) return rc;
-    FixedDesign fd = kb.design(g);
-    if (full) {
-      HIPCHK(hipMemcpyAsync(rb.qV, g.cp.qV.data(), g.cp.qV.size() * 8, hipMemcpyHostToDevice, s));
-      if (!g.gV.empty()) HIPCHK(hipMemcpyAsync(rb.gV, g.gV.data(), g.gV.size() * 4, hipMemcpyHostToDevice, s));
-      fd.qV = rb.qV;
-      fd.gV = rb.gV;
-    }
     const auto after = [&](const CholLaunch& cl) -> int {
-      HIPCHK(launch_fixed_subst(cl, fd, kb.plan, kb.S, s));
-      HIPCHK(launch_fixed_gls(cl, fd, kb.S, kb.b, rb.z2, kb.keep, s));
-      const ReliabFixed rf{kb.S, kb.keep.cf, kb.keep.ks, rb.qa, rb.ga, fd, rb.pev};
+      if (int rc = kb.enqueue(cl, 0, s)) return rc;
       HIPCHK(launch_reliab_fixed(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.r.an, n_pred,
-                                 rb.r.plan, rb.r.vscr, rf, rb.r.rel, s));
+                                 rb.r.plan, rb.r.vscr, kb.reliab(rb.qa, rb.ga, rb.pev), rb.r.rel, s));
       if (n_pred > 0) {
-        HIPCHK(hipMemcpyAsync(rel + b0 * n_pred, rb.r.rel, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
-        if (pev) HIPCHK(hipMemcpyAsync(pev + b0 * n_pred, rb.pev, (size_t)B * n_pred * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(rel + b0 * n_pred, rb.r.rel, (size_t)(B * n_pred) * 8, hipMemcpyDeviceToHost, s));
+        if (pev) HIPCHK(hipMemcpyAsync(pev + b0 * n_pred, rb.pev, (size_t)(B * n_pred) * 8, hipMemcpyDeviceToHost, s));
       }
       if (fc) {
-        HIPCHK(launch_fixed_cov(cl, fd, kb.keep.cf, kb.keep.ks, rb.fc, s));
-        HIPCHK(hipMemcpyAsync(fc + b0 * Co * Co, rb.fc, (size_t)B * Co * Co * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(launch_fixed_cov(cl, kb.design(), kb.keep.cf, kb.keep.ks, rb.fc, s));
+        HIPCHK(hipMemcpyAsync(fc + b0 * Co * Co, rb.fc, (size_t)(B * Co * Co) * 8, hipMemcpyDeviceToHost, s));
       }
       return 0;
     };
     if (!full) return factor_pass(hb, ck, cv, rq, fitness, nullptr, after);
-    // fit_fixed_wide's chunk: the pipeline with the one-workgroup solve, then the second pass on z*
-    double* d_fit = rq.d_fit;
-    Carve cvp = cv;
-    rq.mode = ChunkMode::NoChain;
-    rq.d_fit = rb.fit0;
-    ChunkRes res;
-    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-    if (int rc = after(res.cl)) return rc;
-    CholLaunch cl2 = res.cl;
-    cl2.z = rb.z2;
-    HIPCHK(launch_solve(cl2, nullptr, rb.fit0, rb.ebv2, s));
-    HIPCHK(launch_fixed_fitness(cl2, fd, rb.ebv2, kb.b, d_fit, s));
-    if (model) {
-      if (int rc = rb.r.m.enqueue(hb, ck, cl2, center, effects)) return rc;
-      HIPCHK(hipMemcpyAsync(bout + b0 * nt * Cw, kb.b, (size_t)B * nt * Cw * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
-    return 0;
+    return second_pass(
+        hb, ck, cv, rq, kb.p2, after, [&](const CholLaunch& cl2, double* d_fit) { return kb.fitness(cl2, d_fit, s); },
+        {model ? &rb.r.m : nullptr, center, effects, bout, kb.b, r.Cw, fitness, nullptr});
   });
   if (rc || !model) return rc;
-  // fit_fixed_wide's post-pass
-  fill_intercepts(hb, intercept);
-  const double nan = std::nan("");
-  for (int64_t b = 0; b < batch; ++b) {
-    const bool gblup = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1;
-    bool dead = fixed_cols(gblup, (int)n_cov, (int)L) == 0 && std::isnan(fitness[b]);
-    for (int64_t i = 0; i < nt * Cw; ++i) dead = dead || std::isnan(bout[b * nt * Cw + i]);
-    if (!dead) continue;
-    for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
-    for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
-  }
+  finish_second(hb, fitness, bout, r.Cw, r.cols[0], r.cols[1], nullptr, nullptr, intercept, center);
   return 0;
 }
 
@@ -905,17 +1032,12 @@ int tblup_reliability_batch(tblup_ctx* c, int split_id, const int64_t* animals, 
                             double* intercept, double* center, double* effects, double* reliability) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
-  const bool model = intercept || center || effects;
-  if (model && !(intercept && center && effects))
-    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
-  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
-  std::vector<int32_t> a32((size_t)n_pred);
-  for (int64_t i = 0; i < n_pred; ++i) {
-    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
-    a32[i] = (int32_t)animals[i];
-  }
+  bool model;
+  if (int rc = check_model_out(intercept, center, effects, model)) return rc;
+  std::vector<int32_t> a32;
+  if (int rc = check_animals(c, animals, n_pred, a32)) return rc;
   if (batch == 0 || n_pred == 0) return 0;
   if (!reliability) return fail(TBLUP_ERR_ARG, "null reliability");
   HostBatch hb;
@@ -944,7 +1066,7 @@ int tblup_loo_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int64_
                     double* eval_fitness) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (batch > 0 && !loo_pred) return fail(TBLUP_ERR_ARG, "null loo_pred");
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, fitness != nullptr)) return rc;
@@ -992,18 +1114,14 @@ int tblup_reliability_cov_batch(tblup_ctx* c, int split_id, const double* cov, i
                                 double* pev_total, double* cov_cov) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_cov(c, cov, n_cov)) return rc;
   if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
   const bool model = cov_effects || cov_center || intercept || center || effects;
   if (model && !(cov_effects && cov_center && intercept && center && effects))
     return fail(TBLUP_ERR_ARG, "cov_effects/cov_center/intercept/center/effects are given together or not at all");
-  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
-  std::vector<int32_t> a32((size_t)n_pred);
-  for (int64_t i = 0; i < n_pred; ++i) {
-    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
-    a32[i] = (int32_t)animals[i];
-  }
+  std::vector<int32_t> a32;
+  if (int rc = check_animals(c, animals, n_pred, a32)) return rc;
   // the second solve (the model of the adjusted phenotype and its fitness) runs only for a caller who wants it
   const bool full = model || fitness;
   if (batch == 0 || (n_pred == 0 && !full && !cov_cov)) return 0;
@@ -1011,38 +1129,28 @@ int tblup_reliability_cov_batch(tblup_ctx* c, int split_id, const double* cov, i
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
   fitness = hb.fitness_or_own(fitness);
-  const EvalDims& d = hb.d;
-  const int nt = d.nt, nc = (int)n_cov;
+  const int nc = (int)n_cov;
   const CovPlanes cp = gather_cov(hb, cov, n_cov, full);
-  // q~_a of the listed animals: plane 0 as given, plane 1 centred by the train means, zero past n_cov
-  std::vector<double> h_qa((size_t)2 * n_pred * COVAR_W, 0.0);
-  for (int64_t v = 0; v < n_pred; ++v)
-    for (int64_t j = 0; j < n_cov; ++j) {
-      const double q = cov[animals[v] * n_cov + j];
-      h_qa[v * COVAR_W + j] = q;
-      h_qa[(n_pred + v) * COVAR_W + j] = q - cp.m[j];
-    }
+  const std::vector<double> h_qa = gather_listed(cov, n_cov, cp.m, animals, n_pred);
   const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
     return ReliabCovBufs::carve(cv, hb, B, sk, n_pred, n_cov, model, full, pev_total != nullptr, cov_cov != nullptr);
   };
   // per chunk, behind the pipeline: k_covar keeps the model's GLS step, k_reliab's covariate-adjusted launches
-  // and k_cov_cov read it; a caller who wants the model or its fitness gets tblup_fit_cov_batch's own second
-  // pass (the one-workgroup solve on z*, k_cov_fitness, k_effects) behind them
+  // and k_cov_cov read it; a caller who wants the model or its fitness gets tblup_fit_cov_batch's second pass
   const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
     const int64_t b0 = ck.b0, B = ck.B;
     const ReliabCovBufs rb = carve(cv, B, ck.sum_k);
-    const CovKeepBufs& kb = rb.k;
+    const CovGls& kb = rb.k;
     if (int rc = ws_check(c, cv)) return rc;
     if (n_pred > 0) {
       HIPCHK(hipMemcpyAsync(rb.r.an, a32.data(), (size_t)n_pred * 4, hipMemcpyHostToDevice, s));
       HIPCHK(hipMemcpyAsync(rb.qa, h_qa.data(), h_qa.size() * 8, hipMemcpyHostToDevice, s));
     }
-    HIPCHK(hipMemcpyAsync(kb.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
-    if (full) HIPCHK(hipMemcpyAsync(rb.qV, cp.qV.data(), cp.qV.size() * 8, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(cp, s)) return rc;
     const auto after = [&](const CholLaunch& cl) -> int {
-      HIPCHK(launch_covar(cl, kb.qT, nc, kb.plan, kb.vscr(), kb.b, rb.z2, kb.keep, s));
-      const ReliabCov rcv{kb.keep.sq, kb.keep.cf, kb.keep.ks, rb.qa, nc, rb.pev};
+      if (int rc = kb.enqueue(cl, 0, s)) return rc;
+      const ReliabCov rcv = kb.reliab(rb.qa, rb.pev);
       HIPCHK(launch_reliab(cl, (const int8_t*)c->geno_sm.p, (const int32_t*)c->colsum_all.p, rb.r.an, n_pred,
                            rb.r.plan, rb.r.vscr, &rcv, rb.r.rel, s));
       if (n_pred > 0) {
@@ -1057,41 +1165,12 @@ int tblup_reliability_cov_batch(tblup_ctx* c, int split_id, const double* cov, i
       return 0;
     };
     if (!full) return factor_pass(hb, ck, cv, rq, fitness, nullptr, after);
-    // tblup_fit_cov_batch's chunk: the pipeline with the one-workgroup solve, then the second pass on z*
-    double* d_fit = rq.d_fit;
-    Carve cvp = cv;
-    rq.mode = ChunkMode::NoChain;
-    rq.d_fit = rb.fit0;
-    ChunkRes res;
-    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-    if (int rc = after(res.cl)) return rc;
-    CholLaunch cl2 = res.cl;
-    cl2.z = rb.z2;
-    HIPCHK(launch_solve(cl2, nullptr, rb.fit0, rb.ebv2, s));
-    HIPCHK(launch_cov_fitness(cl2, rb.ebv2, rb.qV, kb.b, nc, d_fit, s));
-    if (model) {
-      if (int rc = rb.r.m.enqueue(hb, ck, cl2, center, effects)) return rc;
-      HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, kb.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
-    }
-    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
-    return 0;
+    return second_pass(
+        hb, ck, cv, rq, kb.p2, after, [&](const CholLaunch& cl2, double* d_fit) { return kb.fitness(cl2, d_fit, s); },
+        {model ? &rb.r.m : nullptr, center, effects, cov_effects, kb.b, n_cov, fitness, nullptr});
   });
   if (rc || !model) return rc;
-  // tblup_fit_cov_batch's post-pass: intercepts, cov_center, and NaN throughout for a model whose covariate
-  // effects are NaN
-  fill_intercepts(hb, intercept);
-  const double nan = std::nan("");
-  for (int64_t b = 0; b < batch; ++b) {
-    const int mode = branch_of(c, offsets[b + 1] - offsets[b], branch);
-    bool dead = false;
-    for (int64_t i = 0; i < nt * n_cov; ++i) dead = dead || std::isnan(cov_effects[b * nt * n_cov + i]);
-    for (int64_t j = 0; j < n_cov; ++j) cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cp.m[j] : 0.0);
-    if (dead) {
-      for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
-      for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
-    }
-  }
+  finish_second(hb, fitness, cov_effects, n_cov, n_cov, n_cov, cp.m.data(), cov_center, intercept, center);
   return 0;
 }
 
@@ -1100,33 +1179,25 @@ int tblup_snp_score_batch(tblup_ctx* c, int split_id, const int64_t* snps, int64
                           double* info, double* q) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
-  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
-  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  std::vector<int32_t> s32;
+  if (int rc = check_snps(c, snps, n_cand, s32)) return rc;
   if (batch == 0 || n_cand == 0) return 0;
-  // lambda = 0 makes the snp branch's V singular: (0, 1), as tblup_loglik_batch
-  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (int rc = check_h2_open(h2)) return rc;
   if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
-  std::vector<int32_t> s32((size_t)n_cand);
-  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
   fitness = hb.fitness_or_own(fitness);
-  const int nt = hb.d.nt;
   const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreBufs::carve(cv, hb, B, n_cand); };
   return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const ScoreBufs sb = carve(cv, B, ck.sum_k);
+    const ScoreBufs sb = carve(cv, ck.B, ck.sum_k);
     HIPCHK(hipMemcpyAsync(sb.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
     return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
       HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, nullptr, sb.sco,
                              sb.inf, sb.q, s));
-      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
-      if (q) HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
-      return 0;
+      return sb.copy_out(hb, ck, n_cand, score, info, q);
     });
   });
 }
@@ -1136,50 +1207,24 @@ int tblup_loglik_batch(tblup_ctx* c, int split_id, const int64_t* idx, const int
                        double* sigma2_g) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
   if (batch == 0 || n_h2 == 0) return 0;
   if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
-  // lambda = 0 makes the snp branch's V singular: (0, 1) here, not tblup_eval_batch's (0, 1]
-  for (int64_t i = 0; i < n_h2 * batch; ++i)
-    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  if (int rc = check_h2_grid(h2, n_h2 * batch)) return rc;
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
-  const int nt = hb.d.nt;
+  const int64_t nt = hb.d.nt;
   const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikBufs::carve(cv, hb, B, n_h2); };
-  // per chunk: its h2 columns up front, the n_h2 passes back to back (each the pipeline at its row of
-  // per-system h2, then k_loglik on the factor it leaves, without waiting for the solve), the results of
-  // every pass copied out behind the last
   return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
-    const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
+    const int64_t B = ck.B;
     const LogLikBufs lb = carve(cv, B, ck.sum_k);
     if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
-    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
-      // redo: a chained solve of some pass gave up a wait -- the factors of all but the last pass are
-      // gone, so every pass runs again whole with the one-workgroup k_solve (the same bits), for the
-      // fitnesses only
-      for (int64_t g = 0; g < n_h2; ++g) {
-        Carve cvp = cv;
-        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
-        rq.d_h2 = lb.h2 + g * B;
-        rq.d_fit = lb.fits + g * B;
-        ChunkRes res;
-        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-        seqs.push_back(res.chain_seq);
-        if (!redo) HIPCHK(launch_loglik(res.cl, nullptr, nullptr, 0, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
-      }
-      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
-        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
-      };
-      if (fitness) HIPCHK(out(fitness + b0, pitch, lb.fits, row));
-      if (redo) return 0;
-      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
-      if (sigma2_g) HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
+    const auto per_pass = [&](const CholLaunch& cl, int64_t g) -> int {
+      HIPCHK(launch_loglik(cl, nullptr, nullptr, 0, lb.ll + g * B * nt, lb.s2 + g * B * nt, c->stream));
       return 0;
-    });
+    };
+    return h2_grid(hb, ck, cv, rq, lb, h2, n_h2, per_pass, fitness, loglik, sigma2_g);
   });
 }
 
@@ -1188,65 +1233,35 @@ int tblup_fit_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n
                         double* cov_effects, double* cov_center, double* intercept, double* center, double* effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_cov(c, cov, n_cov)) return rc;
-  const bool model = intercept || center || effects;
-  if (model && !(intercept && center && effects))
-    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  bool model;
+  if (int rc = check_model_out(intercept, center, effects, model)) return rc;
   if (batch > 0 && (!cov_effects || !cov_center)) return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
   if (!hb.sp) return 0;
   fitness = hb.fitness_or_own(fitness);
-  const EvalDims& d = hb.d;
-  const int nt = d.nt, nc = (int)n_cov;
   const CovPlanes cp = gather_cov(hb, cov, n_cov, true);
-  const std::vector<double>&cov_m = cp.m, &h_qT = cp.qT, &h_qV = cp.qV;
-  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) { return CovBufs::carve(cv, hb, B, sk, n_cov, model); };
-  // per chunk: the pipeline with the one-workgroup solve (nothing to recover; its EBVs are not wanted),
-  // k_covar on the factor and z it leaves, then the solve, the fitness and the effects of the adjusted
-  // phenotype from the corrected z in a buffer of its own
+  using Bufs = WithGls<ModelBufs, CovGls>;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t sk) {
+    return Bufs{ModelBufs::carve(cv, hb, sk, model), CovGls::carve(cv, hb, B, n_cov, false, 1, true)};
+  };
+  // per chunk: the second pass behind k_covar, see second_pass
   const int rc = run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const CovBufs cb = carve(cv, B, ck.sum_k);
+    const Bufs cb = carve(cv, ck.B, ck.sum_k);
     if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpyAsync(cb.qT, h_qT.data(), h_qT.size() * 8, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(cb.qV, h_qV.data(), h_qV.size() * 8, hipMemcpyHostToDevice, s));
-    double* d_fit = rq.d_fit;
-    Carve cvp = cv;
-    rq.mode = ChunkMode::NoChain;
-    rq.d_fit = cb.fit0;
-    ChunkRes res;
-    if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-    HIPCHK(launch_covar(res.cl, cb.qT, nc, cb.plan, cb.vscr, cb.b, cb.z2, CovKeep{}, s));
-    CholLaunch cl2 = res.cl;
-    cl2.z = cb.z2;
-    HIPCHK(launch_solve(cl2, nullptr, cb.fit0, cb.ebv2, s));
-    HIPCHK(launch_cov_fitness(cl2, cb.ebv2, cb.qV, cb.b, nc, d_fit, s));
-    if (model)
-      if (int rc = cb.m.enqueue(hb, ck, cl2, center, effects)) return rc;
-    HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, cb.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(fitness + b0, d_fit, (size_t)B * 8, hipMemcpyDeviceToHost, s));
-    if (ebv) HIPCHK(hipMemcpyAsync(ebv + b0 * nt * d.nV, cb.ebv2, (size_t)B * nt * d.nV * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));   // the chunk's offsets and the host buffers are borrowed until here
-    return 0;
+    if (int rc = cb.k.upload(cp, s)) return rc;
+    return second_pass(
+        hb, ck, cv, rq, cb.k.p2, [&](const CholLaunch& cl) { return cb.k.enqueue(cl, 0, s); },
+        [&](const CholLaunch& cl2, double* d_fit) { return cb.k.fitness(cl2, d_fit, s); },
+        {model ? &cb.o : nullptr, center, effects, cov_effects, cb.k.b, n_cov, fitness, ebv});
   });
   if (rc) return rc;
-  if (model) fill_intercepts(hb, intercept);
   // cov_center: the train rows' column means under snp, 0 under gblup; a model whose covariate effects are
   // NaN (d = 0, collinear covariates) is NaN in every output
-  const double nan = std::nan("");
-  for (int64_t b = 0; b < batch; ++b) {
-    const int mode = branch_of(c, offsets[b + 1] - offsets[b], branch);
-    bool dead = false;
-    for (int64_t i = 0; i < nt * n_cov; ++i) dead = dead || std::isnan(cov_effects[b * nt * n_cov + i]);
-    for (int64_t j = 0; j < n_cov; ++j) cov_center[b * n_cov + j] = dead ? nan : (mode == 2 ? cov_m[j] : 0.0);
-    if (dead && model) {
-      for (int t = 0; t < nt; ++t) intercept[b * nt + t] = nan;
-      for (int64_t i = offsets[b]; i < offsets[b + 1]; ++i) center[i] = nan;
-    }
-  }
+  finish_second(hb, fitness, cov_effects, n_cov, n_cov, n_cov, cp.m.data(), cov_center, intercept, center);
   return 0;
 }
 
@@ -1257,79 +1272,36 @@ int tblup_fit_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t
                           double* effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
-  const bool model = intercept || center || effects;
-  if (model && !(intercept && center && effects))
-    return fail(TBLUP_ERR_ARG, "intercept/center/effects are given together or not at all");
+  bool model;
+  if (int rc = check_model_out(intercept, center, effects, model)) return rc;
   if (batch > 0 && (!group_effects || !group_center)) return fail(TBLUP_ERR_ARG, "null group_effects/group_center");
   if (batch > 0 && n_cov > 0 && (!cov_effects || !cov_center))
     return fail(TBLUP_ERR_ARG, "null cov_effects/cov_center");
-  const int64_t L = n_levels, nc = n_cov;
-  GroupSplit gs;
-  {
-    HostBatch hb;
-    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-    if (!hb.sp) return 0;
-    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
-  }
-  const std::vector<long double>& share = gs.share;
-  const std::vector<double>& cov_m = gs.cov_m;
-  const int64_t nV = gs.nV;
-  const int nt = gs.nt;
   // Routes 0 / 1 through tblup_fit_cov_batch on the expanded design (the same bits as that entry gives); 2 through
   // k_fixed.
-  GroupRoutes gr;
-  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
-  const int64_t(&cols)[2] = gr.cols;
-  const int64_t total = offsets[batch];
-  const double nan = std::nan("");
-  for (int route = 0; route < 3; ++route) {
-    const std::vector<int64_t>& mb = gr.of[route];
-    const int64_t Bs = (int64_t)mb.size();
-    if (!Bs) continue;
-    const SubBatch sub = sub_batch(idx, offsets, mb);
-    const std::vector<int64_t>&so = sub.so, &si = sub.si;
-    const int64_t st = so[Bs];
-    const int64_t Cw = gr.width(route);
-    std::vector<double> fit((size_t)Bs), ev(ebv ? (size_t)Bs * nt * nV : 0), bo((size_t)Bs * nt * Cw);
-    std::vector<double> icpt(model ? (size_t)Bs * nt : 0), cen(model ? (size_t)st : 0), eff(model ? (size_t)nt * st : 0);
+  const GroupCall a{c, split_id, cov, n_cov, group, n_levels, idx, offsets, batch, branch};
+  return for_each_route(a, h2, [&](const Route& r) -> int {
+    const int64_t Bs = r.Bs, Cw = r.Cw, nt = r.gs.nt;
+    std::vector<double> fit((size_t)Bs), ev(ebv ? (size_t)Bs * nt * r.gs.nV : 0), bo((size_t)Bs * nt * Cw);
+    RouteModel rm(r, model);
     double* evp = ebv ? ev.data() : nullptr;
-    double *ip = model ? icpt.data() : nullptr, *cp = model ? cen.data() : nullptr, *ep = model ? eff.data() : nullptr;
     int rc;
-    if (route == 2) {
-      rc = fit_fixed_wide(c, split_id, cov, nc, group, L, Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
-                          bo.data(), ip, cp, ep);
+    if (r.id == 2) {
+      rc = fit_fixed_wide(r, h2, fit.data(), evp, bo.data(), rm.ip, rm.cp, rm.ep);
     } else {
-      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
       std::vector<double> xc((size_t)Bs * Cw);   // that entry's centres (cov_m, share)
-      rc = tblup_fit_cov_batch(c, split_id, x.data(), Cw, si.data(), so.data(), Bs, h2, branch, fit.data(), evp,
-                               bo.data(), xc.data(), ip, cp, ep);
+      rc = tblup_fit_cov_batch(c, split_id, r.x.data(), Cw, r.idx(), r.off(), Bs, h2, branch, fit.data(), evp,
+                               bo.data(), xc.data(), rm.ip, rm.cp, rm.ep);
     }
     if (rc) return rc;
-    for (int64_t i = 0; i < Bs; ++i) {
-      const int64_t b = mb[i];
-      const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
-      const int64_t k = offsets[b + 1] - offsets[b];
-      bool dead = cols[br] == 0 && std::isnan(fit[i]);
-      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
-      if (fitness) fitness[b] = fit[i];
-      if (ebv) std::copy(evp + i * nt * nV, evp + (i + 1) * nt * nV, ebv + b * nt * nV);
-      for (int64_t j = 0; j < nc; ++j)
-        cov_center[b * nc + j] = dead ? nan : (br == 1 ? cov_m[j] : 0.0);
-      for (int64_t l = 0; l < L; ++l) group_center[b * L + l] = dead ? nan : (br == 1 ? (double)share[l] : 0.0);
-      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, nc ? cov_effects + b * nt * nc : nullptr,
-                  group_effects + b * nt * L);
-      for (int t = 0; t < nt; ++t) {
-        if (model) {
-          intercept[b * nt + t] = ip[i * nt + t];
-          std::copy(ep + t * st + so[i], ep + t * st + so[i] + k, effects + t * total + offsets[b]);
-        }
-      }
-      if (model) std::copy(cp + so[i], cp + so[i] + k, center + offsets[b]);
-    }
-  }
-  return 0;
+    r.scatter(fit.data(), 1, fitness);
+    r.scatter(evp, nt * r.gs.nV, ebv);
+    r.put_fixed(bo.data(), fit.data(), cov_effects, group_effects, 1, cov_center, group_center);
+    if (model) rm.scatter(r, intercept, center, effects);
+    return 0;
+  });
 }
 
 int tblup_snp_score_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* snps,
@@ -1338,40 +1310,41 @@ int tblup_snp_score_cov_batch(tblup_ctx* c, int split_id, const double* cov, int
                               double* cov_effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_cov(c, cov, n_cov)) return rc;
   if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
-  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
-  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  std::vector<int32_t> s32;
+  if (int rc = check_snps(c, snps, n_cand, s32)) return rc;
   if (batch == 0 || n_cand == 0) return 0;
-  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (int rc = check_h2_open(h2)) return rc;
   if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
-  std::vector<int32_t> s32((size_t)n_cand);
-  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
   fitness = hb.fitness_or_own(fitness);
   const int nt = hb.d.nt, nc = (int)n_cov;
   const CovPlanes cp = gather_cov(hb, cov, n_cov, false);
-  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return ScoreCovBufs::carve(cv, hb, B, n_cand, n_cov); };
+  using Bufs = WithGls<ScoreBufs, CovGls>;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) {
+    return Bufs{ScoreBufs::carve(cv, hb, B, n_cand), CovGls::carve(cv, hb, B, n_cov, true, 1, false)};
+  };
   // per chunk, behind the pipeline: k_covar keeps the model's GLS step, k_snpscore's launches read it
   return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
     const int64_t b0 = ck.b0, B = ck.B;
-    const ScoreCovBufs sb = carve(cv, B, ck.sum_k);
+    const Bufs bufs = carve(cv, B, ck.sum_k);
+    const ScoreBufs& sb = bufs.o;
+    const CovGls& kb = bufs.k;
     if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpyAsync(sb.s.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(sb.k.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(hipMemcpyAsync(sb.cand, s32.data(), (size_t)n_cand * 4, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(cp, s)) return rc;
     return factor_pass(hb, ck, cv, rq, fitness, nullptr, [&](const CholLaunch& cl) -> int {
-      HIPCHK(launch_covar(cl, sb.k.qT, nc, sb.k.plan, sb.k.vscr(), sb.k.b, nullptr, sb.k.keep, s));
-      const ScoreCov sc{sb.k.keep.sq, sb.k.keep.cf, sb.k.keep.ch, sb.k.keep.ks, sb.k.qT, nc};
-      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.s.cand, n_cand, sb.s.plan, sb.s.vscr, &sc,
-                             sb.s.sco, sb.s.inf, sb.s.q, s));
-      HIPCHK(hipMemcpyAsync(score + b0 * nt * n_cand, sb.s.sco, (size_t)B * nt * n_cand * 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(info + b0 * n_cand, sb.s.inf, (size_t)B * n_cand * 8, hipMemcpyDeviceToHost, s));
-      if (q) HIPCHK(hipMemcpyAsync(q + b0 * nt, sb.s.q, (size_t)B * nt * 8, hipMemcpyDeviceToHost, s));
+      if (int rc = kb.enqueue(cl, 0, s)) return rc;
+      const ScoreCov sc = kb.score();
+      HIPCHK(launch_snpscore(cl, (const int32_t*)c->colsum_all.p, sb.cand, n_cand, sb.plan, sb.vscr, &sc, sb.sco,
+                             sb.inf, sb.q, s));
+      if (int rc = sb.copy_out(hb, ck, n_cand, score, info, q)) return rc;
       if (cov_effects)
-        HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, sb.k.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(cov_effects + b0 * nt * nc, kb.b, (size_t)B * nt * nc * 8, hipMemcpyDeviceToHost, s));
       return 0;
     });
   });
@@ -1382,56 +1355,39 @@ int tblup_loglik_cov_batch(tblup_ctx* c, int split_id, const double* cov, int64_
                            double* fitness, double* loglik, double* sigma2_g, double* cov_effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_cov(c, cov, n_cov)) return rc;
   if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
   if (batch == 0 || n_h2 == 0) return 0;
   if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
-  for (int64_t i = 0; i < n_h2 * batch; ++i)
-    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
+  if (int rc = check_h2_grid(h2, n_h2 * batch)) return rc;
   HostBatch hb;
   if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
-  const int nt = hb.d.nt, nc = (int)n_cov;
+  const int64_t nt = hb.d.nt;
   const CovPlanes cp = gather_cov(hb, cov, n_cov, false);
   // log|Q~_T^T Q~_T| does not depend on h2: once per call, one value per plane
   const double lqq[2] = {log_det_qq(cp.qT.data(), hb.d.nT, hb.d.nTp, n_cov),
                          log_det_qq(cp.qT.data() + (size_t)COVAR_W * hb.d.nTp, hb.d.nT, hb.d.nTp, n_cov)};
-  const auto carve = [&](Carve& cv, int64_t B, int64_t) { return LogLikCovBufs::carve(cv, hb, B, n_h2, n_cov); };
+  using Bufs = WithGls<LogLikBufs, CovGls>;
+  const auto carve = [&](Carve& cv, int64_t B, int64_t) {
+    return Bufs{LogLikBufs::carve(cv, hb, B, n_h2), CovGls::carve(cv, hb, B, n_cov, true, n_h2, false)};
+  };
   // tblup_loglik_batch's passes, each with k_covar (keep mode, no z*) between the pipeline and k_loglik
   return run_host_batch(hb, false, carve, [&](const Chunk& ck, Carve& cv, ChunkReq& rq) -> int {
     const hipStream_t s = c->stream;
-    const int64_t b0 = ck.b0, B = ck.B;
-    const size_t row = (size_t)B * 8, rowt = row * nt, pitch = (size_t)batch * 8;
-    const LogLikCovBufs lc = carve(cv, B, ck.sum_k);
-    const LogLikBufs& lb = lc.l;
-    const CovKeepBufs& kb = lc.k;
+    const int64_t B = ck.B;
+    const Bufs bufs = carve(cv, B, ck.sum_k);
+    const LogLikBufs& lb = bufs.o;
+    const CovGls& kb = bufs.k;
     if (int rc = ws_check(c, cv)) return rc;
-    HIPCHK(hipMemcpy2DAsync(lb.h2, row, h2 + b0, pitch, row, (size_t)n_h2, hipMemcpyHostToDevice, s));
-    HIPCHK(hipMemcpyAsync(kb.qT, cp.qT.data(), cp.qT.size() * 8, hipMemcpyHostToDevice, s));
+    if (int rc = kb.upload(cp, s)) return rc;
     HIPCHK(hipMemcpyAsync(kb.lqq, lqq, sizeof(lqq), hipMemcpyHostToDevice, s));
-    return run_recovering(c, [&](bool redo, std::vector<int32_t>& seqs) -> int {
-      for (int64_t g = 0; g < n_h2; ++g) {
-        Carve cvp = cv;
-        rq.mode = redo ? ChunkMode::NoChain : ChunkMode::Full;
-        rq.d_h2 = lb.h2 + g * B;
-        rq.d_fit = lb.fits + g * B;
-        ChunkRes res;
-        if (int rc = run_chunk(c, rq, cvp, res)) return rc;
-        seqs.push_back(res.chain_seq);
-        if (redo) continue;
-        HIPCHK(launch_covar(res.cl, kb.qT, nc, kb.plan, kb.vscr(), kb.b + g * B * nt * nc, nullptr, kb.keep, s));
-        HIPCHK(launch_loglik(res.cl, kb.keep.ks, kb.lqq, nc, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
-      }
-      const auto out = [&](double* host, size_t hpitch, const double* dev, size_t drow) {   // n_h2 rows to the host
-        return hipMemcpy2DAsync(host, hpitch, dev, drow, drow, (size_t)n_h2, hipMemcpyDeviceToHost, s);
-      };
-      if (fitness) HIPCHK(out(fitness + b0, pitch, lb.fits, row));
-      if (redo) return 0;
-      HIPCHK(out(loglik + b0 * nt, pitch * nt, lb.ll, rowt));
-      if (sigma2_g) HIPCHK(out(sigma2_g + b0 * nt, pitch * nt, lb.s2, rowt));
-      if (cov_effects) HIPCHK(out(cov_effects + b0 * nt * nc, pitch * nt * nc, kb.b, rowt * nc));
+    const auto per_pass = [&](const CholLaunch& cl, int64_t g) -> int {
+      if (int rc = kb.enqueue(cl, g, s)) return rc;
+      HIPCHK(launch_loglik(cl, kb.keep.ks, kb.lqq, kb.nc, lb.ll + g * B * nt, lb.s2 + g * B * nt, s));
       return 0;
-    });
+    };
+    return h2_grid(hb, ck, cv, rq, lb, h2, n_h2, per_pass, fitness, loglik, sigma2_g, cov_effects, kb.b, nt * n_cov);
   });
 }
 
@@ -1441,58 +1397,34 @@ int tblup_snp_score_group_batch(tblup_ctx* c, int split_id, const double* cov, i
                                 double* score, double* info, double* q, double* cov_effects, double* group_effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
   if (batch < 0 || n_cand < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_cand");
-  if (n_cand > 0 && !snps) return fail(TBLUP_ERR_ARG, "null snps");
-  if (int rc = check_indices(c, snps, n_cand)) return rc;
+  std::vector<int32_t> s32;
+  if (int rc = check_snps(c, snps, n_cand, s32)) return rc;
   if (batch == 0 || n_cand == 0) return 0;
-  if (!(h2 > 0.0) || !(h2 < 1.0)) return fail(TBLUP_ERR_ARG, "h2 must be in (0, 1)");
+  if (int rc = check_h2_open(h2)) return rc;
   if (!score || !info) return fail(TBLUP_ERR_ARG, "null score/info");
-  const int64_t L = n_levels, nc = n_cov;
-  GroupSplit gs;
-  {
-    HostBatch hb;
-    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
-  }
-  const int nt = gs.nt;
-  GroupRoutes gr;
-  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
-  std::vector<int32_t> s32((size_t)n_cand);
-  for (int64_t i = 0; i < n_cand; ++i) s32[i] = (int32_t)snp_col(snps[i], c->P);
-  for (int route = 0; route < 3; ++route) {
-    const std::vector<int64_t>& mb = gr.of[route];
-    const int64_t Bs = (int64_t)mb.size();
-    if (!Bs) continue;
-    const SubBatch sub = sub_batch(idx, offsets, mb);
-    const int64_t Cw = gr.width(route);
+  const GroupCall a{c, split_id, cov, n_cov, group, n_levels, idx, offsets, batch, branch};
+  return for_each_route(a, h2, [&](const Route& r) -> int {
+    const int64_t Bs = r.Bs, Cw = r.Cw, nt = r.gs.nt;
     std::vector<double> fit((size_t)Bs), sco((size_t)Bs * nt * n_cand), inf((size_t)Bs * n_cand), qs((size_t)Bs * nt),
         bo((size_t)Bs * nt * Cw);
     int rc;
-    if (route == 2) {
-      rc = score_fixed_wide(c, split_id, cov, nc, group, L, Cw, s32, sub.si.data(), sub.so.data(), Bs, h2, branch,
-                            fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
+    if (r.id == 2) {
+      rc = score_fixed_wide(r, s32, h2, fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
     } else {
-      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
-      rc = tblup_snp_score_cov_batch(c, split_id, x.data(), Cw, snps, n_cand, sub.si.data(), sub.so.data(), Bs, h2,
-                                     branch, fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
+      rc = tblup_snp_score_cov_batch(c, split_id, r.x.data(), Cw, snps, n_cand, r.idx(), r.off(), Bs, h2, branch,
+                                     fit.data(), sco.data(), inf.data(), qs.data(), bo.data());
     }
     if (rc) return rc;
-    for (int64_t i = 0; i < Bs; ++i) {
-      const int64_t b = mb[i];
-      const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
-      bool dead = gr.cols[br] == 0 && std::isnan(fit[i]);
-      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
-      if (fitness) fitness[b] = fit[i];
-      std::copy(sco.begin() + i * nt * n_cand, sco.begin() + (i + 1) * nt * n_cand, score + b * nt * n_cand);
-      std::copy(inf.begin() + i * n_cand, inf.begin() + (i + 1) * n_cand, info + b * n_cand);
-      if (q) std::copy(qs.begin() + i * nt, qs.begin() + (i + 1) * nt, q + b * nt);
-      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, cov_effects ? cov_effects + b * nt * nc : nullptr,
-                  group_effects ? group_effects + b * nt * L : nullptr);
-    }
-  }
-  return 0;
+    r.scatter(fit.data(), 1, fitness);
+    r.scatter(sco.data(), nt * n_cand, score);
+    r.scatter(inf.data(), n_cand, info);
+    r.scatter(qs.data(), nt, q);
+    r.put_fixed(bo.data(), fit.data(), cov_effects, group_effects);
+    return 0;
+  });
 }
 
 int tblup_loglik_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
@@ -1501,58 +1433,33 @@ int tblup_loglik_group_batch(tblup_ctx* c, int split_id, const double* cov, int6
                              double* sigma2_g, double* cov_effects, double* group_effects) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
   if (batch < 0 || n_h2 < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_h2");
   if (batch == 0 || n_h2 == 0) return 0;
   if (!h2 || !loglik) return fail(TBLUP_ERR_ARG, "null h2/loglik");
-  for (int64_t i = 0; i < n_h2 * batch; ++i)
-    if (!(h2[i] > 0.0) || !(h2[i] < 1.0)) return fail(TBLUP_ERR_ARG, "every h2 must be in (0, 1)");
-  const int64_t L = n_levels, nc = n_cov;
-  GroupSplit gs;
-  {
-    HostBatch hb;
-    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2[0], branch, true)) return rc;
-    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
-  }
-  const int nt = gs.nt;
-  GroupRoutes gr;
-  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
-  for (int route = 0; route < 3; ++route) {
-    const std::vector<int64_t>& mb = gr.of[route];
-    const int64_t Bs = (int64_t)mb.size();
-    if (!Bs) continue;
-    const SubBatch sub = sub_batch(idx, offsets, mb);
-    const int64_t Cw = gr.width(route);
+  if (int rc = check_h2_grid(h2, n_h2 * batch)) return rc;
+  const GroupCall a{c, split_id, cov, n_cov, group, n_levels, idx, offsets, batch, branch};
+  return for_each_route(a, h2[0], [&](const Route& r) -> int {
+    const int64_t Bs = r.Bs, Cw = r.Cw, nt = r.gs.nt;
     // the route's h2 columns; its results [n_h2][Bs][..]
     std::vector<double> hs((size_t)n_h2 * Bs), fit(hs.size()), ll(hs.size() * nt), s2(ll.size()), bo(ll.size() * Cw);
     for (int64_t g = 0; g < n_h2; ++g)
-      for (int64_t i = 0; i < Bs; ++i) hs[g * Bs + i] = h2[g * batch + mb[i]];
+      for (int64_t i = 0; i < Bs; ++i) hs[g * Bs + i] = h2[g * batch + r.mb[i]];
     int rc;
-    if (route == 2) {
-      rc = loglik_fixed_wide(c, split_id, cov, nc, group, L, Cw, sub.si.data(), sub.so.data(), Bs, hs.data(), n_h2,
-                             branch, fit.data(), ll.data(), s2.data(), bo.data());
+    if (r.id == 2) {
+      rc = loglik_fixed_wide(r, hs.data(), n_h2, fit.data(), ll.data(), s2.data(), bo.data());
     } else {
-      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
-      rc = tblup_loglik_cov_batch(c, split_id, x.data(), Cw, sub.si.data(), sub.so.data(), Bs, hs.data(), n_h2, branch,
+      rc = tblup_loglik_cov_batch(c, split_id, r.x.data(), Cw, r.idx(), r.off(), Bs, hs.data(), n_h2, branch,
                                   fit.data(), ll.data(), s2.data(), bo.data());
     }
     if (rc) return rc;
-    for (int64_t g = 0; g < n_h2; ++g)
-      for (int64_t i = 0; i < Bs; ++i) {
-        const int64_t b = mb[i], at = g * Bs + i, to = g * batch + b;
-        const int br = branch_of(c, offsets[b + 1] - offsets[b], branch) == 1 ? 0 : 1;
-        bool dead = gr.cols[br] == 0 && std::isnan(fit[at]);
-        for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[at * nt * Cw + e]);
-        if (fitness) fitness[to] = fit[at];
-        std::copy(ll.begin() + at * nt, ll.begin() + (at + 1) * nt, loglik + to * nt);
-        if (sigma2_g) std::copy(s2.begin() + at * nt, s2.begin() + (at + 1) * nt, sigma2_g + to * nt);
-        put_effects(bo.data() + at * nt * Cw, nt, Cw, nc, L, br, dead,
-                    cov_effects ? cov_effects + to * nt * nc : nullptr,
-                    group_effects ? group_effects + to * nt * L : nullptr);
-      }
-  }
-  return 0;
+    r.scatter(fit.data(), 1, fitness, n_h2);
+    r.scatter(ll.data(), nt, loglik, n_h2);
+    r.scatter(s2.data(), nt, sigma2_g, n_h2);
+    r.put_fixed(bo.data(), fit.data(), cov_effects, group_effects, n_h2);
+    return 0;
+  });
 }
 
 int tblup_reliability_group_batch(tblup_ctx* c, int split_id, const double* cov, int64_t n_cov, const int64_t* group,
@@ -1563,7 +1470,7 @@ int tblup_reliability_group_batch(tblup_ctx* c, int split_id, const double* cov,
                                   double* pev_total, double* fixed_cov) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (int rc = check_group(c, cov, n_cov, group, n_levels)) return rc;
   if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
   // (without covariates cov_effects / cov_center are not looked at, as tblup_fit_group_batch)
@@ -1574,99 +1481,65 @@ int tblup_reliability_group_batch(tblup_ctx* c, int split_id, const double* cov,
     return fail(TBLUP_ERR_ARG,
                 "cov_effects/cov_center/group_effects/group_center/intercept/center/effects are given together or not "
                 "at all");
-  if (n_pred > 0 && !animals) return fail(TBLUP_ERR_ARG, "null animals");
-  std::vector<int32_t> a32((size_t)n_pred);
-  for (int64_t i = 0; i < n_pred; ++i) {
-    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
-    a32[i] = (int32_t)animals[i];
-  }
+  std::vector<int32_t> a32;
+  if (int rc = check_animals(c, animals, n_pred, a32)) return rc;
   // the second solve (the model of the adjusted phenotype and its fitness) runs only for a caller who wants it
   const bool full = model || fitness;
   if (batch == 0 || (n_pred == 0 && !full && !fixed_cov)) return 0;
   if (n_pred > 0 && !reliability) return fail(TBLUP_ERR_ARG, "null reliability");
-  const int64_t L = n_levels, nc = n_cov, Co = nc + L;
-  GroupSplit gs;
-  {
-    HostBatch hb;
-    if (int rc = open_host_batch(hb, c, split_id, idx, offsets, batch, h2, branch, true)) return rc;
-    if (int rc = check_group_split(hb, cov, nc, group, L, gs)) return rc;
-  }
-  const int nt = gs.nt;
-  GroupRoutes gr;
-  if (int rc = route_group(c, offsets, batch, branch, nc, L, gr)) return rc;
-  const int64_t total = offsets[batch];
+  const int64_t nc = n_cov, Co = nc + n_levels;
   const double nan = std::nan("");
-  for (int route = 0; route < 3; ++route) {
-    const std::vector<int64_t>& mb = gr.of[route];
-    const int64_t Bs = (int64_t)mb.size();
-    if (!Bs) continue;
-    const SubBatch sub = sub_batch(idx, offsets, mb);
-    const std::vector<int64_t>& so = sub.so;
-    const int64_t st = so[Bs], Cw = gr.width(route), Cm = gr.cols[route == 2 ? 0 : route];
+  const GroupCall a{c, split_id, cov, n_cov, group, n_levels, idx, offsets, batch, branch};
+  return for_each_route(a, h2, [&](const Route& r) -> int {
+    const int64_t Bs = r.Bs, Cw = r.Cw, nt = r.gs.nt, Cm = r.cols[r.id == 2 ? 0 : r.id];
     // A route that is the whole batch (its models are then in batch order) writes the per-animal outputs, and the
     // wide route fixed_cov, straight into the caller's arrays: at 128 columns fixed_cov is 128 KiB a model.  Else the
     // route's own: fixed_cov compact [Cm][Cm] from the covariate entry, in the caller's layout from k_fixed_cov.
-    const bool whole = Bs == batch, fc_own = fixed_cov && !(whole && route == 2);
-    const size_t fc_model = (size_t)(route == 2 ? Co * Co : Cm * Cm);
-    std::vector<double> fit(fitness ? (size_t)Bs : 0), rel(whole ? 0 : (size_t)Bs * n_pred),
+    const bool whole = Bs == batch, fc_own = fixed_cov && !(whole && r.id == 2);
+    const size_t fc_model = (size_t)(r.id == 2 ? Co * Co : Cm * Cm);
+    // (the fitness also tells post_model of a model without a fixed column)
+    std::vector<double> fit(full ? (size_t)Bs : 0), rel(whole ? 0 : (size_t)Bs * n_pred),
         pev(pev_total && !whole ? (size_t)Bs * n_pred : 0), fc(fc_own ? (size_t)Bs * fc_model : 0),
-        bo(model ? (size_t)Bs * nt * Cw : 0), xc(model ? (size_t)Bs * Cw : 0), icpt(model ? (size_t)Bs * nt : 0),
-        cen(model ? (size_t)st : 0), eff(model ? (size_t)nt * st : 0);
+        bo(model ? (size_t)Bs * nt * Cw : 0), xc(model ? (size_t)Bs * Cw : 0);
+    RouteModel rm(r, model);
     const auto opt = [](std::vector<double>& v, bool on) { return on ? v.data() : nullptr; };
-    double *fp = opt(fit, fitness), *bp = opt(bo, model), *ip = opt(icpt, model), *np = opt(cen, model);
-    double *ep = opt(eff, model), *rp = whole ? reliability : rel.data();
+    double *fp = opt(fit, full), *bp = opt(bo, model), *rp = whole ? reliability : rel.data();
     double *pp = whole ? pev_total : opt(pev, pev_total), *cp = fc_own ? fc.data() : fixed_cov;
     int rc;
-    if (route == 2) {
-      rc = reliab_fixed_wide(c, split_id, cov, nc, group, L, Cw, a32, animals, sub.si.data(), so.data(), Bs, h2,
-                             branch, full, fp, rp, pp, cp, bp, ip, np, ep);
+    if (r.id == 2) {
+      rc = reliab_fixed_wide(r, a32, animals, h2, full, fp, rp, pp, cp, bp, rm.ip, rm.cp, rm.ep);
     } else {
-      const std::vector<double> x = expand_design(c, cov, nc, group, Cw, route);
-      rc = tblup_reliability_cov_batch(c, split_id, x.data(), Cw, animals, n_pred, sub.si.data(), so.data(), Bs, h2,
-                                       branch, fp, bp, opt(xc, model), ip, np, ep, rp, pp, cp);
+      rc = tblup_reliability_cov_batch(c, split_id, r.x.data(), Cw, animals, n_pred, r.idx(), r.off(), Bs, h2, branch,
+                                       fp, bp, opt(xc, model), rm.ip, rm.cp, rm.ep, rp, pp, cp);
     }
     if (rc) return rc;
-    for (int64_t i = 0; i < Bs; ++i) {
-      const int64_t b = mb[i], k = offsets[b + 1] - offsets[b];
-      const int br = branch_of(c, k, branch) == 1 ? 0 : 1;
-      if (fitness) fitness[b] = fit[i];
-      for (int64_t v = 0; v < n_pred; ++v) {
-        reliability[b * n_pred + v] = rp[i * n_pred + v];
-        // an animal whose label no train animal has: no design row, so no predicted record (PanelModel.predict's rule)
-        if (pev_total) pev_total[b * n_pred + v] = group[animals[v]] < 0 ? nan : pp[i * n_pred + v];
-      }
-      if (fc_own) {
-        double* out = fixed_cov + b * Co * Co;
-        if (route == 2) {
-          std::copy(cp + i * Co * Co, cp + (i + 1) * Co * Co, out);
-        } else {
-          // the compact G^-1 of the expanded design at the caller's columns: level l is column nc + l - br, and the
-          // reference level of an snp model keeps its zeros (NaN throughout for a model that is NaN)
-          const double* in = cp + i * Cm * Cm;
-          const bool dead = std::isnan(in[0]);
-          for (int64_t oi = 0; oi < Co; ++oi)
-            for (int64_t oj = 0; oj < Co; ++oj) {
-              const int64_t mi = oi < nc ? oi : oi - br, mj = oj < nc ? oj : oj - br;
-              const bool ref = br == 1 && (oi == nc || oj == nc);
-              out[oi * Co + oj] = dead ? nan : (ref ? 0.0 : in[mi * Cm + mj]);
-            }
+    if (fitness) r.scatter(fp, 1, fitness);
+    if (!whole) r.scatter(rp, n_pred, reliability);
+    if (!whole) r.scatter(pp, n_pred, pev_total);
+    // an animal whose label no train animal has: no design row, so no predicted record (PanelModel.predict's rule)
+    for (int64_t i = 0; pev_total && i < Bs; ++i)
+      for (int64_t v = 0; v < n_pred; ++v)
+        if (group[animals[v]] < 0) pev_total[r.mb[i] * n_pred + v] = nan;
+    if (fc_own && r.id == 2) r.scatter(cp, Co * Co, fixed_cov);
+    for (int64_t i = 0; fc_own && r.id != 2 && i < Bs; ++i) {
+      // the compact G^-1 of the expanded design at the caller's columns: level l is column nc + l - br, and the
+      // reference level of an snp model keeps its zeros (NaN throughout for a model that is NaN)
+      const int br = r.br[i];
+      const double* in = cp + i * Cm * Cm;
+      double* out = fixed_cov + r.mb[i] * Co * Co;
+      const bool dead = std::isnan(in[0]);
+      for (int64_t oi = 0; oi < Co; ++oi)
+        for (int64_t oj = 0; oj < Co; ++oj) {
+          const int64_t mi = oi < nc ? oi : oi - br, mj = oj < nc ? oj : oj - br;
+          const bool ref = br == 1 && (oi == nc || oj == nc);
+          out[oi * Co + oj] = dead ? nan : (ref ? 0.0 : in[mi * Cm + mj]);
         }
-      }
-      if (!model) continue;
-      bool dead = gr.cols[br] == 0 && std::isnan(fit[i]);
-      for (int64_t e = 0; e < nt * Cw; ++e) dead = dead || std::isnan(bo[i * nt * Cw + e]);
-      for (int64_t j = 0; j < nc; ++j) cov_center[b * nc + j] = dead ? nan : (br == 1 ? gs.cov_m[j] : 0.0);
-      for (int64_t l = 0; l < L; ++l) group_center[b * L + l] = dead ? nan : (br == 1 ? (double)gs.share[l] : 0.0);
-      put_effects(bo.data() + i * nt * Cw, nt, Cw, nc, L, br, dead, nc ? cov_effects + b * nt * nc : nullptr,
-                  group_effects + b * nt * L);
-      for (int t = 0; t < nt; ++t) {
-        intercept[b * nt + t] = ip[i * nt + t];
-        std::copy(ep + t * st + so[i], ep + t * st + so[i] + k, effects + t * total + offsets[b]);
-      }
-      std::copy(np + so[i], np + so[i] + k, center + offsets[b]);
     }
-  }
-  return 0;
+    if (!model) return 0;
+    r.put_fixed(bp, fp, cov_effects, group_effects, 1, cov_center, group_center);
+    rm.scatter(r, intercept, center, effects);
+    return 0;
+  });
 }
 
 int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, const int64_t* idx,
@@ -1674,7 +1547,7 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
                         const double* effects, int64_t n_traits, double* ebv) {
   clear_error();
   if (int rc = check_ctx(c)) return rc;
-  if (c->n == 0) return fail(TBLUP_ERR_STATE, "context has no genotype panel (DE / decode-only context)");
+  if (int rc = check_panel(c)) return rc;
   if (n_traits < 1 || n_traits > MAXT) return fail(TBLUP_ERR_ARG, "need 1 <= n_traits <= 4");
   if (batch < 0 || n_pred < 0) return fail(TBLUP_ERR_ARG, "negative batch / n_pred");
   if (batch == 0 || n_pred == 0) return 0;
@@ -1684,11 +1557,8 @@ int tblup_predict_batch(tblup_ctx* c, const int64_t* animals, int64_t n_pred, co
   if (int rc = check_counts(offsets, batch, "model")) return rc;
   const int64_t total = offsets[batch];
   if (int rc = check_indices(c, idx, total)) return rc;
-  std::vector<int32_t> a32((size_t)n_pred);
-  for (int64_t i = 0; i < n_pred; ++i) {
-    if (animals[i] < 0 || animals[i] >= c->n) return fail(TBLUP_ERR_ARG, "animal row out of range");
-    a32[i] = (int32_t)animals[i];
-  }
+  std::vector<int32_t> a32;
+  if (int rc = check_animals(c, animals, n_pred, a32)) return rc;
   HIPCHK(hipSetDevice(c->device));
   const int nt = (int)n_traits;
   const ChunkBytes bytes_of = [&](const int64_t*, int64_t B, int64_t sum_k) {
