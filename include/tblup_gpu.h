@@ -430,6 +430,8 @@ int tblup_loglik_cov_batch(tblup_ctx* ctx, int split_id, const double* cov, int6
  *   G = F~_T^T V^{-1} F~_T = C C^T,  h_t = F~_T^T V^{-1} r_t,  P = V^{-1} - V^{-1} F~_T G^{-1} F~_T^T V^{-1},
  *   dof = N - r - C_m,  log|A^T V A| = log|V| - r log lambda + log|G| - log|F~_T^T F~_T|.
  * C_m, so dof and log|F~_T^T F~_T|, differ between the gblup and the snp models of one batch.
+ * Under gblup with a class factor, or with a column of ones in Q, q_P = q - |C^{-1} h_t|^2, sigma2_g and the likelihood
+ * lose as many digits as the squared phenotype mean exceeds its variance: centre the phenotype first.
  *   score / info / q, loglik / sigma2_g, fitness : as the covariate entries have them
  *   cov_effects   : optional out, [n_h2 x] batch x n_traits x n_cov
  *   group_effects : optional out, [n_h2 x] batch x n_traits x n_levels: tblup_fit_group_batch's at this h2, bit

@@ -24,6 +24,7 @@ from oracle import blup_oracle as O
 from tests import model_ref as R
 from tests import reliability_ref as Q
 
+LD = np.longdouble
 H2 = Q.H2
 K40, K300 = 40, Q.K300
 
@@ -69,6 +70,55 @@ def loo_ref(idx, train, geno, pheno, h2, branch="auto", form=None):
         pred = y - eloo
         return {"pred": pred, "leverage": h, "eloo": eloo, "press": float(np.sum(eloo * eloo)),
                 "fitness": abs(O.pearson_r(pred, y)), "gap": float(np.min(1.0 - h))}
+
+
+def loo_wide(idx, train, geno, pheno, h2, branch="auto", form=None):
+    """loo_ref's arithmetic in np.longdouble (the centred rows, d and lambda from the exact counts, one longdouble
+    column Cholesky), the fitness from tests/test_edge_cases_cpu.py::_pearson_wide.  pheno (n,) gives loo_ref's
+    shapes; (n, t) gives pred / eloo (t, n_T), press / fitness (t,) from one factor.  None where the system is
+    not positive definite."""
+    from tests.test_edge_cases_cpu import _pearson_wide
+    T = np.asarray(train)
+    nT = len(T)
+    Y = np.asarray(pheno, dtype=np.float64)
+    one = Y.ndim == 1
+    y = (Y[:, None] if one else Y)[T].astype(LD)
+    branch = R._branch(len(idx), np.asarray(geno).shape[0], branch)
+    _, wt, d, lam = Q._setup(idx, T, geno, h2, branch, LD)
+    if not d > 0:
+        return None
+    c = LD(0) if branch == "gblup" else LD(1) / LD(nT)
+    r = y - (LD(0) if branch == "gblup" else y.sum(axis=0) / LD(nT))
+    if form is None:
+        form = "snp" if wt.shape[1] <= nT else "kernel"
+    if form == "snp":
+        A = (wt.T @ wt) / d
+        A[np.diag_indices_from(A)] += lam
+        L = Q._chol(A)
+        if L is None:
+            return None
+        beta = R._chol_solve(A, (wt.T @ r) / d)
+        s = Q._forward(L, np.ascontiguousarray(wt.T))
+        h = c + np.sum(s * s, axis=0) / d
+        eloo = (r - wt @ beta) / (LD(1) - h)[:, None]
+    else:
+        A = (wt @ wt.T) / d
+        A[np.diag_indices_from(A)] += lam
+        L = Q._chol(A)
+        if L is None:
+            return None
+        alpha = R._chol_solve(A, r)
+        s = Q._forward(L, np.eye(nT, dtype=LD))
+        vtt = np.sum(s * s, axis=0)
+        eloo = lam * alpha / (lam * vtt - c)[:, None]
+        h = LD(1) + c - lam * vtt
+    pred = y - eloo
+    fit = np.array([_pearson_wide(pred[:, t], y[:, t])[0] for t in range(y.shape[1])])
+    out = {"pred": np.ascontiguousarray(pred.T), "leverage": h, "eloo": np.ascontiguousarray(eloo.T),
+           "press": np.sum(eloo * eloo, axis=0), "fitness": fit, "gap": float(np.min(LD(1) - h))}
+    if one:
+        out.update(pred=out["pred"][0], eloo=out["eloo"][0], press=out["press"][0], fitness=float(fit[0]))
+    return out
 
 
 def loo_brute(idx, train, geno, pheno, h2, branch="auto", which=None):

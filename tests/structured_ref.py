@@ -45,15 +45,36 @@ its truth is not zero (z = L^-1 y, the quadratic form q, the log-likelihood), an
 size 1 / lambda into the solution beside values of size one.  Two more inputs are left out because the float64
 restatement itself misses the host bar on them (fit_cols, z_cols): z of (d) under the snp branch, and (d) for snp160
 under forced gblup.  tests/test_structured_host.py::test_inputs_left_out_do_miss_the_host_bar keeps each figure.
+
+Fixed effects (tests/test_gpu_structured_fixed.py, sections G to K).  The class factor is the family label (groups():
+30 levels, confounded with relationship), the designs "cov3" (covariates()), "fam" (the factor) and "fam+n" (the factor
+and the normal covariate; the family-0 indicator of covariates() is collinear with the factor).  cond(G) of
+G = F~^T V^-1 F~ is at most 2.3e5, 7.4e2 and 1.6e6 -- the last over covar_ref.COND_MAX in two cases, which stay:
+STRUCT_COND_MAX = 1e7 is the cap here.  Truths: adj_truth (u_P, v_P, q_P, b, likelihood), relfix_truth (adjusted
+reliability, pev_total, cov_cov / fixed_cov), fixfit_truth (the model of fit(groups=)), loo_truth.  Errors follow the
+rule above; b = [cov_effects, group_effects] is one output vector, a covariance matrix is taken whole.
+Left out too, for the same reason as above (stat_cols, fixfit_cols): (d) under gblup with the class factor for q_P,
+sigma2_g, the log-likelihood, u_P and the SNP effects / EBVs of y* -- the level means absorb the offset and
+q_P = q - |C^-1 h|^2 cancels twelve digits (the float64 restatement is 1.2e6 host bars off at kappa 17); its GLS
+effects b are compared.
+The LOO rule: e_loo = e_t / (1 - h_tt), so pred, eloo, PRESS and the LOO fitness are held to bar / gap,
+gap = min_t (1 - h_tt) of the truth (down to 6.8e-6 at h2 = 0.999999; on (200, 60) dual260 snp it is 1.5e-5 and the
+float64 restatement's eloo is 780 host bars off without that factor, 0.012 with it); the leverages are held to the plain bar.  A case is kept only if
+bar / gap <= LOO_GAP_MAX = 1e-2 (the worst is 6.2e-3), and LOO runs at h2 = 0.4, 0.9999 and 0.999999.
 """
 import functools
 
 import numpy as np
 
 from tests import covar_ref as CV
+from tests import group_ref as GR
 from tests import loglik_ref as LL
+from tests import loo_ref as LO
 from tests import model_ref as R
+from tests import reliab_cov_ref as RC
+from tests import reliab_group_ref as RG
 from tests import reliability_ref as Q
+from tests import score_cov_ref as SC
 from tests import score_ref as S
 from tests.test_edge_cases_cpu import _pearson_wide, blup_wide      # noqa: F401  (blup_wide: re-exported)
 
@@ -434,6 +455,144 @@ def gls_truth(split, gkey, branch, h2):
     mu = LD(0) if br == "gblup" else g["ystar"][T].sum(axis=0) / LD(len(T))
     g["effects"], g["ebv"] = np.ascontiguousarray(eff.T), np.ascontiguousarray((w @ eff + mu).T)
     return g
+
+
+# ---------------------------------------------------------------------------------------------
+# Fixed effects on the panel: the designs, and the truths of the entries that adjust for them
+# ---------------------------------------------------------------------------------------------
+DESIGNS = ("cov3", "fam", "fam+n")
+STRUCT_COND_MAX = 1e7                        # cond(F~^T V^-1 F~) of every structured case (covar_ref.COND_MAX is 1e6)
+LOO_H2S = (0.4, 0.9999, 0.999999)
+LOO_GAP_MAX = 1e-2                           # a LOO case is kept only if bar / gap stays below this
+
+
+def groups():
+    """The class factor: the family label, 29 families of 10 and -1 for the 11 unrelated animals (30 levels).  It is
+    confounded with relationship: nearly in the span of the genotypes."""
+    return panel()["family"]
+
+
+def design(name):
+    """(covariates or None, groups or None) of a design.  "fam+n" takes the normal column only: the first column of
+    covariates() is the indicator of family 0, collinear with the factor."""
+    return {"cov3": (covariates(), None), "fam": (None, groups()),
+            "fam+n": (np.ascontiguousarray(covariates()[:, 2:]), groups())}[name]
+
+
+def design_matrix(name, split, gkey, branch):
+    """The dense fixed design F (n, C) of a model under its fitted branch (tests/group_ref.py::expand) and the
+    number of covariate columns in front of the levels' columns."""
+    cov, grp = design(name)
+    if grp is None:
+        return cov, cov.shape[1]
+    F, _ = GR.expand(cov, grp, panel()["splits"][split][0], fitted_branch(gkey, branch))
+    return F, 0 if cov is None else cov.shape[1]
+
+
+def stat_cols(name, branch, cols=(0, 1, 2, 3, 4)):
+    """The columns of Y whose q_P, log-likelihood, sigma2_g and u_P are compared under a design: not (d) under gblup
+    with the class factor, where the level means absorb the offset and q_P = q - |C^-1 h|^2 cancels twelve digits
+    (tests/test_structured_host.py keeps the float64 restatement's figure)."""
+    return tuple(t for t in cols if not (t == 3 and branch == "gblup" and name != "cov3"))
+
+
+def fixfit_cols(name, branch, gkey=None):
+    """The columns of Y whose SNP effects, EBVs and fitness under a design are compared: fit_cols', and -- as for
+    stat_cols -- not (d) under gblup with the class factor: y* = y - F~ b is 1e6 less 1e6, the float64 restatement
+    rounds it at 1e-10 and its effects are 9.6 host bars off at kappa 17 (tests/test_structured_host.py keeps the
+    figure).  The GLS effects b of (d) are compared everywhere (fit_cols)."""
+    return stat_cols(name, branch, fit_cols(branch, gkey))
+
+
+def _frozen(out):
+    for v in out.values():
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def adj_truth(name, split, gkey, branch, h2):
+    """score_cov_ref.adj_wide of a design for the five columns of Y and cand_snps(), with `cond` of G."""
+    idx, T, _, geno = _args(split, gkey)
+    br = fitted_branch(gkey, branch)
+    F, _ = design_matrix(name, split, gkey, br)
+    out = SC.adj_wide(idx, T, geno, panel()["Y"], F, h2, br, cand_snps())
+    out["cond"] = float(np.linalg.cond(out["G"].astype(np.float64)))
+    return _frozen(out)
+
+
+@functools.lru_cache(maxsize=None)
+def relfix_truth(name, split, gkey, branch, h2):
+    """reliab_cov_ref.vform_wide ("cov3") / reliab_group_ref.vform_wide of a design over all animals: rel, pev and
+    cov_cov, which for the class factor is `fixed_cov` too (covariates then levels, zeros at the snp reference level)."""
+    idx, T, _, geno = _args(split, gkey)
+    br = fitted_branch(gkey, branch)
+    cov, grp = design(name)
+    if grp is None:
+        return _frozen(RC.vform_wide(idx, T, geno, cov, h2, br))
+    out = RG.vform_wide(idx, T, geno, cov, grp, h2, br)
+    keep = np.flatnonzero(np.any(out["fixed_cov"] != 0, axis=0))
+    fc = np.zeros(out["fixed_cov"].shape, dtype=LD)             # (_widen fills a float64 array: refill it in longdouble)
+    fc[np.ix_(keep, keep)] = out["cov_cov"]
+    out["fixed_cov"] = fc
+    return _frozen(out)
+
+
+@functools.lru_cache(maxsize=None)
+def fixfit_truth(name, split, gkey, branch, h2):
+    """The model that fit(covariates=) / fit(groups=) returns under a design, as gls_truth builds it: covar_ref.gls_wide
+    of the expanded design, and fit_wide on [Y, F] -- the effects are those of Y less those of F times b, with nothing
+    rounded to float64 in between.  {b (5, C), m (C,), cov_effects (5, c), group_effects (5, L), group_center (L,),
+    effects (5, k), ebv (5, n) of y*, total (5, n) = ebv + F~ b, fitness (5,) of y*, cond}."""
+    idx, T, V, geno = _args(split, gkey)
+    br = fitted_branch(gkey, branch)
+    F, nc = design_matrix(name, split, gkey, br)
+    Y = panel()["Y"]
+    g = CV.gls_wide(idx, T, geno, Y, F, h2, br)
+    g["cond"] = float(np.linalg.cond(g["G"].astype(np.float64)))
+    e = R.fit_wide(idx, T, geno, np.hstack([Y, F]), h2, br)
+    nt = Y.shape[1]
+    eff = e[:, :nt] - e[:, nt:] @ g["b"].T
+    ref = np.arange(N_ANIMALS) if br == "gblup" else T
+    a = geno[:, idx].astype(np.int64)
+    w = a.astype(LD) - a[ref].sum(axis=0).astype(LD) / LD(len(ref))
+    mu = LD(0) if br == "gblup" else g["ystar"][T].sum(axis=0) / LD(len(T))
+    ebv = (w @ eff + mu).T
+    g["effects"], g["ebv"] = np.ascontiguousarray(eff.T), np.ascontiguousarray(ebv)
+    g["total"] = np.ascontiguousarray(ebv + ((F.astype(LD) - g["m"]) @ g["b"].T).T)
+    g["fitness"] = np.array([_pearson_wide(ebv[t][V], g["ystar"][V, t])[0] for t in range(nt)])
+    g["cov_effects"] = g["b"][:, :nc]
+    if design(name)[1] is not None:
+        L = F.shape[1] - nc + (br == "snp")
+        ge, gc = np.zeros((nt, L), dtype=LD), np.zeros(L, dtype=LD)
+        ge[:, L - (F.shape[1] - nc):] = g["b"][:, nc:]
+        if br == "snp":
+            gc[1:] = g["m"][nc:]
+            gc[0] = LD(1) - np.sum(g["m"][nc:])
+        g["group_effects"], g["group_center"] = ge, gc
+    return _frozen(g)
+
+
+# Leave-one-out: (split, genome, branch, form, h2).  snp160 in both forms, the others in the kernel form; both splits at
+# the top tier, (200, 60) below it.
+LOO_MODELS = (("snp160", "snp", "snp"), ("snp160", "snp", "kernel"), ("dual260", "snp", "kernel"),
+              ("g400", "gblup", "kernel"), ("g130", "gblup", "kernel"))
+LOO_CASES = [(s, g, br, f, h) for h in LOO_H2S for s in SPLITS if s == (200, 60) or h == LOO_H2S[-1]
+             for g, br, f in LOO_MODELS]
+
+
+@functools.lru_cache(maxsize=None)
+def loo_truth(split, gkey, branch, h2, form):
+    """loo_ref.loo_wide of the five columns of Y: pred / eloo (5, n_T), leverage (n_T,), press / fitness (5,) and
+    gap = min_t (1 - h_tt)."""
+    idx, T, _, geno = _args(split, gkey)
+    return _frozen(LO.loo_wide(idx, T, geno, panel()["Y"], h2, fitted_branch(gkey, branch), form))
+
+
+def loo_bar(kap, gap, tol=TOL, host=False):
+    """The LOO rule: pred, eloo, PRESS and fitness are e_t / (1 - h_tt), so they are held to bar / gap."""
+    return (host_bar(kap, tol) if host else bar(kap, tol)) / gap
 
 
 # ---------------------------------------------------------------------------------------------

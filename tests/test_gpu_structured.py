@@ -20,6 +20,10 @@ on every case here.  kappa runs from 15 to 3e7; from about 6e5 on the bar is kap
   D  reliability, log_likelihood, estimate_h2, snp_scores, fit(covariates)
   E  h2 = 1 on singular systems: a clean return, no infinity, bit-identical batch-mates
   F  the one model and column over the bar (forced gblup at k < n_T with the 1e6 offset): strict expected failures
+  G to K  (tests/test_gpu_structured_fixed.py) the entries that adjust for covariates and a class factor confounded
+     with relationship -- adjusted scores and likelihood, adjusted reliabilities, the wide GLS fit -- and leave-one-out
+     under the rule bar / min (1 - h_tt); two more inputs are left out there ((d) under gblup with the class factor;
+     LOO pred without the 1 / gap factor), each with its figure in tests/test_structured_host.py
 
 Each test prints its worst err / bar per quantity (pytest -s); PERFLOG.md holds the figures of the last run.
 """

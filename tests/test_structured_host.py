@@ -3,14 +3,26 @@ tests need, and the bar of tests/test_gpu_structured.py is fair: on every case a
 the float64 restatement (LAPACK, or the restatements' own column Cholesky) is within
 max(TOL / 8, 2 kappa 2^-53) of the longdouble truth, an eighth of what the GPU path is allowed.  The worst
 err / (kappa 2^-53) of each quantity is printed (pytest -s).
+
+The same for the fixed-effect designs of tests/test_gpu_structured_fixed.py: the input conditions (level counts, no
+unseen label, cond(G) <= STRUCT_COND_MAX, v_P >= SPAN_MIN v, bar / gap <= LOO_GAP_MAX), one restatement test per
+truth (adjusted statistics, adjusted uncertainty, fit(groups=), leave-one-out in both forms -- pred, eloo, PRESS and
+the fitness held to host_bar / gap, the LOO rule of tests/structured_ref.py), and the two further left-out inputs: (d)
+under gblup with the class factor, and LOO pred / eloo without the 1 / gap factor.
 """
 import numpy as np
 
 from oracle import blup_oracle as O
 from tests import covar_ref as CV
+from tests import group_ref as GR
+from tests import group_stats_ref as GS
 from tests import loglik_ref as LL
+from tests import loo_ref as LO
 from tests import model_ref as R
+from tests import reliab_cov_ref as RC
+from tests import reliab_group_ref as RG
 from tests import reliability_ref as Q
+from tests import score_cov_ref as SC
 from tests import score_ref as S
 from tests import structured_ref as SR
 
@@ -330,6 +342,182 @@ def test_covariate_restatement():
     w.show("covariates")
 
 
+# ---------------------------------------------------------------------------------------------
+# Fixed effects: the designs' conditions and the float64 restatements of the adjusted entries
+# ---------------------------------------------------------------------------------------------
+def test_fixed_design_input_conditions():
+    """The class factor has 30 levels, each with 5-10 train rows in (200, 60) and 6-10 in (257, 40), and no validation
+    animal carries a label the train rows lack; cond(G) <= STRUCT_COND_MAX in every case (fam+n passes
+    covar_ref.COND_MAX in two: the family directions, where V^-1 is about 1 / eig(K), beside the normal column, where it
+    is about 1 / lambda); v_P >= SPAN_MIN v for every candidate; bar / gap <= LOO_GAP_MAX for every LOO case."""
+    pn = SR.panel()
+    grp = SR.groups()
+    assert len(np.unique(grp)) == 30
+    for s, lo in (((200, 60), 5), ((257, 40), 6)):
+        T, V = pn["splits"][s]
+        lev, n = np.unique(grp[T], return_counts=True)
+        print("levels %s: %d, train rows per level %d-%d" % (s, len(lev), n.min(), n.max()))
+        assert len(lev) == 30 and n.min() == lo and n.max() == 10
+        assert set(grp[V]) <= set(lev) and set(grp[SR.rel_animals()]) <= set(lev)
+    Qm = SR.covariates()
+    np.testing.assert_array_equal(Qm[:, 0], (grp == 0).astype(np.float64))      # why fam+n leaves it out
+    worst_cond, span = {}, (np.inf, None)
+    over = []
+    for name in SR.DESIGNS:
+        for split, gkey, br, h2 in sorted(set(SR.AUX_CASES + SR.LL_CASES), key=str):
+            tr = SR.adj_truth(name, split, gkey, br, h2)
+            F, _ = SR.design_matrix(name, split, gkey, br)
+            assert F.shape[1] == {"cov3": 3, "fam": 30, "fam+n": 31}[name] - (name != "cov3" and br == "snp")
+            label = "%s %s %s %s h2=%s" % (name, split, gkey, br, h2)
+            print("cond(G) %s: %.2e" % (label, tr["cond"]))
+            assert tr["cond"] <= SR.STRUCT_COND_MAX, label
+            if tr["cond"] > CV.COND_MAX:
+                over.append(label)
+            worst_cond[name] = max(worst_cond.get(name, 0.0), tr["cond"])
+            ratio = float(np.min(tr["v"] / tr["v_plain"]))
+            span = min(span, (ratio, label))
+            assert np.all(tr["v"] >= SR.SC.SPAN_MIN * tr["v_plain"]), label
+    print("worst cond(G): %s; over covar_ref.COND_MAX: %s" % (
+        ", ".join("%s %.2e" % kv for kv in worst_cond.items()), over))
+    print("smallest v_P / v: %.2e (%s)" % span)
+    assert all(o.startswith("fam+n") for o in over)
+    worst = (0.0, None)
+    for split, gkey, br, form, h2 in SR.LOO_CASES:
+        tr = SR.loo_truth(split, gkey, br, h2, form)
+        kap = SR.kappa(split, gkey, br, h2, form)
+        r = SR.loo_bar(kap, tr["gap"])
+        label = "%s %s %s %s h2=%s" % (split, gkey, br, form, h2)
+        print("LOO gap %s: %.2e, bar / gap %.2e" % (label, tr["gap"], r))
+        assert 0 < tr["gap"] <= 1 and r <= SR.LOO_GAP_MAX, label
+        worst = max(worst, (r, label))
+    print("largest bar / gap: %.2e (%s)" % worst)
+
+
+def _rel1(got, truth):
+    return float(abs(LD(got) - truth) / max(LD(1), abs(truth)))
+
+
+def test_adjusted_statistics_restatement():
+    """score_cov_ref.adj_ref / group_stats_ref.adj_ref (the same routine on the expanded design) against adj_wide:
+    u_P, v_P, q_P, b, log-likelihood and sigma2_g of every design."""
+    pn = SR.panel()
+    cand = SR.cand_snps()
+    for name in SR.DESIGNS:
+        w = _Ratios()
+        cov, grp = SR.design(name)
+        for split, gkey, br, h2 in sorted(set(SR.AUX_CASES + SR.LL_CASES), key=str):
+            idx, T = pn["genomes"][gkey], pn["splits"][split][0]
+            if grp is None:
+                r = SC.adj_ref(idx, T, pn["geno"], pn["Y"], cov, h2, br, cand)
+            else:
+                r = GS.adj_ref(idx, T, pn["geno"], pn["Y"], cov, grp, h2, br, cand)
+            tr = SR.adj_truth(name, split, gkey, br, h2)
+            kap = SR.kappa(split, gkey, br, h2, "kernel")
+            label = "%s %s %s h2=%s" % (split, gkey, br, h2)
+            for t in SR.stat_cols(name, br):
+                c = label + " (%s)" % SR.COLS[t]
+                w.check("q", SR.relerr([r["q"][t]], [tr["q"][t]]), kap, c)
+                w.check("loglik", _rel1(r["loglik"][t], tr["loglik"][t]), kap, c)
+                w.check("sigma2_g", _rel1(r["sigma2_g"][t], tr["sigma2_g"][t]), kap, c)
+            if (split, gkey, br, h2) not in SR.AUX_CASES:
+                continue
+            w.check("info v", SR.relerr(r["v"], tr["v"]), kap, label)
+            for t in SR.fit_cols(br):
+                c = label + " (%s)" % SR.COLS[t]
+                w.check("b", SR.relerr(r["b"][t], tr["b"][t]), kap, c)
+                if t in SR.stat_cols(name, br):
+                    w.check("score u", SR.relerr(r["u"][t], tr["u"][t]), kap, c)
+        w.show("adjusted statistics, " + name)
+
+
+def test_adjusted_uncertainty_restatement():
+    """reliab_cov_ref.vform_ref / reliab_group_ref.vform_ref against vform_wide on rel_animals(): reliability
+    (absolute, inside [0, 1] and never above the plain one), pev_total, cov_cov / fixed_cov."""
+    pn = SR.panel()
+    an = SR.rel_animals()
+    for name in SR.DESIGNS:
+        w = _Ratios()
+        cov, grp = SR.design(name)
+        for split, gkey, br, h2 in SR.AUX_CASES:
+            idx, T = pn["genomes"][gkey], pn["splits"][split][0]
+            if grp is None:
+                r = RC.vform_ref(idx, T, pn["geno"], cov, h2, br, an)
+                key = "cov_cov"
+            else:
+                r = RG.vform_ref(idx, T, pn["geno"], cov, grp, h2, br, an)
+                key = "fixed_cov"
+                assert not np.any(r["unseen"])
+                if br == "snp":
+                    nc = 0 if cov is None else cov.shape[1]
+                    assert not np.any(r[key][nc]) and not np.any(r[key][:, nc])
+            tr = SR.relfix_truth(name, split, gkey, br, h2)
+            kap = SR.kappa(split, gkey, br, h2, "kernel")
+            hb = SR.host_bar(kap)
+            label = "%s %s %s h2=%s" % (split, gkey, br, h2)
+            plain = SR.rel_truth(split, gkey, br, h2)[an]
+            assert np.all(tr["rel"][an] <= plain + 1e-15) and np.all(tr["rel"][an] > -1e-15), label
+            assert np.all(r["rel"] >= -hb) and np.all(r["rel"] <= plain + hb), label
+            w.check("reliability", float(np.max(np.abs(r["rel"].astype(LD) - tr["rel"][an]))), kap, label)
+            w.check("pev_total", SR.relerr(r["pev"], tr["pev"][an]), kap, label)
+            w.check(key, SR.relerr(r[key], tr[key]), kap, label)
+        w.show("adjusted uncertainty, " + name)
+
+
+def test_group_fit_restatement():
+    """group_ref.group_ref (the GLS of the expanded design, then the oracle's blup and fit_ref of y*) against
+    fixfit_truth under the class factor: level and covariate effects, SNP effects, validation EBVs, fitness."""
+    pn = SR.panel()
+    for name in ("fam", "fam+n"):
+        w = _Ratios()
+        cov, grp = SR.design(name)
+        for split, gkey, br, h2 in SR.AUX_CASES:
+            idx, (T, V) = pn["genomes"][gkey], pn["splits"][split]
+            tr = SR.fixfit_truth(name, split, gkey, br, h2)
+            assert tr["cond"] <= SR.STRUCT_COND_MAX
+            kap = SR.kappa(split, gkey, br, h2, "kernel")
+            for t in SR.fit_cols(br, gkey):
+                c = "%s %s %s h2=%s (%s)" % (split, gkey, br, h2, SR.COLS[t])
+                r = GR.group_ref(idx, T, V, pn["geno"], np.ascontiguousarray(pn["Y"][:, t]), cov, grp, h2, br)
+                np.testing.assert_allclose(r["group_center"], tr["group_center"].astype(np.float64), rtol=1e-14, atol=0)
+                # b is one output vector, covariates then levels: its error is relative to its largest entry
+                got = np.concatenate(([] if cov is None else [r["cov_effects"][0]]) + [r["group_effects"][0]])
+                w.check("b", SR.relerr(got, np.concatenate([tr["cov_effects"][t], tr["group_effects"][t]])), kap, c)
+                if t not in SR.fixfit_cols(name, br, gkey):
+                    continue
+                w.check("effects", SR.relerr(r["effects"][0], tr["effects"][t]), kap, c)
+                w.check("ebv valid", SR.relerr(r["ebv"][0], tr["ebv"][t][V]), kap, c)
+                w.check("fitness", abs(r["fitness"] - tr["fitness"][t]), kap, c)
+        w.show("fit(groups=), " + name)
+
+
+def _loo_host(w, split, gkey, br, form, h2):
+    pn = SR.panel()
+    idx, T = pn["genomes"][gkey], pn["splits"][split][0]
+    tr = SR.loo_truth(split, gkey, br, h2, form)
+    kap = SR.kappa(split, gkey, br, h2, form)
+    scale = 1.0 / tr["gap"]
+    for t in SR.fit_cols(br, gkey):
+        c = "%s %s %s %s h2=%s (%s)" % (split, gkey, br, form, h2, SR.COLS[t])
+        r = LO.loo_ref(idx, T, pn["geno"], pn["Y"][:, t], h2, br, form)
+        if t == 0:
+            w.check("leverage", float(np.max(np.abs(r["leverage"].astype(LD) - tr["leverage"]))), kap, c)
+            assert abs(r["gap"] - tr["gap"]) <= SR.host_bar(kap), c
+        w.check("pred", SR.relerr(r["pred"], tr["pred"][t]) / scale, kap, c)
+        if t in SR.z_cols(br):          # (d) under snp: y - mean(y_T) is rounded at 1e-10 before anything is solved
+            w.check("eloo", SR.relerr(r["eloo"], tr["eloo"][t]) / scale, kap, c)
+        w.check("press", SR.relerr([r["press"]], [tr["press"][t]]) / scale, kap, c)
+        w.check("fitness", abs(r["fitness"] - tr["fitness"][t]) / scale, kap, c)
+
+
+def test_loo_restatement():
+    """loo_ref.loo_ref in both forms against loo_wide: the leverages to host_bar, pred / eloo / PRESS / fitness to
+    host_bar / gap (err * gap is what is checked and printed)."""
+    w = _Ratios()
+    for split, gkey, br, form, h2 in SR.LOO_CASES:
+        _loo_host(w, split, gkey, br, form, h2)
+    w.show("leave-one-out (pred, eloo, press, fitness: err * gap)")
+
+
 def test_inputs_left_out_do_miss_the_host_bar():
     """The inputs of the issue that tests/structured_ref.py leaves out (fit_cols, z_cols, the absolute fitness), each with the float64 restatement's own error on it: over host_bar, so no factor could be held to the
     bar there.  The figures are printed; each is asserted to miss, so a change that makes one of them pass shows up
@@ -370,6 +558,35 @@ def test_inputs_left_out_do_miss_the_host_bar():
     print("fitness relative to |truth|: truth %.4f, err %.2e absolute, %.2e relative (host bar %.2e)" % (
         tf, df, df / tf, SR.host_bar(kap)))
     assert df <= SR.host_bar(kap) < df / tf
+    # (d) under gblup with the class factor: the level means absorb the offset, q_P = q - |C^-1 h|^2 cancels twelve digits
+    split, gkey, br, h2 = (200, 60), "g400", "gblup", 0.4
+    T, V = pn["splits"][split]
+    kap = SR.kappa(split, gkey, br, h2, "kernel")
+    for name in ("fam", "fam+n"):
+        cov, grp = SR.design(name)
+        r = GS.adj_ref(pn["genomes"][gkey], T, pn["geno"], pn["Y"], cov, grp, h2, br, SR.cand_snps())
+        tr = SR.adj_truth(name, split, gkey, br, h2)
+        eq, el = SR.relerr([r["q"][3]], [tr["q"][3]]), _rel1(r["loglik"][3], tr["loglik"][3])
+        eu, eb = SR.relerr(r["u"][3], tr["u"][3]), SR.relerr(r["b"][3], tr["b"][3])
+        print("(d) g400 gblup %s h2=0.4: q_P %.3e, err %.2e = %.2e host bars, loglik %.2e, u_P %.2e = %.1f host bars; "
+              "b %.2e" % (name, float(tr["q"][3]), eq, eq / SR.host_bar(kap), el, eu, eu / SR.host_bar(kap), eb))
+        assert eq > SR.host_bar(kap) and el > SR.host_bar(kap) and eu > SR.host_bar(kap) and eb <= SR.host_bar(kap)
+        g = GR.group_ref(pn["genomes"][gkey], T, V, pn["geno"], np.ascontiguousarray(pn["Y"][:, 3]), cov, grp, h2, br)
+        ft = SR.fixfit_truth(name, split, gkey, br, h2)
+        ee, ev = SR.relerr(g["effects"][0], ft["effects"][3]), SR.relerr(g["ebv"][0], ft["ebv"][3][V])
+        print("  its fit(groups=) model: effects err %.2e = %.1f host bars, validation EBVs %.2e = %.1f" % (
+            ee, ee / SR.host_bar(kap), ev, ev / SR.host_bar(kap)))
+        assert ee > SR.host_bar(kap)
+    # LOO pred / eloo without the 1 / gap factor at h2 = 0.999999
+    split, gkey, br, form, h2 = (200, 60), "dual260", "snp", "kernel", 0.999999
+    tr = SR.loo_truth(split, gkey, br, h2, form)
+    r = LO.loo_ref(pn["genomes"][gkey], pn["splits"][split][0], pn["geno"], pn["Y"][:, 0], h2, br, form)
+    kap = SR.kappa(split, gkey, br, h2, form)
+    ee, eh = SR.relerr(r["eloo"], tr["eloo"][0]), float(np.max(np.abs(r["leverage"].astype(LD) - tr["leverage"])))
+    print("LOO (200, 60) dual260 snp h2=0.999999 (a): gap %.2e; eloo err %.2e = %.0f host bars, %.3f with the 1 / gap "
+          "factor; leverage %.2e = %.3f host bars" % (tr["gap"], ee, ee / SR.host_bar(kap),
+                                                      ee * tr["gap"] / SR.host_bar(kap), eh, eh / SR.host_bar(kap)))
+    assert ee > SR.host_bar(kap) >= ee * tr["gap"] and eh <= SR.host_bar(kap)
 
 
 # ---------------------------------------------------------------------------------------------
